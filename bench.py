@@ -6,17 +6,29 @@ mobocmf/util/blackbox_mfdgp_fitter.py:161-171) for EACH of the 3 surrogates (2 o
 of C3 on the full batch B = N.  `value` = surrogate ELBO steps per second, whole job.  With --gpus N every
 rank trains its own 3 surrogates (weak scaling, no data-path collective: the surrogates are independent,
 SURVEY 8(e)); the single RCCL all-gather of posterior moments for the joint acquisition happens once after
-the timed region and is reported as `exchange_ms`.
+the timed region of a --full run and is reported as `exchange_ms`.
 
     python bench.py --gpus 1 --steps 20 --warmup 3
     python bench.py --gpus N ...            (starts the N ranks itself, one fresh process per GPU, RCCL)
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
-The line's `value` is the median of --repeats (default 5) timed regions of exactly K steps each (all listed in
-`repeat_values`); `roofline` times the GEMM instantiations the layer really launches (column-statistics and dA
-epilogues included), each on its own, and `per_kernel_instep_ms` the same launches INSIDE a training step (HIP events
+A plain run sets up, runs W warm-up steps, times ONE region of exactly K steps (`value`, `ms_per_step` = that region / K),
+writes the outputs of the last step when --dump-outputs DIR is given, and prints the line.  Everything else the bench
+measures is behind --full:
+    python bench.py --gpus 1 --steps K --warmup W --full
+There the line's `value` is the median of --repeats (default 5) timed regions of exactly K steps each (all listed in
+`repeat_values`); `exchange_ms` times the all-gather of posterior moments (a one-rank RCCL group at one GPU);
+`reference_layout` times the same step with every layer at every row and a dense backward, `reference_sizes` the
+reference's own problem size (C1); `roofline` times the GEMM instantiations the layer really launches (column-statistics
+and dA epilogues included), each on its own, and `per_kernel_instep_ms` the same launches INSIDE a training step (HIP events
 recorded by the library around them, mobocmf_layer_desc.probe_events); `cpu_baseline` is 3 warm-up + 10 timed oracle steps on
-the box's host cores.
+the box's host cores, `parity` the HIP path against the oracle at the headline size.  --no-roofline, --no-cpu-baseline,
+--no-dense-leg and --no-rccl drop single parts of it.
+
+--dump-outputs DIR writes what the timed path computed in its last timed step, as a caller of that path receives it:
+`losses.npy` (the per-surrogate loss values the step returns) and one `surrogate<i>.<parameter name>.npy` per trained
+parameter after that step's update (float64; a fixed, seeded sample of the larger arrays if the whole exceeded 64 MB).
+The inputs depend on the arguments only, so two builds run with the same arguments can be compared file by file.
 """
 import argparse
 import json
@@ -420,6 +432,33 @@ def parity_vs_oracle(O, cfg, prob, raw, x, y, fid, eps, device, T=256):
                        "max |oracle|" % (cfg.get("name", "headline config"), T, cfg["S"])}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, losses, models, prefix=""):
+    """--dump-outputs: what the timed path hands its caller after the last timed step -- the loss values that step returned
+    (`losses.npy`) and every trained parameter after its update (`surrogate<i>.<parameter name>.npy`) -- in float64.  Should
+    the whole exceed DUMP_LIMIT_BYTES, the largest arrays are cut to a fixed, seeded sample of their flattened elements (same
+    indices on every run) until it fits.  Called after the device synchronisation that ends the timed region."""
+    import numpy as np
+    host = lambda t: t.detach().to("cpu", torch.float64).numpy()
+    arrays = {"losses": host(losses[0] if len(losses) == 1 else torch.stack([l.reshape(()) for l in losses]))}
+    for i, model in enumerate(models):
+        for name, p in model.named_parameters():
+            arrays["surrogate%d.%s" % (i, name)] = host(p)
+    left, order = DUMP_LIMIT_BYTES, sorted(arrays, key=lambda k: arrays[k].size)
+    for n, name in enumerate(order):
+        cap = left // (8 * (len(order) - n))       # an even share of what is left, smallest arrays first
+        a = arrays[name]
+        if a.size > cap:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=cap, replace=False))
+            arrays[name] = a.reshape(-1)[idx]
+        left -= arrays[name].size * 8
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, prefix + name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def main():
     # stdout carries exactly ONE line (the JSON record): library chatter written to fd 1 from native code (the RCCL
     # banner, gloo's connection messages) is diverted to stderr for the whole run
@@ -443,7 +482,13 @@ def main():
                          "the same surrogates on 1/W of the batch rows + one gradient all-reduce per step (strong scaling)")
     ap.add_argument("--no-overlap", action="store_true",
                     help="serialise each surrogate's layers on one stream (no chain/panel split across streams)")
-    ap.add_argument("--repeats", type=int, default=5, help="timed regions of exactly --steps steps each; value = median")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: repeats, exchange, reference layout and sizes, "
+                         "roofline, per-kernel times, CPU baseline and parity (each --no-* option drops one part)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the losses and trained parameters of the last timed step as DIR/<name>.npy")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed regions of exactly --steps steps each; value = median (default 1, with --full 5)")
     ap.add_argument("--tile-rows", type=int, default=0, help="A/B knob: tile height of the panel products (0 automatic, 64, 128)")
     ap.add_argument("--potrf-cols", type=int, default=None, help="A/B knob: the blocked Cholesky as one launch (0, default) or a launch pair per 64 columns (4 | 1 columns per hand-over)")
     ap.add_argument("--dense-backward", action="store_true",
@@ -464,6 +509,8 @@ def main():
     ap.add_argument("--layer-path", action="store_true",
                     help="small configurations: the layer entry points (HIP-graph replay) instead of the one-launch step")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
     if args.no_overlap:
         from mobocmf_amd.models import MFDGP
         MFDGP.overlap_chains = False
@@ -522,8 +569,8 @@ def main():
             dist.init_process_group("nccl", rank=rank, world_size=world, device_id=device)
         else:
             dist.init_process_group(args.backend, rank=rank, world_size=world)
-    elif not args.no_rccl:
-        # one GPU: a process group of ONE rank on the nccl (= RCCL) backend all the same, so that the exchange below runs the
+    elif args.full and not args.no_rccl:
+        # one GPU, --full: a process group of ONE rank on the nccl (= RCCL) backend all the same, so that the exchange below runs the
         # collective an N-rank job runs (`rccl_ranks`, `exchange_ms` of the record) -- through the launcher's environment when
         # there is one, else through a rendezvous file (no port to collide on).  A box whose RCCL cannot start is reported
         # (`rccl_error`), the step timing does not depend on it.
@@ -619,36 +666,41 @@ def main():
         elapsed_all.append(el)
     elapsed = sorted(elapsed_all)[len(elapsed_all) // 2]       # median repeat; every repeat is listed in the line
     finite = all(bool(torch.isfinite(l).all()) for l in losses)
+    # before anything below runs more steps on these models (per_kernel_instep_ms does)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, losses, [s[0] for s in sur], "rank%d." % rank if world > 1 else "")
 
-    # the path's single exchange: all-gather of the posterior moments on a shared test grid (JES)
-    from mobocmf_amd import parallel
-    T = 256
-    Xg = torch.as_tensor(synthetic.make_problem(d=cfg["d"], L=cfg["L"], M=8, N=T, S=1, seed=99)["x"],
-                         dtype=torch.float64, device=device)
-    torch.cuda.synchronize()
-    t1 = time.perf_counter()
-    with torch.no_grad():
-        local = []
-        for model, _, _, _ in sur:
-            model.eval()
-            mus, vs = model.predict_for_acquisition(Xg, cfg["L"] - 1)
-            model.train()
-            local.append(torch.stack([mus, vs]))
-        local = torch.stack(local)
-        gathered = parallel.all_gather_moments(local)      # (the warm call: communicator set-up, first-use allocations)
+    exchange_ms = exchange_first_ms = ex = local = None
+    if args.full:
+        # the path's single exchange: all-gather of the posterior moments on a shared test grid (JES)
+        from mobocmf_amd import parallel
+        T = 256
+        Xg = torch.as_tensor(synthetic.make_problem(d=cfg["d"], L=cfg["L"], M=8, N=T, S=1, seed=99)["x"],
+                             dtype=torch.float64, device=device)
         torch.cuda.synchronize()
-        exchange_first_ms = (time.perf_counter() - t1) * 1e3
-        ex = []
-        for _ in range(5):      # the collective alone: median of 5
+        t1 = time.perf_counter()
+        with torch.no_grad():
+            local = []
+            for model, _, _, _ in sur:
+                model.eval()
+                mus, vs = model.predict_for_acquisition(Xg, cfg["L"] - 1)
+                model.train()
+                local.append(torch.stack([mus, vs]))
+            local = torch.stack(local)
+            gathered = parallel.all_gather_moments(local)      # (the warm call: communicator set-up, first-use allocations)
             torch.cuda.synchronize()
-            t1 = time.perf_counter()
-            gathered = parallel.all_gather_moments(local)
-            torch.cuda.synchronize()
-            ex.append((time.perf_counter() - t1) * 1e3)
-    exchange_ms = sorted(ex)[2]
+            exchange_first_ms = (time.perf_counter() - t1) * 1e3
+            ex = []
+            for _ in range(5):      # the collective alone: median of 5
+                torch.cuda.synchronize()
+                t1 = time.perf_counter()
+                gathered = parallel.all_gather_moments(local)
+                torch.cuda.synchronize()
+                ex.append((time.perf_counter() - t1) * 1e3)
+        exchange_ms = sorted(ex)[2]
+        finite = finite and bool(torch.isfinite(gathered).all()) and gathered.shape[0] == world * local.shape[0] and \
+            bool(torch.equal(gathered[rank * local.shape[0]:(rank + 1) * local.shape[0]], local))
     rccl_loaded = any("librccl" in ln for ln in open("/proc/self/maps")) if os.path.exists("/proc/self/maps") else None
-    finite = finite and bool(torch.isfinite(gathered).all()) and gathered.shape[0] == world * local.shape[0] and \
-        bool(torch.equal(gathered[rank * local.shape[0]:(rank + 1) * local.shape[0]], local))
 
     # What the record says about rows / columns / executed flops is read off the STEP OBJECT (its layer_rows and the
     # fidelities of the rows it holds, in the order it holds them), never inferred from the CLI flags: with --shard rows every
@@ -670,7 +722,7 @@ def main():
 
     # the same step in the reference's layout -- every layer at every row, dense backward -- timed beside it (one GPU only)
     dense_leg = None
-    if world == 1 and not args.eager and not rows and not args.no_dense_leg and (layer_rows is not None or sparse):
+    if args.full and world == 1 and not args.eager and not rows and not args.no_dense_leg and (layer_rows is not None or sparse):
         from mobocmf_amd import functional as F_
         F_.set_sparse_backward(False)
         try:
@@ -700,7 +752,7 @@ def main():
         del dsteps
 
     small_leg = None
-    if world == 1 and rank == 0 and not args.no_dense_leg and args.config == "C3":
+    if args.full and world == 1 and rank == 0 and not args.no_dense_leg and args.config == "C3":
         small_leg = reference_sizes_leg(device)
     if rank == 0:
         n_sur = n_out if rows else n_out * world
@@ -741,7 +793,7 @@ def main():
             # `exchange_ms` = that collective alone (median of 5 after a warm call), `exchange_first_ms` = the moments of this
             # rank's surrogates + the first (warm-up) collective
             "exchange_ms": exchange_ms, "exchange_first_ms": exchange_first_ms, "exchange_repeats_ms": ex,
-            "exchange_payload_bytes": int(local.numel() * 8),
+            "exchange_payload_bytes": int(local.numel() * 8) if local is not None else None,
             "rccl_ranks": (dist.get_world_size() if dist is not None else 0),
             "backend": (args.backend if dist is not None else None), "librccl_mapped": rccl_loaded, "rccl_error": rccl_error,
             "finite": finite, "step_issue": "eager" if args.eager else (
@@ -749,7 +801,7 @@ def main():
                                                                    if hasattr(tiny, "wgs_used") else "mobocmf_tiny_elbo_step"))
                 if tiny is not None else "hip-graph replay"),
         }
-        if not args.no_roofline:
+        if args.full and not args.no_roofline:
             line["roofline"] = measure_dominant_kernel(cfg, device, n_cols=cols[dom], layer=dom)
             if layer_rows is not None and cols[dom] != cfg["N"] * cfg["S"]:
                 # the same four launches on the panel the reference's layout gives the top layer (every row): the fraction the
@@ -769,7 +821,7 @@ def main():
                            "library around each launch (mobocmf_layer_desc.probe_events), mean of 4 steps; `instep_over_isolated` "
                            "divides by the same launch timed alone (roofline.variants).  Per-kernel durations of the timed "
                            "configuration (3 streams, graph replay): profiles/r05_bench_C3_timed_only_kernel_summary.md"}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cb, parity = cpu_baseline(cfg, device=device)
             line["cpu_baseline"] = cb
             line["parity"] = parity

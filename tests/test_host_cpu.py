@@ -269,6 +269,36 @@ def test_bench_accounting_of_dead_rows_and_active_blocks():
     assert bench.panel_columns(cfg3, [1024, 512, 256]) == [1024, 2048, 1024]
 
 
+def test_bench_dump_outputs_writes_losses_and_parameters(tmp_path):
+    """bench.py --dump-outputs: the last step's losses and every parameter as float64 .npy files; above the size cap the
+    largest arrays become the same seeded sample on every call and the whole fits."""
+    import importlib.util
+    import os
+
+    import torch
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(os.path.dirname(os.path.dirname(__file__)), "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    torch.manual_seed(0)
+    models = [torch.nn.Linear(40, 30, dtype=torch.float64), torch.nn.Linear(3, 2, dtype=torch.float32)]
+    losses = [torch.tensor(1.5, dtype=torch.float64), torch.tensor(-2.0, dtype=torch.float64)]
+    bench.dump_outputs(str(tmp_path / "a"), losses, models)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["losses.npy", "surrogate0.bias.npy", "surrogate0.weight.npy", "surrogate1.bias.npy", "surrogate1.weight.npy"]
+    assert np.load(tmp_path / "a" / "losses.npy").tolist() == [1.5, -2.0]
+    w = np.load(tmp_path / "a" / "surrogate0.weight.npy")
+    assert w.dtype == np.float64 and np.array_equal(w, models[0].weight.detach().numpy())
+    assert np.load(tmp_path / "a" / "surrogate1.weight.npy").dtype == np.float64
+    bench.DUMP_LIMIT_BYTES = 8 * 400
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), losses[:1], models[:1], prefix="rank1.")
+    total = sum(os.path.getsize(tmp_path / "b" / n) - 128 for n in os.listdir(tmp_path / "b"))      # 128-byte .npy header
+    assert total <= 8 * 400
+    ws = [np.load(tmp_path / d / "rank1.surrogate0.weight.npy") for d in ("b", "c")]
+    assert ws[0].shape == (400 - 30 - 1,) and np.array_equal(ws[0], ws[1])
+    assert np.isin(ws[0], models[0].weight.detach().numpy().ravel()).all()
+
+
 def test_tiny_step_descriptor_layout_and_argument_checks():
     """mobocmf_tiny_model as ctypes sees it == as the library sees it (the size queries read fields on both sides of the
     pointer block), the flat-vector / workspace sizes follow the documented layout, and a malformed descriptor is refused on

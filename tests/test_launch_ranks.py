@@ -100,7 +100,7 @@ def test_bench_two_ranks_through_the_launcher_over_gloo():
     surrogates on the HIP path, the exchange is a world-size-2 all-gather (gloo rehearsal of the RCCL call), rank 0 prints
     the ONE record."""
     pr = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--force-device", "0",
-                         "--config", "C1", "--steps", "3", "--warmup", "1", "--repeats", "1", "--no-roofline", "--no-cpu-baseline"],
+                         "--config", "C1", "--steps", "3", "--warmup", "1", "--repeats", "1", "--full", "--no-roofline", "--no-cpu-baseline"],
                         capture_output=True, timeout=600)
     assert pr.returncode == 0, pr.stderr.decode()[-2000:]
     lines = [ln for ln in pr.stdout.decode().splitlines() if ln.strip()]
@@ -108,3 +108,27 @@ def test_bench_two_ranks_through_the_launcher_over_gloo():
     rec = json.loads(lines[0])
     assert rec["n_gpus"] == 2 and rec["rccl_ranks"] == 2 and rec["backend"] == "gloo" and rec["finite"]
     assert rec["config"]["surrogates_per_gpu"] == 3 and rec["value"] > 0 and rec["scaling"] == "weak"
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_times_exactly_its_steps_and_dumps_the_last_step(tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` times one region of K steps and nothing beside it; --dump-outputs
+    writes the last step's losses and trained parameters as float64 .npy files."""
+    import numpy as np
+    pr = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--config", "C1", "--steps", "4",
+                         "--warmup", "2", "--dump-outputs", str(tmp_path)], capture_output=True, timeout=600)
+    assert pr.returncode == 0, pr.stderr.decode()[-2000:]
+    lines = [ln for ln in pr.stdout.decode().splitlines() if ln.strip()]
+    assert len(lines) == 1
+    rec = json.loads(lines[0])
+    assert rec["steps"] == 4 and rec["warmup"] == 2 and len(rec["repeat_values"]) == 1 and rec["finite"]
+    assert rec["ms_per_step"] > 0 and abs(rec["value"] - 3 * 1e3 / rec["ms_per_step"]) < 1e-6 * rec["value"]
+    assert rec["unit"] == "ELBO steps/s" and rec["higher_is_better"] is True and rec["dtype"] == "f64"
+    assert rec["rccl_ranks"] == 0 and rec["exchange_ms"] is None and rec["reference_layout"] is None
+    assert not any(k in rec for k in ("roofline", "per_kernel_instep_ms", "cpu_baseline", "parity"))
+    names = sorted(os.listdir(tmp_path))
+    assert "losses.npy" in names and sum(n.startswith("surrogate2.") for n in names) >= 4
+    losses = np.load(tmp_path / "losses.npy")
+    assert losses.dtype == np.float64 and losses.shape[0] == 3 and np.isfinite(losses).all()
+    for n in names:
+        assert np.load(tmp_path / n).dtype == np.float64

@@ -5,8 +5,9 @@
 #   bash tools/asan_host.sh [cases]      -> log in profiles/<round>_asan_host_fuzz.log (pass the name as $2)
 set -e
 cd "$(dirname "$0")/.."
-B=/tmp/mobocmf_asan_host
-rm -rf $B && mkdir -p $B
+# a build directory of this run's own: a fixed shared path collides with another user's or run's leftovers
+B=$(mktemp -d "${TMPDIR:-/tmp}/mobocmf_asan_host.XXXXXX")
+trap 'rm -rf "$B"' EXIT
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 SAN="-fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer -O1 -g"
 pids=""

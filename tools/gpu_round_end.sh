@@ -16,7 +16,7 @@ if [ "$1" != "nosuite" ]; then
   [ $rc = 0 ] || exit $rc
 fi
 # the record the driver will produce, with the CPU baseline (a few minutes)
-timeout -k 10 600 python bench.py > $O/bench_C3.json 2> $O/bench_C3.err && tail -c 400 $O/bench_C3.json
+timeout -k 10 600 python bench.py --full > $O/bench_C3.json 2> $O/bench_C3.err && tail -c 400 $O/bench_C3.json
 # per-kernel time in the configuration that is timed (the program directly after `--`)
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/p_timed -- python3 bench.py --no-dense-leg --no-roofline --no-cpu-baseline --no-rccl --steps 100 > $O/bench_C3_profiled_timed_only.json 2> /dev/null &&
 python tools/summarize_profile.py $(ls $O/p_timed/*/*kernel_trace.csv | head -1) $O/bench_C3_timed_only_kernel_summary.md > /dev/null &&
@@ -31,7 +31,7 @@ fi
 [ "$1" = "a" ] && exit 0
 # the one-launch steps: C1 / C2 through them and through the layer path, the cooperative step's sweep and phase stamps
 for a in "--config C1" "--config C1 --layer-path" "--config C2" "--config C2 --layer-path" "--config C2 --surrogates 4" "--config C2 --surrogates 1"; do
-  timeout -k 10 200 python bench.py $a --steps 300 --no-cpu-baseline --no-roofline --no-dense-leg --no-rccl 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$a |', round(d['value'],1), 'steps/s |', round(d['ms_per_step']*1e3,1), 'us per bench step |', d['step_issue'], '| repeats', [round(v) for v in d['repeat_values']])"
+  timeout -k 10 200 python bench.py $a --full --steps 300 --no-cpu-baseline --no-roofline --no-dense-leg --no-rccl 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$a |', round(d['value'],1), 'steps/s |', round(d['ms_per_step']*1e3,1), 'us per bench step |', d['step_issue'], '| repeats', [round(v) for v in d['repeat_values']])"
 done | tee $O/bench_small_configs.txt
 timeout -k 10 500 python tools/coop_sweep.py > $O/coop_sweep.txt 2>&1; tail -60 $O/coop_sweep.txt
 if [ -f abtest/libcstamps.so ]; then

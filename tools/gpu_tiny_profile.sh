@@ -7,7 +7,7 @@ rm -rf $O && mkdir -p $O
 {
 echo "== bench.py --config C1 (the reference's own size: Forrester 1D, 2 fidelities, M = N = 16, S = 4), 500 steps x 5 repeats"
 for a in "--config C1" "--config C1 --layer-path" "--config C1 --surrogates 1" "--config C1 --surrogates 1 --layer-path" "--config C1 --surrogates 8"; do
-  timeout -k 10 200 python bench.py $a --steps 500 --no-cpu-baseline --no-roofline --no-dense-leg 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$a |', round(d['value'],1), 'ELBO steps/s |', round(d['ms_per_step']*1e3,1), 'us per bench step |', d['step_issue'], '| repeats', [round(v) for v in d['repeat_values']])"
+  timeout -k 10 200 python bench.py $a --full --steps 500 --no-cpu-baseline --no-roofline --no-dense-leg 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$a |', round(d['value'],1), 'ELBO steps/s |', round(d['ms_per_step']*1e3,1), 'us per bench step |', d['step_issue'], '| repeats', [round(v) for v in d['repeat_values']])"
 done
 echo
 echo "== tools/tiny_sweep.py: ONE surrogate, one launch vs the layer path (HIP-graph replay); the rule's estimate = util/tiny_step.py estimated_us"
