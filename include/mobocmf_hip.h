@@ -221,6 +221,29 @@ int mobocmf_rff_eval(int32_t kind, int32_t d, int32_t F, int64_t n, const double
                      const double* b1, const double* Wf, const double* W2, const double* b2, const double* theta, double s0,
                      double s1, double s2, double* out, mobocmf_stream_t stream);
 
+/* K chain samples (a layer-0 sample and the layers >= 1 recursing on it, the whole function sample of one black-box) at the
+ * same n points in ONE launch: out[k * n + i] = the top layer of sample k at x_i.  The layer recursion stays in a register,
+ * nothing goes back to memory between layers.  params: the samples' operands, ONE device buffer of doubles; desc: DEVICE table
+ * of K * MOBOCMF_RFF_MAX_LAYERS entries, entry k * MOBOCMF_RFF_MAX_LAYERS + l = layer l of sample k (kind 0 for l = 0, kind 1
+ * above it, kind -1 after the top layer; the formulas, operand shapes and scales of mobocmf_rff_eval, operands at the given
+ * offsets into params).  A layer whose operands do not lie inside params_len doubles writes NaN for its sample.  Deterministic
+ * (no atomics): two launches give bitwise identical output. */
+#define MOBOCMF_RFF_MAX_LAYERS 3
+typedef struct mobocmf_rff_layer_desc {
+    int32_t kind;                       /* 0, 1, or -1 = no such layer */
+    int32_t F;                          /* features */
+    int64_t W1, b1, theta, Wf, W2, b2;  /* offsets (doubles) into params: W1 / W2 [F x d], b1 / b2 / Wf [F], theta [F] or [3F] */
+    double s0, s1, s2;                  /* the scales of mobocmf_rff_eval */
+} mobocmf_rff_layer_desc;
+int mobocmf_rff_eval_chains(int32_t K, int32_t d, int64_t n, const double* x, const double* params, int64_t params_len,
+                            const mobocmf_rff_layer_desc* desc, double* out, mobocmf_stream_t stream);
+
+/* Feasibility of grid rows under K_con sampled constraints (MOOP.find_feasible_grid): vals [K_con x n] with row stride ldv
+ * (>= n), thr [K_con]; slack = vals[c][i] - thr[c].  ok[i] = 1 if every slack >= 0 else 0; viol[i] = sum_c min(slack, 0)
+ * summed in the order c = 0, 1, ... */
+int mobocmf_rff_feasibility(int32_t K_con, int64_t n, const double* vals, int64_t ldv, const double* thr, int32_t* ok,
+                            double* viol, mobocmf_stream_t stream);
+
 /* f~[n] = mean[n/div] + sqrt(var[n/div]) * eps[n],  n < n_out  (mfdgp_hidden_layer.py:263-274). */
 int mobocmf_propagate_forward(const double* mean, const double* var, const double* eps, double* f_out, int64_t n_out,
                               int32_t div, mobocmf_stream_t stream);

@@ -72,6 +72,17 @@ class TinyCoupling(ctypes.Structure):
                 ("reserved", ctypes.c_int32)]
 
 
+RFF_MAX_LAYERS = 3        # MOBOCMF_RFF_MAX_LAYERS
+
+
+class RffLayerDesc(ctypes.Structure):
+    """mobocmf_rff_layer_desc: one layer of one chain sample of mobocmf_rff_eval_chains (the kernel reads the table from
+    DEVICE memory)."""
+    _fields_ = [("kind", ctypes.c_int32), ("F", ctypes.c_int32), ("W1", ctypes.c_int64), ("b1", ctypes.c_int64),
+                ("theta", ctypes.c_int64), ("Wf", ctypes.c_int64), ("W2", ctypes.c_int64), ("b2", ctypes.c_int64),
+                ("s0", ctypes.c_double), ("s1", ctypes.c_double), ("s2", ctypes.c_double)]
+
+
 class MobocmfError(RuntimeError):
     pass
 
@@ -141,6 +152,8 @@ SYMBOLS = {
     "mobocmf_coop_work_bytes": [ctypes.POINTER(TinyModel), ctypes.POINTER(_SZ)],
     "mobocmf_coop_elbo_step": [_P, _P, _I32, _I32, _P, _D, _D, _D, _D, _I32, ctypes.POINTER(_I32), _P],
     "mobocmf_rff_eval": [_I32, _I32, _I32, _I64] + [_P] * 8 + [_D, _D, _D, _P, _P],
+    "mobocmf_rff_eval_chains": [_I32, _I32, _I64, _P, _P, _I64, _P, _P, _P],
+    "mobocmf_rff_feasibility": [_I32, _I64, _P, _I64, _P, _P, _P, _P],
     "mobocmf_gram_forward": [_I32, _I32, _P, _P, _I64, _P, _P, _I64, _P, _P, _I64, _P],
     "mobocmf_check_info": [_P, ctypes.POINTER(_I32), _P],
 }

@@ -119,6 +119,15 @@ class JESMOC_MFDGP:
             self.costs_blackboxes[n_f] = {"total": 0.0}
 
     def add_blackbox(self, fidelity, blackbox_name, cost_evaluation=1.0, is_constraint=False):
+        """Registers a black-box's acquisition at ``fidelity`` and adds its cost to the fidelity's total.  Black-boxes
+        sharded over ranks: every rank adds EVERY black-box, so that all ranks weigh the fidelities by the same totals; a
+        black-box another rank holds only has its cost recorded here (returns None)."""
+        held = self.blackbox_mfdgp_fitter_uncond.mfdgp_handlers_cons if is_constraint else \
+            self.blackbox_mfdgp_fitter_uncond.mfdgp_handlers_objs
+        if blackbox_name not in held and not parallel._no_group():
+            self.costs_blackboxes[fidelity]["total"] += cost_evaluation
+            self.costs_blackboxes[fidelity][blackbox_name] = cost_evaluation
+            return None
         mfdgp_uncond = self.blackbox_mfdgp_fitter_uncond.get_model(blackbox_name, is_constraint=is_constraint)
         mfdgp_cond = self.blackbox_mfdgp_fitter_cond.get_model(blackbox_name, is_constraint=is_constraint)
         jes_mfdgp = _JES_MFDGP(fidelity, mfdgp_uncond, mfdgp_cond)
@@ -228,6 +237,11 @@ class JESMOC_MFDGP:
             if best is None or best[0] < w:
                 best = (w, cand, fidelity)
         w, cand, fidelity = best
+        if not parallel._no_group():     # sharded: every rank returns rank 0's choice (ties may break by an ulp)
+            dec = torch.cat([cand.reshape(-1).detach().double(), torch.tensor([float(fidelity)], dtype=torch.float64,
+                                                                             device=cand.device)])
+            parallel.broadcast_(dec, 0)
+            cand, fidelity = dec[:-1].reshape(cand.shape).to(cand.dtype), int(dec[-1])
         if verbose:
             print("Iter:", iteration, "Acquisition:", float(w * self.costs_blackboxes[fidelity]["total"]),
                   " Evaluating fidelity", fidelity, "at", cand[0].cpu().numpy())

@@ -1408,6 +1408,70 @@ def rff_eval(kind, x, fprev, W1, b1, Wf, W2, b2, theta, s0, s1=0.0, s2=0.0):
     return out
 
 
+def rff_eval_chains(x, params, layers):
+    """K chain samples at the rows of ``x`` (n, d) on the GPU in one launch (mobocmf_rff_eval_chains) -> (K, n).  ``params``:
+    1-D float64 device tensor holding every sample's operands; ``layers``: per sample, the list of its layers (layer 0 first),
+    each a dict with kind, F, the offsets W1 / b1 / theta (and Wf / W2 / b2 for kind 1) into ``params`` and the scales
+    s0 / s1 / s2 of ``rff_eval``.  The shapes are checked here, on the host.  No autograd."""
+    lib = _lib.require_device()
+    Lmax = _lib.RFF_MAX_LAYERS
+    with torch.no_grad():
+        x, params = _prep(x.detach()), _prep(params.detach())
+        if x.dim() != 2 or params.dim() != 1 or params.device != x.device:
+            raise _lib.MobocmfError("rff_eval_chains: x must be (n, d) and params 1-D, on one device")
+        n, d = x.shape
+        K, plen = len(layers), params.numel()
+        if not 1 <= K <= 65535 or n < 1 or not 1 <= d <= _lib.MAX_D or plen < 1:
+            raise _lib.MobocmfError("rff_eval_chains: shape mismatch")
+        tab = (_lib.RffLayerDesc * (K * Lmax))()
+        for k, chain in enumerate(layers):
+            if not 1 <= len(chain) <= Lmax:
+                raise _lib.MobocmfError("rff_eval_chains: a chain sample has 1..%d layers" % Lmax)
+            for l in range(Lmax):
+                e = tab[k * Lmax + l]
+                if l >= len(chain):
+                    e.kind = -1
+                    continue
+                L = chain[l]
+                kind, Fn = int(L["kind"]), int(L["F"])
+                if kind != (0 if l == 0 else 1) or Fn < 1:
+                    raise _lib.MobocmfError("rff_eval_chains: layer 0 is kind 0, the layers above it kind 1")
+                need = {"W1": Fn * d, "b1": Fn, "theta": Fn if kind == 0 else 3 * Fn}
+                if kind == 1:
+                    need.update({"Wf": Fn, "W2": Fn * d, "b2": Fn})
+                for name, cnt in need.items():
+                    off = int(L[name])
+                    if off < 0 or off + cnt > plen:
+                        raise _lib.MobocmfError("rff_eval_chains: operand %s of sample %d layer %d lies outside params"
+                                                % (name, k, l))
+                    setattr(e, name, off)
+                e.kind, e.F = kind, Fn
+                e.s0, e.s1, e.s2 = float(L["s0"]), float(L.get("s1", 0.0)), float(L.get("s2", 0.0))
+        desc = torch.frombuffer(bytearray(bytes(tab)), dtype=torch.uint8).to(x.device)
+        out = _empty(K, n, device=x.device)
+        _lib.check(lib.mobocmf_rff_eval_chains(K, d, n, _ptr(x), _ptr(params), plen, _ptr(desc), _ptr(out), _stream()),
+                   "mobocmf_rff_eval_chains")
+    return out
+
+
+def rff_feasibility(vals, thr):
+    """Feasibility of the columns of ``vals`` (K_con, n) -- constraint samples on a grid -- under thresholds ``thr`` (K_con,)
+    (mobocmf_rff_feasibility, the rule of MOOP.find_feasible_grid): (ok (n,) bool, every slack >= 0; violation (n,) float64,
+    sum of min(slack, 0))."""
+    lib = _lib.require_device()
+    with torch.no_grad():
+        if vals.dim() != 2 or vals.shape[0] < 1 or vals.shape[1] < 1 or thr.numel() != vals.shape[0] \
+                or thr.device != vals.device:
+            raise _lib.MobocmfError("rff_feasibility: shape mismatch")
+        vals, thr = _prep(vals.detach()), _prep(thr.detach().reshape(-1))
+        K, n = vals.shape
+        ok = torch.empty(n, dtype=torch.int32, device=vals.device)
+        viol = _empty(n, device=vals.device)
+        _lib.check(lib.mobocmf_rff_feasibility(K, n, _ptr(vals), n, _ptr(thr), _ptr(ok), _ptr(viol), _stream()),
+                   "mobocmf_rff_feasibility")
+    return ok.bool(), viol
+
+
 # ------------------------------------------------------------------------------------------------------------
 # Exact-GP comparison baselines (SURVEY 8(f) N4) on the layer's kernels: Gram (mobocmf_gram_forward), the multi-fidelity
 # combination, the blocked Cholesky + triangular inverse of the chain, the triangular MFMA product with column statistics.

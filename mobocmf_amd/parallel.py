@@ -1,6 +1,7 @@
 """Multi-GPU layout of the path: one process per GPU, independent surrogates sharded over the
 ranks with no data-path collective, and ONE all-gather (RCCL over xGMI; gloo on CPU for tests) per exchange
-point: the per-output posterior moments for the joint acquisition (JESMOC_MFDGP.py:125-135).
+point: the per-output posterior moments for the joint acquisition (JESMOC_MFDGP.py:125-135), the omega-factor moments
+of the conditioned training, and the packed posterior function samples of the Pareto solution (``all_gather_samples``).
 
 Payloads are tiny (<= 0.6 MB), i.e. latency-bound: a single all-gather on the default communicator is the
 whole collective; there is nothing to bucket or overlap.
@@ -227,6 +228,73 @@ def coupled_acquisition(local_acq):
     return torch.cat(all_gather_ragged(local_acq), 0).sum(0)
 
 
+def _exchange_device():
+    """Where a host-built payload travels: the current GPU for RCCL, the host for gloo."""
+    import torch.distributed as dist
+    return torch.device("cuda", torch.cuda.current_device()) if dist.get_backend() == "nccl" else torch.device("cpu")
+
+
+def all_gather_samples(local_bufs, local_indices, roles=None, check=0, local_error=None):
+    """Third exchange point: the packed posterior function samples (``layers.rff.RFFChainSample.pack``) of the black-boxes of
+    every rank, for the Pareto solution of the sampled problem, which needs ALL of them on every rank.
+
+    ``local_bufs``: this rank's 1-D float64 buffers (any number, 0 included); ``local_indices``: the global index of each;
+    ``roles`` (optional): an int per buffer (0 = objective, 1 = constraint), the indices then count per role.  Returns the
+    buffers of all black-boxes in global order -- with ``roles``, one such list per role -- each at its own length (rows
+    travel padded; the row's length field cuts the padding off, the packed header repeats it).  Two ``all_gather_ragged`` calls: one row of metadata per rank (count, longest buffer, malformed arguments,
+    ``check``, ``local_error``), then the buffers padded to the longest one of all ranks, with index, role and real length in
+    front.
+    Every rank enters both, whatever it holds; duplicated or missing indices, ``check`` values (e.g. a hash of the training
+    inputs) that differ between ranks, and a rank reporting ``local_error`` raise the same error on EVERY rank after the
+    collectives, never before (the rule of ``_gather_plan``).
+
+    Payload per black-box of L layers: 5 + 8 L + F (d + 2) + (L - 1) F (2 d + 6) doubles (``rff.packed_length``), about
+    F (d + 2) + F (2 d + 6) for two layers: 128 KB at F = 500, d = 8.  Without a process group: the identity (same checks)."""
+    bufs = [torch.as_tensor(b, dtype=torch.float64).detach().reshape(-1).cpu() for b in local_bufs]
+    idx = [int(i) for i in local_indices]
+    rl = [0] * len(bufs) if roles is None else [int(r) for r in roles]
+    bad = int(len(idx) != len(bufs) or len(rl) != len(bufs) or any(r not in (0, 1) for r in rl))
+    failed = int(local_error is not None)
+    if _no_group():
+        metas, rows = [(len(bufs), bad, float(check), failed)], None
+        if not bad and not failed:
+            rows = [(i, r, b) for i, r, b in zip(idx, rl, bufs)]
+    else:
+        cdev = _exchange_device()
+        lmax = max([b.numel() for b in bufs], default=0)
+        meta = torch.tensor([[len(bufs), lmax, bad, float(check), failed]], dtype=torch.float64, device=cdev)
+        allmeta = torch.cat(all_gather_ragged(meta), 0).cpu()
+        width = int(allmeta[:, 1].max()) + 3
+        ok_here = not bad and not failed
+        pad = torch.zeros(len(bufs) if ok_here else 0, width, dtype=torch.float64)
+        if ok_here:
+            for q, (i, r, b) in enumerate(zip(idx, rl, bufs)):
+                pad[q, 0], pad[q, 1], pad[q, 2], pad[q, 3:3 + b.numel()] = i, r, b.numel(), b
+        got = [t.cpu() for t in all_gather_ragged(pad.to(cdev))]
+        metas = [(int(m[0]), int(m[2]), float(m[3]), int(m[4])) for m in allmeta]
+        rows = [(int(row[0]), int(row[1]), row[3:3 + int(row[2])]) for t in got for row in t]
+    where = lambda col: [q for q, m in enumerate(metas) if m[col]]
+    if where(3):
+        raise RuntimeError("all_gather_samples: drawing the samples failed on rank(s) %s%s" %
+                           (where(3), "" if local_error is None else ": " + str(local_error)))
+    if where(1):
+        raise ValueError("all_gather_samples: one global index and role (0 / 1) per buffer (violated on rank(s) %s)" % where(1))
+    if len({m[2] for m in metas}) > 1:
+        raise ValueError("all_gather_samples: the ranks disagree on the checked value (%s): different training inputs?" %
+                         [m[2] for m in metas])
+    out = []
+    for role in ((0,) if roles is None else (0, 1)):
+        mine = [(i, b) for i, r, b in rows if r == role]
+        got_idx = sorted(i for i, _ in mine)
+        if got_idx != list(range(len(mine))):
+            raise ValueError("all_gather_samples: global %sindices of all ranks must be a permutation of 0..n-1, got %s" %
+                             ("" if roles is None else ("objective ", "constraint ")[role], [i for i, _ in mine]))
+        ordered = [b for _, b in sorted(mine, key=lambda e: e[0])]
+        out.append([b.clone() for b in ordered])
+    return out[0] if roles is None else out
+
+
+_gather_plans = {}
 _gather_plans = {}
 
 

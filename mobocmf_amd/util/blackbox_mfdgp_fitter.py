@@ -346,14 +346,145 @@ class BlackBoxMFDGPFitter:
         self.set_pareto_solution(pareto_set, pareto_front)
         return self.pareto_set, self.pareto_front, self.samples_objs, self.samples_cons
 
-    def sample_and_store_pareto_solution(self, **kw):
+    def sample_and_store_pareto_solution(self, seed=None, **kw):
+        """Pareto solution of one posterior sample of the problem, stored for the conditioned training.
+
+        Single process, ``seed=None``: the reference's procedure on this process's generators (``nFeatures``, ``generator``,
+        ``rng`` pass through).  With a process group (black-boxes sharded over ranks) or a ``seed``: the seeded joint
+        procedure of ``_sample_and_store_pareto_solution_seeded``, identical on every rank and independent of the sharding;
+        with a group and no seed, rank 0 draws the seed from torch's global generator and broadcasts it."""
+        from .. import parallel
         from .moop import NotFeasiblePoints
+        seeded = seed is not None or not parallel._no_group()
+        if seeded:
+            unknown = set(kw) - {"nFeatures"}
+            if unknown:
+                raise TypeError("seeded Pareto sampling takes nFeatures only (got %s)" % sorted(unknown))
+            if seed is None:
+                dev = parallel._exchange_device()
+                t = torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).to(dev)
+                seed = int(parallel.broadcast_(t, 0).cpu()[0])
+        attempt = 0
         while True:
             try:
+                if seeded:
+                    return self._sample_and_store_pareto_solution_seeded(seed, attempt=attempt, **kw)
                 return self._sample_and_store_pareto_solution(**kw)
             except NotFeasiblePoints:
                 print("Not feasible solution found, trying another time!")
                 sys.stdout.flush()
+                attempt += 1
+
+    # status words of one try of the seeded procedure (rank 0's decides; ERROR anywhere makes every rank raise)
+    _FEASIBLE, _INFEASIBLE, _ERROR = 0, 1, 2
+
+    @staticmethod
+    def _blackbox_generator(seed, role, gi, t):
+        """The generator of black-box (role, global index gi)'s sample in try t: a function of these four numbers only, so
+        the draws do not depend on the rank, the world size or the order the black-boxes are visited in."""
+        import hashlib
+        key = hashlib.sha256(("%d:%s:%d:%d" % (int(seed), role, int(gi), int(t))).encode()).digest()
+        return torch.Generator().manual_seed(int.from_bytes(key[:8], "big") >> 1)
+
+    def _draw_chain_samples(self, seed, t, nFeatures):
+        """This rank's chain samples of try t: (packed buffers, global indices, roles 0 = objective / 1 = constraint)."""
+        from ..layers.rff import sample_chain_from_posterior
+        bufs, idx, roles = [], [], []
+        for tag, i, h in self._handlers():
+            gi = self._global_index(h, i)
+            smp = sample_chain_from_posterior(h.mfdgp, nFeatures=nFeatures,
+                                              generator=self._blackbox_generator(seed, tag, gi, t))
+            bufs.append(smp.pack())
+            idx.append(gi)
+            roles.append(0 if tag == "OBJ" else 1)
+        return bufs, idx, roles
+
+    def _agree(self, code, res, n_obj, d):
+        """One status word per rank, all-gathered; rank 0's result broadcast (row count first, then set and front in one
+        buffer).  Every rank makes the same collective calls whatever happened locally."""
+        from .. import parallel
+        dev = parallel._exchange_device() if not parallel._no_group() else torch.device("cpu")
+        P = int(res[0].shape[0]) if (code == self._FEASIBLE and res is not None) else 0
+        status = torch.cat(parallel.all_gather_ragged(torch.tensor([[float(code), float(P)]], dtype=torch.float64,
+                                                                   device=dev)), 0).cpu()
+        errs = [q for q in range(status.shape[0]) if int(status[q, 0]) == self._ERROR]
+        if errs:
+            return self._ERROR, errs
+        code0, P0 = int(status[0, 0]), int(status[0, 1])
+        if code0 != self._FEASIBLE:
+            return code0, None
+        buf = torch.zeros(P0, d + n_obj, dtype=torch.float64, device=dev)
+        if parallel.world()[0] == 0:
+            buf.copy_(torch.cat([res[0], res[1]], 1).to(dev))
+        parallel.broadcast_(buf, 0)
+        buf = buf.cpu()
+        return code0, (buf[:, :d].clone(), buf[:, d:].clone())
+
+    def _sample_and_store_pareto_solution_seeded(self, seed, nFeatures=500, attempt=0):
+        """The Pareto solution of one joint posterior sample of ALL black-boxes, whichever rank holds them.
+
+        Try t draws every local black-box's chain sample from ``_blackbox_generator(seed, role, global index, t)``, all ranks
+        exchange the packed samples (``parallel.all_gather_samples``, which also checks that every rank has the same
+        training inputs) and unpack all of them -- their own too, so every rank holds identical objects -- then run the same
+        MOOP on the grid of ``np.random.default_rng((seed, t))``.  Rank 0's outcome decides (feasible / next try / after
+        MAX_TRIES_FOR_FEASIBLE_GRID tries the least infeasible points / NotFeasiblePoints) and its set and front are
+        broadcast, so every rank stores bitwise the same solution.  An exception on any rank after the exchange makes every
+        rank raise.  ``samples_objs`` / ``samples_cons`` hold all black-boxes' samples in global order.  Without a process
+        group every exchange is the identity and the result is the same as with the black-boxes split over ranks.
+        ``attempt`` (the retries after NotFeasiblePoints) moves the tries to fresh numbers."""
+        import hashlib
+        from .. import parallel
+        from ..layers.rff import RFFChainSample
+        from .moop import MOOP, NotFeasiblePoints
+        inputs = np.ascontiguousarray(self.x_train.detach().cpu().double().numpy())
+        d = inputs.shape[1]
+        xhash = float(int.from_bytes(hashlib.sha256(inputs.tobytes() + str(inputs.shape).encode()).digest()[:6], "big"))
+        thr_src = self.thresholds_cons_global if self.thresholds_cons_global is not None else self.thresholds_cons
+        feasible = -1.0 * thr_src.detach().cpu().double().numpy()
+        dev = torch.device(self.device)
+        sample_dev = dev if dev.type == "cuda" else None
+        tries = MFDGPHandler.MAX_TRIES_FOR_FEASIBLE_GRID
+        t0 = attempt * tries
+        optimizer, objs, cons = None, None, None
+        for t in range(t0, t0 + tries + 1):
+            fallback = t == t0 + tries          # the least infeasible points of the last try's samples
+            if not fallback:
+                err = None
+                try:
+                    bufs, idx, roles = self._draw_chain_samples(seed, t, nFeatures)
+                except Exception as e:          # said inside the exchange: the peers must not wait in it
+                    err, bufs, idx, roles = e, [], [], []
+                allo, allc = parallel.all_gather_samples(bufs, idx, roles=roles, check=xhash, local_error=err)
+            code, res, local_exc = self._ERROR, None, None
+            try:
+                if not fallback:
+                    objs = [RFFChainSample.unpack(b, sample_dev) for b in allo]
+                    cons = [RFFChainSample.unpack(b, sample_dev) for b in allc]
+                    if len(cons) != feasible.shape[0]:
+                        raise ValueError("%d constraint samples but %d thresholds (sharded black-boxes need "
+                                         "set_global_constraint_thresholds)" % (len(cons), feasible.shape[0]))
+                    optimizer = MOOP(objs, cons, input_dim=d, grid_size=self.opt_grid_size * d,
+                                     pareto_set_size=self.pareto_set_size, feasible_values=feasible,
+                                     rng=np.random.default_rng((int(seed), int(t))))
+                    res = optimizer.compute_pareto_solution_from_samples(inputs)
+                else:
+                    res = optimizer.compute_pareto_solution_from_samples(inputs, allow_negative_constraints=True)
+                code = self._FEASIBLE if res is not None else self._INFEASIBLE
+            except Exception as e:
+                local_exc = e
+            code, out = self._agree(code, res, len(objs) if objs is not None else 0, d)
+            if code == self._ERROR:
+                msg = "Pareto sampling failed on rank(s) %s" % out
+                if local_exc is not None:
+                    raise RuntimeError(msg + ": " + repr(local_exc)) from local_exc
+                raise RuntimeError(msg)
+            if code == self._FEASIBLE:
+                break
+        else:
+            raise NotFeasiblePoints("[ERROR] No feasible points were found in the constraint space! # tries: %d." % tries)
+        self.samples_objs, self.samples_cons = objs, cons
+        self.set_pareto_solution(*out)
+        return self.pareto_set, self.pareto_front, self.samples_objs, self.samples_cons
 
     # ------------------------------------------------------------------ conditioned training (SURVEY row N1)
     def set_pareto_solution(self, pareto_set, pareto_front):

@@ -12,7 +12,10 @@ How it differs inside (results equal the reference's own MOOP, pinned by tests/g
     minimum for two objectives, a chunked sweep against the current front otherwise (the reference culls the full array
     once per surviving point);
   * ``compute_pareto_front_and_set_summary_y_space``: farthest-point selection with an incrementally updated
-    min-distance vector, O(n) memory (the reference builds the n x n distance matrix).
+    min-distance vector, O(n) memory (the reference builds the n x n distance matrix);
+  * when every sample is a ``layers.rff.RFFChainSample`` on one GPU, the grid is uploaded once and all samples are
+    evaluated on it in one launch, the feasibility rule runs there too (``_feasible_grid_batched``); the SLSQP refinements
+    stay on the host.  Other samples take the per-callable path.
 """
 import numpy as np
 import scipy.optimize as spo
@@ -71,6 +74,50 @@ class MOOP:
         for s in slack:
             violation += np.minimum(s, 0.0)
         return grid[violation == np.max(violation[violation != 0]), :]
+
+    # ------------------------------------------------------------------ all samples on the grid in one launch
+    def _batched_device(self):
+        """The GPU every sample lives on when all of them are ``RFFChainSample``s of one GPU, else None (the per-callable
+        path)."""
+        from ..layers.rff import RFFChainSample
+        samples = list(self.samples_objs) + list(self.samples_cons)
+        if not samples or not all(isinstance(s, RFFChainSample) for s in samples):
+            return None
+        devs = {s.device for s in samples}
+        dev = devs.pop() if len(devs) == 1 else None
+        return dev if dev is not None and dev.type == "cuda" else None
+
+    def _feasible_grid_batched(self, grid, dev, allow_negative_constraints):
+        """``find_feasible_grid`` + the objective values on the feasible rows, with the grid uploaded once, every objective
+        and constraint sample evaluated in ONE mobocmf_rff_eval_chains launch and the feasibility rule applied on the device
+        (mobocmf_rff_feasibility); only the objectives' values and the per-row flags come back.  Returns (grid, evals) or
+        (None, None)."""
+        from .. import functional as F
+        samples = list(self.samples_objs) + list(self.samples_cons)
+        n_obj, n_con = len(self.samples_objs), len(self.samples_cons)
+        bufs, layers, base = [], [], 0
+        for smp in samples:
+            b = smp.pack()
+            layers.append(smp.layer_offsets(base))
+            bufs.append(b)
+            base += b.numel()
+        params = torch.cat(bufs).to(dev)
+        xd = torch.from_numpy(np.ascontiguousarray(grid)).to(dev)
+        vals = F.rff_eval_chains(xd, params, layers)
+        obj_vals = vals[:n_obj]
+        if not n_con:
+            return grid, obj_vals.cpu().numpy().T
+        thr = self._thresholds(n_con, self.feasible_values)[:n_con]
+        ok, viol = F.rff_feasibility(vals[n_obj:], torch.from_numpy(np.ascontiguousarray(thr, dtype=np.float64)).to(dev))
+        ok = ok.cpu().numpy()
+        if ok.any():
+            rows = np.flatnonzero(ok)
+        elif not allow_negative_constraints:
+            return None, None
+        else:
+            v = viol.cpu().numpy()
+            rows = np.flatnonzero(v == np.max(v[v != 0]))
+        return grid[rows, :], obj_vals.cpu().numpy().T[rows]
 
     # ------------------------------------------------------------------ constrained optimum of one objective
     def _slsqp(self, obj, cons, x0, tol):
@@ -170,12 +217,18 @@ class MOOP:
         rand = np.random.uniform(size=(n_rand, self.input_dim)) if self.rng is None else \
             self.rng.uniform(size=(n_rand, self.input_dim))
         grid = np.concatenate((rand, inputs))
-        grid = self.find_feasible_grid(self.samples_cons, grid, feasible_values=self.feasible_values,
-                                       allow_negative_constraints=allow_negative_constraints) \
-            if len(self.samples_cons) else grid
-        if grid is None:
-            return None
-        evals = np.stack([np.asarray(obj(grid)).reshape(-1) for obj in self.samples_objs], 1)
+        dev = self._batched_device()
+        if dev is not None:
+            grid, evals = self._feasible_grid_batched(grid, dev, allow_negative_constraints)
+            if grid is None:
+                return None
+        else:
+            grid = self.find_feasible_grid(self.samples_cons, grid, feasible_values=self.feasible_values,
+                                           allow_negative_constraints=allow_negative_constraints) \
+                if len(self.samples_cons) else grid
+            if grid is None:
+                return None
+            evals = np.stack([np.asarray(obj(grid)).reshape(-1) for obj in self.samples_objs], 1)
         extra = []
         for j, obj in enumerate(self.samples_objs):
             opt = self.optimize_obj_globally(obj, self.samples_cons, evals[:, j], grid)
