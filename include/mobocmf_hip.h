@@ -475,15 +475,14 @@ typedef struct mobocmf_tiny_coupling {
     const double* thresholds;                /* n_con */
     double log_eps, log_1m_eps;
     double* losses;                          /* n_con + 1: the theta factor term of every constraint, then the omega term */
-    int64_t* barrier;                        /* device word, zero-initialised ONCE by the caller: arrivals at the in-launch barrier.
-                                              * Monotonic: launch k of the record waits for k * n_models arrivals, so ONE record
-                                              * serves ONE launch at a time (launches of a record are ordered on one stream) and
-                                              * always with the same n_models */
-    int32_t* status;                         /* device word, zero-initialised by the caller, only ever OR'd by the launches:
-                                              * bit 0 a workgroup gave up waiting at the barrier (it left its model untouched),
-                                              * bit 1 the launch did not match the record (n_models, T, P): nothing was updated.
-                                              * Sticky across launches -- the caller reads it whenever it checks (every 1000
-                                              * iterations in the fitter) and clears it after rolling back */
+    int64_t* barrier;                        /* device word: arrivals at the in-launch barrier.  Monotonic: launch k of the record
+                                              * waits for k * n_models arrivals, so ONE record serves ONE launch at a time
+                                              * (launches of a record are ordered on one stream) and always with the same n_models */
+    int32_t* status;                         /* device word, only ever OR'd by the launches: bit 0 a workgroup gave up waiting at
+                                              * the barrier, bit 1 the launch did not match the record (n_models, T, P).  The
+                                              * caller zeroes barrier and status together, once before the first launch and
+                                              * again only after reading a non-zero status (the in-launch wait contract:
+                                              * mobocmf_check_info) */
     int32_t n_models;                        /* workgroups (= models) of the launches this record is for; the kernel checks */
     int32_t reserved;
 } mobocmf_tiny_coupling;
@@ -505,10 +504,11 @@ int mobocmf_tiny_elbo_step(const mobocmf_tiny_model* host_models, const mobocmf_
  * wgs_per_model: workgroups sharing one surrogate, 1..64, or 0 = chosen from the widest phase (at most 32); *wgs_used (may be
  * NULL) receives the choice.  Every workgroup of the launch must be resident at once (n_models * wgs_per_model <= what the
  * device holds of this kernel: checked, MOBOCMF_BAD_ARG otherwise -- an ordinary launch, not a cooperative one, so that it can
- * be captured into a graph).  sync_words: 16 * (n_models + 1) device int64, zero-initialised ONCE by the caller and then left to
- * the launches (monotonic arrival counters: a group of words serves one launch at a time, always with the same wgs_per_model
- * and n_models).  A wait that does not end within ~0.3 s is abandoned: info[0] = -1, out[2] = NaN, nothing is updated by that
- * workgroup. */
+ * be captured into a graph).  sync_words: 16 * (n_models + 1) device int64 -- monotonic arrival counters (a group of words
+ * serves one launch at a time, always with the same wgs_per_model and n_models) and, at word 16 * n_models + 1, the status
+ * word of the in-launch wait contract (mobocmf_check_info; bit 0 a wait gave up, bit 1 mode 4 did not match its coupling
+ * record).  The caller zeroes the block once before the first launch and again only after reading a non-zero status; a
+ * workgroup that gives up also sets info[0] = -1 and out[2] = NaN. */
 #define MOBOCMF_COOP_MAX_M 128
 /* OR'd into do_update 2 or 3 of mobocmf_coop_elbo_step: the parameters are the ones of an earlier launch on the same `work`
  * (an acquisition search against fitted models, JESMOC_MFDGP.py:137-184): K_mm, its Cholesky and inverse, U, a and the KL stay as
@@ -585,9 +585,18 @@ int mobocmf_syrk_weighted_f64(int32_t Mr, int64_t Kd, const double* A, int64_t l
                               const mobocmf_tuning* tuning, mobocmf_stream_t stream);
 
 /* Host-side, synchronising: copies the device word and returns MOBOCMF_OK or MOBOCMF_NOT_PD (pivot in *pivot: the 1-based
- * column of the first non-positive pivot; -1 = a one-launch form -- the cooperative step, the one-launch Cholesky
- * (mobocmf_tuning.potrf_cols = 0) -- abandoned a bounded in-launch wait because its workgroups were not resident together:
- * the results of that call are invalid, repeat it with less concurrent work or with the launch-per-step form). */
+ * column of the first non-positive pivot; -1 = a one-launch form abandoned a bounded in-launch wait because its workgroups
+ * were not resident together: the results of that call are invalid, repeat it with less concurrent work or with the
+ * launch-per-step form).
+ * The in-launch wait contract of the one-launch forms (the one-launch Cholesky, mobocmf_tuning.potrf_cols = 0; the cooperative
+ * step; mode 4 of mobocmf_tiny_elbo_step): they are ordinary launches whose workgroups wait for each other, so the host checks
+ * that all of them are resident at once, and every wait is bounded by 1 s of the device's wall clock.  A give-up is reported
+ * only by an atomic OR into a status word, which no later workgroup or launch clears, and every wait releases only while that
+ * word is zero.  Where the counters persist across launches (sync_words of mobocmf_coop_elbo_step, the barrier / status of
+ * mobocmf_tiny_coupling) every later wait then fails at its first poll, so nothing commits parameters, optimiser state, step
+ * counts or random streams until the caller has read the status and zeroed counters and status together.  The one-launch
+ * Cholesky zeroes its words before every launch; its closing launch turns a set status into info = -1 and NaN on the diagonals
+ * of the factor and of the inverse, so that anything computed from them is non-finite even after info is rewritten. */
 int mobocmf_check_info(const int32_t* info, int32_t* pivot, mobocmf_stream_t stream);
 
 #ifdef __cplusplus

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Builds libmobocmf_hip.so for gfx950 (cross-compiles without a GPU).
-# An object is reused only when the hash of everything that went into it -- compiler version, flags, its source, common.h
+# An object is reused only when the hash of everything that went into it -- compiler version, flags, its source, the shared headers
 # and the public header -- equals the stamp written next to it (file times say nothing after a checkout or a flag
 # change).  `build.sh -B` rebuilds everything.
 set -e
@@ -13,7 +13,7 @@ ccver=$($HIPCC --version 2>/dev/null | sha256sum | cut -c1-16)
 objs=""
 pids=""
 for f in gemm_f64 chol gram elementwise rff tiny_step coop_step api; do
-  want=$( (echo "$ccver $FLAGS"; cat $f.hip common.h small_step_common.h tile16.h ../../include/mobocmf_hip.h) | sha256sum | cut -c1-32)
+  want=$( (echo "$ccver $FLAGS"; cat $f.hip common.h inlaunch.h small_step_common.h tile16.h ../../include/mobocmf_hip.h) | sha256sum | cut -c1-32)
   have=$(cat $f.o.stamp 2>/dev/null || true)
   if [ $force = 1 ] || [ ! -f $f.o ] || [ "$want" != "$have" ]; then
     rm -f $f.o $f.o.stamp           # a failed compile must not leave a stale object for the link step

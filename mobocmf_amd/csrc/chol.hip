@@ -7,8 +7,8 @@
 // blocked triangular inverse).  The trailing update A22 -= L21 L21^T runs on the f64 MFMA.
 // Reference behaviour replaced: gpytorch psd_safe_cholesky(K_mm) -> torch.linalg.cholesky_ex.
 #include "common.h"
+#include "inlaunch.h"
 #include "tile16.h"
-#include <atomic>
 #include <cstdlib>
 
 typedef double v4f64 __attribute__((ext_vector_type(4)));
@@ -451,63 +451,16 @@ __global__ __launch_bounds__(256) void syrk64_update_kernel(double* A, int64_t l
 // the rest of step jb meanwhile (X: the panel blocks below and the update of column jb + 1, Y: the update of the columns beyond),
 // and the INVERSE workgroups form L^-1 block row by block row behind them.  Hand-over is by monotonic words per layer (zeroed
 // before the launch): `f` (steps published by the panel workgroup), `pri` (look-ahead blocks of the next step updated), `xd`
-// (panel column complete), and an arrival counter per group.  Every wait is bounded: a workgroup that gives up writes info = -1
-// and leaves, and so do its peers.
+// (panel column complete), and an arrival counter per group.  Every wait is bounded (inlaunch.h): a workgroup that gives up ORs
+// the layer's status word and leaves, and so do its peers at their next wait; finish_l_kernel turns the word into info = -1
+// and a NaN diagonal.
 // Replaces the launch pair potrf_panel4_kernel + syrk64_update_kernel per 64 columns (launch_potrf_z below).
 #define PC_T 512
-#define PC_SPIN (1 << 22)
 #define PC_S (NB * LD64)
 #define PC_LDS_DOUBLES (4 * PC_S)      // the others' four dense blocks; the panel workgroup's 62 tiles (15 872 doubles) fit in it
 #define PC_WORDS 8                     // sync words per layer
+#define PC_STATUS 6                    // ... the one of them that holds the layer's status (inlaunch.h: only ever OR'd)
 
-__device__ __forceinline__ bool pc_wait_ge(unsigned long long* w, unsigned long long target, int* flag_lds) {
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int spins = 0, ok = 1;
-        while (__hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < target) {
-            __builtin_amdgcn_s_sleep(2);
-            if (++spins > PC_SPIN) { ok = 0; break; }
-        }
-        __threadfence();
-        *flag_lds = ok;
-    }
-    __syncthreads();
-    return *flag_lds != 0;
-}
-// publish what the workgroup wrote so far: all its stores are issued (barrier), then one agent-scope release by thread 0
-__device__ __forceinline__ void pc_signal_store(unsigned long long* w, unsigned long long v) {
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        __threadfence();
-        __hip_atomic_store(w, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-}
-__device__ __forceinline__ void pc_signal_add(unsigned long long* w) {
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        __threadfence();
-        atomicAdd(w, 1ull);
-    }
-}
-__device__ __forceinline__ bool pc_barrier(unsigned long long* cnt, unsigned n, int* flag_lds) {
-    __syncthreads();
-    if (n > 1) {
-        if (threadIdx.x == 0) {
-            __threadfence();
-            const unsigned long long old = atomicAdd(cnt, 1ull), target = (old / n + 1ull) * n;
-            int spins = 0, ok = 1;
-            while (__hip_atomic_load(cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < target) {
-                __builtin_amdgcn_s_sleep(2);
-                if (++spins > PC_SPIN) { ok = 0; break; }
-            }
-            __threadfence();
-            *flag_lds = ok;
-        }
-        __syncthreads();
-        return *flag_lds != 0;
-    }
-    return true;
-}
 #ifdef PC_STAMPS
 // diagnostic build (tools/build_variant.sh pcstamps -DPC_STAMPS; tools/chol_stamps.py): wall-clock stamps of the panel workgroup
 __device__ double pc_stamp_buf[1024];
@@ -630,7 +583,8 @@ __device__ __forceinline__ void pc_tasks(int first, int ntask, int step, GetTask
 }
 
 __global__ __launch_bounds__(PC_T) void potrf_coop_kernel(double* A, int64_t ld, int nreal, double* Dinv, double* Ld, InfoZ infoz,
-                                                           int64_t zs, unsigned long long* sync, double* Linv, int nblk, int NT) {
+                                                           int64_t zs, unsigned long long* sync, double* Linv, int nblk, int NT,
+                                                           uint64_t ticks) {
     extern __shared__ __attribute__((aligned(16))) double pc_lds[];
     __shared__ int flag, giveup;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -644,6 +598,7 @@ __global__ __launch_bounds__(PC_T) void potrf_coop_kernel(double* A, int64_t ld,
     unsigned long long* const BART = F + 2;      // barrier of the trailing workgroups
     unsigned long long* const XD = F + 3;        // steps whose panel L[:, jb] is complete
     unsigned long long* const BARI = F + 4;      // barrier of the inverse workgroups
+    unsigned* const status = (unsigned*)(F + PC_STATUS);
     if (tid == 0) giveup = 0;
 #ifdef PC_STAMPS
     int nst = 0;
@@ -667,15 +622,10 @@ __global__ __launch_bounds__(PC_T) void potrf_coop_kernel(double* A, int64_t ld,
             // wavefronts 4-7: the next block row's two blocks, as soon as the other workgroups are through with them
             auto try_fetch = [&](bool block) {
                 if (fetched) return;
-                bool ready = jb == 0;
-                if (!ready) {
-                    int spins = 0;
-                    for (;;) {
-                        ready = __hip_atomic_load(PRI, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= target;
-                        if (ready || !block) break;
-                        __builtin_amdgcn_s_sleep(2);
-                        if (++spins > PC_SPIN) { giveup = 1; break; }
-                    }
+                bool ready = jb == 0 || il_poll_ge(PRI, target);
+                if (!ready && block) {
+                    ready = il_spin_ge<2>(PRI, target, status, ticks);
+                    if (!ready) giveup = 1;
                 }
                 if (ready) {
                     __threadfence();
@@ -775,7 +725,7 @@ __global__ __launch_bounds__(PC_T) void potrf_coop_kernel(double* A, int64_t ld,
             }
             __syncthreads();
             if (giveup) {
-                if (tid == 0) *info = -1;
+                if (tid == 0) il_abandon(status, 1);
                 return;
             }
             PCSTAMP(3);
@@ -797,7 +747,7 @@ __global__ __launch_bounds__(PC_T) void potrf_coop_kernel(double* A, int64_t ld,
             }
             PCSTAMP(4);
             if (!need) {
-                if (Linv) pc_signal_store(F, (unsigned long long)(jb + 1));      // (the others invert the last block row)
+                if (Linv) il_publish_store(F, (unsigned long long)(jb + 1));      // (the others invert the last block row)
                 break;
             }
             // (D) look-ahead: L[jb+1, jb] = A[jb+1, jb] L_jj^-T, tile (a, tj) from the k tiles <= tj (the inverse is lower triangular);
@@ -911,15 +861,12 @@ __global__ __launch_bounds__(PC_T) void potrf_coop_kernel(double* A, int64_t ld,
 #pragma unroll
                     for (int r = 0; r < 4; ++r)
                         ((pc_gw)Pi)[(int64_t)(wr * 32 + t * 16 + lk + 4 * r) * ld + 2 * NB + wc * 16 + li] = cd[t][r] - acc[t][r];
-                pc_signal_store(PRI, (unsigned long long)(jb + 1));
+                il_publish_store(PRI, (unsigned long long)(jb + 1));
             }
             __syncthreads();
         };
         for (int jb = 0; jb + 2 < nreal; ++jb) {
-            if (!pc_wait_ge(F, (unsigned long long)(jb + 1), &flag)) {
-                if (tid == 0) *info = -1;
-                return;
-            }
+            if (!il_wait_ge<2>(F, (unsigned long long)(jb + 1), status, ticks, &flag)) return;
             const int64_t j0 = (int64_t)jb * NB;
             pc_load64(S1, Dinv + (int64_t)jb * NB * NB, NB, tid);
             pc_load64(S2, A + (int64_t)(jb + 1) * NB * ld + j0, ld, tid);
@@ -930,11 +877,8 @@ __global__ __launch_bounds__(PC_T) void potrf_coop_kernel(double* A, int64_t ld,
             } else {
                 for (int i = jb + 3 + tw - 1; i < nreal; i += NR) do_row(jb, i, false);
             }
-            if (!pc_barrier(BART, (unsigned)NT, &flag)) {
-                if (tid == 0) *info = -1;
-                return;
-            }
-            if (tw == 0 && NI > 0) pc_signal_store(XD, (unsigned long long)(jb + 1));      // (every L[i, jb] is written: the barrier)
+            if (!il_barrier<2>(BART, (unsigned)NT, status, ticks, &flag)) return;
+            if (tw == 0 && NI > 0) il_publish_store(XD, (unsigned long long)(jb + 1));      // (every L[i, jb] is written: the barrier)
             // Y, column by column: task u of the packed lower triangle of order nrem.  Task 0 -- block (jb+2, jb+2) -- is done;
             // tasks 1 and nrem -- (jb+3, jb+2), (jb+3, jb+3) -- are the first workgroup's, the rest the others'
             const int nrem = nreal - jb - 2, ntr = nrem * (nrem + 1) / 2;
@@ -956,10 +900,8 @@ __global__ __launch_bounds__(PC_T) void potrf_coop_kernel(double* A, int64_t ld,
                 if (NR == 0) pc_tasks<true>(0, ntr - nspecial, 1, rest_task, -1.0, S0, S3, tid, wr, wc, lane);
             } else {
                 pc_tasks<true>(tw - 1, ntr - nspecial, NR, rest_task, -1.0, S0, S3, tid, wr, wc, lane);
-                if (jb + 3 < nreal && !pc_barrier(BART + 3, (unsigned)NR, &flag)) {      // this step's Y before the next step's X
-                    if (tid == 0) *info = -1;
+                if (jb + 3 < nreal && !il_barrier<2>(BART + 3, (unsigned)NR, status, ticks, &flag))      // this step's Y before the next step's X
                     return;
-                }
             }
         }
         return;
@@ -982,16 +924,11 @@ __global__ __launch_bounds__(PC_T) void potrf_coop_kernel(double* A, int64_t ld,
             g[(int64_t)r * ldi + c] = eye && r == c ? 1.0 : 0.0;
         }
     }
-    if (!pc_barrier(BARI, (unsigned)NI, &flag)) {
-        if (tid == 0) *info = -1;
-        return;
-    }
+    if (!il_barrier<2>(BARI, (unsigned)NI, status, ticks, &flag)) return;
     for (int jb = 0; jb < nreal; ++jb) {
-        if (!pc_wait_ge(F, (unsigned long long)(jb + 1), &flag) ||
-            (jb + 2 < nreal && !pc_wait_ge(XD, (unsigned long long)(jb + 1), &flag))) {
-            if (tid == 0) *info = -1;
+        if (!il_wait_ge<2>(F, (unsigned long long)(jb + 1), status, ticks, &flag) ||
+            (jb + 2 < nreal && !il_wait_ge<2>(XD, (unsigned long long)(jb + 1), status, ticks, &flag)))
             return;
-        }
         const int64_t j0 = (int64_t)jb * NB;
         pc_load64(S1, Dinv + (int64_t)jb * NB * NB, NB, tid);
         __syncthreads();
@@ -1018,10 +955,7 @@ __global__ __launch_bounds__(PC_T) void potrf_coop_kernel(double* A, int64_t ld,
             }
         }
         if (jb + 1 == nreal) break;
-        if (!pc_barrier(BARI, (unsigned)NI, &flag)) {
-            if (tid == 0) *info = -1;
-            return;
-        }
+        if (!il_barrier<2>(BARI, (unsigned)NI, status, ticks, &flag)) return;
         // Zu: S_ic += L[i, jb] X[jb, c], i > jb, c <= jb
         const int nc = jb + 1, ntask = (nreal - jb - 1) * nc;
         pc_tasks<false>(iw, ntask, NI,
@@ -1031,10 +965,7 @@ __global__ __launch_bounds__(PC_T) void potrf_coop_kernel(double* A, int64_t ld,
                                           Linv + (int64_t)i * NB * ldi + (int64_t)c * NB, ldi};
                         },
                         1.0, S0, S3, tid, wr, wc, lane);
-        if (!pc_barrier(BARI, (unsigned)NI, &flag)) {
-            if (tid == 0) *info = -1;
-            return;
-        }
+        if (!il_barrier<2>(BARI, (unsigned)NI, status, ticks, &flag)) return;
     }
 }
 
@@ -1056,14 +987,27 @@ int launch_tril_inplace(double* A, int64_t ld, int n, hipStream_t s) {
 // buffers the triangular inverse and U = L^-1 L_S fill only on and below the block diagonal (no separate zero launches)
 // Diagonal blocks >= nreal lie entirely in the identity padding of K_mm (no panel touched them): their Ld / Dinv blocks are
 // set to the identity HERE (round 3: a launch of their own) and the diagonal of A with them.
+// After the one-launch form (sync: its words, else null) a layer whose status word is set was abandoned: info[z] <- -1 and NaN
+// on the diagonals of the factor, of Dinv and of the inverse the launch formed (Linv, ld n, may be null), so that whatever is
+// computed from them is not finite even after a later call has rewritten info.
 __global__ void finish_l_kernel(double* A, int64_t ld, int n, double* Ld, double* Dinv, int nreal, int64_t zs, double* z0,
-                                double* z1) {
+                                double* z1, const unsigned long long* sync, InfoZ infoz, double* Linv) {
     int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= (int64_t)n * n) return;
     A += blockIdx.z * zs; Ld += blockIdx.z * zs; Dinv += blockIdx.z * zs;
     if (z0) z0[blockIdx.z * zs + idx] = 0.0;
     if (z1) z1[blockIdx.z * zs + idx] = 0.0;
     int i = (int)(idx / n), j = (int)(idx % n);
+    if (sync && *(const unsigned*)(sync + blockIdx.z * PC_WORDS + PC_STATUS) != 0) {
+        if (idx == 0) *infoz.p[blockIdx.z] = -1;
+        if (i == j) {
+            const double nan = __builtin_nan("");
+            A[(int64_t)i * ld + i] = nan;
+            Dinv[(int64_t)(i / NB) * NB * NB + (i % NB) * (NB + 1)] = nan;
+            if (Linv) Linv[blockIdx.z * zs + idx] = nan;
+            return;
+        }
+    }
     if (i / NB == j / NB) {
         const int b = i / NB;
         const int64_t e = (int64_t)b * NB * NB + (i % NB) * NB + (j % NB);
@@ -1116,32 +1060,25 @@ int launch_potrf_z(double* A, int64_t ld, int Mp, int M, double* Dinv, double* L
     InfoZ iz = {};
     for (int z = 0; z < nz; ++z) iz.p[z] = info[z];      // (re)set by the first panel
     bool one_launch = false;
+    double* linv = nullptr;       // the inverse the one-launch form formed
     if (sync && tune().potrf_cols == 0 && nreal >= 3 && nreal <= 16) {
         double* Linv = inverse_done && zero0 ? zero0 : nullptr;
         int NT = 1, NI = 0;
         potrf_coop_workgroups(nreal, nz, Linv != nullptr, NT, NI);
         const int G = 1 + NT + NI;
         const size_t shm = (size_t)PC_LDS_DOUBLES * sizeof(double);
-        static std::atomic<uint64_t> granted{0};      // one write-once bit per device: the dynamic-LDS attribute was set there
-        int devid = 0, cus = 0;
-        HIP_TRY(hipGetDevice(&devid));
-        const uint64_t bit = devid >= 0 && devid < 64 ? 1ull << devid : 0ull;
-        if (!(granted.load() & bit)) {
-            HIP_TRY(hipFuncSetAttribute((const void*)potrf_coop_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-            granted.fetch_or(bit);
-        }
         // every workgroup of the launch waits for its peers inside the launch: all of them must be resident at once (an
         // ordinary launch, not a cooperative one: the bound is checked here, the waits inside are bounded)
-        int per_cu = 0;
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)potrf_coop_kernel, PC_T, shm));
-        HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, devid));
-        if (per_cu >= 1 && (int64_t)G * nz <= (int64_t)per_cu * cus) {
+        IlGuard gd;
+        if (const int rc = il_guard((const void*)potrf_coop_kernel, PC_T, shm, (int)shm, gd)) return rc;
+        if ((int64_t)G * nz <= gd.resident) {
             HIP_TRY(hipMemsetAsync(sync, 0, (size_t)potrf_sync_bytes(nz), s));
             hipLaunchKernelGGL(potrf_coop_kernel, dim3(G, nz), dim3(PC_T), shm, s, A, ld, nreal, Dinv, Ld, iz, zs,
-                               (unsigned long long*)sync, Linv, Mp / NB, NT);
+                               (unsigned long long*)sync, Linv, Mp / NB, NT, gd.wait_ticks);
             one_launch = true;
             if (Linv) {
                 *inverse_done = 1;
+                linv = Linv;
                 zero0 = nullptr;      // (written in full by the launch: not cleared below)
             }
         }
@@ -1160,7 +1097,7 @@ int launch_potrf_z(double* A, int64_t ld, int Mp, int M, double* Dinv, double* L
     (void)nblk;
     int64_t n2 = (int64_t)Mp * Mp;
     hipLaunchKernelGGL(finish_l_kernel, dim3((unsigned)((n2 + 255) / 256), 1, nz), dim3(256), 0, s, A, ld, Mp, Ld, Dinv, nreal,
-                       zs, zero0, zero1);
+                       zs, zero0, zero1, one_launch ? (const unsigned long long*)sync : nullptr, iz, linv);
     return hipGetLastError() == hipSuccess ? MOBOCMF_OK : MOBOCMF_HIP_ERROR;
 }
 

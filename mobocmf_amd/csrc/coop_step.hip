@@ -21,9 +21,9 @@
 // Modes (do_update): 0 gradients only, 1 the step, 2 forward only, 3 input gradients (acquisition search: `grad` <- d/dx of the
 // seeded top-layer moments, nothing else written), 4 the conditioned iteration in one launch (all models'
 // workgroups meet once more after the forward and form the theta / omega factor gradients, as tiny_step.hip's mode 4).
-#include <atomic>
 
 #include "common.h"
+#include "inlaunch.h"
 #include "small_step_common.h"
 #include "tile16.h"
 
@@ -37,8 +37,6 @@ constexpr int KSMAX = 8;                         // slabs of the weighted syrk H
 constexpr int XLD = 17;                          // leading dimension of an [Mp][16] column block in LDS
 constexpr int NMAT = 7 + 2 * KSMAX;              // M x M matrices of a layer in `work`
 constexpr int PHEAD = 4;                         // leading scalars of a column block's partial record
-constexpr int SPIN_LIMIT = 1 << 21;      // polls of an in-launch barrier before it is abandoned (~1.5 s): the wait is for peers of the SAME launch,
-                                         // which are resident (checked on the host) -- it ends unless the counters were tampered with
 
 struct CGeom {
     int L, M, Mp, nt, ntri, d, S;
@@ -118,29 +116,6 @@ __device__ __forceinline__ void batched(int n, int tid, LoadF ld, StoreF st) {
 #pragma unroll
         for (int b = 0; b < B; ++b) { const int e = base + b * CT; if (e < n) st(e, v[b]); }
     }
-}
-
-// The in-launch barrier of the k workgroups of one surrogate (or of the whole grid): monotonic arrival counter, agent-scope
-// fences on both sides (L2 write-back before arriving, invalidate after leaving: the workgroups sit on different XCDs).
-// A wait that does not end (a workgroup of the launch not resident) is abandoned: returns false, the caller leaves the kernel.
-__device__ __forceinline__ bool group_barrier(unsigned long long* cnt, unsigned n, int* flag_lds) {
-    __syncthreads();
-    if (n > 1) {
-        if (threadIdx.x == 0) {
-            __threadfence();
-            const unsigned long long old = atomicAdd(cnt, 1ull), target = (old / n + 1ull) * n;
-            int spins = 0, ok = 1;
-            while (__hip_atomic_load(cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < target) {
-                __builtin_amdgcn_s_sleep(2);
-                if (++spins > SPIN_LIMIT) { ok = 0; break; }
-            }
-            __threadfence();
-            *flag_lds = ok;
-        }
-        __syncthreads();
-        return *flag_lds != 0;
-    }
-    return true;
 }
 
 // One 16 x 16 tile of T X for a column block X [k][XLD] in LDS and a matrix T given k-major in global memory (Tk[k * ld + row]
@@ -226,7 +201,8 @@ __device__ __forceinline__ T* uni(T* p) {
 struct Ctx {
     const mobocmf_tiny_model* models;
     double* lds;                        // behind descriptor, geometry and context
-    unsigned long long *mcnt, *gcnt;    // arrival counters: this surrogate's workgroups / the whole grid
+    unsigned long long *mcnt, *gcnt;    // arrival counters: this surrogate's workgroups / the whole grid; gcnt[1]: the launch's
+                                        // status word (inlaunch.h)
     double lr, b1, b2, aeps;
     int k, wj, do_update, n_stamp;
 };
@@ -778,18 +754,19 @@ PHASE_FN void ph_elbo() {
 }
 
 
-PHASE_FN bool ph_couple() {
+PHASE_FN bool ph_couple(uint64_t wait_ticks) {
     CTX_LOCALS;
         // the conditioned iteration in one launch: all models' top-layer moments are in memory; the whole grid meets, the first
         // workgroup of every model forms the theta / omega factor gradients of its model (tiny_step.hip coupling_seeds), the
         // model's workgroups meet again
         const mobocmf_tiny_coupling& cpl = *md.coupling;
+        unsigned* const status = (unsigned*)(cx->gcnt + 1);
         if (cpl.n_models * k != (int)gridDim.x || cpl.T < 1 || cpl.T > 256 || cpl.P < 1) {
-            if (tid == 0 && wj == 0) { atomicOr(cpl.status, 2); md.info[0] = -2; md.out[2] = __builtin_nan(""); }
+            if (tid == 0 && wj == 0) { il_abandon(status, 2); md.info[0] = -2; md.out[2] = __builtin_nan(""); }
             return false;
         }
-        if (!group_barrier(cx->gcnt, gridDim.x, (int*)(sc + 30))) {
-            if (tid == 0 && wj == 0) { atomicOr(cpl.status, 1); md.info[0] = -1; md.out[2] = __builtin_nan(""); }
+        if (!il_barrier<2>(cx->gcnt, gridDim.x, status, wait_ticks, (int*)(sc + 30))) {
+            if (tid == 0 && wj == 0) { md.info[0] = -1; md.out[2] = __builtin_nan(""); }
             return false;
         }
         if (wj == 0) coupling_seeds<CT>(models, md, g.ncol[L - 1], W + g.cpl_off, sc + 16);
@@ -1529,14 +1506,16 @@ PHASE_FN void ph_adam() {
 }
 
 
-#define MODEL_BARRIER(id) do { CSTAMP(id); if (!group_barrier(cx->mcnt, (unsigned)k, (int*)(sc + 30))) { if (tid == 0) { md.info[0] = -1; md.out[2] = __builtin_nan(""); } return; } CSTAMP(99); } while (0)
+// the barrier of the surrogate's k workgroups (inlaunch.h il_barrier; a give-up is in the launch's status word gcnt[1])
+#define MODEL_BARRIER(id) do { CSTAMP(id); if (!il_barrier<2>(cx->mcnt, (unsigned)k, (unsigned*)(cx->gcnt + 1), wait_ticks, (int*)(sc + 30))) { if (tid == 0) { md.info[0] = -1; md.out[2] = __builtin_nan(""); } return; } CSTAMP(99); } while (0)
 
 // PREDICT: the instantiation for an acquisition search (mode 3, and mode 2 with MOBOCMF_STEP_CHAIN_VALID) -- a kernel of its own, so
 // that the training step's kernel carries none of its code (with the input-gradient phases inlined into ONE kernel the training
 // step lost ~1.5 %: 316.5 -> 321.5 us at C2)
 template <bool PREDICT>
 __global__ __launch_bounds__(CT) void coop_step_kernel(const mobocmf_tiny_model* models_, int k_, unsigned long long* sync_words,
-                                                       double lr_, double b1_, double b2_, double aeps_, int do_update_) {
+                                                       double lr_, double b1_, double b2_, double aeps_, int do_update_,
+                                                       uint64_t wait_ticks) {
     extern __shared__ __attribute__((aligned(16))) double lds_all[];
     {
         // the surrogate's descriptor, its geometry and the phases' context: into LDS once (a descriptor field read through the
@@ -1592,7 +1571,7 @@ __global__ __launch_bounds__(CT) void coop_step_kernel(const mobocmf_tiny_model*
         return;
     } else {
     if (do_update == 4) {
-        if (!ph_couple()) return;
+        if (!ph_couple(wait_ticks)) return;
         MODEL_BARRIER(15);
     }
     for (int l = L - 1; l >= 0; --l) {
@@ -1699,19 +1678,10 @@ int mobocmf_coop_elbo_step(const mobocmf_tiny_model* host_models, const mobocmf_
     const size_t shm = coop_lds_bytes(mpmax);
     const bool predict = do_update == 3 || chain_valid;
     const void* kfn = predict ? (const void*)coop_step_kernel<true> : (const void*)coop_step_kernel<false>;
-    static std::atomic<uint64_t> granted[2] = {{0}, {0}};      // one write-once bit per device and instantiation: the dynamic-LDS attribute was set there
-    int devid = 0;
-    HIP_TRY(hipGetDevice(&devid));
-    const uint64_t bit = devid >= 0 && devid < 64 ? 1ull << devid : 0ull;
-    if (shm > 64 * 1024 && !(granted[predict].load() & bit)) {
-        HIP_TRY(hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        granted[predict].fetch_or(bit);
-    }
     // every workgroup of the launch waits for its peers inside the launch: all of them must be resident at once
-    int per_cu = 0, cus = 0;
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kfn, CT, shm));
-    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, devid));
-    const int64_t resident = (int64_t)per_cu * cus;
+    IlGuard gd;
+    if (const int rc = il_guard(kfn, CT, shm, 160 * 1024, gd)) return rc;
+    const int64_t resident = gd.resident;
     int k = wgs_per_model;
     if (k == 0) {
         k = want < 32 ? want : 32;
@@ -1722,10 +1692,10 @@ int mobocmf_coop_elbo_step(const mobocmf_tiny_model* host_models, const mobocmf_
     if (wgs_used) *wgs_used = k;
     if (predict)
         hipLaunchKernelGGL(coop_step_kernel<true>, dim3((unsigned)(n_models * k)), dim3(CT), shm, (hipStream_t)stream, dev_models, k,
-                           (unsigned long long*)sync_words, lr, beta1, beta2, eps, do_update | chain_valid);
+                           (unsigned long long*)sync_words, lr, beta1, beta2, eps, do_update | chain_valid, gd.wait_ticks);
     else
         hipLaunchKernelGGL(coop_step_kernel<false>, dim3((unsigned)(n_models * k)), dim3(CT), shm, (hipStream_t)stream, dev_models, k,
-                           (unsigned long long*)sync_words, lr, beta1, beta2, eps, do_update);
+                           (unsigned long long*)sync_words, lr, beta1, beta2, eps, do_update, gd.wait_ticks);
     return hipGetLastError() == hipSuccess ? MOBOCMF_OK : MOBOCMF_HIP_ERROR;
 }
 

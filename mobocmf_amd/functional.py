@@ -1268,6 +1268,36 @@ class InLaunchWaitAbandoned(FloatingPointError):
     together (too many such launches in flight on the device, or a partition with few CUs).  The call's results are invalid."""
 
 
+class InLaunchSync:
+    """The device words of a one-launch form whose counters persist across launches (the cooperative step, the conditioned
+    iteration): arrival counters and, at ``status_index``, the status word its launches only ever OR (include/mobocmf_hip.h,
+    mobocmf_coop_elbo_step).  Only this owner clears them, all together.  ``stream``: the one the launches run on (None: the
+    current stream)."""
+
+    def __init__(self, words, status_index, stream=None):
+        self.words, self.status_index, self.stream = words, status_index, stream
+
+    def ptr(self, index):
+        return self.words[index].data_ptr()
+
+    def _stream(self):
+        return self.stream if self.stream is not None else torch.cuda.current_stream(self.words.device)
+
+    def check(self, what):
+        """Synchronising: raises InLaunchWaitAbandoned if a launch since the last reset gave up a wait (the words are cleared)."""
+        self._stream().synchronize()
+        st = int(self.words[self.status_index].item())
+        if st:
+            self.reset()
+            raise InLaunchWaitAbandoned("%s: %s (status %d)" % (what, "a workgroup gave up an in-launch wait" if st & 1 else
+                                                                "the launch did not match its coupling record", st))
+
+    def reset(self):
+        """Zeroes the counters and the status word, ordered with the launches on the owner's stream."""
+        with torch.cuda.stream(self._stream()):
+            self.words.zero_()
+
+
 def raise_if_abandoned(pivot, what="Cholesky"):
     """``pivot`` as returned by check_info: -1 is not a failed pivot but an abandoned in-launch wait (include/mobocmf_hip.h,
     mobocmf_check_info)."""

@@ -11,6 +11,7 @@ import ctypes
 import torch
 
 from .. import _lib
+from .. import functional as F
 from . import tiny_step as TS
 
 MAX_COLUMNS = 16384      # rows[l] * S per layer this binding accepts
@@ -52,19 +53,17 @@ class _CoopLaunch:
     def _eligible_conditioned(model, x, fid):
         return eligible(model, x, fid)
 
-    def _sync_words(self):
-        sw = self.__dict__.get("_sync")
-        if sw is None:
-            sw = torch.zeros(16 * (len(self.models) + 1), dtype=torch.int64, device=self.device)
-            self._sync = sw
-            self._order_after_setup()      # (the zero fill runs on the current stream, the launches on self.stream)
-        return sw
+    def _new_sync(self):
+        # per model 16 words (its arrival counter first), then the grid's counter and the launch's status word
+        n = len(self.models)
+        return F.InLaunchSync(torch.zeros(16 * (n + 1), dtype=torch.int64, device=self.device), 16 * n + 1, self.stream)
 
     def _launch(self, mode):
         lib = _lib.require_device()
         used = ctypes.c_int32(0)
         _lib.check(lib.mobocmf_coop_elbo_step(ctypes.cast(self.host, ctypes.c_void_p), ctypes.c_void_p(self._dev_table.data_ptr()),
-                                              len(self.models), int(self.wgs_per_model), ctypes.c_void_p(self._sync_words().data_ptr()),
+                                              len(self.models), int(self.wgs_per_model),
+                                              ctypes.c_void_p(self.in_launch_sync().ptr(0)),
                                               self.lr, self.betas[0], self.betas[1], self.eps, int(mode), ctypes.byref(used),
                                               ctypes.c_void_p(self.stream.cuda_stream)),
                    "mobocmf_coop_elbo_step")
@@ -73,12 +72,6 @@ class _CoopLaunch:
 
 class CoopELBOStep(_CoopLaunch, TS.TinyELBOStep):
     """``step()`` == one full-batch ELBO step of EVERY model of the group, one launch (see ``TinyELBOStep`` for the arguments)."""
-
-    def restore(self):
-        super().restore()
-        # a barrier that was abandoned leaves its arrival counter out of step: start the counters afresh
-        with torch.cuda.stream(self.stream):
-            self._sync_words().zero_()
 
 
 class CoopConditionedStep(_CoopLaunch, TS.TinyConditionedStep):
@@ -95,11 +88,6 @@ class CoopConditionedStep(_CoopLaunch, TS.TinyConditionedStep):
         self._factors()
         self._launch(1)
 
-    def restore(self):
-        super().restore()
-        with torch.cuda.stream(self.stream):
-            self._sync_words().zero_()
-
 
 MAX_PREDICT_COLUMNS = 4096      # T * S per layer beyond which the layer path (frozen chains) is the better search engine
 
@@ -110,14 +98,29 @@ def fits_predict(model, fidelity, T, d):
     return T * S <= MAX_PREDICT_COLUMNS and TS.fits_predict(model, fidelity, T, d, speed_rule=False, max_m=_lib.COOP_MAX_M)
 
 
-class CoopPredictGroup(TS.TinyPredictGroup):
+class CoopPredictGroup(_CoopLaunch, TS.TinyPredictGroup):
     """``TinyPredictGroup`` for mid-size models (32 < M <= 128): predictive moments of several fitted models at the same T test
     points in ONE cooperative launch (mode 2), their gradient w.r.t. the test points in one more (mode 3) -- the acquisition
-    search of the reference's later BO iterations (JESMOC_MFDGP.py:137-184 against M = N = 33 ... 75 surrogates)."""
+    search of the reference's later BO iterations (JESMOC_MFDGP.py:137-184 against M = N = 33 ... 75 surrogates).  A give-up of
+    an in-launch wait is reported by ``thaw()``, at the end of the search."""
     _work_bytes_fn = "mobocmf_coop_work_bytes"
     wgs_per_model = 0
+    lr, betas, eps = 0.0, (0.9, 0.999), 1e-8      # (no update in modes 2 / 3)
     _frozen = False            # inside freeze() ... thaw(): the models' parameters do not change between launches
     _chain_ready = False       # ... and a launch since freeze() has left their chains (L^-1, U, a) in the workspaces
+
+    @property
+    def stream(self):
+        return torch.cuda.current_stream(self.device)
+
+    def _order_after_setup(self):
+        pass      # (the words are zero-filled on the stream the launches run on)
+
+    def _new_sync(self):
+        n = len(self.models)
+        return F.InLaunchSync(torch.zeros(16 * (n + 1), dtype=torch.int64, device=self.device), 16 * n + 1)
+
+    in_launch_sync = TS.TinyELBOStep.in_launch_sync
 
     @staticmethod
     def _fits(model, fidelity, T, d):
@@ -130,20 +133,15 @@ class CoopPredictGroup(TS.TinyPredictGroup):
             self._frozen, self._chain_ready = True, False
 
     def thaw(self):
+        """Ends the search; synchronising: raises InLaunchWaitAbandoned if a launch since the last thaw() gave up a wait (its
+        moments were invalid; the words are cleared, the next search starts afresh)."""
         self._frozen = self._chain_ready = False
+        sync = self.__dict__.get("sync")
+        if sync is not None:
+            sync.check("cooperative predict group")
 
     def _launch(self, mode):
-        lib = _lib.require_device()
-        sw = self.__dict__.get("_sync")
-        if sw is None:
-            sw = self._sync = torch.zeros(16 * (len(self.models) + 1), dtype=torch.int64, device=self.device)
         if self._frozen and self._chain_ready:
             mode = int(mode) | _lib.STEP_CHAIN_VALID
+        super()._launch(mode)
         self._chain_ready = self._frozen
-        used = ctypes.c_int32(0)
-        _lib.check(lib.mobocmf_coop_elbo_step(ctypes.cast(self.host, ctypes.c_void_p), ctypes.c_void_p(self._dev_table.data_ptr()),
-                                              len(self.models), int(self.wgs_per_model), ctypes.c_void_p(sw.data_ptr()),
-                                              0.0, 0.9, 0.999, 1e-8, int(mode), ctypes.byref(used),
-                                              ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)),
-                   "mobocmf_coop_elbo_step")
-        self.wgs_used = used.value

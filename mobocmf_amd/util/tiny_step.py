@@ -12,6 +12,7 @@ import os
 import torch
 
 from .. import _lib
+from .. import functional as F
 from .. import gp
 
 MAX_COLUMNS = 1024      # rows[l] * S per layer: hard limit of this binding
@@ -303,15 +304,32 @@ class TinyELBOStep:
         return self.losses[:, 1]
 
     # ------------------------------------------------------------------ verdicts / roll-back (as GraphedELBOStep)
+    def in_launch_sync(self):
+        """The counters and status word of the launches' in-launch waits (functional.InLaunchSync), made on first use; None
+        for a kernel without such waits."""
+        sync = self.__dict__.get("sync")
+        if sync is None:
+            sync = self.sync = self._new_sync()
+            if sync is not None:
+                self._order_after_setup()      # (zero-filled on the current stream)
+        return sync
+
+    def _new_sync(self):
+        return None
+
     def check(self):
-        """Synchronising: raises if a Cholesky of the last step failed or a loss is not finite."""
+        """Synchronising: raises if a launch since the last check gave up an in-launch wait (functional.InLaunchWaitAbandoned),
+        a Cholesky of the last step failed or a loss is not finite."""
         from ..layers.mfdgp_hidden_layer import NotPSDError
         self.stream.synchronize()
+        sync = self.__dict__.get("sync")
+        if sync is not None:
+            sync.check("one-launch step")
         if bool((self.infos != 0).any()):
             i, l = [int(v) for v in torch.nonzero(self.infos)[0]]
             code = int(self.infos[i, l])
             if code < 0:      # (-1: a workgroup gave up waiting at an in-launch barrier; -2: the launch did not match its coupling record)
-                raise FloatingPointError("one-launch step: in-launch barrier abandoned in model %d (info %d)" % (i, code))
+                raise F.InLaunchWaitAbandoned("one-launch step: in-launch barrier abandoned in model %d (info %d)" % (i, code))
             raise NotPSDError("K_mm not positive definite in model %d layer %d (pivot %d)" % (i, l, code))
         if not bool(torch.isfinite(self.losses).all()):
             raise FloatingPointError("non-finite ELBO")
@@ -323,8 +341,11 @@ class TinyELBOStep:
                           [l._rng(self.device).clone() for m in self.models for l in m._layers()])
 
     def restore(self):
-        """Back to the last snapshot (parameters, optimiser state, eps streams)."""
+        """Back to the last snapshot (parameters, optimiser state, eps streams); the in-launch counters and status start afresh."""
         self.stream.synchronize()
+        sync = self.__dict__.get("sync")
+        if sync is not None:
+            sync.reset()
         ps, ea, eq, steps, rngs = self._snap[:5]
         with torch.no_grad(), torch.cuda.stream(self.stream):      # (ordered with the launches that follow on this stream)
             for p, s0 in zip([p for m in self.models for p in m.parameters()], ps):
@@ -451,10 +472,7 @@ class TinyConditionedStep(TinyELBOStep):
         cp.front, cp.thresholds = front.data_ptr(), thr.data_ptr()
         cp.log_eps, cp.log_1m_eps = log_e, log_1me
         cp.losses = self.factor_losses.data_ptr()
-        self._barrier = torch.zeros(1, dtype=torch.int64, device=self.device)
-        cp.barrier = self._barrier.data_ptr()
-        self._status = torch.zeros(1, dtype=torch.int32, device=self.device)      # sticky: OR'd by the launches, read by check()
-        cp.status = self._status.data_ptr()
+        cp.barrier, cp.status = self._barrier.data_ptr(), self._status.data_ptr()
         cp.n_models = len(self.models)
         self._coupling = torch.frombuffer(bytearray(bytes(cp)), dtype=torch.uint8).to(self.device)
         for k in range(len(self.models)):
@@ -493,18 +511,6 @@ class TinyConditionedStep(TinyELBOStep):
         self._factors()
         self._launch(1)
 
-    def check(self):
-        """As TinyELBOStep.check, plus the sticky status word of the one-launch form: a workgroup that gave up waiting at the
-        in-launch barrier -- in ANY iteration since the last check, not only the last one -- left its model untouched while its
-        peers moved on; that is reported like a failed Cholesky (the fitter rolls back to its last snapshot)."""
-        super().check()
-        st = int(self._status.item())
-        if st:
-            self._status.zero_()
-            raise FloatingPointError("one-launch conditioned iteration: %s (status %d)" %
-                                     ("a workgroup timed out at the in-launch barrier" if st & 1 else
-                                      "the launch did not match its coupling record", st))
-
     def step(self):
         if self.use_graph:
             if self.__dict__.get("_graph") is None:
@@ -536,13 +542,27 @@ class TinyConditionedStep(TinyELBOStep):
         super().snapshot()
         self._snap = self._snap + (None if self.xrng is None else self.xrng.clone(),)
 
+    def _new_sync(self):
+        return F.InLaunchSync(torch.zeros(2, dtype=torch.int64, device=self.device), 1, self.stream)
+
+    @property
+    def _barrier(self):
+        """The coupling record's arrival counter: a view of the word in front of the status word in ``in_launch_sync()``."""
+        sync = self.in_launch_sync()
+        return sync.words[sync.status_index - 1:sync.status_index]
+
+    @property
+    def _status(self):
+        """The coupling record's status word (only ever OR'd by the launches; cleared with the counter by ``sync``)."""
+        sync = self.in_launch_sync()
+        return sync.words[sync.status_index:sync.status_index + 1]
+
     def restore(self):
         super().restore()
         xr = self._snap[-1]
-        with torch.cuda.stream(self.stream):
-            if xr is not None:
+        if xr is not None:
+            with torch.cuda.stream(self.stream):
                 self.xrng.copy_(xr)
-            self._status.zero_()
 
 
 class _TinyMomentsFn(torch.autograd.Function):

@@ -385,6 +385,90 @@ def test_coop_predict_group_matches_predict_for_acquisition_and_its_input_gradie
         assert rel(mus, mt) < 1e-8 and rel(v, vt) < 1e-7 and rel(Xb.grad, Xc.grad) < 1e-6
 
 
+def _state(step):
+    """Everything a step commits: parameters, Adam state, step counts, random streams."""
+    t = [p.detach().clone() for m in step.models for p in m.parameters()] + [x.clone() for x in step.exp_avg]
+    t += [x.clone() for x in step.exp_avg_sq] + [step.steps_done.clone()]
+    t += [l._rng(step.device).clone() for m in step.models for l in m._layers()]
+    return t + ([] if getattr(step, "xrng", None) is None else [step.xrng.clone()])
+
+
+def _abandoned_steps_commit_nothing_and_restore_resumes(step):
+    """With the status word set every barrier fails at its first poll: three steps change nothing (bitwise), check() raises;
+    after restore() five steps give bit for bit what five steps from the same snapshot gave before the status was set."""
+    from mobocmf_amd import functional as F
+    step.step()
+    step.check()
+    assert step.wgs_used > 1      # (a barrier of one workgroup is a no-op)
+    step.snapshot()
+    for _ in range(5):
+        step.step()
+    step.check()
+    clean = _state(step) + [step.losses.clone()]
+    step.restore()
+    torch.cuda.synchronize()
+    start = _state(step)
+    sync = step.in_launch_sync()
+    sync.words[sync.status_index].fill_(1)
+    torch.cuda.synchronize()
+    for _ in range(3):
+        step.step()
+    torch.cuda.synchronize()
+    assert all(torch.equal(a, b) for a, b in zip(start, _state(step)))
+    with pytest.raises(F.InLaunchWaitAbandoned):
+        step.check()
+    step.restore()
+    for _ in range(5):
+        step.step()
+    step.check()
+    assert all(torch.equal(a, b) for a, b in zip(clean, _state(step) + [step.losses.clone()]))
+
+
+def test_coop_step_with_the_status_set_commits_nothing_and_resumes_after_restore():
+    cfg = CASES[0]
+    prob, x, y, fid, eps = _problem(cfg)
+    model = synthetic.model_from_problem(prob, num_samples_for_training=cfg["S"], device=DEV)
+    _abandoned_steps_commit_nothing_and_restore_resumes(_coop([model], [x], [y], [fid], [eps]))
+
+
+def test_coop_conditioned_iteration_with_the_status_set_commits_nothing_and_resumes_after_restore():
+    from mobocmf_amd.util.coop_step import CoopConditionedStep
+    fitter, *_rest = _cond_setup(48, 48, d=4, seed=3)
+    step = CoopConditionedStep(fitter, lr=1e-3)
+    _abandoned_steps_commit_nothing_and_restore_resumes(step)
+    assert step.one_launch
+
+
+def test_coop_predict_group_reports_an_abandoned_wait_at_thaw():
+    """A search whose launches gave up a wait raises at thaw() (its moments were invalid), clears the words and forgets its
+    chains; the next search is right."""
+    from mobocmf_amd import functional as F
+    from mobocmf_amd.util.coop_step import CoopPredictGroup
+    from tests.test_hip_model import build_model
+    c = PRED[0]
+    M, N, d, S, fidelity, T = c["M"], c["N"], c["d"], c["S"], c["f"], c["T"]
+    models = [build_model(synthetic.make_problem(d=d, L=2, M=M, N=N, S=S, seed=s), S_train=S, S_acq=S) for s in (1, 2)]
+    X = torch.rand(T, d, dtype=torch.float64, generator=torch.Generator().manual_seed(4)).to(DEV)
+    grp = CoopPredictGroup(models, fidelity, T, d)
+    sync = grp.in_launch_sync()
+    sync.words[sync.status_index].fill_(1)
+    grp.freeze()
+    grp.acquisition_moments(X)
+    assert grp.wgs_used > 1
+    with pytest.raises(F.InLaunchWaitAbandoned):
+        grp.thaw()
+    assert not grp._chain_ready and not bool(sync.words.any())
+    grp.freeze()
+    mus, v = grp.acquisition_moments(X)
+    grp.thaw()
+    with torch.no_grad():
+        for i, m in enumerate(models):
+            m.eval()
+            mu, vv = m.predict_for_acquisition(X, fidelity)
+            m.train()
+            assert rel(mus[i], mu) < 1e-6 and rel(v[i], vv) < 1e-5
+
+
 def test_coupled_jes_at_mid_sizes_goes_through_the_cooperative_launch():
     """JESMOC_MFDGP.coupled_acq (JESMOC_MFDGP.py:38-52,125-135) for surrogates of M = N = 40 (iteration ~25 of the reference's
     loop): value and candidate gradient through CoopPredictGroup (two launches for all six models) equal the layer path's."""

@@ -468,9 +468,10 @@ def test_one_launch_conditioned_iteration_equals_the_three_launch_form():
 def test_in_launch_barrier_gives_up_instead_of_hanging():
     """The one-launch conditioned iteration waits for its models' workgroups at an arrival counter.  A wait that cannot end
     (here: the counter is knocked out of step, so the last workgroup waits for arrivals that never come) is abandoned after
-    ~0.2-0.5 s: the model is flagged, its loss poisoned, ``check()`` raises -- the device is not hung, and the next launches
+    the bound (include/mobocmf_hip.h: 1 s): the model is flagged, its loss poisoned, ``check()`` raises -- the device is not hung, and the next launches
     run (the fitter then rolls back and continues on the layer path)."""
     import time
+    from mobocmf_amd import functional as F
     from mobocmf_amd.layers.mfdgp_hidden_layer import NotPSDError
     from mobocmf_amd.util.tiny_step import TinyConditionedStep
     from tests.test_hip_conditioned import _fitter
@@ -487,7 +488,7 @@ def test_in_launch_barrier_gives_up_instead_of_hanging():
     step._barrier.fill_(1)               # 3 workgroups: arrivals 2, 3, 4 -- the third waits for a 6 that never comes
     t0 = time.perf_counter()
     step.step()
-    with pytest.raises((NotPSDError, FloatingPointError)):
+    with pytest.raises((NotPSDError, F.InLaunchWaitAbandoned)):
         step.check()
     assert time.perf_counter() - t0 < 5.0
     step.restore()
@@ -498,11 +499,13 @@ def test_in_launch_barrier_gives_up_instead_of_hanging():
     step.check()                          # the device is fine
 
 
-def test_barrier_timeout_at_a_non_check_iteration_is_sticky_and_leaves_the_model_untouched():
+def test_barrier_timeout_at_a_non_check_iteration_is_sticky_and_no_later_iteration_commits():
     """The fitter checks every 1000 iterations only (blackbox_mfdgp_fitter.ITER_PRINT).  A workgroup that gives up at the
     in-launch barrier in iteration k must (i) not update its model from its peers' unpublished moments -- parameters, Adam
-    state, step count and random streams stay as they were -- and (ii) still be reported by a check() many iterations later,
-    although the launches in between rewrite ``info`` and the losses: the coupling's status word is only ever OR'd."""
+    state, step count and random streams stay as they were -- and (ii) still be reported by a check() many iterations later:
+    the status word is only ever OR'd, and (iii) every later iteration fails at its first barrier poll until restore(), so
+    nothing commits in between (every model's state stays bitwise as it was)."""
+    from mobocmf_amd import functional as F
     from mobocmf_amd.util.tiny_step import TinyConditionedStep
     from tests.test_hip_conditioned import _fitter
     fitter, _ = _fitter(2, 1, 12)
@@ -530,13 +533,22 @@ def test_barrier_timeout_at_a_non_check_iteration_is_sticky_and_leaves_the_model
     assert torch.equal(step.exp_avg[k], adam_before[k]) and int(step.steps_done[k]) == int(steps_before[k])
     other = [i for i in range(len(step.models)) if i != k]
     assert all(int(step.steps_done[i]) == int(steps_before[i]) + 1 for i in other)      # ... its peers completed
-    step._barrier.zero_()                # the disturbance was transient: the following iterations run normally
-    for _ in range(3):
+
+    def state():
+        return ([p.detach().clone() for m in step.models for p in m.parameters()], [t.clone() for t in step.exp_avg],
+                [t.clone() for t in step.exp_avg_sq], step.steps_done.clone(),
+                [l._rng(step.device).clone() for m in step.models for l in m._layers()],
+                None if step.xrng is None else step.xrng.clone())
+    after = state()
+    step._barrier.zero_()                # the counter is back in step, but the status is set: every barrier of the
+    for _ in range(3):                   # following launches fails at its first poll
         step.step()
     torch.cuda.synchronize()
-    assert not bool((step.infos != 0).any()) and bool(torch.isfinite(step.losses).all())      # overwritten by now
-    with pytest.raises(FloatingPointError):
-        step.check()                     # ... but the status word remembers
+    for a, b in zip(after, state()):      # ... so no model commits anything
+        for x, y in zip(a if isinstance(a, list) else [a], b if isinstance(b, list) else [b]):
+            assert (x is None and y is None) or torch.equal(x, y)
+    with pytest.raises(F.InLaunchWaitAbandoned):
+        step.check()                     # ... and the status word remembers
     step.restore()
     step.step()
     step.check()

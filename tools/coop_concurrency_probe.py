@@ -39,9 +39,9 @@ for it in range(iters):
         inf = [int(s.infos.min()) for s in steps]
         if min(inf) < 0:
             print("iteration", it, "infos", inf, "wgs", [s.wgs_used for s in steps], "detail (info words)", [s.infos.cpu().tolist() for s in steps],
-                  "sync words", [s._sync_words()[::16].cpu().tolist() for s in steps])
+                  "sync words", [s.in_launch_sync().words[::16].cpu().tolist() for s in steps])
             bad += 1
             for s in steps:
                 s.infos.zero_()
-                s._sync_words().zero_()
+                s.in_launch_sync().reset()
 print("dummy streams %d, %d step objects, %d iterations%s: %d bad checks, %.2f s" % (ndummy, nobj, iters, " (serialised)" if sync else "", bad, time.perf_counter() - t0))
