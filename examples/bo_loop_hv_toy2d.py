@@ -1,0 +1,112 @@
+#!/usr/bin/env python3
+"""The reference's BO loop with its score (toy_synthetic_2D_JESMOCMF.py:533-627) on the toy 2-D problem of
+bo_iteration_toy2d.py: after every iteration the fitted models recommend a Pareto set on a fixed seeded grid of 1000 d points
+(``BlackBoxMFDGPFitter.recommend``), and its true hypervolume, the true optimum's on the same grid and the counts are appended
+to ``hypervolumes.txt`` in the reference's six columns:
+
+    hv_iter  optimal_hv  feasible  num_infeasible  num_optimal_points_fini  num_optimal_points_ini
+
+``--acq jes`` (default) chooses the next point with bo_iteration_toy2d.run (the cost-weighted JES acquisition), ``--acq random``
+with the reference's random baseline (Random_choice).  Objectives are minimised, the constraint is feasible when >= 0; the
+reference point of the hypervolume is (1000, 1000), as there.
+
+    python examples/bo_loop_hv_toy2d.py [--iters 5] [--acq jes|random] [--epochs 300] [--seed 0] [--out .]
+"""
+import argparse
+import faulthandler
+import os
+import sys
+import time
+
+import numpy as np
+
+faulthandler.enable()
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from bo_iteration_toy2d import blackboxes, run  # noqa: E402
+from mobocmf_amd.acquisition_functions.Random_choice import Random_choice  # noqa: E402
+from mobocmf_amd.models.mfdgp import TL  # noqa: E402
+from mobocmf_amd.util.blackbox_mfdgp_fitter import BlackBoxMFDGPFitter  # noqa: E402
+from mobocmf_amd.util.hypervolume import HV  # noqa: E402
+from mobocmf_amd.util.moop import MOOP  # noqa: E402
+
+REF_POINT = np.array([1000.0, 1000.0])
+
+
+def fit_only(x, fid, epochs, seed, device="cuda"):
+    """The unconditioned fit of bo_iteration_toy2d.run alone: what the random baseline recommends from."""
+    torch.manual_seed(seed)
+    fitter = BlackBoxMFDGPFitter(2, x.shape[0], num_epochs_1=epochs, num_epochs_2=epochs, type_lengthscale=TL.MEDIAN,
+                                 device=device)
+    fitter.verbose = False
+    for name, (lo, hi, is_con) in blackboxes().items():
+        y = np.where(fid == 0, lo(x), hi(x))
+        fitter.initialize_mfdgp(torch.from_numpy(x), torch.from_numpy(y)[:, None], torch.from_numpy(fid)[:, None], name,
+                                is_constraint=is_con)
+    fitter.train_mfdgps()
+    return fitter
+
+
+def score(fitter, grid):
+    """The six numbers of one iteration (toy_synthetic_2D_JESMOCMF.py:537-618) on the true high-fidelity functions."""
+    bb = blackboxes()
+    objs = [hi for _, hi, is_con in bb.values() if not is_con]
+    cons = [hi for _, hi, is_con in bb.values() if is_con]
+    ind = HV(ref_point=REF_POINT)
+    rec_set, _, _ = fitter.recommend(grid, min_feasible_prob=0.999)
+    true_cons = np.stack([c(rec_set) for c in cons], 1) if rec_set.shape[0] else np.zeros((0, len(cons)))
+    feasible = not np.any(true_cons < 0)
+    num_ini = rec_set.shape[0]
+    rec_set = rec_set[np.all(true_cons >= 0, axis=1)]
+    num_fini = rec_set.shape[0]
+    hv_iter = ind(np.stack([f(rec_set) for f in objs], 1)) if num_fini else 0.0
+    ok = np.all(np.stack([c(grid) for c in cons], 1) > 0, axis=1)
+    feas_objs = np.stack([f(grid) for f in objs], 1)[ok]
+    optimal_hv = ind(feas_objs[MOOP.compute_pareto_front(feas_objs)]) if feas_objs.shape[0] else 0.0
+    return hv_iter, optimal_hv, float(feasible), num_ini - num_fini, num_fini, num_ini
+
+
+def loop_hv(iters=5, acq="jes", seed=0, out_dir=".", epochs=300, verbose=True, **kw):
+    """``iters`` BO iterations, each one scored and appended to ``out_dir``/hypervolumes.txt; returns the rows."""
+    rng = np.random.default_rng(seed)
+    x = rng.uniform(size=(20, 2))
+    fid = np.concatenate([np.zeros(14), np.ones(6)])
+    grid = np.random.default_rng((seed, 1000)).uniform(size=(1000 * 2, 2))
+    chooser = None
+    if acq == "random":
+        chooser = Random_choice(input_size=2, num_fidelities=2, seed=seed)
+        for f in range(2):
+            for name in blackboxes():
+                chooser.add_blackbox(f, name, cost_evaluation=1.0 if f == 0 else 10.0)
+    rows = []
+    path = os.path.join(out_dir, "hypervolumes.txt")
+    for it in range(iters):
+        t0 = time.perf_counter()
+        if acq == "random":
+            fitter = fit_only(x, fid, epochs, seed + it)
+            cand, fidelity = chooser.get_nextpoint_coupled(iteration=it)
+        else:
+            fitter, _, cand, fidelity = run(seed=seed + it, data=(x, fid), epochs=epochs, verbose=False, **kw)
+        row = score(fitter, grid)
+        with open(path, "a") as f:
+            print("%lf %lf %lf %lf %lf %lf" % row, file=f)
+        rows.append(row)
+        x = np.vstack([x, cand.detach().cpu().numpy().reshape(1, -1)])
+        fid = np.concatenate([fid, [float(fidelity)]])
+        if verbose:
+            print("Iter: %d  HV recommendation %.6f  optimal %.6f  feasible %d  points %d/%d  (%.1f s)" %
+                  (it, row[0], row[1], row[2], row[4], row[5], time.perf_counter() - t0))
+    return rows
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iters", type=int, default=5)
+    ap.add_argument("--acq", choices=["jes", "random"], default="jes")
+    ap.add_argument("--epochs", type=int, default=300)
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--out", default=".")
+    a = ap.parse_args()
+    loop_hv(iters=a.iters, acq=a.acq, seed=a.seed, out_dir=a.out, epochs=a.epochs)

@@ -244,6 +244,31 @@ int mobocmf_rff_eval_chains(int32_t K, int32_t d, int64_t n, const double* x, co
 int mobocmf_rff_feasibility(int32_t K_con, int64_t n, const double* vals, int64_t ldv, const double* thr, int32_t* ok,
                             double* viol, mobocmf_stream_t stream);
 
+/* Recommendation of the BO driver: the probably-feasible, non-dominated rows of predicted objectives (all minimised).
+ * vals [k x n] with row stride ldv (>= n); con_mean / con_var [K_con x n] with row stride ldc (>= n), the Gaussian predictions
+ * of K_con constraints (K_con = 0: every row is feasible, the pointers may be NULL); noise [K_con] subtracted from the
+ * variances (NULL = none).  Row i is feasible when 0.5 erfc(-(m / sqrt(v - noise)) / sqrt(2)) > p_min for every constraint:
+ * v - noise < 0 makes it infeasible, v - noise == 0 leaves the sign of m to decide.  mask[i] = 1 for the rows of the front:
+ * feasible, no NaN objective, and no other such row j with vals[.][j] <= vals[.][i] everywhere and either != somewhere or
+ * j < i (MOOP.compute_pareto_front on the feasible rows: of exactly equal rows the first is kept); 0 otherwise.
+ * counts [3] (DEVICE): feasible rows, front rows, feasible rows with a NaN objective (they are never kept and dominate
+ * nothing).  1 <= k <= MOBOCMF_PARETO_MAX_K, 0 <= n <= 2^31 - 1.  Deterministic; three launches on `stream`, no workspace. */
+#define MOBOCMF_PARETO_MAX_K 16
+int mobocmf_pareto_mask(int32_t k, int64_t n, const double* vals, int64_t ldv, int32_t K_con, const double* con_mean,
+                        const double* con_var, int64_t ldc, const double* noise, double p_min, int32_t* mask, int64_t* counts,
+                        mobocmf_stream_t stream);
+
+/* Exact hypervolume of P points [P x k] (row stride ldp >= k, all objectives minimised) against ref [k] (DEVICE): the volume of
+ * the union of the boxes [p, ref] over the points that weakly dominate ref (the others add nothing, pymoo's rule); duplicates
+ * and dominated points are allowed, P = 0 gives 0.  Work O(P^(k-1)): 1 <= k <= MOBOCMF_HV_MAX_K and P <= 65536 (k <= 3),
+ * 1024 (k = 4), 256 (k = 5), MOBOCMF_BAD_ARG beyond.  Host-side, synchronising: *hv is a HOST double, written after the
+ * launches on `stream` have finished; NaN in the points or in ref returns MOBOCMF_BAD_ARG.  Bitwise reproducible (fixed
+ * summation order, no floating-point atomics).  workspace: mobocmf_hypervolume_workspace_bytes(k, P) bytes of device memory. */
+#define MOBOCMF_HV_MAX_K 5
+int mobocmf_hypervolume_workspace_bytes(int32_t k, int64_t P, size_t* bytes);
+int mobocmf_hypervolume(int32_t k, int64_t P, const double* pts, int64_t ldp, const double* ref, double* hv, void* workspace,
+                        size_t workspace_bytes, mobocmf_stream_t stream);
+
 /* f~[n] = mean[n/div] + sqrt(var[n/div]) * eps[n],  n < n_out  (mfdgp_hidden_layer.py:263-274). */
 int mobocmf_propagate_forward(const double* mean, const double* var, const double* eps, double* f_out, int64_t n_out,
                               int32_t div, mobocmf_stream_t stream);

@@ -1502,6 +1502,61 @@ def rff_feasibility(vals, thr):
     return ok.bool(), viol
 
 
+def pareto_mask(vals, con_mean=None, con_var=None, noise=None, p_min=0.999):
+    """The recommendation rule of the reference's BO driver in one call (mobocmf_pareto_mask): ``vals`` (k, n) objective values
+    (minimised), optionally ``con_mean`` / ``con_var`` (K_con, n) Gaussian constraint predictions and ``noise`` (K_con,) to
+    subtract from their variances.  A row is feasible when Phi(m / sqrt(v - noise)) > p_min for every constraint; the mask
+    keeps the feasible rows that MOOP.compute_pareto_front keeps among them (of equal rows the first).  Feasible rows with a NaN
+    objective are never kept.  Returns (mask (n,) bool, counts (3,) int64 = feasible rows, front rows, feasible NaN rows), both
+    on the device.  No autograd."""
+    lib = _lib.require_device()
+    with torch.no_grad():
+        if vals.dim() != 2 or not 1 <= vals.shape[0] <= _lib.PARETO_MAX_K:
+            raise _lib.MobocmfError("pareto_mask: vals must be (k, n) with 1 <= k <= %d" % _lib.PARETO_MAX_K)
+        vals = _prep(vals.detach())
+        k, n = vals.shape
+        K_con = 0
+        if con_mean is not None or con_var is not None:
+            if con_mean is None or con_var is None or con_mean.dim() != 2 or tuple(con_mean.shape) != tuple(con_var.shape) \
+                    or con_mean.shape[1] != n:
+                raise _lib.MobocmfError("pareto_mask: con_mean and con_var must both be (K_con, n)")
+            con_mean, con_var = _prep(con_mean.detach()), _prep(con_var.detach())
+            K_con = con_mean.shape[0]
+        if noise is not None:
+            noise = _prep(torch.as_tensor(noise, dtype=torch.float64, device=vals.device).reshape(-1))
+            if noise.numel() != K_con:
+                raise _lib.MobocmfError("pareto_mask: noise needs one entry per constraint")
+        mask = torch.empty(n, dtype=torch.int32, device=vals.device)
+        counts = torch.empty(3, dtype=torch.int64, device=vals.device)
+        _lib.check(lib.mobocmf_pareto_mask(k, n, _ptr(vals), max(n, 1), K_con, _ptr(con_mean), _ptr(con_var), max(n, 1),
+                                           _ptr(noise), float(p_min), _ptr(mask), _ptr(counts), _stream()),
+                   "mobocmf_pareto_mask")
+    return mask.bool(), counts
+
+
+def hypervolume(front, ref_point):
+    """Exact hypervolume (mobocmf_hypervolume) of ``front`` (P, k) -- minimised objectives -- against ``ref_point`` (k,): the
+    volume of the union of the boxes [p, ref] over the points that weakly dominate ref.  1 <= k <= 5, P within the bound of
+    ``_lib.HV_MAX_POINTS``; NaN input and larger shapes raise.  Returns a Python float (synchronises); bitwise reproducible."""
+    lib = _lib.require_device()
+    with torch.no_grad():
+        if front.dim() != 2 or not 1 <= front.shape[1] <= _lib.HV_MAX_K:
+            raise _lib.MobocmfError("hypervolume: front must be (P, k) with 1 <= k <= %d" % _lib.HV_MAX_K)
+        front = _prep(front.detach())
+        P, k = front.shape
+        ref = _prep(torch.as_tensor(ref_point, dtype=torch.float64).reshape(-1).to(front.device))
+        if ref.numel() != k:
+            raise _lib.MobocmfError("hypervolume: ref_point needs %d entries" % k)
+        nb = _lib._SZ()
+        _lib.check(lib.mobocmf_hypervolume_workspace_bytes(k, P, ctypes.byref(nb)),
+                   "mobocmf_hypervolume_workspace_bytes (k = %d, P = %d; bound %d points)" % (k, P, _lib.HV_MAX_POINTS[k]))
+        ws = scratch_buffer(nb.value, front.device)
+        out = ctypes.c_double()
+        _lib.check(lib.mobocmf_hypervolume(k, P, _ptr(front), k, _ptr(ref), ctypes.byref(out), _ptr(ws), nb.value, _stream()),
+                   "mobocmf_hypervolume (NaN in the front or the reference point?)")
+    return out.value
+
+
 # ------------------------------------------------------------------------------------------------------------
 # Exact-GP comparison baselines (SURVEY 8(f) N4) on the layer's kernels: Gram (mobocmf_gram_forward), the multi-fidelity
 # combination, the blocked Cholesky + triangular inverse of the chain, the triangular MFMA product with column statistics.

@@ -726,6 +726,82 @@ class BlackBoxMFDGPFitter:
         torch.cuda.current_stream(dev).wait_stream(step.stream)
         return num_iters, step
 
+    # ------------------------------------------------------------------ recommendation (the reference's BO driver)
+    def recommend(self, grid, min_feasible_prob=0.999, output_scaling=None):
+        """The recommended Pareto set of the reference's BO loop (toy_synthetic_2D_JESMOCMF.py:537-573): every black-box's
+        top-fidelity ``predict_for_acquisition`` moments on ``grid`` (n, d), the top layer's likelihood noise subtracted from
+        the constraint variances, optionally un-standardised (``output_scaling``: black-box name -> (mean, std); means
+        m std + mean, variances and noise times std^2), then ONE ``functional.pareto_mask``: the grid rows where every
+        constraint has Phi(m / sqrt(v - noise)) > ``min_feasible_prob`` and whose predicted objective means are
+        non-dominated among those rows.
+
+        With the black-boxes sharded over ranks every rank gathers the moment rows of all of them
+        (``parallel.all_gather_ragged``), orders them by role and global index and computes the same mask: every rank returns
+        the same result.  Returns (pareto_set (P, d) ndarray, predicted_front (P, n_obj) ndarray, info dict with the grid
+        mask and the counts of feasible, front and NaN rows).  Raises when a feasible row has a NaN predicted objective,
+        and on every rank when any rank failed to predict."""
+        from .. import _lib, parallel
+        from .. import functional as F
+        _lib.require_device()
+        dev = torch.device(self.device)
+        if dev.type != "cuda":
+            raise _lib.MobocmfError("recommend: the fitter's models must live on the GPU (device=%r)" % self.device)
+        grid_np = np.ascontiguousarray(grid.detach().cpu().numpy() if torch.is_tensor(grid) else np.asarray(grid),
+                                       dtype=np.float64)
+        if grid_np.ndim != 2:
+            raise _lib.MobocmfError("recommend: grid must be (n, d)")
+        n = grid_np.shape[0]
+        top = self.num_fidelities - 1
+        names = {id(h): name for name, h in list(self.mfdgp_handlers_objs.items()) + list(self.mfdgp_handlers_cons.items())}
+        rows, err = [], None
+        try:
+            x = torch.from_numpy(grid_np).to(dev)
+            with torch.no_grad():
+                for tag, i, h in self._handlers():
+                    mean, var = h.mfdgp.predict_for_acquisition(x, top)
+                    mean, var = mean.reshape(-1), var.reshape(-1)
+                    noise = getattr(h.mfdgp, h.mfdgp.name_hidden_layer_likelihood + str(top)).noise.reshape(-1)[0]
+                    noise = noise.to(dev, torch.float64)
+                    if output_scaling is not None:
+                        mu, sd = output_scaling[names[id(h)]]
+                        mean, var, noise = mean * float(sd) + float(mu), var * float(sd) ** 2, noise * float(sd) ** 2
+                    head = torch.tensor([0.0 if tag == "OBJ" else 1.0, float(self._global_index(h, i))], dtype=torch.float64,
+                                        device=dev)
+                    rows.append(torch.cat([head, noise.reshape(1), mean, var]))
+            local = torch.stack(rows) if rows else torch.zeros(0, 3 + 2 * n, dtype=torch.float64, device=dev)
+        except Exception as e:                   # said inside the exchange: the peers must not wait in it
+            err = e
+            local = torch.full((1, 3 + 2 * n), -1.0, dtype=torch.float64, device=dev)
+        allr = torch.cat(parallel.all_gather_ragged(local), 0).to(dev)
+        if err is not None:
+            raise RuntimeError("recommend: prediction failed on this rank: %r" % err) from err
+        if bool((allr[:, 0] < 0).any()):
+            raise RuntimeError("recommend: prediction failed on another rank")
+        head = allr[:, :2].cpu().numpy()
+        order = np.lexsort((head[:, 1], head[:, 0]))          # objectives, then constraints, each in global order
+        allr = allr[torch.from_numpy(order).to(dev)]
+        role, gi = head[order, 0], head[order, 1]
+        for r in (0.0, 1.0):
+            idx = gi[role == r]
+            if not np.array_equal(idx, np.arange(idx.size)):
+                raise RuntimeError("recommend: the %s global indices over all ranks are %s, not 0..%d"
+                                   % ("objective" if r == 0 else "constraint", idx.tolist(), idx.size - 1))
+        obj, con = allr[role == 0.0], allr[role == 1.0]
+        if obj.shape[0] == 0:
+            raise _lib.MobocmfError("recommend: no objective")
+        vals = obj[:, 3:3 + n]
+        if con.shape[0]:
+            mask, counts = F.pareto_mask(vals, con[:, 3:3 + n], con[:, 3 + n:], con[:, 2], p_min=min_feasible_prob)
+        else:
+            mask, counts = F.pareto_mask(vals, p_min=min_feasible_prob)
+        counts = counts.cpu().tolist()
+        if counts[2]:
+            raise _lib.MobocmfError("recommend: %d probably-feasible grid rows have a NaN predicted objective" % counts[2])
+        mask_np = mask.cpu().numpy()
+        front = vals.T[mask].cpu().numpy()
+        info = {"mask": mask_np, "num_feasible": counts[0], "num_front": counts[1], "num_nan": counts[2]}
+        return grid_np[mask_np], front, info
+
     def mfdgps_to_train_mode(self):
         for _, _, h in self._handlers():
             h.mfdgp.train()
