@@ -34,7 +34,7 @@ def blackboxes():
 
 
 def run(epochs=300, cond_iters=200, acq_iters=50, n_low=14, n_high=6, grid=100, seed=0, device="cuda", verbose=True,
-        data=None):
+        data=None, model_kwargs=None):
     rng = np.random.default_rng(seed)
     torch.manual_seed(seed)
     np.random.seed(seed)
@@ -44,7 +44,7 @@ def run(epochs=300, cond_iters=200, acq_iters=50, n_low=14, n_high=6, grid=100, 
     else:
         x, fid = data
     fitter = BlackBoxMFDGPFitter(2, x.shape[0], num_epochs_1=epochs, num_epochs_2=epochs, pareto_set_size=10,
-                                 opt_grid_size=grid, type_lengthscale=TL.MEDIAN, device=device)
+                                 opt_grid_size=grid, type_lengthscale=TL.MEDIAN, device=device, **(model_kwargs or {}))
     fitter.verbose = False
     for name, (lo, hi, is_con) in blackboxes().items():
         y = np.where(fid == 0, lo(x), hi(x))

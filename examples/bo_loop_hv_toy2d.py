@@ -10,7 +10,11 @@ to ``hypervolumes.txt`` in the reference's six columns:
 with the reference's random baseline (Random_choice).  Objectives are minimised, the constraint is feasible when >= 0; the
 reference point of the hypervolume is (1000, 1000), as there.
 
+``--num-inducing M`` caps the inducing points of every surrogate at M; ``--inducing greedy`` then chooses them among the
+training rows by greedy conditional variance (``inducing_selection="greedy_variance"``) instead of taking the first M rows.
+
     python examples/bo_loop_hv_toy2d.py [--iters 5] [--acq jes|random] [--epochs 300] [--seed 0] [--out .]
+                                        [--num-inducing M] [--inducing first|greedy]
 """
 import argparse
 import faulthandler
@@ -35,11 +39,11 @@ from mobocmf_amd.util.moop import MOOP  # noqa: E402
 REF_POINT = np.array([1000.0, 1000.0])
 
 
-def fit_only(x, fid, epochs, seed, device="cuda"):
+def fit_only(x, fid, epochs, seed, device="cuda", model_kwargs=None):
     """The unconditioned fit of bo_iteration_toy2d.run alone: what the random baseline recommends from."""
     torch.manual_seed(seed)
     fitter = BlackBoxMFDGPFitter(2, x.shape[0], num_epochs_1=epochs, num_epochs_2=epochs, type_lengthscale=TL.MEDIAN,
-                                 device=device)
+                                 device=device, **(model_kwargs or {}))
     fitter.verbose = False
     for name, (lo, hi, is_con) in blackboxes().items():
         y = np.where(fid == 0, lo(x), hi(x))
@@ -68,8 +72,12 @@ def score(fitter, grid):
     return hv_iter, optimal_hv, float(feasible), num_ini - num_fini, num_fini, num_ini
 
 
-def loop_hv(iters=5, acq="jes", seed=0, out_dir=".", epochs=300, verbose=True, **kw):
+def loop_hv(iters=5, acq="jes", seed=0, out_dir=".", epochs=300, verbose=True, num_inducing=None, inducing="first", **kw):
     """``iters`` BO iterations, each one scored and appended to ``out_dir``/hypervolumes.txt; returns the rows."""
+    model_kwargs = {}
+    if num_inducing is not None:
+        model_kwargs = dict(num_inducing=num_inducing,
+                            inducing_selection="greedy_variance" if inducing == "greedy" else "first")
     rng = np.random.default_rng(seed)
     x = rng.uniform(size=(20, 2))
     fid = np.concatenate([np.zeros(14), np.ones(6)])
@@ -85,10 +93,11 @@ def loop_hv(iters=5, acq="jes", seed=0, out_dir=".", epochs=300, verbose=True, *
     for it in range(iters):
         t0 = time.perf_counter()
         if acq == "random":
-            fitter = fit_only(x, fid, epochs, seed + it)
+            fitter = fit_only(x, fid, epochs, seed + it, model_kwargs=model_kwargs)
             cand, fidelity = chooser.get_nextpoint_coupled(iteration=it)
         else:
-            fitter, _, cand, fidelity = run(seed=seed + it, data=(x, fid), epochs=epochs, verbose=False, **kw)
+            fitter, _, cand, fidelity = run(seed=seed + it, data=(x, fid), epochs=epochs, verbose=False,
+                                            model_kwargs=model_kwargs, **kw)
         row = score(fitter, grid)
         with open(path, "a") as f:
             print("%lf %lf %lf %lf %lf %lf" % row, file=f)
@@ -108,5 +117,9 @@ if __name__ == "__main__":
     ap.add_argument("--epochs", type=int, default=300)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--out", default=".")
+    ap.add_argument("--num-inducing", type=int, default=None, help="inducing points per surrogate (default: every training row)")
+    ap.add_argument("--inducing", choices=["first", "greedy"], default="first",
+                    help="with --num-inducing: the first M training rows, or M rows by greedy conditional variance")
     a = ap.parse_args()
-    loop_hv(iters=a.iters, acq=a.acq, seed=a.seed, out_dir=a.out, epochs=a.epochs)
+    loop_hv(iters=a.iters, acq=a.acq, seed=a.seed, out_dir=a.out, epochs=a.epochs, num_inducing=a.num_inducing,
+            inducing=a.inducing)

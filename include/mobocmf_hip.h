@@ -269,6 +269,33 @@ int mobocmf_hypervolume_workspace_bytes(int32_t k, int64_t P, size_t* bytes);
 int mobocmf_hypervolume(int32_t k, int64_t P, const double* pts, int64_t ldp, const double* ref, double* hv, void* workspace,
                         size_t workspace_bytes, mobocmf_stream_t stream);
 
+/* Inducing-point selection by greedy conditional variance: the incomplete pivoted Cholesky of K_nn under the kind-0 kernel
+ * (the one mobocmf_gram_forward(kind 0) evaluates).  x [N x d] row-major (1 <= d <= MOBOCMF_MAX_D), hyp = [a, ls[0..d)].
+ * Step j picks the row with the largest residual d = diag(K_nn - K_nm K_mm^-1 K_mn) over the rows picked so far -- of
+ * bitwise-equal residuals the lowest row, so step 0 is row 0 -- and stops before a pick whose residual is <= tol_rel * a or
+ * not positive (tol_rel = 0: until max_points).  Residuals are clamped at 0 after every update; a picked row's is exactly 0.
+ * Outputs (all DEVICE): idx [max_points] rows in pick order (-1 beyond count), count [1], resid [max_points] the residual of
+ * each pick when it was picked (0 beyond count), diag [N] the final residuals, info [1].
+ * Refusals.  MOBOCMF_BAD_ARG (host-visible, nothing is launched): N < 1, N > MOBOCMF_INDUCING_MAX_ROWS, max_points < 1,
+ * > N or > MOBOCMF_INDUCING_MAX_POINTS, d out of range, tol_rel negative or not finite, form not 0 / 1 / 2, form 1 with
+ * N > MOBOCMF_INDUCING_ONE_WG_MAX_ROWS (one compute unit would be held for minutes), a NULL pointer, a
+ * workspace smaller than mobocmf_select_inducing_workspace_bytes(N, max_points).  info (device-visible): 1 = a non-finite
+ * entry of x, 2 = a hyper-parameter that is non-finite, not positive, or a lengthscale whose reciprocal overflows; then
+ * count = 0, idx = -1, resid and diag NaN.  info = 0 otherwise.  No host synchronisation inside the call.
+ * form: 0 = by size | 1 = one workgroup, one launch, all steps (the BO loop's sizes) | 2 = one launch per pivot over many
+ * workgroups (max_points + 3 launches; the pivot stays on the device, launches after the stop do nothing).  A row's
+ * update is the same instruction sequence in one thread in both forms: idx, resid and diag are bitwise equal between them
+ * and from run to run.
+ * workspace: 32 KiB + N * max_points doubles of device memory (the factor, [max_points][N]): 32 MiB at N = 8192,
+ * max_points = 512 (resident in the Infinity Cache), 512 MiB at N = 65536, max_points = 1024. */
+#define MOBOCMF_INDUCING_MAX_POINTS 4096
+#define MOBOCMF_INDUCING_MAX_ROWS 262144
+#define MOBOCMF_INDUCING_ONE_WG_MAX_ROWS 32768
+int mobocmf_select_inducing_workspace_bytes(int64_t N, int32_t max_points, size_t* bytes);
+int mobocmf_select_inducing(int64_t N, int32_t d, const double* x, const double* hyp, int32_t max_points, double tol_rel,
+                            int32_t form, int32_t* idx, int32_t* count, double* resid, double* diag, int32_t* info,
+                            void* workspace, size_t workspace_bytes, mobocmf_stream_t stream);
+
 /* f~[n] = mean[n/div] + sqrt(var[n/div]) * eps[n],  n < n_out  (mfdgp_hidden_layer.py:263-274). */
 int mobocmf_propagate_forward(const double* mean, const double* var, const double* eps, double* f_out, int64_t n_out,
                               int32_t div, mobocmf_stream_t stream);

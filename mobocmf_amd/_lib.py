@@ -157,12 +157,17 @@ SYMBOLS = {
     "mobocmf_pareto_mask": [_I32, _I64, _P, _I64, _I32, _P, _P, _I64, _P, _D, _P, _P, _P],
     "mobocmf_hypervolume_workspace_bytes": [_I32, _I64, ctypes.POINTER(_SZ)],
     "mobocmf_hypervolume": [_I32, _I64, _P, _I64, _P, ctypes.POINTER(_D), _P, _SZ, _P],
+    "mobocmf_select_inducing_workspace_bytes": [_I64, _I32, ctypes.POINTER(_SZ)],
+    "mobocmf_select_inducing": [_I64, _I32, _P, _P, _I32, _D, _I32, _P, _P, _P, _P, _P, _P, _SZ, _P],
     "mobocmf_gram_forward": [_I32, _I32, _P, _P, _I64, _P, _P, _I64, _P, _P, _I64, _P],
     "mobocmf_check_info": [_P, ctypes.POINTER(_I32), _P],
 }
 MAX_D, MAX_XDIV = 32, 48        # MOBOCMF_MAX_D / MOBOCMF_MAX_XDIV of include/mobocmf_hip.h
 PARETO_MAX_K, HV_MAX_K = 16, 5   # MOBOCMF_PARETO_MAX_K / MOBOCMF_HV_MAX_K
 HV_MAX_POINTS = {1: 65536, 2: 65536, 3: 65536, 4: 1024, 5: 256}   # the work bound of mobocmf_hypervolume
+INDUCING_MAX_POINTS, INDUCING_MAX_ROWS = 4096, 262144             # MOBOCMF_INDUCING_MAX_POINTS / MOBOCMF_INDUCING_MAX_ROWS
+INDUCING_ONE_WG_MAX_ROWS = 32768                                  # MOBOCMF_INDUCING_ONE_WG_MAX_ROWS (form 1 beyond it is refused)
+INDUCING_INFO = {1: "a non-finite entry of x", 2: "a non-finite or non-positive hyper-parameter"}   # info of mobocmf_select_inducing
 
 _lib = None
 

@@ -1557,6 +1557,43 @@ def hypervolume(front, ref_point):
     return out.value
 
 
+def select_inducing(x, hyp, max_points, tol_rel=0.0, form=None):
+    """Inducing points by greedy conditional variance (mobocmf_select_inducing): the incomplete pivoted Cholesky of K_nn
+    under the kind-0 kernel with ``hyp`` = [outputscale, lengthscales] (``hyp_len(0, d)`` entries).  Every step picks the row
+    of ``x`` (N, d) with the largest residual diag(K_nn - K_nm K_mm^-1 K_mn) -- ties: the lowest row -- and stops after
+    ``max_points`` picks or before a pick whose residual is <= ``tol_rel`` * outputscale.  ``form``: None = by size, 1 = the
+    one-workgroup launch (N <= ``_lib.INDUCING_ONE_WG_MAX_ROWS``), 2 = one launch per pivot (bitwise the same result).
+    Returns (idx [count] int64 in pick order, resid [count] the residual of each pick when it was picked, diag [N] the
+    residuals left).  Synchronises once to read ``count``; non-finite ``x`` / ``hyp`` and non-positive hyper-parameters raise."""
+    lib = _lib.require_device()
+    with torch.no_grad():
+        if x.dim() != 2 or not 1 <= x.shape[1] <= _lib.MAX_D:
+            raise _lib.MobocmfError("select_inducing: x must be (N, d) with 1 <= d <= %d" % _lib.MAX_D)
+        x = _prep(x.detach())
+        N, d = x.shape
+        hyp = _prep(torch.as_tensor(hyp, dtype=torch.float64).detach().reshape(-1).to(x.device))
+        if hyp.numel() != hyp_len(0, d):
+            raise _lib.MobocmfError("select_inducing: hyp needs %d entries (outputscale, then d lengthscales)" % hyp_len(0, d))
+        max_points, form = int(max_points), 0 if form is None else int(form)
+        nb = _lib._SZ()
+        _lib.check(lib.mobocmf_select_inducing_workspace_bytes(N, max_points, ctypes.byref(nb)),
+                   "mobocmf_select_inducing_workspace_bytes (N = %d, max_points = %d; 1 <= max_points <= min(N, %d), N <= %d)"
+                   % (N, max_points, _lib.INDUCING_MAX_POINTS, _lib.INDUCING_MAX_ROWS))
+        ws = scratch_buffer(nb.value, x.device)
+        idx = _empty(max_points, dtype=torch.int32, device=x.device)
+        head = _empty(2, dtype=torch.int32, device=x.device)           # count, info
+        resid = _empty(max_points, device=x.device)
+        diag = _empty(N, device=x.device)
+        _lib.check(lib.mobocmf_select_inducing(N, d, _ptr(x), _ptr(hyp), max_points, float(tol_rel), form, _ptr(idx),
+                                               ctypes.c_void_p(head.data_ptr()), _ptr(resid), _ptr(diag),
+                                               ctypes.c_void_p(head.data_ptr() + 4), _ptr(ws), nb.value, _stream()),
+                   "mobocmf_select_inducing (form 1 takes at most %d rows)" % _lib.INDUCING_ONE_WG_MAX_ROWS)
+        count, info = (int(v) for v in head.tolist())
+        if info != 0:
+            raise _lib.MobocmfError("select_inducing refused its input: %s (info = %d)" % (_lib.INDUCING_INFO.get(info, "?"), info))
+    return idx[:count].long(), resid[:count], diag
+
+
 # ------------------------------------------------------------------------------------------------------------
 # Exact-GP comparison baselines (SURVEY 8(f) N4) on the layer's kernels: Gram (mobocmf_gram_forward), the multi-fidelity
 # combination, the blocked Cholesky + triangular inverse of the chain, the triangular MFMA product with column statistics.

@@ -5,6 +5,8 @@ Extensions (documented in DESIGN.md; defaults reproduce the reference):
   * ``num_inducing`` / ``inducing_points``: decouple M from N (reference: Z = all training inputs, F6).
   * ``num_samples_for_training`` (S): S-fold sample replication through layers >= 1 during training
     (reference: exactly one sample, F7); the ELBO then averages the S samples of each row.
+  * ``inducing_selection="greedy_variance"`` (with ``num_inducing``): the inducing inputs are chosen among the training rows by
+    greedy conditional variance on the GPU (``functional.select_inducing``) instead of taking the first ``num_inducing`` rows.
   * more than two fidelities: Z~_l = [Z_x, m_{l-1}] for every l >= 1 (reference works for 2 only, F8).
 """
 from enum import Enum
@@ -45,8 +47,16 @@ class MFDGP(nn.Module):
     def __init__(self, x_train, y_train, fidelities, num_fidelities, type_lengthscale=TL.MEDIAN,
                  num_samples_for_acquisition=25, previously_trained_model=None, ini_inducing_using_layer_0=False,
                  use_only_highest_fidelity=False, init_params_to_prior_and_fix_them=False,
-                 num_inducing=None, inducing_points=None, num_samples_for_training=1, median_mode="reference"):
+                 num_inducing=None, inducing_points=None, num_samples_for_training=1, median_mode="reference",
+                 inducing_selection="first", inducing_tol=0.0, inducing_device=None):
         super().__init__()
+        if inducing_selection not in ("first", "greedy_variance"):
+            raise ValueError("inducing_selection must be 'first' or 'greedy_variance', got %r" % (inducing_selection,))
+        self.inducing_selection = inducing_selection
+        self.inducing_tol = float(inducing_tol)
+        self.inducing_indices = None         # greedy_variance: the picked rows of x_train in pick order (per layer: a list)
+        self.inducing_residuals = None       # ... the residual of each pick when it was picked
+        self.inducing_max_residual = None    # ... the largest residual left over the candidates
         self.init_params_to_prior_and_fix_them = init_params_to_prior_and_fix_them
         self._eval_mode = False
         self.num_samples_for_acquisition = num_samples_for_acquisition
@@ -55,11 +65,17 @@ class MFDGP(nn.Module):
         self.ini_inducing_using_layer_0 = ini_inducing_using_layer_0
         self.median_mode = median_mode
         self.input_dims = x_train.shape[-1]
+        x_select = x_train.detach()          # greedy selection runs where the data is, before it moves to the host
         x_train, y_train, fidelities = x_train.detach().cpu(), y_train.detach().cpu(), fidelities.detach().cpu()
         y_high_std = np.std(y_train[(fidelities == num_fidelities - 1).flatten()].numpy())
 
+        self._Zx_layer = None                # only-highest-fidelity + greedy selection: each layer's own inducing inputs
         if inducing_points is None and num_inducing is not None:
-            inducing_points = x_train[:num_inducing]
+            if inducing_selection == "greedy_variance":
+                inducing_points = self._select_inducing_greedy(x_select, x_train, fidelities, num_fidelities, num_inducing,
+                                                               type_lengthscale, previously_trained_model, inducing_device)
+            else:
+                inducing_points = x_train[:num_inducing]
         self._Zx_user = inducing_points
 
         hidden_layers = []
@@ -115,9 +131,54 @@ class MFDGP(nn.Module):
             return 0.01 * torch.ones(self.input_dims)
         raise ValueError("Wrong type of lengthscale.")
 
+    def _select_inducing_greedy(self, x_select, x_train, fidelities, num_fidelities, num_inducing, type_lengthscale,
+                                previously_trained_model, inducing_device):
+        """Inducing inputs by greedy conditional variance (functional.select_inducing) under layer 0's hyper-parameters: the
+        trained ones of ``previously_trained_model`` when there is one (a BO loop selects under last iteration's
+        lengthscales), otherwise the values layer 0 is about to be initialised with.  Candidates: every training row, or --
+        ``use_only_highest_fidelity`` -- each layer's own rows.  There is no CPU fallback: the data must be on the GPU or
+        ``inducing_device`` must name one."""
+        if x_select.is_cuda:
+            dev = x_select.device
+        elif inducing_device is not None and torch.device(inducing_device).type == "cuda":
+            dev = torch.device(inducing_device)
+        else:
+            raise F._lib.MobocmfError("inducing_selection='greedy_variance' runs on the GPU and has no CPU fallback: pass "
+                                      "x_train on the GPU or inducing_device='cuda'")
+        d = self.input_dims
+        if previously_trained_model is not None:
+            cm = getattr(previously_trained_model, previously_trained_model.name_hidden_layer + "0").covar_module
+            a, ls = cm.outputscale.detach().reshape(-1)[:1], cm.base_kernel.lengthscale.detach().reshape(-1)
+        elif self.init_params_to_prior_and_fix_them:
+            a, ls = torch.ones(1), torch.full((d,), 0.25 * d)
+        else:
+            a = torch.ones(1)
+            ls = self.get_init_lengthscale(type_lengthscale, inputs=x_train[(fidelities == 0).flatten(), :]).reshape(-1)
+        hyp = torch.cat((a.double().cpu(), (ls.double().cpu() * torch.ones(d, dtype=torch.float64)))).to(dev)
+
+        def pick(rows):
+            with torch.cuda.device(dev):
+                xs = x_select.to(dev).double()
+                xs = xs if rows is None else xs[rows.to(dev)]
+                idx, resid, diag = F.select_inducing(xs, hyp, min(int(num_inducing), xs.shape[0]), tol_rel=self.inducing_tol)
+                idx, resid, left = idx.cpu(), resid.cpu(), float(diag.max())
+            return (idx if rows is None else rows[idx]), resid, left
+
+        if not self.use_only_highest_fidelity:
+            self.inducing_indices, self.inducing_residuals, self.inducing_max_residual = pick(None)
+            return x_train[self.inducing_indices]
+        picks = [pick(torch.nonzero(fidelities[:, 0] == i).flatten()) for i in range(num_fidelities)]
+        self.inducing_indices = [p[0] for p in picks]
+        self.inducing_residuals = [p[1] for p in picks]
+        self.inducing_max_residual = [p[2] for p in picks]
+        self._Zx_layer = [x_train[p[0]] for p in picks]
+        return None
+
     def find_good_initial_inducing_points_and_values(self, x_train, y_train, fidelities, layer):
         """mfdgp.py:290-317 with the O(M N^2) loop replaced by one argmin over distances."""
-        if self._Zx_user is not None:
+        if self._Zx_layer is not None:
+            inducing_points = self._Zx_layer[layer]
+        elif self._Zx_user is not None:
             inducing_points = self._Zx_user
         elif self.use_only_highest_fidelity:
             inducing_points = x_train[fidelities[:, 0] == layer, :]

@@ -50,6 +50,8 @@ class MFDGPHandler:
     def __init__(self, x_train, y_train, fidelities_train, num_fidelities, batch_size, type_lengthscale,
                  previously_trained_model=None, init_params_to_prior_and_fix_them=False,
                  use_only_highest_fidelity=False, device="cuda", **model_kwargs):
+        if model_kwargs.get("inducing_selection", "first") != "first":
+            model_kwargs.setdefault("inducing_device", device)     # the selection runs where the model will live
         self.mfdgp = MFDGP(x_train, y_train, fidelities_train, num_fidelities=num_fidelities,
                            type_lengthscale=type_lengthscale, previously_trained_model=previously_trained_model,
                            use_only_highest_fidelity=use_only_highest_fidelity,
