@@ -296,6 +296,44 @@ int mobocmf_select_inducing(int64_t N, int32_t d, const double* x, const double*
                             int32_t form, int32_t* idx, int32_t* count, double* resid, double* diag, int32_t* info,
                             void* workspace, size_t workspace_bytes, mobocmf_stream_t stream);
 
+/* ---- Mini-batches drawn on the device.  Replaces the host loader -- DataLoader(dataset, batch_size, shuffle=True),
+ * blackbox_mfdgp_fitter.py:35 -- and the batch loop of the epoch closure (:156-173) inside a captured step: a replay sees a fresh
+ * batch without the host.  Epoch e visits the rows in the order of a stateless keyed bijection of 0..N-1 (a Feistel network
+ * with Philox4x32-10 round functions keyed by (seed, e, round), cycle-walking for values >= N; csrc/minibatch_perm.h, DESIGN
+ * 5.3): position i of epoch e is a pure function of (seed, e, N, i).  Batch k of an epoch holds positions kB .. min((k+1)B, N)-1;
+ * there are nb = ceil(N / B) batches, the last one ragged when B does not divide N (the loader's drop_last = False).
+ *
+ * state: 3 DEVICE int64 {seed, step, status}, caller-owned; step counts the batches drawn so far (epoch = step / nb,
+ *   k = step % nb), status is 0 or a sticky MOBOCMF_MINIBATCH_* code.
+ * mobocmf_minibatch_indices (one workgroup): writes src[0..rows) = the source rows of the batch (int64), with order_by_fidelity = 1
+ *   sorted stably by DESCENDING fidelity (fid[row] truncated to an integer level, clamped to 0..L-1) so that the rows no upper
+ *   layer needs are contiguous at the end; writes counts[l] = #{rows of the batch with fid >= l}, l < L (int64); advances step.
+ *   Guard: rows_expected is the number of rows the caller's buffers (and its captured graph) are made for.  If batch k has a
+ *   different number, or step is negative, or status is already set, the launch sets status and writes neither src, counts nor
+ *   step; it never writes beyond rows_expected entries of src.
+ * mobocmf_minibatch_gather (grid-wide, whole rows): xb[r][:] = x[src[r]][:], yb[r] = y[src[r]], fidb[r] = fid[src[r]] for
+ *   r < rows, x [N x d] row-major; 16-byte accesses when d is even and x / xb are 16-byte aligned.  Rows whose src is outside
+ *   0..N-1 are skipped; nothing is written when status is set.
+ * mobocmf_minibatch_accumulate: sums[0..1] += (loss, kl) of the step just taken (restarted at the first batch of an epoch),
+ *   sums[2..3] = the sums of the last finished epoch -- what the reference prints per epoch (:156-173) -- without a host read.
+ * mobocmf_minibatch_permutation_host: out[i] = source row of position i of the epoch, on the HOST, from the same definition:
+ *   for tests and for callers that ask which rows a step used.  Not a training path.
+ * MOBOCMF_BAD_ARG (host-visible, nothing is launched): N < 1 or > MOBOCMF_MINIBATCH_MAX_ROWS, B < 1 or >= that bound, L < 1 or
+ *   > MOBOCMF_MINIBATCH_MAX_LEVELS, d < 1 or > MOBOCMF_MAX_D, rows_expected < 1 or > min(B, N), rows > N, a negative epoch, a NULL
+ *   pointer. */
+#define MOBOCMF_MINIBATCH_MAX_ROWS 2147483648LL
+#define MOBOCMF_MINIBATCH_MAX_LEVELS 8
+#define MOBOCMF_MINIBATCH_ROWS_MISMATCH 1
+#define MOBOCMF_MINIBATCH_BAD_STATE 2
+int mobocmf_minibatch_permutation_host(int64_t seed, int64_t epoch, int64_t N, int64_t* out);
+int mobocmf_minibatch_indices(int64_t N, int64_t B, int32_t L, const double* fid, int32_t order_by_fidelity,
+                              int64_t rows_expected, int64_t* state, int64_t* src, int64_t* counts, mobocmf_stream_t stream);
+int mobocmf_minibatch_gather(int64_t N, int32_t d, int64_t rows, const double* x, const double* y, const double* fid,
+                             const int64_t* src, const int64_t* state, double* xb, double* yb, double* fidb,
+                             mobocmf_stream_t stream);
+int mobocmf_minibatch_accumulate(int64_t N, int64_t B, const int64_t* state, const double* loss, const double* kl, double* sums,
+                                 mobocmf_stream_t stream);
+
 /* f~[n] = mean[n/div] + sqrt(var[n/div]) * eps[n],  n < n_out  (mfdgp_hidden_layer.py:263-274). */
 int mobocmf_propagate_forward(const double* mean, const double* var, const double* eps, double* f_out, int64_t n_out,
                               int32_t div, mobocmf_stream_t stream);

@@ -159,6 +159,10 @@ SYMBOLS = {
     "mobocmf_hypervolume": [_I32, _I64, _P, _I64, _P, ctypes.POINTER(_D), _P, _SZ, _P],
     "mobocmf_select_inducing_workspace_bytes": [_I64, _I32, ctypes.POINTER(_SZ)],
     "mobocmf_select_inducing": [_I64, _I32, _P, _P, _I32, _D, _I32, _P, _P, _P, _P, _P, _P, _SZ, _P],
+    "mobocmf_minibatch_permutation_host": [_I64, _I64, _I64, _P],
+    "mobocmf_minibatch_indices": [_I64, _I64, _I32, _P, _I32, _I64, _P, _P, _P, _P],
+    "mobocmf_minibatch_gather": [_I64, _I32, _I64] + [_P] * 9,
+    "mobocmf_minibatch_accumulate": [_I64, _I64, _P, _P, _P, _P, _P],
     "mobocmf_gram_forward": [_I32, _I32, _P, _P, _I64, _P, _P, _I64, _P, _P, _I64, _P],
     "mobocmf_check_info": [_P, ctypes.POINTER(_I32), _P],
 }
@@ -168,6 +172,10 @@ HV_MAX_POINTS = {1: 65536, 2: 65536, 3: 65536, 4: 1024, 5: 256}   # the work bou
 INDUCING_MAX_POINTS, INDUCING_MAX_ROWS = 4096, 262144             # MOBOCMF_INDUCING_MAX_POINTS / MOBOCMF_INDUCING_MAX_ROWS
 INDUCING_ONE_WG_MAX_ROWS = 32768                                  # MOBOCMF_INDUCING_ONE_WG_MAX_ROWS (form 1 beyond it is refused)
 INDUCING_INFO = {1: "a non-finite entry of x", 2: "a non-finite or non-positive hyper-parameter"}   # info of mobocmf_select_inducing
+
+MINIBATCH_MAX_ROWS, MINIBATCH_MAX_LEVELS = 2 ** 31, 8              # MOBOCMF_MINIBATCH_MAX_ROWS / MOBOCMF_MINIBATCH_MAX_LEVELS
+MINIBATCH_STATUS = {1: "the batch does not have the rows the step was built for (host and device step counts differ)",
+                    2: "a negative step count"}                   # status word of mobocmf_minibatch_indices
 
 _lib = None
 

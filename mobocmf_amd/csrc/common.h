@@ -169,14 +169,19 @@ static inline int hyp_len(int kind, int d) { return kind == 0 ? 1 + d : 5 + 2 * 
 // ------------------------------------------------------------------ eps of the training branch (elementwise.hip, tiny_step.hip)
 // counter-based Philox4x32-10 keyed by (seed, call counter, row) + Box-Muller in float64: the draw of
 // mobocmf_propagate_rng_forward, shared with the one-launch step so that both produce the same eps from the same state
+// the round multipliers and key increments (Salmon et al. 2011), shared with the host / device copy of minibatch_perm.h
+#define PHILOX_M0 0xD2511F53u
+#define PHILOX_M1 0xCD9E8D57u
+#define PHILOX_W0 0x9E3779B9u
+#define PHILOX_W1 0xBB67AE85u
 __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
                                               uint32_t (&out)[4]) {
 #pragma unroll
     for (int r = 0; r < 10; ++r) {
-        const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+        const uint32_t hi0 = __umulhi(PHILOX_M0, c0), lo0 = PHILOX_M0 * c0;
+        const uint32_t hi1 = __umulhi(PHILOX_M1, c2), lo1 = PHILOX_M1 * c2;
         c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+        k0 += PHILOX_W0; k1 += PHILOX_W1;
     }
     out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
 }

@@ -1595,6 +1595,79 @@ def select_inducing(x, hyp, max_points, tol_rel=0.0, form=None):
 
 
 # ------------------------------------------------------------------------------------------------------------
+# Mini-batches drawn on the device (csrc/minibatch.hip).  Thin wrappers: they only enqueue launches on the
+# current stream and read nothing back, so a captured step may contain them.
+# ------------------------------------------------------------------------------------------------------------
+def minibatch_state(seed, device):
+    """int64 [seed, step, status] of one sampler on ``device``: step counts the batches drawn, status is 0 or a sticky code
+    of ``_lib.MINIBATCH_STATUS``.  The launches advance it on the device."""
+    _lib.require_device()
+    return torch.tensor([int(seed), 0, 0], dtype=torch.int64, device=device)
+
+
+def _mb_i64(t, n, what):
+    if not t.is_cuda or t.dtype != torch.int64 or not t.is_contiguous() or t.numel() < n:
+        raise _lib.MobocmfError("mobocmf_amd: %s must be a contiguous int64 GPU tensor of at least %d entries" % (what, n))
+    return t
+
+
+def minibatch_indices(state, fid, batch_size, num_levels, src, counts, order_by_fidelity=True):
+    """The next batch of the sampler ``state``: ``src[:rows]`` = its source rows (``rows = src.numel()`` is what the caller
+    expects the batch to have: ``batch_size``, or the ragged rest for the last batch of an epoch), ordered stably by descending
+    fidelity when asked; ``counts[l]`` = number of its rows with fidelity >= l.  Advances the step count.  If the batch does
+    not have ``rows`` rows the launch only sets ``state[2]`` (see ``minibatch_check``)."""
+    lib = _lib.require_device()
+    fid = _prep(fid)
+    N, rows = fid.numel(), src.numel()
+    _mb_i64(state, 3, "state"), _mb_i64(src, 1, "src"), _mb_i64(counts, num_levels, "counts")
+    _lib.check(lib.mobocmf_minibatch_indices(N, int(batch_size), int(num_levels), _ptr(fid), int(bool(order_by_fidelity)), rows,
+                                             _ptr(state), _ptr(src), _ptr(counts), _stream()),
+               "mobocmf_minibatch_indices (N = %d, batch_size = %d, levels = %d, rows = %d)" % (N, batch_size, num_levels, rows))
+
+
+def minibatch_gather(state, src, x, y, fid, xb, yb, fidb):
+    """xb[r] = x[src[r]], yb[r] = y[src[r]], fidb[r] = fid[src[r]] for the ``src.numel()`` rows of the batch (whole rows of
+    ``x`` (N, d)); into caller-owned buffers."""
+    lib = _lib.require_device()
+    x, y, fid = _prep(x), _prep(y), _prep(fid)
+    N, d = x.shape
+    rows = src.numel()
+    _mb_i64(state, 3, "state"), _mb_i64(src, 1, "src")
+    for t, n, what in ((xb, rows * d, "xb"), (yb, rows, "yb"), (fidb, rows, "fidb")):
+        if not t.is_cuda or t.dtype != torch.float64 or not t.is_contiguous() or t.numel() != n:
+            raise _lib.MobocmfError("mobocmf_amd: %s must be a contiguous float64 GPU tensor of %d entries" % (what, n))
+    if y.numel() != N or fid.numel() != N:
+        raise _lib.MobocmfError("mobocmf_amd: minibatch_gather needs one y and one fidelity per row of x")
+    _lib.check(lib.mobocmf_minibatch_gather(N, d, rows, _ptr(x), _ptr(y), _ptr(fid), _ptr(src), _ptr(state), _ptr(xb), _ptr(yb),
+                                            _ptr(fidb), _stream()), "mobocmf_minibatch_gather (N = %d, d = %d)" % (N, d))
+
+
+def minibatch_accumulate(state, num_data, batch_size, loss, kl, sums):
+    """sums[0:2] += (loss, kl) of the step just taken (restarted at the first batch of an epoch); sums[2:4] = the sums of the
+    last finished epoch."""
+    lib = _lib.require_device()
+    _lib.check(lib.mobocmf_minibatch_accumulate(int(num_data), int(batch_size), _ptr(state), _ptr(loss), _ptr(kl), _ptr(sums),
+                                                _stream()), "mobocmf_minibatch_accumulate")
+
+
+def minibatch_check(state):
+    """Synchronising: raises if a launch of the sampler refused its batch (``state[2]`` set)."""
+    status = int(state[2])
+    if status != 0:
+        raise FloatingPointError("mini-batch sampler: %s (status = %d)" % (_lib.MINIBATCH_STATUS.get(status, "?"), status))
+
+
+def minibatch_permutation(seed, epoch, num_data):
+    """Host-side: the source rows of positions 0..num_data-1 of ``epoch`` (int64 CPU tensor), from the definition the index
+    launch uses -- which rows a step used, without asking the device.  Not a training path."""
+    lib = _lib.load()
+    out = torch.empty(int(num_data), dtype=torch.int64)
+    _lib.check(lib.mobocmf_minibatch_permutation_host(int(seed), int(epoch), int(num_data), ctypes.c_void_p(out.data_ptr())),
+               "mobocmf_minibatch_permutation_host")
+    return out
+
+
+# ------------------------------------------------------------------------------------------------------------
 # Exact-GP comparison baselines (SURVEY 8(f) N4) on the layer's kernels: Gram (mobocmf_gram_forward), the multi-fidelity
 # combination, the blocked Cholesky + triangular inverse of the chain, the triangular MFMA product with column statistics.
 # Evaluation only (no autograd): fitting the baselines' hyper-parameters differentiates the plain-torch statement.

@@ -68,6 +68,10 @@ class MFDGPHandler:
         self.num_data = x_train.shape[0]
         self.num_fidelities = num_fidelities
         self.global_index = None       # position among ALL objectives (or constraints) when surrogates are sharded over ranks
+        # the captured mini-batch step's sampler: int64 {seed, step, status} on the device, made at the first training phase and
+        # kept across phases; ``minibatch_seed`` (None: drawn from torch's CPU generator) fixes its seed
+        self.minibatch_seed = None
+        self.minibatch_state = None
 
 
 class BlackBoxMFDGPFitter:
@@ -304,17 +308,78 @@ class BlackBoxMFDGPFitter:
         step.stream.synchronize()
         return num_epochs, step
 
+    def _train_mfdgp_minibatch(self, fix_variational_hypers, num_epochs, lr):
+        """batch_size < num_data on a GPU: every surrogate's mini-batch step is captured (GraphedMiniBatchStep: the batch is
+        drawn, ordered and gathered on the device inside the graph) and the surrogates advance in lockstep on their streams.
+        An epoch is ``nb = ceil(num_data / batch_size)`` steps, as in the reference's loader loop (:156-173); each surrogate
+        has its own sampler state, so the batches it sees do not depend on which other surrogates train next to it.
+        Handlers share ``batch_size`` and the inputs, so either all of them are full-batch or none is; a handler whose batch
+        happened to cover its data would run here as one batch per epoch (nb = 1), correct but without the dead-row pruning
+        of the full-batch captured step."""
+        from .graphed_step import GraphedMiniBatchStep
+        from .. import functional as F
+        from ..layers.mfdgp_hidden_layer import NotPSDError
+        steps = []
+        for slot, (tag, n, h) in enumerate(self._handlers()):
+            h.mfdgp.fix_variational_hypers(fix_variational_hypers)
+            x, y, fid = h.train_dataset.tensors
+            for layer in h.mfdgp._layers():     # the layers' seeds first, then the sampler's: the order the step itself uses
+                layer._rng(x.device)
+            if h.minibatch_state is None or h.minibatch_state.device != x.device:
+                seed = h.minibatch_seed if h.minibatch_seed is not None else int(torch.randint(1, 2 ** 62, (), dtype=torch.int64))
+                h.minibatch_state = F.minibatch_state(seed, x.device)
+            steps.append((tag, n, GraphedMiniBatchStep(h.mfdgp, h.elbo, x, y, fid, h.batch_size, lr=lr,
+                                                       stream=self._stream_for(slot, x.device),
+                                                       sampler_state=h.minibatch_state)))
+        for _, _, g in steps:
+            g.snapshot()
+            g.last_good = -1
+        most = max(g.nb for _, _, g in steps)
+        for i in range(num_epochs):
+            for k in range(most):
+                for _, _, g in steps:
+                    if k < g.nb:
+                        g.step()
+            if (i % ITER_PRINT) == 0 or (i + 1) == num_epochs:
+                for tag, n, g in steps:
+                    try:
+                        g.check()
+                        g.snapshot()
+                        g.last_good = i
+                    except (NotPSDError, FloatingPointError) as err:
+                        # as the full-batch path: back to the last verified state (the sampler's included, so the same
+                        # batches are drawn again) and eagerly from there, with the per-step jitter ladder
+                        redo = i - g.last_good
+                        warnings.warn("%s %d: %s -- rolling back %d epochs and redoing them eagerly" % (tag, n, err, redo))
+                        g.restore_and_go_eager()
+                        for _ in range(redo * g.nb):
+                            g.step()
+                        g.check()
+                        g.snapshot()
+                        g.last_good = i
+                    if self.verbose:
+                        print("[%s: " % tag, n, "] Epoch:", i, "/", num_epochs, ". Avg. Neg. ELBO per epoch:",
+                              g.epoch_loss.item(), "\t KL per epoch:", g.epoch_kl.item())
+                        sys.stdout.flush()
+        for _, _, g in steps:
+            g.stream.synchronize()
+            g.model.set_check_pd(True)
+            g.retire()
+
     def train_mfdgps(self, use_graphs=None):
-        """2-phase Adam schedule of the reference (:175-176).  ``use_graphs`` (default: automatically when every
-        handler trains on the full batch, as all the reference's examples do) selects the HIP-graph fast path."""
+        """2-phase Adam schedule of the reference (:175-176).  ``use_graphs`` (default: on a GPU) selects the HIP-graph fast
+        path: the full-batch captured step when every handler trains on the full batch (as all the reference's examples
+        do), the captured mini-batch step (batches drawn on the device) when ``batch_size < num_data``.  ``use_graphs=False``
+        keeps the reference's host loader."""
         full_batch = all(h.batch_size >= h.num_data for _, _, h in self._handlers())
         if use_graphs is None:
-            use_graphs = full_batch and str(self.device).startswith("cuda")
-        if use_graphs and not full_batch:
-            raise ValueError("the graphed step needs batch_size >= number of training points")
-        if use_graphs:
+            use_graphs = str(self.device).startswith("cuda")
+        if use_graphs and full_batch:
             self._train_mfdgp_graphed(True, self.num_epochs_1, self.lr_1)
             self._train_mfdgp_graphed(False, self.num_epochs_2, self.lr_2)
+        elif use_graphs:      # the one-launch steps (TinyELBOStep / CoopELBOStep) are full-batch kernels: not taken here
+            self._train_mfdgp_minibatch(True, self.num_epochs_1, self.lr_1)
+            self._train_mfdgp_minibatch(False, self.num_epochs_2, self.lr_2)
         else:
             self._train_mfdgp(self.update_model, fix_variational_hypers=True, num_epochs=self.num_epochs_1, lr=self.lr_1)
             self._train_mfdgp(self.update_model, fix_variational_hypers=False, num_epochs=self.num_epochs_2, lr=self.lr_2)

@@ -6,6 +6,9 @@ dozen large GEMMs; issued eagerly from Python that costs ~2 ms of host time per 
 the small configurations (C1, C2) and half of what it needs at C3.  All library calls only enqueue work on the
 caller's stream and use caller-owned memory, so the whole step is capturable; a replay costs tens of microseconds.
 Fresh eps is drawn inside the graph (torch's captured Philox state advances on every replay).
+
+GraphedMiniBatchStep is the same step on a mini-batch that the step draws on the device (csrc/minibatch.hip): one captured graph
+per batch shape, a fresh batch at every replay.
 """
 import os
 
@@ -267,3 +270,169 @@ class GraphedConditionedStep(GraphedELBOStep):
         loss.backward()
         self.loss.copy_(loss.detach())
         self.model.clear_kl_cache()
+
+
+class _BatchShape:
+    """The static buffers (and the captured graph) of one batch size of GraphedMiniBatchStep."""
+
+    def __init__(self, rows, d, S, dev, fixed_eps, warm_step):
+        self.rows = rows
+        self.x = torch.zeros(rows, d, dtype=torch.float64, device=dev)
+        self.y = torch.zeros(rows, 1, dtype=torch.float64, device=dev)
+        self.fid = torch.zeros(rows, 1, dtype=torch.float64, device=dev)
+        self.src = torch.zeros(rows, dtype=torch.int64, device=dev)
+        self.loss = torch.zeros((), dtype=torch.float64, device=dev)
+        self.kl = torch.zeros((), dtype=torch.float64, device=dev)
+        # given per batch position for the full batch (batch_size * S per layer): the ragged batch uses its first rows * S
+        self.eps = None if fixed_eps is None else [None if e is None else e.reshape(-1)[:rows * S].contiguous()
+                                                   for e in fixed_eps]
+        self.warm_step = warm_step      # a step count whose batch has this many rows (warm-up runs on it)
+        self.graph = self.grads = None
+
+
+class GraphedMiniBatchStep(GraphedELBOStep):
+    """step() == one ELBO step on a mini-batch of ``batch_size`` rows that the step itself draws ON THE DEVICE
+    (functional.minibatch_indices / minibatch_gather: the loader of blackbox_mfdgp_fitter.py:35 and the batch loop :156-173):
+    a replay of the captured step sees a fresh batch without the host.  ``num_data // batch_size`` full batches and, when
+    ``batch_size`` does not divide ``num_data``, one ragged batch make an epoch.
+
+    Batch size, layer row counts and the ELBO's ``batch / num_data`` scale are host values baked into a capture, so the step
+    holds ONE GRAPH PER SHAPE (full, ragged) over the same model, optimiser (its step count lives on the device) and sampler
+    state; the host mirrors the step count to pick the graph, and the index launch checks the pick (``rows_expected``; a
+    mismatch sets the sampler's status, which ``check()`` raises on).  With ``order_by_fidelity`` the batch is ordered by
+    descending fidelity: the rows the upper layers do not need are contiguous, and the zero-gradient block skipping of the
+    layer backward drops their tiles (the forward stays dense over the batch: no ``rows=`` pruning, the per-fidelity counts
+    change from batch to batch).  ``fixed_eps`` is per batch POSITION (``batch_size * S`` per layer >= 1).
+
+    ``src`` / ``counts`` / ``grads``: source rows of the last batch, its per-level counts #{fid >= l} and its gradients (in the
+    order of ``model.parameters()``); ``epoch_loss`` / ``epoch_kl``:
+    the sums over the last finished epoch, accumulated on the device."""
+
+    def __init__(self, model, elbo, x, y, fidelities, batch_size, lr, betas=(0.9, 0.999), eps=1e-8, use_graph=True,
+                 stream=None, warmup=3, fixed_eps=None, order_by_fidelity=True, sampler_state=None):
+        from .. import _lib
+        from .. import functional as F
+        self.model, self.elbo = model, elbo
+        self.S = model.num_samples_for_training
+        self.L = model.num_hidden_layers
+        if self.L > _lib.MINIBATCH_MAX_LEVELS:
+            raise ValueError("the mini-batch step takes at most %d fidelities" % _lib.MINIBATCH_MAX_LEVELS)
+        self.layer_rows = self.row_order = None
+        self.x, self.y, self.fid = x.contiguous(), y.contiguous(), fidelities.contiguous()
+        dev = x.device
+        self.num_data = N = x.shape[0]
+        if int(elbo.num_data) != N:
+            raise ValueError("the ELBO scales the KL by batch / num_data: elbo.num_data must be the number of rows of x")
+        self.batch_size = B = max(1, min(int(batch_size), N))
+        self.nb = (N + B - 1) // B
+        self.order_by_fidelity = bool(order_by_fidelity)
+        self.use_graph = use_graph
+        self.stream = stream if stream is not None else torch.cuda.Stream(device=dev)
+        self.optimizer = F.FusedAdam([p for p in model.parameters()], lr=lr, betas=betas, eps=eps)
+        self._minus_one = torch.full((), -1.0, dtype=torch.float64, device=dev)
+        self.graph = self.graph_update = self._snap = None
+        self.fixed_eps = fixed_eps
+        model.set_check_pd(False)
+        model.clear_kl_cache()
+        for layer in model._layers():
+            layer._rng(dev)
+        if sampler_state is None:      # drawn once from torch's CPU generator, after the layers' streams (as layer._rng)
+            sampler_state = F.minibatch_state(int(torch.randint(1, 2 ** 62, (), dtype=torch.int64)), dev)
+        self.state = sampler_state
+        self._host_step = int(self.state[1])      # the host's mirror of the device step count: which graph to replay
+        d = x.shape[1]
+        ragged = N % B
+        self.shapes = [_BatchShape(B, d, self.S, dev, fixed_eps, 0)]
+        if ragged:
+            self.shapes.append(_BatchShape(ragged, d, self.S, dev, fixed_eps, self.nb - 1))
+        self._shape = self.shapes[0]
+        self.counts = torch.zeros(_lib.MINIBATCH_MAX_LEVELS, dtype=torch.int64, device=dev)
+        self.sums = torch.zeros(4, dtype=torch.float64, device=dev)
+        self.epoch_loss, self.epoch_kl = self.sums[2], self.sums[3]
+        self.loss, self.kl, self.src = self._shape.loss, self._shape.kl, self._shape.src
+        self.stream.wait_stream(torch.cuda.current_stream(dev))
+        if use_graph:
+            self._capture(warmup)
+
+    def _shape_for(self, step):
+        last = len(self.shapes) > 1 and step % self.nb == self.nb - 1
+        return self.shapes[1] if last else self.shapes[0]
+
+    def _fwd_bwd(self):
+        from .. import functional as F
+        b = self._shape
+        self.optimizer.zero_grad(set_to_none=True)
+        F.minibatch_indices(self.state, self.fid, self.batch_size, self.L, b.src, self.counts, self.order_by_fidelity)
+        F.minibatch_gather(self.state, b.src, self.x, self.y, self.fid, b.x, b.y, b.fid)
+        out = self.model(b.x, eps=b.eps)      # reference layout: every layer over the whole batch
+        res = self.elbo(out, b.y.T, b.fid)
+        res[0].backward(gradient=self._minus_one)
+        b.grads = [p.grad for p in self.model.parameters()]      # under capture: static, rewritten by every replay of this shape
+        neg = getattr(self.elbo, "last_neg_elbo", None)
+        if neg is not None:
+            b.loss, b.kl = neg, res[1].detach()
+        else:
+            torch.neg(res[0].detach(), out=b.loss)
+            b.kl.copy_(res[1].detach())
+        F.minibatch_accumulate(self.state, self.num_data, self.batch_size, b.loss, b.kl, self.sums)
+        self.model.clear_kl_cache()
+
+    def _capture_on_stream(self, warmup):
+        with torch.cuda.stream(self.stream):
+            snapshot = [p.detach().clone() for p in self.model.parameters()]
+            self._rng_snapshot = [(l, l._rng(self.x.device).clone()) for l in self.model._layers()]
+            state0, sums0 = self.state.clone(), self.sums.clone()
+            # BOTH shapes warm up and are captured before the first real step (_reset_after_warmup zeroes the optimiser
+            # state); a shape warms up on a step count whose batch has its rows, and the sampler state is put back afterwards
+            # like the layers' eps streams
+            for b in self.shapes:
+                warm = torch.tensor([int(state0[0]), b.warm_step, 0], dtype=torch.int64, device=self.x.device)
+                self._shape = b
+                for _ in range(warmup):
+                    self.state.copy_(warm)
+                    self._eager()
+            self._reset_after_warmup(snapshot)
+            self.state.copy_(state0)
+            self.sums.copy_(sums0)
+            for b in self.shapes:
+                self._shape = b
+                b.graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(b.graph, stream=self.stream, capture_error_mode="thread_local"):
+                    self._eager()
+            self.graph = self.shapes[0].graph
+
+    def retire(self):
+        for b in self.shapes:
+            b.graph = None
+        super().retire()
+
+    def step(self):
+        """Enqueues one mini-batch step on ``self.stream``; ``self.loss`` / ``self.kl`` / ``self.src`` are the batch's."""
+        b = self._shape_for(self._host_step)
+        with torch.cuda.stream(self.stream):
+            if self.graph is not None:
+                b.graph.replay()
+            else:          # the same launches, uncaptured
+                self._shape = b
+                self._eager()
+        self._host_step += 1
+        self.loss, self.kl, self.src, self.grads = b.loss, b.kl, b.src, b.grads
+        return self.loss, self.kl
+
+    def snapshot(self):
+        super().snapshot()
+        with torch.cuda.stream(self.stream):      # with the sampler: a rollback replays the same batches
+            self._snap_sampler = (self.state.clone(), self.sums.clone(), self._host_step)
+
+    def restore_and_go_eager(self):
+        state, sums, self._host_step = self._snap_sampler
+        with torch.cuda.stream(self.stream):      # the copies go where the next steps run
+            super().restore_and_go_eager()
+            self.state.copy_(state)
+            self.sums.copy_(sums)
+
+    def check(self):
+        from .. import functional as F
+        self.stream.synchronize()
+        F.minibatch_check(self.state)
+        super().check()
