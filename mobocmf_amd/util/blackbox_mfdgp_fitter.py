@@ -22,10 +22,70 @@ import numpy as np
 import torch
 from torch.utils.data import DataLoader, TensorDataset
 
+from .. import _lib, parallel
+from .. import functional as F
+from ..gp import MultivariateNormal as MVN
+from ..layers.mfdgp_hidden_layer import NotPSDError
 from ..mlls.variational_elbo_mf import VariationalELBOMF
 from ..models.mfdgp import MFDGP, TL
+from . import coop_step, graphed_step, tiny_step
 
 ITER_PRINT = 1000
+
+REDO_EAGERLY, HAND_OVER = "redo eagerly", "hand over"      # what run_verified does after a failed verdict
+
+
+def run_verified(steps, num_iters, on_failure, labels, unit, report=None):
+    """The training loop of every captured and one-launch path: ``num_iters`` iterations of the step objects in ``steps``
+    (GraphedELBOStep and its subclasses, TinyELBOStep and its: ``step / check / snapshot / restore... / close``), their state
+    verified on the host every ITER_PRINT iterations and after the last one -- nothing in between reads the device.
+
+    An iteration is ``g.nb`` steps of every ``g`` (1 where a step object has no ``nb``), the objects advancing in lockstep.
+    At a verification each object in turn is checked (``check`` synchronises its stream), snapshotted when it passed and
+    then reported (``report(i, j, g)``, None: silent); ``last_good`` is kept per object, so per surrogate where ``steps`` holds
+    one object per surrogate and per group where it holds one object for all of them.  When ``check`` raises NotPSDError or
+    FloatingPointError -- a replayed graph or a launch without the host in it cannot retry with more jitter -- the object goes
+    back to its last verified state and, with ``on_failure``
+      REDO_EAGERLY  redoes the iterations since then itself (``restore_and_go_eager``: per-step jitter ladder, as the reference
+                    at every step) and stays eager for the rest of the phase;
+      HAND_OVER     is closed and returned with the number of iterations that stand: the caller continues on another path.
+                    Takes a single object: others would be left where the iteration had taken them.
+    ``labels[j]`` opens object j's warning, ``unit`` names the iterations in it.  Returns (iterations completed, the object that
+    handed over or None); when all were completed every object has been closed."""
+    assert on_failure != HAND_OVER or len(steps) == 1
+    nbs = [getattr(g, "nb", 1) for g in steps]
+    last_good = [-1] * len(steps)          # last iteration whose state was verified
+    for g in steps:
+        g.snapshot()
+    for i in range(num_iters):
+        for k in range(max(nbs, default=0)):
+            for g, nb in zip(steps, nbs):
+                if k < nb:
+                    g.step()
+        if (i % ITER_PRINT) == 0 or (i + 1) == num_iters:
+            for j, (g, nb) in enumerate(zip(steps, nbs)):
+                try:
+                    g.check()
+                except (NotPSDError, FloatingPointError) as err:
+                    redo = i - last_good[j]
+                    msg = "%s%s -- rolling back %d %s" % (labels[j], err, redo, unit)
+                    if on_failure == HAND_OVER:
+                        warnings.warn(msg + "; the layer path continues")
+                        g.restore()
+                        g.close()
+                        return last_good[j] + 1, g
+                    warnings.warn(msg + " and redoing them eagerly")
+                    g.restore_and_go_eager()
+                    for _ in range(redo * nb):
+                        g.step()
+                    g.check()
+                g.snapshot()
+                last_good[j] = i
+                if report is not None:
+                    report(i, j, g)
+    for g in steps:
+        g.close()
+    return num_iters, None
 
 
 def _prod(t, dim):
@@ -149,8 +209,7 @@ class BlackBoxMFDGPFitter:
         opts = []
         for _, _, h in self._handlers():
             h.mfdgp.fix_variational_hypers(fix_variational_hypers)
-            from ..functional import FusedAdam
-            opts.append(FusedAdam(list(h.mfdgp.parameters()), lr=lr))      # torch.optim.Adam's update in one launch
+            opts.append(F.FusedAdam(list(h.mfdgp.parameters()), lr=lr))      # torch.optim.Adam's update in one launch
         for (tag, n, h), optimizer in zip(self._handlers(), opts):
             for i in range(num_epochs):
                 loss_iter, kl_iter = func_update_model(h.mfdgp, h.elbo, optimizer, h.train_loader)
@@ -208,7 +267,6 @@ class BlackBoxMFDGPFitter:
         after the other, :134-152; they share nothing, so the result only differs in which N(0,1) draws each gets).
         The rows are shuffled once (see the module docstring): the step runs GPyTorch's general branch, as the
         reference's shuffled batches do."""
-        from .graphed_step import GraphedELBOStep
         # the reference's own sizes (M = N = tens of points): every surrogate's whole step in ONE launch per epoch
         done, tiny = self._train_mfdgp_tiny(fix_variational_hypers, num_epochs, lr)
         if done >= num_epochs:
@@ -219,43 +277,24 @@ class BlackBoxMFDGPFitter:
             h.mfdgp.fix_variational_hypers(fix_variational_hypers)
             x, y, fid = h.train_dataset.tensors
             perm = self.shuffled_rows(x.shape[0], x.device)
-            steps.append((tag, n, GraphedELBOStep(h.mfdgp, h.elbo, x[perm].contiguous(), y[perm].contiguous(),
-                                                  fid[perm].contiguous(), lr=lr, stream=self._stream_for(slot, x.device))))
+            steps.append(graphed_step.GraphedELBOStep(h.mfdgp, h.elbo, x[perm].contiguous(), y[perm].contiguous(),
+                                                      fid[perm].contiguous(), lr=lr, stream=self._stream_for(slot, x.device)))
             if tiny is not None:      # a Cholesky failed in the one-launch step: this path (jitter ladder) takes over its state
-                tiny.export_adam_state(slot, steps[-1][2].optimizer)
-        from ..layers.mfdgp_hidden_layer import NotPSDError
-        for _, _, g in steps:
-            g.snapshot()
-            g.last_good = -1                # last epoch whose state was verified
-        for i in range(num_epochs):
-            for _, _, g in steps:
-                g.step()
-            if (i % ITER_PRINT) == 0 or (i + 1) == num_epochs:
-                for tag, n, g in steps:
-                    try:
-                        g.check()
-                        g.snapshot()
-                        g.last_good = i
-                    except (NotPSDError, FloatingPointError) as err:
-                        # a replayed graph cannot retry with more jitter: roll back to the last verified state and redo
-                        # the epochs since then eagerly (per-step jitter ladder, as the reference); the surrogate then
-                        # stays eager for the rest of the phase
-                        redo = i - g.last_good
-                        warnings.warn("%s %d: %s -- rolling back %d epochs and redoing them eagerly" % (tag, n, err, redo))
-                        g.restore_and_go_eager()
-                        for _ in range(redo):
-                            g.step()
-                        g.check()
-                        g.snapshot()
-                        g.last_good = i
-                    if self.verbose:
-                        print("[%s: " % tag, n, "] Epoch:", i, "/", num_epochs, ". Avg. Neg. ELBO per epoch:",
-                              g.loss.item(), "\t KL per epoch:", g.kl.item())
-                        sys.stdout.flush()
-        for _, _, g in steps:
-            g.stream.synchronize()
-            g.model.set_check_pd(True)
-            g.retire()
+                tiny.export_adam_state(slot, steps[-1].optimizer)
+        self._run_layer_path(steps, num_epochs, lambda g: (g.loss, g.kl))
+
+    def _run_layer_path(self, steps, num_epochs, loss_kl):
+        """run_verified over one step object per surrogate, each redoing its own lost epochs; ``loss_kl(g)``: what to print."""
+        hs = self._handlers()
+        report = lambda i, j, g: self._print_epoch(hs[j][0], hs[j][1], i, num_epochs, *loss_kl(g))
+        run_verified(steps, num_epochs, REDO_EAGERLY, ["%s %d: " % (tag, n) for tag, n, _ in hs], "epochs",
+                     report if self.verbose else None)
+
+    @staticmethod
+    def _print_epoch(tag, n, i, num_epochs, loss, kl):
+        print("[%s: " % tag, n, "] Epoch:", i, "/", num_epochs, ". Avg. Neg. ELBO per epoch:", loss.item(),
+              "\t KL per epoch:", kl.item())
+        sys.stdout.flush()
 
     use_tiny_step = True      # False: always the layer path (A/B, tests)
 
@@ -264,9 +303,6 @@ class BlackBoxMFDGPFitter:
         per epoch for all of them.  Returns (epochs completed, step object or None): fewer than ``num_epochs`` when the
         surrogates do not fit (0, None) or when a Cholesky failed -- the state is then rolled back to the last verified epoch
         and the layer path, which can retry with more jitter as the reference does at every step, continues from there."""
-        from . import coop_step
-        from .tiny_step import TinyELBOStep, eligible
-        from ..layers.mfdgp_hidden_layer import NotPSDError
         hs = self._handlers()
         if not self.use_tiny_step or not hs:
             return 0, None
@@ -275,8 +311,8 @@ class BlackBoxMFDGPFitter:
         data = [h.train_dataset.tensors for _, _, h in hs]
         # M <= 32 and narrow panels: one workgroup per surrogate (csrc/tiny_step.hip); up to M = 128: several workgroups per
         # surrogate, MFMA products (csrc/coop_step.hip); beyond that, or for wide panels, the layer path
-        if all(x.is_cuda and eligible(h.mfdgp, x, fid) for (_, _, h), (x, _, fid) in zip(hs, data)):
-            cls = TinyELBOStep
+        if all(x.is_cuda and tiny_step.eligible(h.mfdgp, x, fid) for (_, _, h), (x, _, fid) in zip(hs, data)):
+            cls = tiny_step.TinyELBOStep
         elif all(x.is_cuda and coop_step.worthwhile(h.mfdgp, x, fid) for (_, _, h), (x, _, fid) in zip(hs, data)):
             cls = coop_step.CoopELBOStep
         else:
@@ -285,28 +321,13 @@ class BlackBoxMFDGPFitter:
         step = cls([h.mfdgp for _, _, h in hs], [h.num_data for _, _, h in hs], [t[0] for t in data],
                    [t[1] for t in data], [t[2] for t in data], lr=lr, stream=self._stream_for(0, dev))
         step.stream.wait_stream(torch.cuda.current_stream(dev))
-        step.snapshot()
-        last_good = -1
-        for i in range(num_epochs):
-            step.step()
-            if (i % ITER_PRINT) == 0 or (i + 1) == num_epochs:
-                try:
-                    step.check()
-                except (NotPSDError, FloatingPointError) as err:
-                    warnings.warn("%s -- rolling back %d epochs; the layer path continues" % (err, i - last_good))
-                    step.restore()
-                    torch.cuda.current_stream(dev).wait_stream(step.stream)
-                    return last_good + 1, step
-                step.snapshot()
-                last_good = i
-                if self.verbose:
-                    out = step.losses.cpu()
-                    for k, (tag, n, _) in enumerate(hs):
-                        print("[%s: " % tag, n, "] Epoch:", i, "/", num_epochs, ". Avg. Neg. ELBO per epoch:",
-                              out[k, 2].item(), "\t KL per epoch:", out[k, 1].item())
-                    sys.stdout.flush()
-        step.stream.synchronize()
-        return num_epochs, step
+
+        def report(i, _, step):
+            out = step.losses.cpu()
+            for k, (tag, n, _) in enumerate(hs):
+                self._print_epoch(tag, n, i, num_epochs, out[k, 2], out[k, 1])
+
+        return run_verified([step], num_epochs, HAND_OVER, [""], "epochs", report if self.verbose else None)[0], step
 
     def _train_mfdgp_minibatch(self, fix_variational_hypers, num_epochs, lr):
         """batch_size < num_data on a GPU: every surrogate's mini-batch step is captured (GraphedMiniBatchStep: the batch is
@@ -316,9 +337,6 @@ class BlackBoxMFDGPFitter:
         Handlers share ``batch_size`` and the inputs, so either all of them are full-batch or none is; a handler whose batch
         happened to cover its data would run here as one batch per epoch (nb = 1), correct but without the dead-row pruning
         of the full-batch captured step."""
-        from .graphed_step import GraphedMiniBatchStep
-        from .. import functional as F
-        from ..layers.mfdgp_hidden_layer import NotPSDError
         steps = []
         for slot, (tag, n, h) in enumerate(self._handlers()):
             h.mfdgp.fix_variational_hypers(fix_variational_hypers)
@@ -328,43 +346,11 @@ class BlackBoxMFDGPFitter:
             if h.minibatch_state is None or h.minibatch_state.device != x.device:
                 seed = h.minibatch_seed if h.minibatch_seed is not None else int(torch.randint(1, 2 ** 62, (), dtype=torch.int64))
                 h.minibatch_state = F.minibatch_state(seed, x.device)
-            steps.append((tag, n, GraphedMiniBatchStep(h.mfdgp, h.elbo, x, y, fid, h.batch_size, lr=lr,
-                                                       stream=self._stream_for(slot, x.device),
-                                                       sampler_state=h.minibatch_state)))
-        for _, _, g in steps:
-            g.snapshot()
-            g.last_good = -1
-        most = max(g.nb for _, _, g in steps)
-        for i in range(num_epochs):
-            for k in range(most):
-                for _, _, g in steps:
-                    if k < g.nb:
-                        g.step()
-            if (i % ITER_PRINT) == 0 or (i + 1) == num_epochs:
-                for tag, n, g in steps:
-                    try:
-                        g.check()
-                        g.snapshot()
-                        g.last_good = i
-                    except (NotPSDError, FloatingPointError) as err:
-                        # as the full-batch path: back to the last verified state (the sampler's included, so the same
-                        # batches are drawn again) and eagerly from there, with the per-step jitter ladder
-                        redo = i - g.last_good
-                        warnings.warn("%s %d: %s -- rolling back %d epochs and redoing them eagerly" % (tag, n, err, redo))
-                        g.restore_and_go_eager()
-                        for _ in range(redo * g.nb):
-                            g.step()
-                        g.check()
-                        g.snapshot()
-                        g.last_good = i
-                    if self.verbose:
-                        print("[%s: " % tag, n, "] Epoch:", i, "/", num_epochs, ". Avg. Neg. ELBO per epoch:",
-                              g.epoch_loss.item(), "\t KL per epoch:", g.epoch_kl.item())
-                        sys.stdout.flush()
-        for _, _, g in steps:
-            g.stream.synchronize()
-            g.model.set_check_pd(True)
-            g.retire()
+            steps.append(graphed_step.GraphedMiniBatchStep(h.mfdgp, h.elbo, x, y, fid, h.batch_size, lr=lr,
+                                                           stream=self._stream_for(slot, x.device),
+                                                           sampler_state=h.minibatch_state))
+        # a rollback takes the sampler's state back too, so the redone epochs draw the same batches again
+        self._run_layer_path(steps, num_epochs, lambda g: (g.epoch_loss, g.epoch_kl))
 
     def train_mfdgps(self, use_graphs=None):
         """2-phase Adam schedule of the reference (:175-176).  ``use_graphs`` (default: on a GPU) selects the HIP-graph fast
@@ -420,7 +406,6 @@ class BlackBoxMFDGPFitter:
         ``rng`` pass through).  With a process group (black-boxes sharded over ranks) or a ``seed``: the seeded joint
         procedure of ``_sample_and_store_pareto_solution_seeded``, identical on every rank and independent of the sharding;
         with a group and no seed, rank 0 draws the seed from torch's global generator and broadcasts it."""
-        from .. import parallel
         from .moop import NotFeasiblePoints
         seeded = seed is not None or not parallel._no_group()
         if seeded:
@@ -469,7 +454,6 @@ class BlackBoxMFDGPFitter:
     def _agree(self, code, res, n_obj, d):
         """One status word per rank, all-gathered; rank 0's result broadcast (row count first, then set and front in one
         buffer).  Every rank makes the same collective calls whatever happened locally."""
-        from .. import parallel
         dev = parallel._exchange_device() if not parallel._no_group() else torch.device("cpu")
         P = int(res[0].shape[0]) if (code == self._FEASIBLE and res is not None) else 0
         status = torch.cat(parallel.all_gather_ragged(torch.tensor([[float(code), float(P)]], dtype=torch.float64,
@@ -500,7 +484,6 @@ class BlackBoxMFDGPFitter:
         group every exchange is the identity and the result is the same as with the black-boxes split over ranks.
         ``attempt`` (the retries after NotFeasiblePoints) moves the tries to fresh numbers."""
         import hashlib
-        from .. import parallel
         from ..layers.rff import RFFChainSample
         from .moop import MOOP, NotFeasiblePoints
         inputs = np.ascontiguousarray(self.x_train.detach().cpu().double().numpy())
@@ -581,7 +564,6 @@ class BlackBoxMFDGPFitter:
     def loss_theta_factors(self, cs_mean, cs_var, threshold):
         """:227-233.  On the GPU one launch (functional.cond_factors); host tensors: the plain torch statement."""
         if cs_mean.is_cuda:
-            from .. import functional as F
             thr = threshold.reshape(1) if torch.is_tensor(threshold) else torch.tensor([float(threshold)], dtype=cs_mean.dtype,
                                                                                      device=cs_mean.device)
             return F.cond_factors([], [], [cs_mean.reshape(-1)], [cs_var.reshape(-1)], None, thr,
@@ -600,7 +582,6 @@ class BlackBoxMFDGPFitter:
             raise ValueError("omega factors: %d constraint rows but %d thresholds (sharded surrogates need "
                              "set_global_constraint_thresholds)" % (len(cm), thr.numel()))
         if ref.is_cuda and len(fm) <= 8 and len(cm) <= 8:
-            from .. import functional as F
             front = self._cached_const(("front", id(pareto_front)), lambda: pareto_front.contiguous())
             return F.cond_factors(fm, fv, cm, cv, front, thr, float(np.log(self.eps)), float(np.log(1.0 - self.eps)))
         fs_mean, fs_var = torch.stack(fm), torch.stack(fv)
@@ -632,9 +613,6 @@ class BlackBoxMFDGPFitter:
         instead of three.  ``eps``: optional {name: [None, eps_l1, ...]} with draws for the concatenated rows.
         With surrogates sharded over ranks the omega factors need every model's (mean, var) at x_tilde: the local ones
         carry gradient, the others arrive as constants through one all-gather (mobocmf_amd.parallel)."""
-        from .. import parallel
-        from .. import functional as F
-        from ..gp import MultivariateNormal as MVN
         P, T = self.pareto_set.shape[0], x_tilde.shape[0]
         # The loss is a signed sum of scalar terms.  They are collected and combined in ONE launch at the end, the rows of every
         # layer's moments are split into their three ranges (training batch | Pareto set | x~) by one autograd node per layer,
@@ -701,9 +679,6 @@ class BlackBoxMFDGPFitter:
         """ONE Adam over all models' parameters, kernel hyper-parameters frozen (:245-268, :345-354).  On the GPU the
         whole iteration (x~ draw, joint loss over all surrogates, backward, Adam) is replayed from a HIP graph; a failed
         Cholesky inside a replay rolls back to the last verified state and continues eagerly (jitter ladder)."""
-        from .. import parallel
-        from ..layers.mfdgp_hidden_layer import NotPSDError
-        from .graphed_step import GraphedConditionedStep
         for _, _, h in self._handlers():
             h.mfdgp.fix_variational_hypers_cond(True)
         num_iters = self.num_epochs_2 if num_iters is None else num_iters
@@ -719,35 +694,14 @@ class BlackBoxMFDGPFitter:
             done, tiny = self._train_conditioned_tiny(num_iters)
             num_iters -= done
         if num_iters > 0:
-            step = GraphedConditionedStep(self, lr=self.lr_2, use_graph=use_graphs,
-                                          stream=self._stream_for(0, self.pareto_set.device) if self.pareto_set.is_cuda else None)
+            step = graphed_step.GraphedConditionedStep(self, lr=self.lr_2, use_graph=use_graphs,
+                                                       stream=self._stream_for(0, self.pareto_set.device)
+                                                       if self.pareto_set.is_cuda else None)
             if tiny is not None:      # a Cholesky failed there: this path (jitter ladder) continues with its optimiser state
                 for k in range(len(tiny.models)):
                     tiny.export_adam_state(k, step.optimizer)
-            step.snapshot()
-        last_good = -1
-        for i in range(num_iters):
-            step.step()
-            if (i % ITER_PRINT) == 0 or (i + 1) == num_iters:
-                try:
-                    step.check()
-                    step.snapshot()
-                except (NotPSDError, FloatingPointError) as err:
-                    warnings.warn("conditioned training: %s -- rolling back %d iterations and redoing them eagerly" %
-                                  (err, i - last_good))
-                    step.restore_and_go_eager()
-                    for _ in range(i - last_good):
-                        step.step()
-                    step.check()
-                    step.snapshot()
-                last_good = i
-                if self.verbose:
-                    print("Iter:", i, "/", num_iters, ". Neg. ELBO per iter:", step.loss.item())
-                    sys.stdout.flush()
-        if num_iters > 0:
-            step.stream.synchronize()
-            torch.cuda.current_stream(self.pareto_set.device).wait_stream(step.stream)
-            step.retire()
+            run_verified([step], num_iters, REDO_EAGERLY, ["conditioned training: "], "iterations",
+                         self._report_iter(num_iters))
         for _, _, h in self._handlers():
             h.iter_train_loader = None
             h.mfdgp.set_check_pd(True)
@@ -756,13 +710,10 @@ class BlackBoxMFDGPFitter:
         """Conditioned training through TinyConditionedStep when every surrogate fits it.  Returns (iterations completed, step
         or None): fewer than ``num_iters`` when the surrogates do not fit (0, None) or after a failed Cholesky (state rolled
         back to the last verified iteration; the layer path continues)."""
-        from .. import _lib
-        from ..layers.mfdgp_hidden_layer import NotPSDError
-        from .coop_step import CoopConditionedStep
-        from .tiny_step import TinyConditionedStep
         dev = self.pareto_set.device
         step = None
-        for cls in (TinyConditionedStep, CoopConditionedStep):      # M <= 32 in one workgroup per surrogate, M <= 128 in several
+        # M <= 32 in one workgroup per surrogate, M <= 128 in several
+        for cls in (tiny_step.TinyConditionedStep, coop_step.CoopConditionedStep):
             try:
                 step = cls(self, lr=self.lr_2, stream=self._stream_for(0, dev))
                 break
@@ -771,27 +722,15 @@ class BlackBoxMFDGPFitter:
         if step is None:
             return 0, None
         step.stream.wait_stream(torch.cuda.current_stream(dev))
-        step.snapshot()
-        last_good = -1
-        for i in range(num_iters):
-            step.step()
-            if (i % ITER_PRINT) == 0 or (i + 1) == num_iters:
-                try:
-                    step.check()
-                except (NotPSDError, FloatingPointError) as err:
-                    warnings.warn("conditioned training: %s -- rolling back %d iterations; the layer path continues" %
-                                  (err, i - last_good))
-                    step.restore()
-                    torch.cuda.current_stream(dev).wait_stream(step.stream)
-                    return last_good + 1, step
-                step.snapshot()
-                last_good = i
-                if self.verbose:
-                    print("Iter:", i, "/", num_iters, ". Neg. ELBO per iter:", step.loss.item())
-                    sys.stdout.flush()
-        step.stream.synchronize()
-        torch.cuda.current_stream(dev).wait_stream(step.stream)
-        return num_iters, step
+        return run_verified([step], num_iters, HAND_OVER, ["conditioned training: "], "iterations",
+                            self._report_iter(num_iters))[0], step
+
+    def _report_iter(self, num_iters):
+        """run_verified's ``report`` of the conditioned drivers (None when not verbose)."""
+        def report(i, _, step):
+            print("Iter:", i, "/", num_iters, ". Neg. ELBO per iter:", step.loss.item())
+            sys.stdout.flush()
+        return report if self.verbose else None
 
     # ------------------------------------------------------------------ recommendation (the reference's BO driver)
     def recommend(self, grid, min_feasible_prob=0.999, output_scaling=None):
@@ -807,8 +746,6 @@ class BlackBoxMFDGPFitter:
         the same result.  Returns (pareto_set (P, d) ndarray, predicted_front (P, n_obj) ndarray, info dict with the grid
         mask and the counts of feasible, front and NaN rows).  Raises when a feasible row has a NaN predicted objective,
         and on every rank when any rank failed to predict."""
-        from .. import _lib, parallel
-        from .. import functional as F
         _lib.require_device()
         dev = torch.device(self.device)
         if dev.type != "cuda":

@@ -14,6 +14,10 @@ import os
 
 import torch
 
+from .. import _lib
+from .. import functional as F
+from ..layers.mfdgp_hidden_layer import NotPSDError
+
 
 class GraphedELBOStep:
     """step() == one full-batch ELBO step on static (x, y, fidelities).  Falls back to eager with ``use_graph=False``.
@@ -24,7 +28,7 @@ class GraphedELBOStep:
 
     def __init__(self, model, elbo, x, y, fidelities, lr, betas=(0.9, 0.999), eps=1e-8, use_graph=True, stream=None,
                  warmup=3, fixed_eps=None, prune_rows=True):
-        self.model, self.elbo = model, elbo
+        self.elbo = elbo
         self.S = model.num_samples_for_training
         self.L = model.num_hidden_layers
         # Dead rows: the ELBO keeps, per layer, the rows of that layer's fidelity (variational_elbo_mf.py:33-38), so a row of
@@ -34,8 +38,7 @@ class GraphedELBOStep:
         # Same ELBO and gradients as evaluating every layer at every row; the upper layers' panels shrink to their share.
         self.layer_rows = None
         self.row_order = None      # permutation applied to the caller's rows (None: kept): step.x == x[row_order]
-        from ..functional import ELBO_MAX_LAYERS
-        if prune_rows and self.L > ELBO_MAX_LAYERS:
+        if prune_rows and self.L > F.ELBO_MAX_LAYERS:
             prune_rows = False     # pruned layer outputs need the fused ELBO (<= ELBO_MAX_LAYERS fidelities): reference layout
         if prune_rows and self.L > 1:
             fidv = fidelities.reshape(-1)
@@ -50,27 +53,33 @@ class GraphedELBOStep:
                 self.layer_rows = counts
                 self.row_order = order
         self.x, self.y, self.fid = x, y, fidelities
-        self.use_graph = use_graph
-        self.stream = stream if stream is not None else torch.cuda.Stream(device=x.device)
-        params = [p for p in model.parameters()]
-        from ..functional import FusedAdam
-        if os.environ.get("MOBOCMF_TORCH_ADAM"):      # A/B knob: torch's capturable Adam (seven foreach launches)
-            self.optimizer = torch.optim.Adam(params, lr=lr, betas=betas, eps=eps, capturable=True)
-        else:
-            self.optimizer = FusedAdam(params, lr=lr, betas=betas, eps=eps)     # one launch; step count on the device
-        self.loss = torch.zeros((), dtype=torch.float64, device=x.device)
-        self._minus_one = torch.full((), -1.0, dtype=torch.float64, device=x.device)
-        self.kl = torch.zeros((), dtype=torch.float64, device=x.device)
-        self.graph = None
-        self.graph_update = None
-        self._snap = None
         self.fixed_eps = fixed_eps     # list (eps[l] for layer l >= 1) reused every step: deterministic tests
+        optimizer = None
+        if os.environ.get("MOBOCMF_TORCH_ADAM"):      # A/B knob: torch's capturable Adam (seven foreach launches)
+            optimizer = torch.optim.Adam(list(model.parameters()), lr=lr, betas=betas, eps=eps, capturable=True)
+        self._setup(model, x.device, lr, betas, eps, use_graph, stream, optimizer=optimizer)
+        if use_graph:
+            self._capture(warmup)
+
+    def _setup(self, model, device, lr, betas, eps, use_graph, stream, optimizer=None):
+        """What every captured step starts from, whatever its loss: stream, optimiser, loss / KL buffers, empty graph and
+        snapshot slots, the model(s) put into the no-host-sync state, the layers' eps streams seeded.  Not every subclass uses
+        all of it: the conditioned step's backward needs no ``_minus_one``, and the mini-batch step rebinds ``loss`` / ``kl`` to
+        its batch shapes' buffers."""
+        self.model = model
+        self.use_graph = use_graph
+        self.stream = stream if stream is not None else torch.cuda.Stream(device=device)
+        if optimizer is None:          # one launch; step count on the device
+            optimizer = F.FusedAdam(list(model.parameters()), lr=lr, betas=betas, eps=eps)
+        self.optimizer = optimizer
+        self.loss = torch.zeros((), dtype=torch.float64, device=device)
+        self.kl = torch.zeros((), dtype=torch.float64, device=device)
+        self._minus_one = torch.full((), -1.0, dtype=torch.float64, device=device)
+        self.graph = self.graph_update = self._snap = None
         model.set_check_pd(False)      # no host sync inside the step; call check() when a verdict is needed
         model.clear_kl_cache()         # an older graph would pin AccumulateGrad nodes to another stream (capture-illegal)
         for layer in model._layers():  # the layers' eps streams get their seeds here, in a fixed order, eager or captured
-            layer._rng(x.device)
-        if use_graph:
-            self._capture(warmup)
+            layer._rng(device)
 
     def _fwd_bwd(self):
         self.optimizer.zero_grad(set_to_none=True)
@@ -80,13 +89,17 @@ class GraphedELBOStep:
         res = self.elbo(out, self.y.T, self.fid)
         # d(-ELBO): the sign goes in as the upstream gradient (no negation node, no ones fill, no negation backward)
         res[0].backward(gradient=self._minus_one)
+        self._record_loss(res, self)
+        self.model.clear_kl_cache()
+
+    def _record_loss(self, res, dst):
+        """The step's -ELBO and scaled KL, from the ELBO's result ``res``, into ``dst.loss`` / ``dst.kl``."""
         neg = getattr(self.elbo, "last_neg_elbo", None)
         if neg is not None:      # the fused ELBO launch wrote -elbo next to elbo: no negation / copy launches
-            self.loss, self.kl = neg, res[1].detach()
+            dst.loss, dst.kl = neg, res[1].detach()
         else:
-            torch.neg(res[0].detach(), out=self.loss)
-            self.kl.copy_(res[1].detach())
-        self.model.clear_kl_cache()
+            torch.neg(res[0].detach(), out=dst.loss)
+            dst.kl.copy_(res[1].detach())
 
     def _exchange(self):
         """Between backward and the update; a no-op for a surrogate that lives on one GPU (RowShardedELBOStep
@@ -101,7 +114,6 @@ class GraphedELBOStep:
         self._update()
 
     def _capture(self, warmup):
-        from .. import functional as F
         cur = torch.cuda.current_stream(self.x.device)
         self.stream.wait_stream(cur)
         F.take_capture_pins()          # pins left behind by a capture that aborted elsewhere are not this graph's
@@ -113,13 +125,18 @@ class GraphedELBOStep:
             self._pinned_scratch = F.take_capture_pins()
         cur.wait_stream(self.stream)
 
+    def _snapshot_before_warmup(self):
+        """The parameters (returned) and the layers' eps streams (seed, call counter) as ``_reset_after_warmup`` puts them
+        back: warm-up draws must not count either -- the first replay then draws exactly what the first eager step would
+        have drawn."""
+        snapshot = [p.detach().clone() for p in self.model.parameters()]
+        self._rng_snapshot = [(l, l._rng(self.x.device).clone()) for l in self.model._layers()]
+        return snapshot
+
     def _capture_on_stream(self, warmup):
         with torch.cuda.stream(self.stream):
             # the side-stream warm-up also sizes the per-stream scratch arena and the optimizer state
-            snapshot = [p.detach().clone() for p in self.model.parameters()]
-            # the layers' eps streams (seed, call counter): warm-up draws must not count either -- the first replay then
-            # draws exactly what the first eager step would have drawn
-            self._rng_snapshot = [(l, l._rng(self.x.device).clone()) for l in self.model._layers()]
+            snapshot = self._snapshot_before_warmup()
             for _ in range(warmup):
                 self._eager()
             self._reset_after_warmup(snapshot)
@@ -150,12 +167,20 @@ class GraphedELBOStep:
             self.optimizer.zero_grad(set_to_none=True)
 
     def retire(self):
-        """Drop the graph and this step's entry in the scratch arena (the fitter calls it when a training phase ends)."""
-        from .. import functional as F
+        """Drop the graph and this step's entry in the scratch arena (``close`` calls it when a training phase ends)."""
         self.stream.synchronize()
         self.graph = self.graph_update = None
         self._pinned_scratch = None
         F.release_scratch(self.stream)
+
+    def close(self):
+        """The end of a training phase: the models check their Choleskys on the host again, the graph goes, and the current
+        stream continues after everything this step enqueued.  (The stream is idle before a subclass's ``retire`` drops its
+        graphs; ``retire`` synchronises again for the callers that use it alone.)"""
+        self.stream.synchronize()
+        self.model.set_check_pd(True)
+        self.retire()
+        torch.cuda.current_stream(self.x.device).wait_stream(self.stream)
 
     def step(self):
         """Enqueues one step on ``self.stream``; ``self.loss`` / ``self.kl`` hold the step's -ELBO and scaled KL."""
@@ -195,8 +220,6 @@ class GraphedELBOStep:
 
     def check(self):
         """Synchronising: raises if a Cholesky of the last step failed or the loss is not finite."""
-        from .. import functional as F
-        from ..layers.mfdgp_hidden_layer import NotPSDError
         self.stream.synchronize()
         for layer in self.model._layers():
             if layer._info is not None:
@@ -240,22 +263,10 @@ class GraphedConditionedStep(GraphedELBOStep):
                  fixed_x_tilde=None):
         self.fitter = fitter
         self.fixed_x_tilde = fixed_x_tilde      # deterministic tests: the same x~ at every iteration
-        models = [h.mfdgp for _, _, h in fitter._handlers()]
-        self.model = _ModelGroup(models)
         dev = fitter.pareto_set.device
         self.device, self.d, self.n_tilde = dev, fitter.pareto_set.shape[1], n_tilde
-        self.use_graph = use_graph
-        self.stream = stream if stream is not None else torch.cuda.Stream(device=dev)
-        from ..functional import FusedAdam
-        self.optimizer = FusedAdam(list(self.model.parameters()), lr=lr, betas=betas, eps=eps)
-        self.loss = torch.zeros((), dtype=torch.float64, device=dev)
-        self.kl = torch.zeros((), dtype=torch.float64, device=dev)
-        self.graph = self.graph_update = self._snap = None
         self.x = fitter.pareto_set            # (only its device is used by the base class)
-        self.model.set_check_pd(False)
-        self.model.clear_kl_cache()
-        for layer in self.model._layers():
-            layer._rng(dev)
+        self._setup(_ModelGroup(h.mfdgp for _, _, h in fitter._handlers()), dev, lr, betas, eps, use_graph, stream)
         if use_graph:
             self._capture(warmup)
 
@@ -310,9 +321,7 @@ class GraphedMiniBatchStep(GraphedELBOStep):
 
     def __init__(self, model, elbo, x, y, fidelities, batch_size, lr, betas=(0.9, 0.999), eps=1e-8, use_graph=True,
                  stream=None, warmup=3, fixed_eps=None, order_by_fidelity=True, sampler_state=None):
-        from .. import _lib
-        from .. import functional as F
-        self.model, self.elbo = model, elbo
+        self.elbo = elbo
         self.S = model.num_samples_for_training
         self.L = model.num_hidden_layers
         if self.L > _lib.MINIBATCH_MAX_LEVELS:
@@ -326,16 +335,8 @@ class GraphedMiniBatchStep(GraphedELBOStep):
         self.batch_size = B = max(1, min(int(batch_size), N))
         self.nb = (N + B - 1) // B
         self.order_by_fidelity = bool(order_by_fidelity)
-        self.use_graph = use_graph
-        self.stream = stream if stream is not None else torch.cuda.Stream(device=dev)
-        self.optimizer = F.FusedAdam([p for p in model.parameters()], lr=lr, betas=betas, eps=eps)
-        self._minus_one = torch.full((), -1.0, dtype=torch.float64, device=dev)
-        self.graph = self.graph_update = self._snap = None
         self.fixed_eps = fixed_eps
-        model.set_check_pd(False)
-        model.clear_kl_cache()
-        for layer in model._layers():
-            layer._rng(dev)
+        self._setup(model, dev, lr, betas, eps, use_graph, stream)
         if sampler_state is None:      # drawn once from torch's CPU generator, after the layers' streams (as layer._rng)
             sampler_state = F.minibatch_state(int(torch.randint(1, 2 ** 62, (), dtype=torch.int64)), dev)
         self.state = sampler_state
@@ -359,7 +360,6 @@ class GraphedMiniBatchStep(GraphedELBOStep):
         return self.shapes[1] if last else self.shapes[0]
 
     def _fwd_bwd(self):
-        from .. import functional as F
         b = self._shape
         self.optimizer.zero_grad(set_to_none=True)
         F.minibatch_indices(self.state, self.fid, self.batch_size, self.L, b.src, self.counts, self.order_by_fidelity)
@@ -368,19 +368,13 @@ class GraphedMiniBatchStep(GraphedELBOStep):
         res = self.elbo(out, b.y.T, b.fid)
         res[0].backward(gradient=self._minus_one)
         b.grads = [p.grad for p in self.model.parameters()]      # under capture: static, rewritten by every replay of this shape
-        neg = getattr(self.elbo, "last_neg_elbo", None)
-        if neg is not None:
-            b.loss, b.kl = neg, res[1].detach()
-        else:
-            torch.neg(res[0].detach(), out=b.loss)
-            b.kl.copy_(res[1].detach())
+        self._record_loss(res, b)
         F.minibatch_accumulate(self.state, self.num_data, self.batch_size, b.loss, b.kl, self.sums)
         self.model.clear_kl_cache()
 
     def _capture_on_stream(self, warmup):
         with torch.cuda.stream(self.stream):
-            snapshot = [p.detach().clone() for p in self.model.parameters()]
-            self._rng_snapshot = [(l, l._rng(self.x.device).clone()) for l in self.model._layers()]
+            snapshot = self._snapshot_before_warmup()
             state0, sums0 = self.state.clone(), self.sums.clone()
             # BOTH shapes warm up and are captured before the first real step (_reset_after_warmup zeroes the optimiser
             # state); a shape warms up on a step count whose batch has its rows, and the sampler state is put back afterwards
@@ -432,7 +426,6 @@ class GraphedMiniBatchStep(GraphedELBOStep):
             self.sums.copy_(sums)
 
     def check(self):
-        from .. import functional as F
         self.stream.synchronize()
         F.minibatch_check(self.state)
         super().check()

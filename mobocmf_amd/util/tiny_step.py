@@ -358,6 +358,12 @@ class TinyELBOStep:
             for layer, s0 in zip([l for m in self.models for l in m._layers()], rngs):
                 layer._rng(self.device).copy_(s0)
 
+    def close(self):
+        """The end of this step's part of a training phase (finished, or rolled back for the layer path to continue): the
+        current stream goes on after everything the step enqueued.  The object stays usable (``export_adam_state``)."""
+        self.stream.synchronize()
+        torch.cuda.current_stream(self.device).wait_stream(self.stream)
+
     def export_adam_state(self, i, optimizer):
         """Copies model i's moment estimates and step count into a FusedAdam over ``list(models[i].parameters())`` (the
         layer-path step that takes over after a failed Cholesky keeps the optimiser's memory)."""

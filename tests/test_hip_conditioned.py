@@ -89,6 +89,73 @@ def test_conditioned_training_runs_and_reduces_the_loss():
     assert fc.pareto_set is not fitter.pareto_set
 
 
+def _conditioned_fitter_with_a_failing_verdict(monkeypatch, cls):
+    """A fitter ready for conditioned training whose second verdict through ``cls.check`` fails -- on the host: the exception is
+    injected, nothing is faulted on the device -- and the GraphedConditionedStep objects that training constructs."""
+    from mobocmf_amd.layers.mfdgp_hidden_layer import NotPSDError
+    from mobocmf_amd.util import blackbox_mfdgp_fitter as BF
+    from mobocmf_amd.util import graphed_step
+    monkeypatch.setattr(BF, "ITER_PRINT", 4)
+    fitter, _ = _fitter(2, 1, 12)
+    g = torch.Generator().manual_seed(1)
+    fitter.set_pareto_solution(torch.rand(5, 2, dtype=torch.float64, generator=g),
+                               torch.randn(5, 2, dtype=torch.float64, generator=g) * 0.3)
+    fitter.lr_2 = 5e-3
+    calls = {"n": 0}
+    real_check = cls.check
+
+    def failing_check(self):
+        calls["n"] += 1
+        if calls["n"] == 2:      # the verdict at iteration 4 (iteration 0 passed)
+            raise NotPSDError("injected")
+        return real_check(self)
+
+    monkeypatch.setattr(cls, "check", failing_check)
+    made = []
+    real_init = graphed_step.GraphedConditionedStep.__init__
+    monkeypatch.setattr(graphed_step.GraphedConditionedStep, "__init__",
+                        lambda self, *a, **k: (real_init(self, *a, **k), made.append(self))[0])
+    return fitter, made
+
+
+def test_captured_conditioned_training_redoes_the_iterations_after_a_failed_verdict(monkeypatch):
+    import warnings
+    from mobocmf_amd.util.graphed_step import GraphedConditionedStep
+    fitter, made = _conditioned_fitter_with_a_failing_verdict(monkeypatch, GraphedConditionedStep)
+    fitter.use_tiny_step = False                               # the captured iteration from the start
+    with warnings.catch_warnings(record=True) as w:
+        warnings.simplefilter("always")
+        fitter.train_conditioned_mfdgps(num_iters=10)
+    assert any("conditioned training: injected -- rolling back 4 iterations and redoing them eagerly" in str(m.message) for m in w)
+    step, = made
+    assert step.use_graph and int(step.optimizer.steps_done) == 10
+    for _, _, h in fitter._handlers():
+        assert all(bool(torch.isfinite(p).all()) for p in h.mfdgp.parameters())
+        assert h.iter_train_loader is None
+
+
+def test_one_launch_conditioned_training_hands_over_to_the_layer_path_after_a_failed_verdict(monkeypatch):
+    import warnings
+    from mobocmf_amd.util.blackbox_mfdgp_fitter import BlackBoxMFDGPFitter
+    from mobocmf_amd.util.tiny_step import TinyELBOStep
+    fitter, made = _conditioned_fitter_with_a_failing_verdict(monkeypatch, TinyELBOStep)
+    handed = []
+    real_tiny = BlackBoxMFDGPFitter._train_conditioned_tiny
+    monkeypatch.setattr(BlackBoxMFDGPFitter, "_train_conditioned_tiny",
+                        lambda self, n: (handed.append(real_tiny(self, n)), handed[-1])[1])
+    with warnings.catch_warnings(record=True) as w:
+        warnings.simplefilter("always")
+        fitter.train_conditioned_mfdgps(num_iters=10)
+    assert any("conditioned training: injected -- rolling back 4 iterations; the layer path continues" in str(m.message) for m in w)
+    (done, tiny), = handed
+    assert done == 1 < 10 and tiny is not None                # iteration 0 stands
+    step, = made                                              # the layer path took over ...
+    assert int(step.optimizer.steps_done) == 10               # ... with the step count (1 + 9 of its own) and the moments
+    assert sum(float(st["exp_avg_sq"].abs().sum()) for st in step.optimizer.state.values() if "exp_avg_sq" in st) > 0
+    for _, _, h in fitter._handlers():
+        assert all(bool(torch.isfinite(p).all()) for p in h.mfdgp.parameters())
+
+
 def test_graphed_conditioned_step_equals_eager():
     """HIP-graph replay of the joint conditioned iteration == the eager iteration (same x~ every step)."""
     from mobocmf_amd.util.graphed_step import GraphedConditionedStep

@@ -335,6 +335,41 @@ def test_fitter_trains_on_captured_minibatches(monkeypatch):
     assert len(made) == before + 6
 
 
+def test_fitter_redoes_the_epochs_since_the_last_verdict_after_a_failed_one(monkeypatch):
+    """A verdict that fails on the captured mini-batch path (injected on the host: nothing is faulted on the device) rolls the
+    surrogate back to the last verified epoch, sampler included, and the phase finishes eagerly with every step counted once."""
+    import warnings
+    from mobocmf_amd.layers.mfdgp_hidden_layer import NotPSDError
+    from mobocmf_amd.util import blackbox_mfdgp_fitter as BF
+    from mobocmf_amd.util import graphed_step
+    monkeypatch.setattr(BF, "ITER_PRINT", 3)
+    epochs = 7
+    fitter = _toy_fitter(["obj0"], [55], epochs=epochs)
+    calls = {"n": 0}
+    real_check = graphed_step.GraphedMiniBatchStep.check
+
+    def failing_check(self):
+        calls["n"] += 1
+        if calls["n"] == 2:      # the verdict at epoch 3 (epoch 0 passed)
+            raise NotPSDError("injected")
+        return real_check(self)
+
+    monkeypatch.setattr(graphed_step.GraphedMiniBatchStep, "check", failing_check)
+    made = []
+    real_init = graphed_step.GraphedMiniBatchStep.__init__
+    monkeypatch.setattr(graphed_step.GraphedMiniBatchStep, "__init__", lambda self, *a, **k: (real_init(self, *a, **k), made.append(self))[0])
+    with warnings.catch_warnings(record=True) as w:
+        warnings.simplefilter("always")
+        fitter._train_mfdgp_minibatch(True, epochs, 3e-3)
+    assert any("rolling back 3 epochs and redoing them eagerly" in str(m.message) for m in w)
+    g, = made
+    assert g.nb == 4 and calls["n"] == 4                      # verdicts at epochs 0, 3 (failed), 3 again after the redo, 6 (the last)
+    assert int(g.optimizer.steps_done) == epochs * g.nb
+    assert g.state.cpu().tolist() == [55, epochs * g.nb, 0]   # the sampler went back with the parameters
+    for p in fitter.get_model("obj0").parameters():
+        assert bool(torch.isfinite(p).all())
+
+
 def test_fitter_keeps_the_full_batch_path_when_the_batch_covers_the_data(monkeypatch):
     from mobocmf_amd.util import graphed_step
     from mobocmf_amd.util.blackbox_mfdgp_fitter import BlackBoxMFDGPFitter
