@@ -238,6 +238,73 @@ typedef struct mobocmf_rff_layer_desc {
 int mobocmf_rff_eval_chains(int32_t K, int32_t d, int64_t n, const double* x, const double* params, int64_t params_len,
                             const mobocmf_rff_layer_desc* desc, double* out, mobocmf_stream_t stream);
 
+/* K chain samples AND their input gradients at n points: vals[k * n + i] = sample k at x_i (the value of
+ * mobocmf_rff_eval_chains, another summation order), grads[(k * n + i) * d + c] = d sample_k / d x_c at x_i.  Operands: those of
+ * mobocmf_rff_eval_chains.  Forward mode through the layer recursion, df_l/dx = (partial f_l / partial x) +
+ * (partial f_l / partial f_{l-1}) df_{l-1}/dx, with per feature j of kind 1
+ *   d/dx     = -(theta[j] s0 fprev sin(a1) + theta[F+j] s1 sin(a1 + Wf[j] fprev)) W1[j] - theta[2F+j] s2 sin(a2) W2[j]
+ *   d/dfprev =   theta[j] s0 cos(a1) - theta[F+j] s1 Wf[j] sin(a1 + Wf[j] fprev)           (a1 = W1[j].x + b1[j], a2 likewise)
+ * One wavefront per (sample, point): the features are split over its 64 lanes and summed across them in a fixed order.  A
+ * layer whose operands do not lie inside params_len doubles writes NaN for its sample (values and gradients) and is never
+ * read.  Deterministic (no atomics): two launches give bitwise identical output. */
+int mobocmf_rff_chains_value_grad(int32_t K, int32_t d, int64_t n, const double* x, const double* params, int64_t params_len,
+                                  const mobocmf_rff_layer_desc* desc, double* vals, double* grads, mobocmf_stream_t stream);
+
+/* Settings of mobocmf_rff_refine; they travel with the call (NULL = the defaults mobocmf_rff_refine_options_init writes). */
+typedef struct mobocmf_rff_refine_options {
+    uint32_t struct_size;   /* sizeof(mobocmf_rff_refine_options) of the caller (set by mobocmf_rff_refine_options_init) */
+    int32_t outer;          /* multiplier rounds (default 8, 1..64) */
+    int32_t inner;          /* projected-gradient steps per round (default 30, 1..1024) */
+    int32_t backtracks;     /* step reductions per inner step after its first trial (default 6, 0..32) */
+    int32_t restore;        /* feasibility-restoration steps after the last round (default 4, 0..32) */
+    int32_t recentre;       /* 1 (default): after a round that did not cut the largest violation to a quarter, the next round
+                             * starts from the start's best feasible point so far (the iterate may have strayed into another
+                             * basin of a nonconvex constraint); 0: it continues from the iterate */
+    double step0;           /* initial step (default 0.05) */
+    double step_shrink;     /* factor of one backtrack (default 0.25, in (0, 1)) */
+    double step_grow;       /* factor on an accepted step when the curvature estimate is unusable (default 2, >= 1) */
+    double rho0;            /* initial penalty (default 10) */
+    double rho_growth;      /* penalty factor when the largest violation did not fall to a quarter (default 4, >= 1) */
+    double armijo;          /* sufficient-decrease constant (default 1e-4, in (0, 1)) */
+    double restore_margin;  /* slack the restoration aims for (default 1e-9, >= 0) */
+} mobocmf_rff_refine_options;
+int mobocmf_rff_refine_options_init(mobocmf_rff_refine_options* opt);
+
+/* Constrained multi-start refinement of chain samples in one launch (the refinement stage of MOOP): problem p minimises chain
+ * obj[p] over the box [0, 1]^d subject to chain(con[con_off[p] + i])(x) - thr[con_off[p] + i] >= 0, i < con_cnt[p], from the R
+ * starts x0[p][r].  params / params_len / desc: the K chains, as for mobocmf_rff_eval_chains.  obj, con_off, con_cnt [P] are
+ * HOST arrays (they travel as launch arguments; P <= MOBOCMF_REFINE_MAX_PROBLEMS, con_cnt[p] <= MOBOCMF_REFINE_MAX_CON);
+ * con [n_con] (int32) and thr [n_con] are DEVICE arrays (NULL when n_con = 0).
+ *
+ * Method, per start, on one workgroup (features over its lanes, sums in a fixed order): augmented Lagrangian in the
+ * Powell-Hestenes-Rockafellar form, merit = f + sum_i (max(0, lambda_i - rho s_i)^2 - lambda_i^2) / (2 rho) with the slacks
+ * s_i; `inner` projected-gradient steps per round, each with Armijo backtracking on the merit (first trial step: the
+ * Barzilai-Borwein estimate of the last accepted step, else step_grow times it); after a round lambda_i = max(0, lambda_i -
+ * rho s_i) and rho grows when the largest violation did not fall to a quarter (the next round then restarts from the best
+ * feasible point found so far, see `recentre`); after the last round up to `restore` steps
+ * x <- clamp(x - (2 V / |grad V|^2) grad V), V = 1/2 sum_i max(0, restore_margin - s_i)^2, bring an iterate that ends just
+ * outside the feasible set back into it.  Every trip count is fixed by the options: no data-dependent waits, no workgroup
+ * waits on another.  Every iterate is clamped to the box.
+ *
+ * Per start:   xs [P x R x d], fs [P x R], slack_min [P x R] = the best FEASIBLE point evaluated (by the kernel's own values:
+ *              every slack >= 0), the start (clamped) included -- so fs <= f(x0) for a feasible start -- its value and its
+ *              smallest slack (+inf without constraints).  No feasible point (or a NaN start, which is not iterated): fs =
+ *              NaN, xs / slack_min = the last iterate (the start itself if it held a NaN).
+ * Per problem: x_best [P x d], f_best [P], start_best [P] (int32) = the start result with the smallest fs, ties to the lowest r
+ *              (reduced on the device by a second small launch on the same stream); status [P] (int32): 0 = refinement moved
+ *              away from that start, 1 = x_best is the (clamped) start start_best itself, 2 = no start has a feasible result
+ *              (an invalid descriptor or chain index, NaN or infeasible starts): f_best = NaN, start_best = -1, x_best = NaN.
+ * Bitwise reproducible across launches.  MOBOCMF_BAD_ARG: a null pointer, P < 1, P > MOBOCMF_REFINE_MAX_PROBLEMS, R < 1, d
+ * outside 1..MOBOCMF_MAX_D, K < 1, obj[p] outside [0, K), con_cnt[p] < 0 or > MOBOCMF_REFINE_MAX_CON, a constraint range
+ * outside [0, n_con), or options outside their ranges. */
+#define MOBOCMF_REFINE_MAX_PROBLEMS 64
+#define MOBOCMF_REFINE_MAX_CON 32
+int mobocmf_rff_refine(int32_t P, int32_t R, int32_t d, int32_t K, const int32_t* obj, const int32_t* con_off,
+                       const int32_t* con_cnt, int32_t n_con, const int32_t* con, const double* thr, const double* x0,
+                       const double* params, int64_t params_len, const mobocmf_rff_layer_desc* desc,
+                       const mobocmf_rff_refine_options* opt, double* xs, double* fs, double* slack_min, double* x_best,
+                       double* f_best, int32_t* start_best, int32_t* status, mobocmf_stream_t stream);
+
 /* Feasibility of grid rows under K_con sampled constraints (MOOP.find_feasible_grid): vals [K_con x n] with row stride ldv
  * (>= n), thr [K_con]; slack = vals[c][i] - thr[c].  ok[i] = 1 if every slack >= 0 else 0; viol[i] = sum_c min(slack, 0)
  * summed in the order c = 0, 1, ... */

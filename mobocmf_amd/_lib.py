@@ -83,6 +83,21 @@ class RffLayerDesc(ctypes.Structure):
                 ("s0", ctypes.c_double), ("s1", ctypes.c_double), ("s2", ctypes.c_double)]
 
 
+REFINE_MAX_PROBLEMS, REFINE_MAX_CON = 64, 32      # MOBOCMF_REFINE_MAX_PROBLEMS / MOBOCMF_REFINE_MAX_CON
+REFINE_STATUS = {0: "refinement moved away from the best start", 1: "the best start itself is returned",
+                 2: "no start has a feasible result"}            # status of mobocmf_rff_refine
+
+
+class RffRefineOptions(ctypes.Structure):
+    """mobocmf_rff_refine_options: the settings of mobocmf_rff_refine, passed with the call (NULL = defaults)."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("outer", ctypes.c_int32), ("inner", ctypes.c_int32),
+                ("backtracks", ctypes.c_int32), ("restore", ctypes.c_int32), ("recentre", ctypes.c_int32),
+                ("step0", ctypes.c_double),
+                ("step_shrink", ctypes.c_double), ("step_grow", ctypes.c_double), ("rho0", ctypes.c_double),
+                ("rho_growth", ctypes.c_double), ("armijo", ctypes.c_double), ("restore_margin", ctypes.c_double)]
+    KNOBS = tuple(n for n, _ in _fields_[1:])
+
+
 class MobocmfError(RuntimeError):
     pass
 
@@ -154,6 +169,10 @@ SYMBOLS = {
     "mobocmf_rff_eval": [_I32, _I32, _I32, _I64] + [_P] * 8 + [_D, _D, _D, _P, _P],
     "mobocmf_rff_eval_chains": [_I32, _I32, _I64, _P, _P, _I64, _P, _P, _P],
     "mobocmf_rff_feasibility": [_I32, _I64, _P, _I64, _P, _P, _P, _P],
+    "mobocmf_rff_chains_value_grad": [_I32, _I32, _I64, _P, _P, _I64, _P, _P, _P, _P],
+    "mobocmf_rff_refine_options_init": [ctypes.POINTER(RffRefineOptions)],
+    "mobocmf_rff_refine": [_I32, _I32, _I32, _I32, _P, _P, _P, _I32, _P, _P, _P, _P, _I64, _P,
+                           ctypes.POINTER(RffRefineOptions)] + [_P] * 7 + [_P],
     "mobocmf_pareto_mask": [_I32, _I64, _P, _I64, _I32, _P, _P, _I64, _P, _D, _P, _P, _P],
     "mobocmf_hypervolume_workspace_bytes": [_I32, _I64, ctypes.POINTER(_SZ)],
     "mobocmf_hypervolume": [_I32, _I64, _P, _I64, _P, ctypes.POINTER(_D), _P, _SZ, _P],

@@ -11,6 +11,7 @@
 // broadcasts; the F x n feature matrix the reference materialises (and a library matmul + cos + matvec would, 256 MB per
 // block at d = 8) never exists.  The argument W1.x is shared by the first two blocks of kind 1.  FP64 cos-bound.
 #include "common.h"
+#include "rff_desc.h"
 
 #define RFF_T 256     // threads = grid points per workgroup
 #define RFF_FC 64     // features per LDS chunk
@@ -142,15 +143,6 @@ __device__ __forceinline__ double rff_chain_layer(const mobocmf_rff_layer_desc& 
         }
     }
     return KIND == 0 ? s0 * acc : acc;
-}
-
-// operands of a layer descriptor inside params[0, len)
-__device__ __forceinline__ bool rff_desc_ok(const mobocmf_rff_layer_desc& L, int l, int d, int64_t len) {
-    if (L.kind != (l == 0 ? 0 : 1) || L.F < 1) return false;
-    const int64_t F = L.F, Fd = F * d;
-    auto in = [len](int64_t off, int64_t cnt) { return off >= 0 && off <= len - cnt; };
-    if (!in(L.W1, Fd) || !in(L.b1, F) || !in(L.theta, L.kind == 0 ? F : 3 * F)) return false;
-    return L.kind == 0 || (in(L.Wf, F) && in(L.W2, Fd) && in(L.b2, F));
 }
 
 template <int DB>

@@ -1438,13 +1438,56 @@ def rff_eval(kind, x, fprev, W1, b1, Wf, W2, b2, theta, s0, s1=0.0, s2=0.0):
     return out
 
 
+def _rff_chain_table(what, layers, d, plen, device):
+    """The DEVICE table of mobocmf_rff_layer_desc of ``layers`` (see ``rff_eval_chains``), every shape and offset checked
+    against ``plen`` doubles of params here, on the host."""
+    Lmax = _lib.RFF_MAX_LAYERS
+    K = len(layers)
+    tab = (_lib.RffLayerDesc * (K * Lmax))()
+    for k, chain in enumerate(layers):
+        if not 1 <= len(chain) <= Lmax:
+            raise _lib.MobocmfError("%s: a chain sample has 1..%d layers" % (what, Lmax))
+        for l in range(Lmax):
+            e = tab[k * Lmax + l]
+            if l >= len(chain):
+                e.kind = -1
+                continue
+            L = chain[l]
+            kind, Fn = int(L["kind"]), int(L["F"])
+            if kind != (0 if l == 0 else 1) or Fn < 1:
+                raise _lib.MobocmfError("%s: layer 0 is kind 0, the layers above it kind 1" % what)
+            need = {"W1": Fn * d, "b1": Fn, "theta": Fn if kind == 0 else 3 * Fn}
+            if kind == 1:
+                need.update({"Wf": Fn, "W2": Fn * d, "b2": Fn})
+            for name, cnt in need.items():
+                off = int(L[name])
+                if off < 0 or off + cnt > plen:
+                    raise _lib.MobocmfError("%s: operand %s of sample %d layer %d lies outside params" % (what, name, k, l))
+                setattr(e, name, off)
+            e.kind, e.F = kind, Fn
+            e.s0, e.s1, e.s2 = float(L["s0"]), float(L.get("s1", 0.0)), float(L.get("s2", 0.0))
+    return torch.frombuffer(bytearray(bytes(tab)), dtype=torch.uint8).to(device)
+
+
+def _rff_chain_args(what, x, params, layers):
+    """(x, params, n, d, K, plen) of a call on chain samples, checked as ``rff_eval_chains`` documents."""
+    if not (torch.is_tensor(x) and torch.is_tensor(params)) or x.dim() != 2 or params.dim() != 1 or params.device != x.device \
+            or x.device.type != "cuda":
+        raise _lib.MobocmfError("%s: x must be (n, d) and params 1-D, on one GPU" % what)
+    x, params = _prep(x.detach()), _prep(params.detach())
+    n, d = x.shape
+    K, plen = len(layers), params.numel()
+    if not 1 <= K <= 65535 or n < 1 or not 1 <= d <= _lib.MAX_D or plen < 1:
+        raise _lib.MobocmfError("%s: shape mismatch" % what)
+    return x, params, n, d, K, plen
+
+
 def rff_eval_chains(x, params, layers):
     """K chain samples at the rows of ``x`` (n, d) on the GPU in one launch (mobocmf_rff_eval_chains) -> (K, n).  ``params``:
     1-D float64 device tensor holding every sample's operands; ``layers``: per sample, the list of its layers (layer 0 first),
     each a dict with kind, F, the offsets W1 / b1 / theta (and Wf / W2 / b2 for kind 1) into ``params`` and the scales
     s0 / s1 / s2 of ``rff_eval``.  The shapes are checked here, on the host.  No autograd."""
     lib = _lib.require_device()
-    Lmax = _lib.RFF_MAX_LAYERS
     with torch.no_grad():
         x, params = _prep(x.detach()), _prep(params.detach())
         if x.dim() != 2 or params.dim() != 1 or params.device != x.device:
@@ -1453,34 +1496,87 @@ def rff_eval_chains(x, params, layers):
         K, plen = len(layers), params.numel()
         if not 1 <= K <= 65535 or n < 1 or not 1 <= d <= _lib.MAX_D or plen < 1:
             raise _lib.MobocmfError("rff_eval_chains: shape mismatch")
-        tab = (_lib.RffLayerDesc * (K * Lmax))()
-        for k, chain in enumerate(layers):
-            if not 1 <= len(chain) <= Lmax:
-                raise _lib.MobocmfError("rff_eval_chains: a chain sample has 1..%d layers" % Lmax)
-            for l in range(Lmax):
-                e = tab[k * Lmax + l]
-                if l >= len(chain):
-                    e.kind = -1
-                    continue
-                L = chain[l]
-                kind, Fn = int(L["kind"]), int(L["F"])
-                if kind != (0 if l == 0 else 1) or Fn < 1:
-                    raise _lib.MobocmfError("rff_eval_chains: layer 0 is kind 0, the layers above it kind 1")
-                need = {"W1": Fn * d, "b1": Fn, "theta": Fn if kind == 0 else 3 * Fn}
-                if kind == 1:
-                    need.update({"Wf": Fn, "W2": Fn * d, "b2": Fn})
-                for name, cnt in need.items():
-                    off = int(L[name])
-                    if off < 0 or off + cnt > plen:
-                        raise _lib.MobocmfError("rff_eval_chains: operand %s of sample %d layer %d lies outside params"
-                                                % (name, k, l))
-                    setattr(e, name, off)
-                e.kind, e.F = kind, Fn
-                e.s0, e.s1, e.s2 = float(L["s0"]), float(L.get("s1", 0.0)), float(L.get("s2", 0.0))
-        desc = torch.frombuffer(bytearray(bytes(tab)), dtype=torch.uint8).to(x.device)
+        desc = _rff_chain_table("rff_eval_chains", layers, d, plen, x.device)
         out = _empty(K, n, device=x.device)
         _lib.check(lib.mobocmf_rff_eval_chains(K, d, n, _ptr(x), _ptr(params), plen, _ptr(desc), _ptr(out), _stream()),
                    "mobocmf_rff_eval_chains")
+    return out
+
+
+def rff_chains_value_grad(x, params, layers):
+    """K chain samples and their input gradients at the rows of ``x`` (n, d) on the GPU in one launch
+    (mobocmf_rff_chains_value_grad) -> (vals (K, n), grads (K, n, d)).  Operands and checks: ``rff_eval_chains``.  No
+    autograd."""
+    lib = _lib.require_device()
+    with torch.no_grad():
+        x, params, n, d, K, plen = _rff_chain_args("rff_chains_value_grad", x, params, layers)
+        desc = _rff_chain_table("rff_chains_value_grad", layers, d, plen, x.device)
+        vals, grads = _empty(K, n, device=x.device), _empty(K, n, d, device=x.device)
+        _lib.check(lib.mobocmf_rff_chains_value_grad(K, d, n, _ptr(x), _ptr(params), plen, _ptr(desc), _ptr(vals),
+                                                     _ptr(grads), _stream()), "mobocmf_rff_chains_value_grad")
+    return vals, grads
+
+
+def rff_refine_options(**kw):
+    """The settings of ``rff_refine`` (mobocmf_rff_refine_options): the library's defaults with ``kw`` (outer, inner, backtracks,
+    restore, recentre, step0, step_shrink, step_grow, rho0, rho_growth, armijo, restore_margin) replaced."""
+    opt = _lib.RffRefineOptions()
+    _lib.check(_lib.load().mobocmf_rff_refine_options_init(ctypes.byref(opt)), "mobocmf_rff_refine_options_init")
+    for name, v in kw.items():
+        if name not in _lib.RffRefineOptions.KNOBS:
+            raise _lib.MobocmfError("rff_refine_options: no option %r" % name)
+        setattr(opt, name, v)
+    return opt
+
+
+def rff_refine(x0, params, layers, obj, cons=None, thr=None, options=None):
+    """Constrained multi-start refinement of chain samples in one launch (mobocmf_rff_refine).  ``x0`` (P, R, d): R starts for
+    each of P problems; ``params`` / ``layers``: the chain samples, as for ``rff_eval_chains``; problem p minimises chain
+    ``obj[p]`` over [0, 1]^d subject to chain ``cons[p][i]`` (x) >= ``thr[p][i]`` (``cons`` / ``thr``: per problem a sequence,
+    possibly empty; None = no constraints); ``options``: ``rff_refine_options(...)`` or a dict of its keywords.  Returns a
+    dict of device tensors: per start ``xs`` (P, R, d), ``fs`` (P, R), ``slack_min`` (P, R) -- the best feasible point
+    evaluated from that start, NaN ``fs`` if there is none -- and per problem ``x_best`` (P, d), ``f_best`` (P,),
+    ``start_best`` (P,) int32, ``status`` (P,) int32 (``_lib.REFINE_STATUS``).  No autograd, no host synchronisation."""
+    lib = _lib.require_device()
+    with torch.no_grad():
+        if not torch.is_tensor(x0) or x0.dim() != 3:
+            raise _lib.MobocmfError("rff_refine: x0 must be (P, R, d)")
+        P, R, d = x0.shape
+        if P < 1 or R < 1:
+            raise _lib.MobocmfError("rff_refine: x0 must be (P, R, d) with P, R >= 1")
+        xf, params, _, d, K, plen = _rff_chain_args("rff_refine", x0.reshape(P * R, d), params, layers)
+        obj = [int(o) for o in obj]
+        cons = [[] for _ in obj] if cons is None else [[int(c) for c in cs] for cs in cons]
+        thr = [[] for _ in obj] if thr is None else [torch.as_tensor(ts, dtype=torch.float64).reshape(-1).tolist()
+                                                     for ts in thr]
+        if len(obj) != P or len(cons) != P or len(thr) != P or not 1 <= P <= _lib.REFINE_MAX_PROBLEMS:
+            raise _lib.MobocmfError("rff_refine: one objective, one constraint list and one threshold list per problem "
+                                    "(at most %d problems)" % _lib.REFINE_MAX_PROBLEMS)
+        for p in range(P):
+            if not 0 <= obj[p] < K or any(not 0 <= c < K for c in cons[p]):
+                raise _lib.MobocmfError("rff_refine: problem %d names a chain outside 0..%d" % (p, K - 1))
+            if len(cons[p]) != len(thr[p]) or len(cons[p]) > _lib.REFINE_MAX_CON:
+                raise _lib.MobocmfError("rff_refine: problem %d needs one threshold per constraint (at most %d)"
+                                        % (p, _lib.REFINE_MAX_CON))
+        if isinstance(options, dict):
+            options = rff_refine_options(**options)
+        cnt = [len(c) for c in cons]
+        off = [sum(cnt[:p]) for p in range(P)]
+        n_con = sum(cnt)
+        i32 = lambda v: (ctypes.c_int32 * len(v))(*v)
+        dev = xf.device
+        con_d = torch.tensor([c for cs in cons for c in cs], dtype=torch.int32).to(dev) if n_con else None
+        thr_d = torch.tensor([t for ts in thr for t in ts], dtype=torch.float64).to(dev) if n_con else None
+        desc = _rff_chain_table("rff_refine", layers, d, plen, dev)
+        out = {"xs": _empty(P, R, d, device=dev), "fs": _empty(P, R, device=dev), "slack_min": _empty(P, R, device=dev),
+               "x_best": _empty(P, d, device=dev), "f_best": _empty(P, device=dev),
+               "start_best": torch.empty(P, dtype=torch.int32, device=dev),
+               "status": torch.empty(P, dtype=torch.int32, device=dev)}
+        _lib.check(lib.mobocmf_rff_refine(P, R, d, K, i32(obj), i32(off), i32(cnt), n_con, _ptr(con_d), _ptr(thr_d), _ptr(xf),
+                                          _ptr(params), plen, _ptr(desc),
+                                          None if options is None else ctypes.byref(options),
+                                          *[_ptr(out[k]) for k in ("xs", "fs", "slack_min", "x_best", "f_best", "start_best",
+                                                                   "status")], _stream()), "mobocmf_rff_refine")
     return out
 
 

@@ -280,6 +280,14 @@ class RFFChainSample:
         params, layers = self.device_operands(xd.device)
         return Fn.rff_eval_chains(xd, params, [layers])[0]
 
+    def value_and_grad(self, xd):
+        """xd (n, d) on the GPU -> (values (n,), input gradients (n, d)) there, every row in one launch
+        (mobocmf_rff_chains_value_grad)."""
+        from .. import functional as Fn
+        params, layers = self.device_operands(xd.device)
+        vals, grads = Fn.rff_chains_value_grad(xd, params, [layers])
+        return vals[0], grads[0]
+
     def __call__(self, x, gradient=False):
         xt = torch.as_tensor(np.asarray(x), dtype=torch.float64)
         if xt.dim() == 1:

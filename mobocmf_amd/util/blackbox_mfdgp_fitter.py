@@ -138,7 +138,10 @@ class BlackBoxMFDGPFitter:
 
     def __init__(self, num_fidelities, batch_size, lr_1=0.003, lr_2=0.001, num_epochs_1=5000, num_epochs_2=15000,
                  pareto_set_size=50, opt_grid_size=1000, eps=1e-8, decoupled_evals=False,
-                 type_lengthscale=TL.MEDIAN, device="cuda", **model_kwargs):
+                 type_lengthscale=TL.MEDIAN, device="cuda", pareto_refine="slsqp", **model_kwargs):
+        if pareto_refine not in ("slsqp", "device"):
+            raise ValueError("pareto_refine must be 'slsqp' or 'device' (got %r)" % (pareto_refine,))
+        self.pareto_refine = pareto_refine      # MOOP's refine: host SLSQP | the one-launch refinement on the GPU
         self.num_obj = 0
         self.num_con = 0
         self.models_uncond_trained = False
@@ -376,17 +379,20 @@ class BlackBoxMFDGPFitter:
         """One posterior function sample per black-box (top layer), then the feasible Pareto set of the sampled
         problem on a random grid + the training inputs (blackbox_mfdgp_fitter.py:181-216)."""
         from .moop import MOOP, NotFeasiblePoints
-        samples_objs = [h.mfdgp.sample_function_from_each_layer(nFeatures=nFeatures, generator=generator)[-1]
-                        for h in self.mfdgp_handlers_objs.values()]
+        if self.pareto_refine == "device":      # the same function for the same generator, as tensors MOOP can refine on the GPU
+            from ..layers.rff import sample_chain_from_posterior
+            draw = lambda h: sample_chain_from_posterior(h.mfdgp, nFeatures=nFeatures, generator=generator)
+        else:
+            draw = lambda h: h.mfdgp.sample_function_from_each_layer(nFeatures=nFeatures, generator=generator)[-1]
+        samples_objs = [draw(h) for h in self.mfdgp_handlers_objs.values()]
         inputs = self.x_train.detach().cpu().double().numpy()
         feasible = -1.0 * self.thresholds_cons.numpy()
         optimizer = None
         for _ in range(MFDGPHandler.MAX_TRIES_FOR_FEASIBLE_GRID):
-            samples_cons = [h.mfdgp.sample_function_from_each_layer(nFeatures=nFeatures, generator=generator)[-1]
-                            for h in self.mfdgp_handlers_cons.values()]
+            samples_cons = [draw(h) for h in self.mfdgp_handlers_cons.values()]
             optimizer = MOOP(samples_objs, samples_cons, input_dim=inputs.shape[1],
                              grid_size=self.opt_grid_size * inputs.shape[1], pareto_set_size=self.pareto_set_size,
-                             feasible_values=feasible, rng=rng)
+                             feasible_values=feasible, rng=rng, refine=self.pareto_refine)
             res = optimizer.compute_pareto_solution_from_samples(inputs)
             if res is not None:
                 break
@@ -515,7 +521,7 @@ class BlackBoxMFDGPFitter:
                                          "set_global_constraint_thresholds)" % (len(cons), feasible.shape[0]))
                     optimizer = MOOP(objs, cons, input_dim=d, grid_size=self.opt_grid_size * d,
                                      pareto_set_size=self.pareto_set_size, feasible_values=feasible,
-                                     rng=np.random.default_rng((int(seed), int(t))))
+                                     rng=np.random.default_rng((int(seed), int(t))), refine=self.pareto_refine)
                     res = optimizer.compute_pareto_solution_from_samples(inputs)
                 else:
                     res = optimizer.compute_pareto_solution_from_samples(inputs, allow_negative_constraints=True)

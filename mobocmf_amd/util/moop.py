@@ -15,7 +15,11 @@ How it differs inside (results equal the reference's own MOOP, pinned by tests/g
     min-distance vector, O(n) memory (the reference builds the n x n distance matrix);
   * when every sample is a ``layers.rff.RFFChainSample`` on one GPU, the grid is uploaded once and all samples are
     evaluated on it in one launch, the feasibility rule runs there too (``_feasible_grid_batched``); the SLSQP refinements
-    stay on the host.  Other samples take the per-callable path.
+    stay on the host.  Other samples take the per-callable path;
+  * ``refine="device"`` (opt-in; such samples only) replaces the SLSQP run per objective by ONE launch of the multi-start
+    augmented-Lagrangian refinement ``functional.rff_refine``: ``refine_starts`` starts per objective, the best feasible grid
+    rows, chosen on the device from the grid values that stay there.  The results differ from the default's (other optima
+    are found, never worse than the grid's best), so the golden results are pinned with the default only.
 """
 import numpy as np
 import scipy.optimize as spo
@@ -34,7 +38,13 @@ def _weakly_dominated_by_any(front, p):
 class MOOP:
 
     def __init__(self, samples_objs, samples_cons, input_dim, grid_size=1000, pareto_set_size=None, feasible_values=0.0,
-                 min_distance_between_points=1e-6, rng=None):
+                 min_distance_between_points=1e-6, rng=None, refine="slsqp", refine_starts=16):
+        if refine not in ("slsqp", "device"):
+            raise ValueError("refine must be 'slsqp' or 'device' (got %r)" % (refine,))
+        if int(refine_starts) < 1:
+            raise ValueError("refine_starts must be >= 1")
+        self.refine = refine
+        self.refine_starts = int(refine_starts)
         self.samples_objs = samples_objs
         self.samples_cons = samples_cons
         self.input_dim = input_dim
@@ -91,7 +101,8 @@ class MOOP:
         """``find_feasible_grid`` + the objective values on the feasible rows, with the grid uploaded once, every objective
         and constraint sample evaluated in ONE mobocmf_rff_eval_chains launch and the feasibility rule applied on the device
         (mobocmf_rff_feasibility); only the objectives' values and the per-row flags come back.  Returns (grid, evals) or
-        (None, None)."""
+        (None, None).  What the device refinement needs stays in ``self._grid_dev``: the packed samples, the uploaded grid, the
+        objective values and the feasible rows' indices (None on the least-infeasible fallback: no row is a valid start)."""
         from .. import functional as F
         samples = list(self.samples_objs) + list(self.samples_cons)
         n_obj, n_con = len(self.samples_objs), len(self.samples_cons)
@@ -105,19 +116,45 @@ class MOOP:
         xd = torch.from_numpy(np.ascontiguousarray(grid)).to(dev)
         vals = F.rff_eval_chains(xd, params, layers)
         obj_vals = vals[:n_obj]
+        self._grid_dev = {"params": params, "layers": layers, "x": xd, "obj_vals": obj_vals, "rows": None}
         if not n_con:
+            self._grid_dev["rows"] = torch.arange(grid.shape[0], device=dev)
             return grid, obj_vals.cpu().numpy().T
         thr = self._thresholds(n_con, self.feasible_values)[:n_con]
         ok, viol = F.rff_feasibility(vals[n_obj:], torch.from_numpy(np.ascontiguousarray(thr, dtype=np.float64)).to(dev))
         ok = ok.cpu().numpy()
         if ok.any():
             rows = np.flatnonzero(ok)
+            self._grid_dev["rows"] = torch.from_numpy(rows).to(dev)
         elif not allow_negative_constraints:
             return None, None
         else:
             v = viol.cpu().numpy()
             rows = np.flatnonzero(v == np.max(v[v != 0]))
         return grid[rows, :], obj_vals.cpu().numpy().T[rows]
+
+    # ------------------------------------------------------------------ every objective's constrained optimum in one launch
+    def _refine_device(self, evals, feasible_grid):
+        """The optima ``optimize_obj_globally`` looks for, all objectives in ONE ``functional.rff_refine`` call: per objective
+        the ``refine_starts`` best feasible grid rows (by value, then row index; fewer if fewer rows are feasible) are the
+        starts, taken on the device from the grid values kept there.  An optimum is accepted as there: it improves on the
+        grid's best value and is feasible (the kernel returns feasible points only).  Returns the list of (1, d) optima."""
+        from .. import functional as F
+        g = self._grid_dev
+        if g["rows"] is None:
+            return []
+        n_obj, n_con = len(self.samples_objs), len(self.samples_cons)
+        rows, R = g["rows"], min(self.refine_starts, int(g["rows"].numel()))
+        x0 = []
+        for j in range(n_obj):
+            order = torch.argsort(g["obj_vals"][j][rows], stable=True)[:R]      # stable: ties in row order
+            x0.append(g["x"][rows[order]])
+        thr = self._thresholds(n_con, self.feasible_values)[:n_con]
+        out = F.rff_refine(torch.stack(x0), g["params"], g["layers"], obj=list(range(n_obj)),
+                           cons=[list(range(n_obj, n_obj + n_con))] * n_obj, thr=[thr] * n_obj)
+        x_best, f_best = out["x_best"].cpu().numpy(), out["f_best"].cpu().numpy()
+        status = out["status"].cpu().numpy()
+        return [x_best[j][None] for j in range(n_obj) if status[j] == 0 and f_best[j] < np.min(evals[:, j])]
 
     # ------------------------------------------------------------------ constrained optimum of one objective
     def _slsqp(self, obj, cons, x0, tol):
@@ -218,6 +255,9 @@ class MOOP:
             self.rng.uniform(size=(n_rand, self.input_dim))
         grid = np.concatenate((rand, inputs))
         dev = self._batched_device()
+        if self.refine == "device" and dev is None:
+            raise ValueError("MOOP(refine='device') needs every sample to be an RFFChainSample on one GPU "
+                             "(layers.rff.sample_chain_from_posterior); there is no host fallback")
         if dev is not None:
             grid, evals = self._feasible_grid_batched(grid, dev, allow_negative_constraints)
             if grid is None:
@@ -229,9 +269,13 @@ class MOOP:
             if grid is None:
                 return None
             evals = np.stack([np.asarray(obj(grid)).reshape(-1) for obj in self.samples_objs], 1)
+        if self.refine == "device":
+            optima = self._refine_device(evals, grid)
+        else:
+            optima = [self.optimize_obj_globally(obj, self.samples_cons, evals[:, j], grid)
+                      for j, obj in enumerate(self.samples_objs)]
         extra = []
-        for j, obj in enumerate(self.samples_objs):
-            opt = self.optimize_obj_globally(obj, self.samples_cons, evals[:, j], grid)
+        for opt in optima:
             if opt is not None and np.min(np.sqrt(((grid - opt) ** 2).sum(1))) > 1e-6:
                 extra.append(opt)
         if extra:

@@ -8,6 +8,15 @@
                  against the per-callable path (per sample: grid upload, one mobocmf_rff_eval per layer, values back)
   moop_batched_ms / moop_per_callable_ms
                  the whole MOOP.compute_pareto_solution_from_samples (SLSQP refinements included) on both paths
+  refine_slsqp_ms / refine_device_ms
+                 the refinement stage alone, every objective's constrained optimum from the same grid values: the host SLSQP
+                 runs (MOOP.optimize_obj_globally) against ONE mobocmf_rff_refine launch (16 starts per objective, start
+                 selection and read-back included).  For these and the next two fields every constraint's threshold is the 0.4
+                 quantile of its sample on the grid, so that constraints are active (the -10 of the fields above leaves every
+                 constraint inactive); refine_device_minus_slsqp: per objective, device optimum - SLSQP optimum (the grid's
+                 best where a refinement returns nothing)
+  moop_slsqp_refine_ms / moop_device_refine_ms
+                 the whole MOOP at those thresholds with refine="slsqp" / refine="device"
 
 One JSON line per run on stdout.  Times are medians of --reps runs after one warm-up, each ending in a device synchronise.
 
@@ -85,6 +94,30 @@ def bench_K(K, d, F, N, reps):
     a, b = moop(chains), moop(calls)
     rec["moop_same_set"] = bool(np.array_equal(a[0].numpy(), b[0].numpy()))
     rec["moop_front_max_rel_diff"] = float(np.abs(a[1].numpy() - b[1].numpy()).max() / max(1.0, np.abs(b[1].numpy()).max()))
+
+    # the refinement stage, constraints active
+    vals = Fn.rff_eval_chains(torch.from_numpy(grid).cuda(), params, layers).cpu().numpy()
+    thr_q = np.array([np.quantile(vals[n_obj + i], 0.4) for i in range(K - n_obj)])
+
+    def moop_q(refine):
+        return MOOP(chains[:n_obj], chains[n_obj:], input_dim=d, grid_size=1000 * d, pareto_set_size=50,
+                    feasible_values=thr_q, rng=np.random.default_rng(2), refine=refine)
+
+    m = moop_q("device")
+    fgrid, evals = m._feasible_grid_batched(grid, torch.device("cuda", 0), False)
+    slsqp = lambda: [m.optimize_obj_globally(chains[j], chains[n_obj:], evals[:, j], fgrid) for j in range(n_obj)]
+    rec["refine_slsqp_ms"] = _timed(slsqp, max(1, reps // 2))
+    rec["refine_device_ms"] = _timed(lambda: m._refine_device(evals, fgrid), reps)
+    best = lambda opts: [float(evals[:, j].min()) if o is None else float(chains[j](o)[0]) for j, o in enumerate(opts)]
+    f_slsqp = best(slsqp())
+    out = Fn.rff_refine(torch.stack([torch.from_numpy(fgrid[np.argsort(evals[:, j], kind="stable")[:m.refine_starts]]).cuda()
+                                     for j in range(n_obj)]), params, layers, obj=list(range(n_obj)),
+                        cons=[list(range(n_obj, K))] * n_obj, thr=[thr_q] * n_obj)
+    f_dev = [min(float(f), float(evals[:, j].min())) if np.isfinite(f) else float(evals[:, j].min())
+             for j, f in enumerate(out["f_best"].cpu().numpy())]
+    rec["refine_device_minus_slsqp"] = [a - b for a, b in zip(f_dev, f_slsqp)]
+    rec["moop_slsqp_refine_ms"] = _timed(lambda: moop_q("slsqp").compute_pareto_solution_from_samples(inputs), max(1, reps // 2))
+    rec["moop_device_refine_ms"] = _timed(lambda: moop_q("device").compute_pareto_solution_from_samples(inputs), reps)
     return rec
 
 
