@@ -756,6 +756,32 @@ int mobocmf_syrk_weighted_f64(int32_t Mr, int64_t Kd, const double* A, int64_t l
  * of the factor and of the inverse, so that anything computed from them is non-finite even after info is rewritten. */
 int mobocmf_check_info(const int32_t* info, int32_t* pivot, mobocmf_stream_t stream);
 
+/* Natural-gradient step of the variational distributions q(u) = N(m, L_S L_S^T) of n layers of equal M, in place (DESIGN.md,
+ * "Natural gradients"): with G_S = dloss/dS obtained from g_LS by the reverse-mode Cholesky rule,
+ *     S_new^-1 = S^-1 + 2 gamma_t scale G_S,     m_new = m - gamma_t scale S_new g_m,
+ * returned as L_new = L_S T (lower triangular, the diagonal signs of L_S kept) with T T^T = (I + 2 gamma_t scale Psi)^-1,
+ * Psi = sym(Phi(L_S^T g_LS)).  g_m [M] and g_LS [M x M] are the gradients of the caller's loss; `scale` is what turns that loss
+ * into -ELBO (num_data / batch rows for a loss of the form data terms summed over the batch - (batch / num_data) KL: 1 on the
+ * full batch), so that gamma = 1 is the exact conjugate step.  Of L_S and g_LS
+ * (row-major, ld M) only the lower triangle is read, and only the lower triangle of L_S is written.
+ * Schedule, evaluated on the device: gamma_t = min(gamma, gamma_init (gamma / gamma_init)^(t / warmup_steps)) with t =
+ * step_count[0] (ONE device int64, which the call increments); warmup_steps = 0: gamma_t = gamma.
+ * Failure rule: info[z] (device int32, one per layer) receives the pivot report of the factorisation of I + 2 gamma_t scale Psi
+ * (0 = positive definite; the contract of mobocmf_check_info, -1 = abandoned in-launch wait included).  A layer with info != 0
+ * keeps its m and L_S bitwise and skipped[z] (device int32, one per layer, caller-zeroed) is incremented; the step counter
+ * advances all the same.  Nothing is read on the host: capturable.  Two calls on the same inputs give bitwise equal results.
+ * Arrays of pointers are HOST arrays of n entries (device pointers inside).  workspace: mobocmf_natgrad_workspace_bytes(M, n)
+ * bytes of device memory, 256-byte aligned.
+ * MOBOCMF_BAD_ARG (host-visible, before any HIP call): a NULL pointer, n outside 1..4, M outside 1..MOBOCMF_NATGRAD_MAX_M,
+ * gamma, gamma_init or scale not positive and finite, gamma_init > gamma, warmup_steps < 0, a malformed tuning record;
+ * MOBOCMF_WORKSPACE_TOO_SMALL: bytes below the reported size. */
+#define MOBOCMF_NATGRAD_MAX_M 1024
+int mobocmf_natgrad_workspace_bytes(int32_t M, int32_t n, size_t* bytes);
+int mobocmf_natgrad_step(int32_t n, int32_t M, double* const* m, double* const* L_S, const double* const* g_m,
+                         const double* const* g_LS, double gamma, double gamma_init, int32_t warmup_steps, double scale,
+                         int64_t* step_count, int32_t* const* skipped, int32_t* const* info, void* workspace, size_t bytes,
+                         const mobocmf_tuning* tuning, mobocmf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -184,7 +184,10 @@ SYMBOLS = {
     "mobocmf_minibatch_accumulate": [_I64, _I64, _P, _P, _P, _P, _P],
     "mobocmf_gram_forward": [_I32, _I32, _P, _P, _I64, _P, _P, _I64, _P, _P, _I64, _P],
     "mobocmf_check_info": [_P, ctypes.POINTER(_I32), _P],
+    "mobocmf_natgrad_workspace_bytes": [_I32, _I32, ctypes.POINTER(_SZ)],
+    "mobocmf_natgrad_step": [_I32, _I32, _P, _P, _P, _P, _D, _D, _I32, _D, _P, _P, _P, _P, _SZ, ctypes.POINTER(Tuning), _P],
 }
+NATGRAD_MAX_M, NATGRAD_MAX_LAYERS = 1024, 4      # MOBOCMF_NATGRAD_MAX_M, layers per mobocmf_natgrad_step call
 MAX_D, MAX_XDIV = 32, 48        # MOBOCMF_MAX_D / MOBOCMF_MAX_XDIV of include/mobocmf_hip.h
 PARETO_MAX_K, HV_MAX_K = 16, 5   # MOBOCMF_PARETO_MAX_K / MOBOCMF_HV_MAX_K
 HV_MAX_POINTS = {1: 65536, 2: 65536, 3: 65536, 4: 1024, 5: 256}   # the work bound of mobocmf_hypervolume

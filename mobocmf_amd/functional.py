@@ -1232,9 +1232,10 @@ class FusedAdam:
             elif p.grad is not None:
                 p.grad.zero_()
 
-    def step(self):
+    def step(self, exclude=()):
+        """``exclude``: ids of parameters another update takes this step (FusedNatGradAdam)."""
         lib = _lib.require_device()
-        idx = [i for i, p in enumerate(self.params) if p.grad is not None]
+        idx = [i for i, p in enumerate(self.params) if p.grad is not None and id(p) not in exclude]
         if not idx:
             return
         n = len(idx)
@@ -1250,6 +1251,137 @@ class FusedAdam:
         N = (ctypes.c_int64 * n)(*[self.params[i].numel() for i in idx])
         _lib.check(lib.mobocmf_adam_multi(n, P, G, M, V, N, self.lr, self.betas[0], self.betas[1], self.eps,
                                           _ptr(self.steps_done), _stream()), "mobocmf_adam_multi")
+
+
+def natgrad_step(ms, LSs, g_ms, g_LSs, gamma, gamma_init, warmup_steps, scale, step_count, skipped, info):
+    """mobocmf_natgrad_step: the natural-gradient update of q(u) = N(m, L_S L_S^T) for the layers of the lists (equal M, at most
+    ``_lib.NATGRAD_MAX_LAYERS``), in place.  ``g_ms`` / ``g_LSs``: the loss gradients; ``scale`` turns the loss into -ELBO
+    (num_data / batch rows for VariationalELBOMF's loss: 1 on the full batch).  ``step_count``: one device int64 (drives the gamma schedule, incremented); ``skipped`` /
+    ``info``: int32 tensors with one word per layer, or lists of one-element int32 tensors (``skipped`` counts the steps a layer was left unchanged because
+    I + 2 gamma Psi was not positive definite, ``info`` is that factorisation's pivot report).  Only enqueues: capturable."""
+    lib = _lib.require_device()
+    n = len(ms)
+    if not (len(LSs) == len(g_ms) == len(g_LSs) == n) or n < 1:
+        raise _lib.MobocmfError("natgrad_step: one m, L_S, g_m and g_LS per layer")
+    M = ms[0].numel()
+    for m, L, gm, gL in zip(ms, LSs, g_ms, g_LSs):
+        for t in (m, L, gm, gL):
+            if not t.is_cuda or t.dtype != torch.float64 or not t.is_contiguous():
+                raise _lib.MobocmfError("natgrad_step: contiguous float64 GPU tensors only (there is no CPU fallback)")
+        if m.numel() != M or tuple(L.shape) != (M, M) or gm.numel() != M or tuple(gL.shape) != (M, M):
+            raise _lib.MobocmfError("natgrad_step: the layers of one call share M (m [M], L_S [M x M])")
+    if step_count.dtype != torch.int64 or step_count.numel() != 1 or not step_count.is_cuda:
+        raise _lib.MobocmfError("natgrad_step: step_count is one int64 on the GPU")
+    words = lambda w: [w.reshape(-1)[z:z + 1] for z in range(w.numel())] if torch.is_tensor(w) else list(w)
+    skipped, info = words(skipped), words(info)
+    for w in skipped + info:
+        if w.dtype != torch.int32 or w.numel() != 1 or not w.is_cuda:
+            raise _lib.MobocmfError("natgrad_step: skipped and info hold one int32 per layer on the GPU")
+    if len(skipped) != n or len(info) != n:
+        raise _lib.MobocmfError("natgrad_step: skipped and info hold one int32 per layer on the GPU")
+    nbytes = ctypes.c_size_t()
+    _lib.check(lib.mobocmf_natgrad_workspace_bytes(M, n, ctypes.byref(nbytes)), "mobocmf_natgrad_workspace_bytes")
+    ws = scratch_buffer(nbytes.value, ms[0].device)
+    arr = lambda vals: (ctypes.c_void_p * n)(*vals)
+    tn = current_tuning()
+    _lib.check(lib.mobocmf_natgrad_step(n, M, arr([t.data_ptr() for t in ms]), arr([t.data_ptr() for t in LSs]),
+                                        arr([t.data_ptr() for t in g_ms]), arr([t.data_ptr() for t in g_LSs]), float(gamma),
+                                        float(gamma_init), int(warmup_steps), float(scale), _ptr(step_count),
+                                        arr([w.data_ptr() for w in skipped]), arr([w.data_ptr() for w in info]),
+                                        _ptr(ws), nbytes.value,
+                                        ctypes.byref(tn), _stream()), "mobocmf_natgrad_step")
+
+
+class FusedNatGradAdam:
+    """Natural gradients for q(u), Adam for the rest.  Every layer of ``model_or_models`` (one model -- anything with
+    ``_layers()`` / ``parameters()`` -- or a list / tuple of them) whose ``variational_mean`` AND ``chol_variational_covar`` both carry a
+    gradient in a step is moved by ``natgrad_step``; every other parameter -- and the mean of a layer whose L_S is frozen --
+    by the one ``mobocmf_adam_multi`` launch of FusedAdam.  ``elbo_scale`` (a number, or one per model) is the factor between
+    the loss the gradients are of and (an unbiased estimate of) -ELBO: VariationalELBOMF returns the data terms summed over the
+    batch minus (batch / num_data) KL, so the factor is num_data / batch -- 1 on the full batch and for the conditioned loss;
+    ``set_elbo_scale`` changes it between steps (the mini-batch step's ragged batch).  With it gamma = 1 is the exact conjugate
+    step.  Layers are grouped by (M, elbo_scale) in calls of at most ``_lib.NATGRAD_MAX_LAYERS``; each call has its own device
+    step counter for the gamma schedule.  The counters live in ``state`` with Adam's moments, so what snapshots, rolls
+    back or zeroes the optimiser state covers them.  Duck-types FusedAdam (zero_grad / step / state)."""
+
+    def __init__(self, model_or_models, lr, betas=(0.9, 0.999), eps=1e-8, gamma=0.1, gamma_init=1e-4, warmup_steps=100,
+                 elbo_scale=1.0):
+        models = list(model_or_models) if isinstance(model_or_models, (list, tuple)) else [model_or_models]
+        scales = list(elbo_scale) if isinstance(elbo_scale, (list, tuple)) else [elbo_scale] * len(models)
+        if len(scales) != len(models) or not all(float(sc) > 0.0 for sc in scales):
+            raise ValueError("FusedNatGradAdam: one positive elbo_scale per model")
+        self.gamma, self.gamma_init, self.warmup_steps = float(gamma), float(gamma_init), int(warmup_steps)
+        if not (self.gamma > 0.0 and 0.0 < self.gamma_init <= self.gamma and self.warmup_steps >= 0):
+            raise ValueError("FusedNatGradAdam: 0 < gamma_init <= gamma and warmup_steps >= 0")
+        params, seen = [], set()
+        for mdl in models:
+            for p in mdl.parameters():
+                if id(p) not in seen:
+                    seen.add(id(p))
+                    params.append(p)
+        if not params or not params[0].is_cuda:
+            raise ValueError("FusedNatGradAdam: the natural-gradient update runs on the GPU only (CPU tensors given)")
+        self.adam = FusedAdam(params, lr=lr, betas=betas, eps=eps)
+        self.params, self.lr, self.betas, self.eps = self.adam.params, self.adam.lr, self.adam.betas, self.adam.eps
+        self.steps_done = self.adam.steps_done
+        by_key, n_layers = {}, 0
+        for mdl, sc in zip(models, scales):
+            for layer in mdl._layers():      # layer k of the models, in their order, owns word k of skipped / info
+                vd = layer.variational_strategy._variational_distribution
+                m, L = vd.variational_mean, vd.chol_variational_covar
+                if m.numel() > _lib.NATGRAD_MAX_M:
+                    raise ValueError("FusedNatGradAdam: at most %d inducing points per layer" % _lib.NATGRAD_MAX_M)
+                by_key.setdefault((m.numel(), float(sc)), []).append((m, L, n_layers))
+                n_layers += 1
+        self.groups = []      # [M, scale, [(m, L_S, word)]]
+        for (M, sc), pairs in by_key.items():
+            for k in range(0, len(pairs), _lib.NATGRAD_MAX_LAYERS):
+                self.groups.append([M, sc, pairs[k:k + _lib.NATGRAD_MAX_LAYERS]])
+        self.num_layers = n_layers
+        dev = params[0].device
+        self.natgrad_steps = torch.zeros(max(1, len(self.groups)), dtype=torch.int64, device=dev)
+        self.words = torch.zeros(2, max(1, n_layers), dtype=torch.int32, device=dev)      # one host copy reads both rows
+        self.skipped, self.info = self.words[0], self.words[1]
+        self.state = dict(self.adam.state)
+        self.state["__natgrad__"] = {"step": self.natgrad_steps, "words": self.words}
+
+    def zero_grad(self, set_to_none=True):
+        self.adam.zero_grad(set_to_none)
+
+    def set_elbo_scale(self, value):
+        """One factor for every layer from the next ``step`` on (a host value: a captured step bakes it in)."""
+        if not float(value) > 0.0:
+            raise ValueError("FusedNatGradAdam: elbo_scale must be positive")
+        for group in self.groups:
+            group[1] = float(value)
+
+    def step(self):
+        taken = set()
+        calls = []
+        for gi, (M, sc, pairs) in enumerate(self.groups):
+            live = [(m, L, w) for m, L, w in pairs if m.grad is not None and L.grad is not None]
+            if not live:
+                continue
+            calls.append((gi, sc, live))
+            for m, L, _ in live:
+                taken.add(id(m))
+                taken.add(id(L))
+        cont = lambda g: g if g.is_contiguous() else g.contiguous()
+        for gi, sc, live in calls:
+            natgrad_step([m.data for m, _, _ in live], [L.data for _, L, _ in live], [cont(m.grad) for m, _, _ in live],
+                         [cont(L.grad) for _, L, _ in live], self.gamma, self.gamma_init, self.warmup_steps, sc,
+                         self.natgrad_steps[gi], [self.skipped[w:w + 1] for _, _, w in live],
+                         [self.info[w:w + 1] for _, _, w in live])
+        self.adam.step(exclude=taken)
+
+    def skipped_steps(self):
+        """Synchronising (one device-to-host copy): per layer, in the order of the models' layers, how many steps left it unchanged
+        because I + 2 gamma Psi was not positive definite.  Raises InLaunchWaitAbandoned if the last factorisation of a layer
+        abandoned an in-launch wait."""
+        skipped, info = self.words.cpu().tolist()
+        for piv in info[:self.num_layers]:
+            raise_if_abandoned(piv, "natural-gradient step")
+        return skipped[:self.num_layers]
 
 
 def check_info(info):

@@ -55,6 +55,7 @@ def run_verified(steps, num_iters, on_failure, labels, unit, report=None):
     assert on_failure != HAND_OVER or len(steps) == 1
     nbs = [getattr(g, "nb", 1) for g in steps]
     last_good = [-1] * len(steps)          # last iteration whose state was verified
+    skipped_seen = [0] * len(steps)
     for g in steps:
         g.snapshot()
     for i in range(num_iters):
@@ -81,6 +82,10 @@ def run_verified(steps, num_iters, on_failure, labels, unit, report=None):
                     g.check()
                 g.snapshot()
                 last_good[j] = i
+                total = sum(getattr(g, "skipped", ()))      # natural-gradient steps that left a layer's q(u) unchanged (read by check)
+                if total > skipped_seen[j]:
+                    print("%s%d natural-gradient steps skipped so far (I + 2 gamma Psi not positive definite)" % (labels[j], total))
+                    skipped_seen[j] = total
                 if report is not None:
                     report(i, j, g)
     for g in steps:
@@ -138,9 +143,17 @@ class BlackBoxMFDGPFitter:
 
     def __init__(self, num_fidelities, batch_size, lr_1=0.003, lr_2=0.001, num_epochs_1=5000, num_epochs_2=15000,
                  pareto_set_size=50, opt_grid_size=1000, eps=1e-8, decoupled_evals=False,
-                 type_lengthscale=TL.MEDIAN, device="cuda", pareto_refine="slsqp", **model_kwargs):
+                 type_lengthscale=TL.MEDIAN, device="cuda", pareto_refine="slsqp", variational_optimizer="adam",
+                 natgrad_gamma=0.1, natgrad_gamma_init=1e-4, natgrad_warmup_steps=100, **model_kwargs):
         if pareto_refine not in ("slsqp", "device"):
             raise ValueError("pareto_refine must be 'slsqp' or 'device' (got %r)" % (pareto_refine,))
+        if variational_optimizer not in ("adam", "natgrad"):
+            raise ValueError("variational_optimizer must be 'adam' or 'natgrad' (got %r)" % (variational_optimizer,))
+        # "natgrad": q(u) of every layer moves by natural gradients inside the captured layer-path steps (both training phases
+        # and the conditioned fit), Adam keeps the other parameters; the one-launch steps are not taken
+        self.variational_optimizer = variational_optimizer
+        self.natgrad_gamma, self.natgrad_gamma_init = natgrad_gamma, natgrad_gamma_init
+        self.natgrad_warmup_steps = natgrad_warmup_steps
         self.pareto_refine = pareto_refine      # MOOP's refine: host SLSQP | the one-launch refinement on the GPU
         self.num_obj = 0
         self.num_con = 0
@@ -199,6 +212,16 @@ class BlackBoxMFDGPFitter:
             self.objs_train = torch.cat((self.objs_train, y_train.cpu().double()), 1)
             self.mfdgp_handlers_objs[blackbox_name] = handler
             self.num_obj += 1
+
+    def _natgrad(self):
+        return getattr(self, "variational_optimizer", "adam") == "natgrad"
+
+    def _optimizer_kwargs(self):
+        """The captured steps' optimiser keywords."""
+        if not self._natgrad():
+            return {}
+        return dict(variational_optimizer="natgrad", natgrad_gamma=self.natgrad_gamma, natgrad_gamma_init=self.natgrad_gamma_init,
+                    natgrad_warmup_steps=self.natgrad_warmup_steps)
 
     def _handlers(self):
         return [("OBJ", n, h) for n, h in enumerate(self.mfdgp_handlers_objs.values())] + \
@@ -271,7 +294,7 @@ class BlackBoxMFDGPFitter:
         The rows are shuffled once (see the module docstring): the step runs GPyTorch's general branch, as the
         reference's shuffled batches do."""
         # the reference's own sizes (M = N = tens of points): every surrogate's whole step in ONE launch per epoch
-        done, tiny = self._train_mfdgp_tiny(fix_variational_hypers, num_epochs, lr)
+        done, tiny = (0, None) if self._natgrad() else self._train_mfdgp_tiny(fix_variational_hypers, num_epochs, lr)
         if done >= num_epochs:
             return
         num_epochs -= done
@@ -281,7 +304,8 @@ class BlackBoxMFDGPFitter:
             x, y, fid = h.train_dataset.tensors
             perm = self.shuffled_rows(x.shape[0], x.device)
             steps.append(graphed_step.GraphedELBOStep(h.mfdgp, h.elbo, x[perm].contiguous(), y[perm].contiguous(),
-                                                      fid[perm].contiguous(), lr=lr, stream=self._stream_for(slot, x.device)))
+                                                      fid[perm].contiguous(), lr=lr, stream=self._stream_for(slot, x.device),
+                                                      **self._optimizer_kwargs()))
             if tiny is not None:      # a Cholesky failed in the one-launch step: this path (jitter ladder) takes over its state
                 tiny.export_adam_state(slot, steps[-1].optimizer)
         self._run_layer_path(steps, num_epochs, lambda g: (g.loss, g.kl))
@@ -351,7 +375,7 @@ class BlackBoxMFDGPFitter:
                 h.minibatch_state = F.minibatch_state(seed, x.device)
             steps.append(graphed_step.GraphedMiniBatchStep(h.mfdgp, h.elbo, x, y, fid, h.batch_size, lr=lr,
                                                            stream=self._stream_for(slot, x.device),
-                                                           sampler_state=h.minibatch_state))
+                                                           sampler_state=h.minibatch_state, **self._optimizer_kwargs()))
         # a rollback takes the sampler's state back too, so the redone epochs draw the same batches again
         self._run_layer_path(steps, num_epochs, lambda g: (g.epoch_loss, g.epoch_kl))
 
@@ -363,6 +387,9 @@ class BlackBoxMFDGPFitter:
         full_batch = all(h.batch_size >= h.num_data for _, _, h in self._handlers())
         if use_graphs is None:
             use_graphs = str(self.device).startswith("cuda")
+        if self._natgrad() and not use_graphs:
+            raise ValueError("variational_optimizer='natgrad' lives in the captured steps on the GPU: not with use_graphs=False "
+                             "(the host loader) or CPU tensors")
         if use_graphs and full_batch:
             self._train_mfdgp_graphed(True, self.num_epochs_1, self.lr_1)
             self._train_mfdgp_graphed(False, self.num_epochs_2, self.lr_2)
@@ -694,15 +721,18 @@ class BlackBoxMFDGPFitter:
         if use_graphs and not full_batch:
             raise ValueError("a captured conditioned step needs batch_size >= number of training points (mini-batches come "
                              "from a host-side loader)")
+        if self._natgrad() and not full_batch:
+            raise ValueError("variational_optimizer='natgrad' needs batch_size >= number of training points in the conditioned "
+                             "fit (mini-batches come from a host-side loader)")
         tiny = None
-        if use_graphs and self.use_tiny_step and parallel.world()[1] == 1:
+        if use_graphs and self.use_tiny_step and parallel.world()[1] == 1 and not self._natgrad():
             # the reference's own sizes: the whole iteration in 3 + n_con launches (util/tiny_step.py)
             done, tiny = self._train_conditioned_tiny(num_iters)
             num_iters -= done
         if num_iters > 0:
             step = graphed_step.GraphedConditionedStep(self, lr=self.lr_2, use_graph=use_graphs,
                                                        stream=self._stream_for(0, self.pareto_set.device)
-                                                       if self.pareto_set.is_cuda else None)
+                                                       if self.pareto_set.is_cuda else None, **self._optimizer_kwargs())
             if tiny is not None:      # a Cholesky failed there: this path (jitter ladder) continues with its optimiser state
                 for k in range(len(tiny.models)):
                     tiny.export_adam_state(k, step.optimizer)

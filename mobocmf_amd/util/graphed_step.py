@@ -22,12 +22,16 @@ from ..layers.mfdgp_hidden_layer import NotPSDError
 class GraphedELBOStep:
     """step() == one full-batch ELBO step on static (x, y, fidelities).  Falls back to eager with ``use_graph=False``.
     With ``prune_rows`` the rows are reordered once by descending fidelity: ``self.x`` etc. are ``x[self.row_order]``
-    (``row_order`` is None when the caller's order was kept); per-row quantities map back through it."""
+    (``row_order`` is None when the caller's order was kept); per-row quantities map back through it.
+    ``variational_optimizer="natgrad"``: every layer's q(u) moves by natural gradients (functional.FusedNatGradAdam, schedule
+    ``natgrad_gamma`` / ``natgrad_gamma_init`` / ``natgrad_warmup_steps``), Adam keeps the other parameters; "adam" (default) is
+    the one FusedAdam launch over all of them."""
 
     exchanges = False      # True in subclasses whose step has a collective between backward and update
 
     def __init__(self, model, elbo, x, y, fidelities, lr, betas=(0.9, 0.999), eps=1e-8, use_graph=True, stream=None,
-                 warmup=3, fixed_eps=None, prune_rows=True):
+                 warmup=3, fixed_eps=None, prune_rows=True, variational_optimizer="adam", natgrad_gamma=0.1,
+                 natgrad_gamma_init=1e-4, natgrad_warmup_steps=100):
         self.elbo = elbo
         self.S = model.num_samples_for_training
         self.L = model.num_hidden_layers
@@ -54,12 +58,38 @@ class GraphedELBOStep:
                 self.row_order = order
         self.x, self.y, self.fid = x, y, fidelities
         self.fixed_eps = fixed_eps     # list (eps[l] for layer l >= 1) reused every step: deterministic tests
-        optimizer = None
-        if os.environ.get("MOBOCMF_TORCH_ADAM"):      # A/B knob: torch's capturable Adam (seven foreach launches)
+        # "natgrad": q(u) of every layer by natural gradients, Adam on the rest.  The full-batch loss is -ELBO itself
+        # (VariationalELBOMF: data terms summed over the batch - (batch / num_data) KL): scale num_data / batch
+        optimizer = self._variational_optimizer(variational_optimizer, model, x.device, lr, betas, eps,
+                                                float(elbo.num_data) / x.shape[0], natgrad_gamma, natgrad_gamma_init,
+                                                natgrad_warmup_steps)
+        if optimizer is None and os.environ.get("MOBOCMF_TORCH_ADAM"):      # A/B knob: torch's capturable Adam (seven foreach launches)
             optimizer = torch.optim.Adam(list(model.parameters()), lr=lr, betas=betas, eps=eps, capturable=True)
         self._setup(model, x.device, lr, betas, eps, use_graph, stream, optimizer=optimizer)
         if use_graph:
             self._capture(warmup)
+
+    def _variational_optimizer(self, kind, model, device, lr, betas, eps, elbo_scale, gamma, gamma_init, warmup_steps):
+        """The optimiser ``_setup`` is handed for ``variational_optimizer=kind``: None for "adam" (``_setup`` then builds the
+        default FusedAdam), a FusedNatGradAdam for "natgrad".  ``elbo_scale``: what turns the step's loss into -ELBO."""
+        if kind == "adam":
+            return None
+        if kind != "natgrad":
+            raise ValueError("variational_optimizer must be 'adam' or 'natgrad' (got %r)" % (kind,))
+        if self.exchanges:
+            raise ValueError("variational_optimizer='natgrad' is not available for a row-sharded step (the gradients are "
+                             "exchanged between backward and update); shard the surrogates over the ranks instead")
+        if torch.device(device).type != "cuda":
+            raise ValueError("variational_optimizer='natgrad' runs on the GPU only (CPU tensors given)")
+        return F.FusedNatGradAdam(model, lr=lr, betas=betas, eps=eps, gamma=gamma, gamma_init=gamma_init,
+                                  warmup_steps=warmup_steps, elbo_scale=elbo_scale)
+
+    skipped = ()      # what the last check() read
+
+    def skipped_steps(self):
+        """Synchronising: the natural-gradient steps that left a layer unchanged, per layer ([] with Adam)."""
+        fn = getattr(self.optimizer, "skipped_steps", None)
+        return fn() if fn is not None else []
 
     def _setup(self, model, device, lr, betas, eps, use_graph, stream, optimizer=None):
         """What every captured step starts from, whatever its loss: stream, optimiser, loss / KL buffers, empty graph and
@@ -227,6 +257,7 @@ class GraphedELBOStep:
                 F.raise_if_abandoned(pivot, "layer %d" % layer.num_layer)
                 if pivot != 0:
                     raise NotPSDError("K_mm not positive definite in layer %d" % layer.num_layer)
+        self.skipped = self.skipped_steps()      # (raises when a natural-gradient factorisation abandoned an in-launch wait)
         if not bool(torch.isfinite(self.loss)):
             raise FloatingPointError("non-finite ELBO")
 
@@ -260,13 +291,18 @@ class GraphedConditionedStep(GraphedELBOStep):
     (no host reads); x~ is drawn inside the graph, so every replay sees new points."""
 
     def __init__(self, fitter, lr, betas=(0.9, 0.999), eps=1e-8, use_graph=True, stream=None, warmup=3, n_tilde=10,
-                 fixed_x_tilde=None):
+                 fixed_x_tilde=None, variational_optimizer="adam", natgrad_gamma=0.1, natgrad_gamma_init=1e-4,
+                 natgrad_warmup_steps=100):
         self.fitter = fitter
         self.fixed_x_tilde = fixed_x_tilde      # deterministic tests: the same x~ at every iteration
         dev = fitter.pareto_set.device
         self.device, self.d, self.n_tilde = dev, fitter.pareto_set.shape[1], n_tilde
         self.x = fitter.pareto_set            # (only its device is used by the base class)
-        self._setup(_ModelGroup(h.mfdgp for _, _, h in fitter._handlers()), dev, lr, betas, eps, use_graph, stream)
+        group = _ModelGroup(h.mfdgp for _, _, h in fitter._handlers())
+        # the joint loss carries every surrogate's -ELBO whole (conditioned_loss: coefficient -num_data / B): scale 1
+        optimizer = self._variational_optimizer(variational_optimizer, group.models, dev, lr, betas, eps, 1.0, natgrad_gamma,
+                                                natgrad_gamma_init, natgrad_warmup_steps)
+        self._setup(group, dev, lr, betas, eps, use_graph, stream, optimizer=optimizer)
         if use_graph:
             self._capture(warmup)
 
@@ -320,7 +356,8 @@ class GraphedMiniBatchStep(GraphedELBOStep):
     the sums over the last finished epoch, accumulated on the device."""
 
     def __init__(self, model, elbo, x, y, fidelities, batch_size, lr, betas=(0.9, 0.999), eps=1e-8, use_graph=True,
-                 stream=None, warmup=3, fixed_eps=None, order_by_fidelity=True, sampler_state=None):
+                 stream=None, warmup=3, fixed_eps=None, order_by_fidelity=True, sampler_state=None,
+                 variational_optimizer="adam", natgrad_gamma=0.1, natgrad_gamma_init=1e-4, natgrad_warmup_steps=100):
         self.elbo = elbo
         self.S = model.num_samples_for_training
         self.L = model.num_hidden_layers
@@ -336,7 +373,10 @@ class GraphedMiniBatchStep(GraphedELBOStep):
         self.nb = (N + B - 1) // B
         self.order_by_fidelity = bool(order_by_fidelity)
         self.fixed_eps = fixed_eps
-        self._setup(model, dev, lr, betas, eps, use_graph, stream)
+        # (a mini-batch's loss is (rows / num_data) times an unbiased estimate of -ELBO: _update sets the batch's own scale)
+        optimizer = self._variational_optimizer(variational_optimizer, model, dev, lr, betas, eps, float(N) / B, natgrad_gamma,
+                                                natgrad_gamma_init, natgrad_warmup_steps)
+        self._setup(model, dev, lr, betas, eps, use_graph, stream, optimizer=optimizer)
         if sampler_state is None:      # drawn once from torch's CPU generator, after the layers' streams (as layer._rng)
             sampler_state = F.minibatch_state(int(torch.randint(1, 2 ** 62, (), dtype=torch.int64)), dev)
         self.state = sampler_state
@@ -354,6 +394,11 @@ class GraphedMiniBatchStep(GraphedELBOStep):
         self.stream.wait_stream(torch.cuda.current_stream(dev))
         if use_graph:
             self._capture(warmup)
+
+    def _update(self):
+        if hasattr(self.optimizer, "set_elbo_scale"):      # a host value, baked into this shape's graph
+            self.optimizer.set_elbo_scale(float(self.num_data) / self._shape.rows)
+        self.optimizer.step()
 
     def _shape_for(self, step):
         last = len(self.shapes) > 1 and step % self.nb == self.nb - 1

@@ -148,6 +148,41 @@ int main(int argc, char** argv) {
         }
         REQUIRE(mobocmf_tiny_elbo_step(&t, &t, 1, 1e-3, 0.9, 0.999, 1e-8, (int32_t)U(-1, 3), nullptr) == MOBOCMF_BAD_ARG);
     }
+    // the natural-gradient step: size queries over random (M, n) -- refused outside 1..MOBOCMF_NATGRAD_MAX_M x 1..4, otherwise n equal
+    // 256-byte-aligned blocks that hold the M x M operands of the sequence -- and the step's argument checks, which refuse on the
+    // host (the pointers below are never dereferenced: a refused call launches nothing)
+    int ng_ok = 0, ng_bad = 0;
+    for (int icase = 0; icase < ncases; ++icase) {
+        const int32_t M = (int32_t)U(-2, MOBOCMF_NATGRAD_MAX_M + 8), n = (int32_t)U(-1, 6);
+        size_t nb = 0, nb1 = 0;
+        const bool ok = M >= 1 && M <= MOBOCMF_NATGRAD_MAX_M && n >= 1 && n <= 4;
+        REQUIRE((mobocmf_natgrad_workspace_bytes(M, n, &nb) == MOBOCMF_OK) == ok);
+        REQUIRE(mobocmf_natgrad_workspace_bytes(M, n, nullptr) == MOBOCMF_BAD_ARG);
+        double* tab[4] = {(double*)4096, (double*)4096, (double*)4096, (double*)4096};
+        const double* ctab[4] = {tab[0], tab[0], tab[0], tab[0]};
+        int32_t* wtab[4] = {(int32_t*)4096, (int32_t*)4096, (int32_t*)4096, (int32_t*)4096};
+        if (!ok) {
+            ++ng_bad;
+            REQUIRE(mobocmf_natgrad_step(n, M, tab, tab, ctab, ctab, 0.1, 1e-4, 100, 1.0, (int64_t*)4096, wtab, wtab, (void*)4096,
+                                         (size_t)1 << 40, nullptr, nullptr) == MOBOCMF_BAD_ARG);
+            continue;
+        }
+        ++ng_ok;
+        const size_t Mp = ((size_t)M + 127) / 128 * 128;
+        REQUIRE(mobocmf_natgrad_workspace_bytes(M, 1, &nb1) == MOBOCMF_OK && nb == nb1 * (size_t)n && nb1 % 256 == 0);
+        REQUIRE(nb1 >= 10 * Mp * Mp * sizeof(double));
+        REQUIRE(mobocmf_natgrad_step(n, M, tab, tab, ctab, ctab, 0.1, 1e-4, 100, 1.0, (int64_t*)4096, wtab, wtab, (void*)4096,
+                                     nb - 256, nullptr, nullptr) == MOBOCMF_WORKSPACE_TOO_SMALL);
+        const double bad_gamma[] = {0.0, -1.0, 1e-5};      // (1e-5 < gamma_init)
+        REQUIRE(mobocmf_natgrad_step(n, M, tab, tab, ctab, ctab, bad_gamma[U(0, 2)], 1e-4, 100, 1.0, (int64_t*)4096, wtab, wtab,
+                                     (void*)4096, nb, nullptr, nullptr) == MOBOCMF_BAD_ARG);
+        REQUIRE(mobocmf_natgrad_step(n, M, tab, tab, ctab, ctab, 0.1, 1e-4, -1, 1.0, (int64_t*)4096, wtab, wtab, (void*)4096, nb,
+                                     nullptr, nullptr) == MOBOCMF_BAD_ARG);
+        REQUIRE(mobocmf_natgrad_step(n, M, tab, tab, ctab, nullptr, 0.1, 1e-4, 100, 1.0, (int64_t*)4096, wtab, wtab, (void*)4096, nb,
+                                     nullptr, nullptr) == MOBOCMF_BAD_ARG);
+    }
+    std::printf("fuzz_workspaces: mobocmf_natgrad_step: %d shapes sized, %d refused, every step call refused on the host\n", ng_ok,
+                ng_bad);
     std::printf("fuzz_workspaces: mobocmf_tiny_model: %d descriptors sized, %d refused, every step call refused on the host\n",
                 tiny_ok, tiny_bad);
     std::printf("fuzz_workspaces: %d cases: %d valid (%d carved out of exact-size host buffers, %lld regions written, %d above the "
