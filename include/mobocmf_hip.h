@@ -208,6 +208,14 @@ int mobocmf_predictive_covariance(const mobocmf_layer_desc* desc, const double* 
  * else NULL).  K is row-major with ldk >= n2 and must hold round_up(n1, 32) rows (rows >= n1 are written as zeros). */
 int mobocmf_gram_forward(int32_t kind, int32_t d, const double* x1, const double* f1, int64_t n1, const double* x2,
                          const double* f2, int64_t n2, const double* hyp, double* K, int64_t ldk, mobocmf_stream_t stream);
+/* The same with the column side given as a layer gives it: nbase2 base rows x2 [nbase2 x d], each replicated xdiv times
+ * (1..MOBOCMF_MAX_XDIV), column j = row j / xdiv of x2 with f2[j]; f2 holds nbase2 * xdiv values and K has nbase2 * xdiv
+ * columns (ldk >= nbase2 * xdiv).  This is the launch of a layer's K_mn, replica fast paths included (xdiv 8 / 16 with f2
+ * and K 16-byte aligned and ldk even; any other xdiv or alignment takes the general path, same values).  knn (may be NULL)
+ * receives the nbase2 * xdiv prior variances k(column j, column j).  Columns >= nbase2 * xdiv of K are not written. */
+int mobocmf_gram_forward_rep(int32_t kind, int32_t d, const double* x1, const double* f1, int64_t n1, const double* x2,
+                             const double* f2, int64_t nbase2, int32_t xdiv, const double* hyp, double* K, int64_t ldk,
+                             double* knn, mobocmf_stream_t stream);
 
 /* One random-Fourier-feature function sample of a layer evaluated at n points (mfdgp_hidden_layer.py:326-337, :402-444; the
  * Pareto-grid evaluation of moop.py:232-272), without materialising the F x n feature matrix:
@@ -702,8 +710,20 @@ int mobocmf_exact_gp_predict(int32_t n, int64_t nt, const double* Kts, int64_t l
 
 /* The f64 MFMA GEMM used by the layer (exposed for tests and for the roofline measurement of bench.py):
  * C[Mr x Nc] (+)= alpha * A[Mr x Kd] * B, B is [Kd x Nc] (trans_b = 0) or [Nc x Kd] (trans_b = 1).
- * Mr, Nc multiples of 128, Kd multiple of 16, leading dimensions even, pointers 16-byte aligned.
- * tri: bit 0 A lower-triangular, bit 1 A upper-triangular, bit 2 B lower, bit 3 B upper (square operands).
+ * Mr, Nc multiples of 128, Kd multiple of 16, leading dimensions even, pointers 16-byte aligned.  Other sizes are accepted
+ * only where a kernel that handles them takes the product under the given tuning, MOBOCMF_BAD_ARG otherwise: all three
+ * multiples of 16 and <= tuning.small_gemm_max (small-operand kernel); Mr, Nc multiples of 64 and Kd of 32, all <=
+ * tuning.mid_gemm_max (mid-size kernel); A B form with Mr, Kd multiples of 128 and <= tuning.small_panel_max, B not
+ * triangular and Nc any multiple of 16 with (Nc / 16) (Mr / 128) <= 512 (whole-block panel kernel).
+ * tri: bit 0 A lower-triangular, bit 1 A upper-triangular, bit 2 B lower, bit 3 B upper (square operands; for B the flag
+ * names the triangle of the logical Kd x Nc operand, whichever way it is stored).
+ * Triangular-operand contract: the UNUSED TRIANGLE MUST HOLD ZEROS.  The flags only let a kernel skip work: with the operand
+ * cut into 128 x 128 blocks from its origin, a block that lies wholly in the unused triangle (strictly beyond the block
+ * diagonal) is never read and may hold anything; the blocks on the diagonal are read whole, and an entry of the unused
+ * triangle inside them enters the product as stored.  (The small-operand kernels happen to mask those entries on load, the
+ * mid-size and tiled kernels multiply them; which kernel runs is a matter of the tuning thresholds, so no caller may count
+ * on the masking.  Every triangular operand of the layer -- L^-1, U, their transposes, dU, dL -- is stored with its zeros.)
+ * The same holds for the triangular A of mobocmf_gemm_f64_epilogue.
  * tuning: NULL = defaults (the small / mid-size operand thresholds decide which kernel a product runs on). */
 int mobocmf_gemm_f64(int32_t tri, int32_t trans_b, int32_t Mr, int64_t Nc, int64_t Kd, const double* A, int64_t lda,
                      const double* B, int64_t ldb, double* C, int64_t ldc, double alpha, int32_t accumulate,
@@ -720,7 +740,10 @@ int mobocmf_gemm_f64(int32_t tri, int32_t trans_b, int32_t Mr, int64_t Nc, int64
  * B is [Kd x Nc] (no transposed form).  stream_out: non-temporal stores of C.  Pointers an epilogue does not use: NULL.
  * col_activity (NULL = dense): DEVICE array of one int32 per 128 columns of C; the column blocks marked 0 are left unwritten
  * (their row-dot partials zeroed) -- how the tests drive the block skipping of the layer backward directly.  The tile
- * height / pairing come from `tuning`. */
+ * height / pairing come from `tuning`.  Where the whole-block panel kernel takes the product (A B form, Mr and Kd multiples
+ * of 128 and <= tuning.small_panel_max, at most 512 workgroups of 128 rows x 16 columns) Nc may be any multiple of 16; it then
+ * writes Nc / 16 row-dot partial rows, the tiled kernel 2 * (Nc / 128).  col_activity then holds one word per STARTED 128
+ * columns, ceil(Nc / 128) words: the last word governs the partial block. */
 int mobocmf_gemm_f64_epilogue(int32_t tri, int32_t epi, int32_t Mr, int64_t Nc, int64_t Kd, const double* A, int64_t lda,
                               const double* B, int64_t ldb, double* C, int64_t ldc, double alpha, int32_t stream_out,
                               double* colsq_part, double* coldot_part, const double* avec, const double* bscale,

@@ -1093,6 +1093,20 @@ int mobocmf_gram_forward(int32_t kind, int32_t d, const double* x1, const double
     return launch_gram_fwd(g, (hipStream_t)stream);
 }
 
+int mobocmf_gram_forward_rep(int32_t kind, int32_t d, const double* x1, const double* f1, int64_t n1, const double* x2,
+                             const double* f2, int64_t nbase2, int32_t xdiv, const double* hyp, double* K, int64_t ldk,
+                             double* knn, mobocmf_stream_t stream) {
+    if ((kind != 0 && kind != 1) || d < 1 || d > MOBOCMF_MAX_D || !x1 || !x2 || !hyp || !K || n1 < 1 || nbase2 < 1 ||
+        xdiv < 1 || xdiv > MOBOCMF_MAX_XDIV || n1 > 0x7fffffff || nbase2 > 0x7fffffff || ldk < nbase2 * xdiv ||
+        (kind == 1 && (!f1 || !f2)))
+        return MOBOCMF_BAD_ARG;
+    GramArgs g = {};
+    g.kind = kind; g.d = d; g.xdiv = xdiv; g.zdiv = 1;
+    g.x = x2; g.f = f2; g.nbase = nbase2; g.Zx = x1; g.zf = f1; g.M = (int)n1; g.hyp = hyp;
+    g.K = K; g.ldk = ldk; g.Mp = (int)round_up(n1, 32); g.Np = nbase2 * xdiv; g.knn = knn; g.jitter = 0.0; g.is_kmm = 0;
+    return launch_gram_fwd(g, (hipStream_t)stream);
+}
+
 int mobocmf_gemm_f64_epilogue(int32_t tri, int32_t epi, int32_t Mr, int64_t Nc, int64_t Kd, const double* A, int64_t lda,
                               const double* B, int64_t ldb, double* C, int64_t ldc, double alpha, int32_t stream_out,
                               double* colsq_part, double* coldot_part, const double* avec, const double* bscale,

@@ -892,7 +892,8 @@ static int tile_rows(const GemmArgs& g, bool B_T, int splitk) {
 
 int launch_gemm(const GemmArgs& g0, bool B_T, int splitk, hipStream_t s) {
     GemmArgs g = g0;
-    if (g.Mr % BM || g.Nc % BN || g.Kd % BK) return MOBOCMF_BAD_ARG;
+    // (the whole-block panel kernel below takes widths that are multiples of 16; every other kernel needs whole 128-column tiles)
+    if (g.Mr % BM || g.Nc % 16 || g.Kd % BK) return MOBOCMF_BAD_ARG;
     // block activity is honoured where the kernels implement it, and ignored (dense product: the same result) elsewhere
     if (B_T || g.batched || splitk > 1) g.colact = nullptr;
     if (g.kact) {
@@ -908,6 +909,7 @@ int launch_gemm(const GemmArgs& g0, bool B_T, int splitk, hipStream_t s) {
         if (g.epi == EPI_DA) return launch_small_panel<EPI_DA>(g, s);
         return launch_small_panel<EPI_STORE>(g, s);
     }
+    if (g.Nc % BN) return MOBOCMF_BAD_ARG;
     if (B_T && splitk <= 1 && small_gemm_ok(g, true)) return launch_small_gemm(g, true, s);   // small weighted syrk
     // batched small products (the 128 / 256-wide merges of the blocked triangular inverse): a handful of tiles each, pure
     // latency on the 128 x 128 x 16 pipeline (19-23 us per launch at M = 512), ~7 us on the small-operand kernel
@@ -1777,7 +1779,9 @@ int launch_gemm_auto(const GemmArgs& g0, bool B_T, double* ws, int64_t ws_elems,
     int64_t nk = g.Kd / BK;
     if (g.tri) nk = (nk + 1) / 2;
     int sk = 1;
-    if (!g.batched && g.epi == EPI_STORE && ntile * nz < 96 * nz && ntile < 96 && nk >= 8) {
+    // (ntile = 0: narrower or lower than one tile -- never sliced; launch_gemm hands it to the whole-block panel kernel or
+    // declines it)
+    if (!g.batched && g.epi == EPI_STORE && ntile > 0 && ntile * nz < 96 * nz && ntile < 96 && nk >= 8) {
         sk = (int)(512 / (ntile * nz));      // up to one round of resident workgroups
         if (sk > nk / 2) sk = (int)(nk / 2);
         if (sk >= 8) sk &= ~7;

@@ -963,6 +963,8 @@ class _ElboFusedFn(torch.autograd.Function):
             if sp is not None:
                 means[l], vars_[l], raws[l] = next(it), next(it), next(it)
                 gm[l], gv[l], gr[l] = _empty_like(means[l]), _empty_like(vars_[l]), _empty_like(raws[l])
+                if means[l].numel() == 0:      # a layer of no rows has no storage: the kernel sees it as absent and writes nothing
+                    gr[l].zero_()
         gkl = _empty(1, device=dev)
         ge = None if g_elbo is None else _prep(g_elbo)
         gs = None if g_skl is None else _prep(g_skl)
@@ -1535,19 +1537,30 @@ def gemm_f64_epilogue(A, B, C, tri, epi, alpha=1.0, stream_out=False, colsq_part
     return C
 
 
-def gram(kind, x1, f1, x2, f2, hyp):
+def gram(kind, x1, f1, x2, f2, hyp, xdiv=1, knn=False):
     """Dense k([x1, f1], [x2, f2]) of a layer's kernel (n1 x n2), no autograd: the evaluated prior of
-    MFDGPHiddenLayer.forward."""
+    MFDGPHiddenLayer.forward.  ``xdiv`` > 1: ``x2`` holds base rows, each replicated ``xdiv`` times (column j = row
+    j // xdiv of x2 with f2[j]; f2 holds x2.shape[0] * xdiv values) -- the launch of a layer's K_mn
+    (mobocmf_gram_forward_rep).  ``knn``: also return the prior variances of the columns, (K, knn)."""
     lib = _lib.require_device()
     with torch.no_grad():
         x1, f1, x2, f2, hyp = (_prep(None if t is None else t.detach()) for t in (x1, f1, x2, f2, hyp))
-        n1, n2, d = x1.shape[0], x2.shape[0], x1.shape[1]
-        if x2.shape[1] != d or hyp.numel() != hyp_len(kind, d) or not 1 <= d <= _lib.MAX_D:
+        n1, nb2, d = x1.shape[0], x2.shape[0], x1.shape[1]
+        if not 1 <= int(xdiv) <= _lib.MAX_XDIV:
+            raise _lib.MobocmfError("gram: xdiv 1..%d" % _lib.MAX_XDIV)
+        n2 = nb2 * int(xdiv)
+        if x2.shape[1] != d or hyp.numel() != hyp_len(kind, d) or not 1 <= d <= _lib.MAX_D or \
+                (kind == 1 and (f1 is None or f2 is None or f1.numel() != n1 or f2.numel() != n2)):
             raise _lib.MobocmfError("gram: shape mismatch")
         K = _empty((n1 + 31) // 32 * 32, n2, device=x1.device)
-        _lib.check(lib.mobocmf_gram_forward(kind, d, _ptr(x1), _ptr(f1), n1, _ptr(x2), _ptr(f2), n2, _ptr(hyp), _ptr(K),
-                                            K.stride(0), _stream()), "mobocmf_gram_forward")
-    return K[:n1]
+        if int(xdiv) == 1 and not knn:
+            _lib.check(lib.mobocmf_gram_forward(kind, d, _ptr(x1), _ptr(f1), n1, _ptr(x2), _ptr(f2), n2, _ptr(hyp), _ptr(K),
+                                                K.stride(0), _stream()), "mobocmf_gram_forward")
+            return K[:n1]
+        kd = _empty(n2, device=x1.device) if knn else None
+        _lib.check(lib.mobocmf_gram_forward_rep(kind, d, _ptr(x1), _ptr(f1), n1, _ptr(x2), _ptr(f2), nb2, int(xdiv), _ptr(hyp),
+                                                _ptr(K), K.stride(0), _ptr(kd), _stream()), "mobocmf_gram_forward_rep")
+    return (K[:n1], kd) if knn else K[:n1]
 
 
 def rff_eval(kind, x, fprev, W1, b1, Wf, W2, b2, theta, s0, s1=0.0, s2=0.0):

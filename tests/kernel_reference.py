@@ -1,0 +1,483 @@
+"""References and direct C-ABI callers shared by the kernel conformance tests ("Kernel conformance tests").
+
+Three things live here so that the CPU proof (tests/test_kernel_reference_cpu.py) and the GPU tests use the same objects:
+
+* exact inputs -- integer operands in [-4, 4], optionally times powers of two along dimensions an output does not sum over.
+  Every product and every partial sum of them is an integer (times one power of two) below 2^53, hence exactly
+  representable: the float64 result does not depend on summation order, FMA use, k-slicing, slab reduction or tile shape,
+  and a correct kernel is BITWISE equal to the reference under every tuning;
+* high-precision references (numpy.longdouble with a 64-bit significand, else mpmath) for inexact data, with the a-priori
+  componentwise bounds the rounding tests assert;
+* callers of the product / Gram / ELBO entry points that pass pointers, leading dimensions and tunings through unchanged
+  (functional._prep would make every operand contiguous).
+"""
+import ctypes
+
+import numpy as np
+import torch
+
+U = 2.0 ** -53                       # unit roundoff of float64
+NAN = float("nan")
+
+# ------------------------------------------------------------------------------------------------------- shapes (Mr, Nc, Kd)
+# Product families of mobocmf_gemm_f64 and the tuning that forces each (gemm_f64.hip: launch_gemm_auto).  The tiled shapes
+# miss the whole-block panel kernel by their size (Kd no multiple of 128, or Mr > 512); the square one needs small_panel_max.
+TILED = dict(small_gemm_max=16, mid_gemm_max=0)
+GEMM_FAMILIES = {
+    "small": [((16, 16, 16), {}), ((48, 32, 80), {}), ((384, 384, 384), {})],
+    "mid4": [(s, dict(mid_gemm_waves=4)) for s in ((512, 512, 512), (64, 448, 128), (1024, 64, 192), (640, 640, 640))],
+    "mid8": [(s, dict(mid_gemm_waves=8)) for s in ((512, 512, 512), (64, 448, 128), (1024, 64, 192), (640, 640, 640))],
+    "mid32": [(s, dict(mid_gemm_waves=32)) for s in ((512, 512, 512), (64, 448, 128), (1024, 64, 192), (640, 640, 640))],
+    "tiled": [((128, 128, 16), TILED), ((256, 384, 144), TILED), ((1152, 128, 128), TILED), ((1152, 128, 128), {}),
+              ((256, 256, 256), dict(TILED, small_panel_max=16))],
+}
+# The whole-block panel kernel under the plain entry point, at widths below one 128-column tile: every other kernel declines
+# these (A B form only).  GEMM_DECLINED (shape, trans_b, tuning): no kernel takes them, MOBOCMF_BAD_ARG.
+GEMM_PANEL = [((512, 48, 512), {}), ((256, 48, 256), TILED), ((128, 16, 128), TILED)]
+GEMM_DECLINED = [((512, 48, 512), 1, {}), ((1152, 64, 1152), 0, {}), ((256, 48, 256), 0, dict(TILED, small_panel_max=16)),
+                 ((64, 128, 128), 0, TILED), ((512, 48, 520), 0, {})]
+BAD_ARG = 1                             # MOBOCMF_BAD_ARG (include/mobocmf_hip.h)
+TRI_FLAGS = (0, 1, 2, 4, 8, 1 | 4, 1 | 8, 2 | 4)      # every combination the chain, the Cholesky and natgrad launch
+EPI_MR = (128, 256, 384, 640)                           # Kd = Mr; 384 and 640: an odd number of row blocks
+EPI_NC_TILED = (128, 384)
+EPI_NC_PANEL = (16, 48, 144, 128, 384)
+SYRK_MR = (128, 256, 384, 640)
+SYRK_KD = (128, 256, 1024, 2176)
+
+
+def gemm_shapes():
+    return sorted({s for fam in GEMM_FAMILIES.values() for s, _ in fam} | {s for s, _ in GEMM_PANEL})
+
+
+# ------------------------------------------------------------------------------------------------------------ exact inputs
+def exact_ints(shape, seed):
+    """Integers in [-4, 4] as int64."""
+    return np.random.default_rng(seed).integers(-4, 5, size=shape).astype(np.int64)
+
+
+def tile_scales(n, block, seed):
+    """2^e per index, e in [-100, 100]: constant on blocks of ``block`` indices, neighbouring blocks >= 2^160 apart (even
+    blocks 2^80..2^100, odd blocks 2^-100..2^-80) -- a block that is wrong but quiet cannot hide behind a loud one."""
+    rng = np.random.default_rng(seed)
+    nb = (n + block - 1) // block
+    e = np.where(np.arange(nb) % 2 == 0, rng.integers(80, 101, nb), -rng.integers(80, 101, nb))
+    return np.exp2(np.repeat(e, block)[:n].astype(np.float64))
+
+
+def tri_mask(n, lower):
+    i = np.arange(n)
+    return (i[:, None] >= i[None, :]) if lower else (i[:, None] <= i[None, :])
+
+
+def gemm_operands(Mr, Nc, Kd, tri, seed=0):
+    """Integer A [Mr x Kd] and logical B [Kd x Nc] with the zeros of the triangles ``tri`` names (int64)."""
+    A, B = exact_ints((Mr, Kd), seed + 1), exact_ints((Kd, Nc), seed + 2)
+    if tri & 3:
+        assert Mr == Kd
+        A = A * tri_mask(Mr, bool(tri & 1))
+    if tri & 12:
+        assert Kd == Nc
+        B = B * tri_mask(Kd, bool(tri & 4))
+    return A, B
+
+
+def tri_ok(tri, Mr, Nc, Kd):
+    return (not (tri & 3) or Mr == Kd) and (not (tri & 12) or Kd == Nc)
+
+
+def exactness_margin(absA, absB):
+    """max_i sum_k |a_ik| max_j |b_kj| >= sum_k |a_ik||b_kj| for every output -- an upper bound of EVERY partial sum in EVERY
+    order; the result is exact while it stays below 2^53."""
+    return int((np.abs(absA).astype(np.int64) @ np.abs(absB).astype(np.int64).max(1)).max())
+
+
+def imatmul(A, B):
+    """Exact int64 product (torch's integer matmul: numpy's runs one scalar loop)."""
+    return (torch.from_numpy(np.ascontiguousarray(A, dtype=np.int64)) @ torch.from_numpy(np.ascontiguousarray(B, dtype=np.int64))).numpy()
+
+
+def fmatmul(A, B):
+    """The same product through float64 BLAS, as int64: tests/test_kernel_reference_cpu.py proves it bitwise equal to
+    imatmul for every shape used (that IS the exactness condition), so the references below take the fast one."""
+    return (np.asarray(A, np.float64) @ np.asarray(B, np.float64)).astype(np.int64)
+
+
+def unused_block_poison(a, lower, block=128):
+    """Copy of the float matrix ``a`` (a triangular operand stored with its zeros) with NaN in every block x block block
+    that lies wholly in the unused triangle -- where the contract of mobocmf_gemm_f64 says nothing is read."""
+    a = a.copy()
+    n = a.shape[0]
+    bi = np.arange(n) // block
+    beyond = (bi[:, None] < bi[None, :]) if lower else (bi[:, None] > bi[None, :])
+    a[beyond] = np.nan
+    return a
+
+
+EPI_ALPHA = -0.5
+
+
+def epilogue_case(Mr, Nc, tri, seed=0, scaled=None):
+    """Operands of mobocmf_gemm_f64_epilogue at Kd = Mr as (integers, scales): A triangular per ``tri`` (1 lower, 2 upper, 0
+    dense), B, Aaux [Mr x Nc], avec [Mr], bscale / gmu / cgv [Nc].  ``scaled``: None | 'rows' (A, avec, Aaux rows times
+    2^e per 128-row block: every output that does not sum over rows -- C, the row dots -- stays exact) | 'cols' (B, gmu, cgv
+    columns times 2^e per 128-column block: C and the column statistics stay exact)."""
+    c = dict(A=gemm_operands(Mr, Nc, Mr, tri & 3, seed)[0], B=exact_ints((Mr, Nc), seed + 2),
+             Aaux=exact_ints((Mr, Nc), seed + 3), avec=exact_ints(Mr, seed + 4), bscale=exact_ints(Nc, seed + 5),
+             gmu=exact_ints(Nc, seed + 6), cgv=exact_ints(Nc, seed + 7))
+    c["rs"] = tile_scales(Mr, 128, seed + 8) if scaled == "rows" else np.ones(Mr)
+    c["cs"] = tile_scales(Nc, 128, seed + 9) if scaled == "cols" else np.ones(Nc)
+    return c
+
+
+def epilogue_inputs(c):
+    """The float64 operands a kernel is given (integers times their power-of-two scales: exact)."""
+    f = lambda a: a.astype(np.float64)
+    rs, cs = c["rs"], c["cs"]
+    return dict(A=f(c["A"]) * rs[:, None], B=f(c["B"]) * cs[None, :], Aaux=f(c["Aaux"]) * rs[:, None], avec=f(c["avec"]) * rs,
+                bscale=f(c["bscale"]), gmu=f(c["gmu"]) * cs, cgv=f(c["cgv"]) * cs)
+
+
+def epilogue_ref_int(c, epi):
+    """Exact integer results, scales left out: 2 C, and for epi 1 (4 colsq, 2 coldot), for epi 2 the row dots (alpha = -1/2)."""
+    AB = fmatmul(c["A"], c["B"])
+    if epi < 2:
+        C2 = -AB
+        return dict(C2=C2, colsq4=(C2 * C2).sum(0), coldot2=c["avec"] @ C2)
+    C2 = -c["bscale"][None, :] * AB + 2 * c["avec"][:, None] * c["gmu"][None, :] - 4 * c["Aaux"] * c["cgv"][None, :]
+    return dict(C2=C2, rowdot=c["Aaux"] @ c["gmu"])
+
+
+def epilogue_ref(c, epi):
+    """The same as float64 with the scales applied (exact: integers below 2^53 times powers of two)."""
+    r = epilogue_ref_int(c, epi)
+    f = lambda a: a.astype(np.float64)
+    rs, cs = c["rs"], c["cs"]
+    out = dict(C=f(r["C2"]) * 0.5 * rs[:, None] * cs[None, :])
+    if epi == 1:
+        out["colsq"] = f(r["colsq4"]) * 0.25 * cs * cs
+        out["coldot"] = f(r["coldot2"]) * 0.5 * cs
+    if epi == 2:
+        out["rowdot"] = f(r["rowdot"]) * rs
+    return out
+
+
+def syrk_case(Mr, Kd, seed=0, kact=None, scaled=False):
+    """A [Mr x Kd], w [Kd] integers (w zero on the 128-blocks ``kact`` marks inactive), row scales of A."""
+    A, w = exact_ints((Mr, Kd), seed + 11), exact_ints(Kd, seed + 12)
+    if kact is not None:
+        w = w * np.repeat(np.asarray(kact, np.int64), 128)
+    return dict(A=A, w=w, rs=tile_scales(Mr, 128, seed + 13) if scaled else np.ones(Mr))
+
+
+def syrk_ref(c):
+    H = fmatmul(c["A"] * c["w"][None, :], c["A"].T)
+    return H.astype(np.float64) * c["rs"][:, None] * c["rs"][None, :]
+
+
+ACTIVITY = {"all": lambda n: [1] * n, "none": lambda n: [0] * n, "first": lambda n: [1] + [0] * (n - 1),
+            "last": lambda n: [0] * (n - 1) + [1]}
+
+
+# ------------------------------------------------------------------------------------------- high-precision references
+HAVE_LONGDOUBLE = np.finfo(np.longdouble).nmant >= 63
+
+
+def matmul_hp(A, B):
+    """A @ B in extended precision, returned as longdouble (error K 2^-64 |A||B|: 2^-11 of the float64 bound)."""
+    if HAVE_LONGDOUBLE:
+        return np.asarray(A, np.longdouble) @ np.asarray(B, np.longdouble)
+    import mpmath
+    mpmath.mp.dps = 50
+    C = mpmath.matrix(np.asarray(A, np.float64).tolist()) * mpmath.matrix(np.asarray(B, np.float64).tolist())
+    return np.array(C.tolist(), dtype=np.float64).astype(np.longdouble)
+
+
+def ld(a):
+    return np.asarray(a, np.longdouble)
+
+
+def componentwise_ok(got, ref, R, n_ops):
+    """|got - ref| <= (n_ops + 2) 2^-53 R elementwise; returns (ok, worst ratio err / (2^-53 R))."""
+    err = np.abs(ld(got) - ref)
+    bound = (n_ops + 2) * ld(U) * R
+    ratio = float(np.max(np.where(R > 0, err / np.where(R > 0, ld(U) * R, 1), np.where(err > 0, np.inf, 0))))
+    return bool(np.all(err <= bound)), ratio
+
+
+# ---- Gram kernels (include/mobocmf_hip.h, mobocmf_layer_desc):
+#   kind 0  k = alpha exp(-arg1),                                   arg = 1/2 sum_k ((x_k - z_k) / ls_k)^2
+#   kind 1  k = a1 E1 nu f f' + a1 E1 af Ef + a2 E2                 (three terms, exponents arg1, arg1 + argf, arg2)
+# Per-element bound c (2 + |arg|) 2^-53 |term|, summed over the terms.  c is MEASURED on the float64 CPU restatement
+# (oracle/mfdgp_oracle.gram) against the longdouble reference on the inputs of gram_case below, by
+# tests/test_kernel_reference_cpu.py::test_gram_constant_is_the_measured_one: worst ratio err / ((2 + |arg|) 2^-53 sum|term|)
+# over kind 0 / 1, d in {1, 2, 3, 8, 9, 32}, measured 7.24 (kind 0, d = 2, where the restatement's x / ls - z / ls cancels; 2.9 to
+# 4.6 at the other d), recorded rounded up as GRAM_RATIO_MEASURED; the device uses another summation order, FMA and
+# precomputed reciprocal lengthscales, each worth a few u |arg|, hence c = 4 x that = 29.2.
+GRAM_RATIO_MEASURED = 7.3
+GRAM_C = 4.0 * GRAM_RATIO_MEASURED
+GRAM_D = (1, 2, 3, 8, 9, 32)
+GRAM_XDIV = (1, 3, 8, 16, 48)
+GRAM_N1 = (1, 31, 33)
+GRAM_NBASE2 = (1, 127, 129)
+
+
+def gram_case(kind, d, n1, nbase2, xdiv, seed=0):
+    """Inputs of one Gram case (float64 numpy): lengthscales log-uniform in [0.05, 1.5] (d <= 3) or [0.05, 0.08] (|arg|
+    reaches the thousands at d = 32), some columns sitting on rows of x1 so that entries of order one exist beside the underflowing ones."""
+    rng = np.random.default_rng(1000 * kind + 10 * d + seed)
+    x1 = rng.random((n1, d))
+    x2 = rng.random((nbase2, d))
+    k = min(n1, nbase2, 5)
+    x2[:k] = x1[:k] + 1e-3 * rng.standard_normal((k, d))
+    hi = 1.5 if d <= 3 else 0.08                 # many short lengthscales at large d: exponents past float64's range
+    ls = lambda n: np.exp(rng.uniform(np.log(0.05), np.log(hi if n > 1 else 1.5), n))
+    if kind == 0:
+        hyp = np.concatenate([[0.7 + rng.random()], ls(d)])
+        return dict(x1=x1, f1=None, x2=x2, f2=None, hyp=hyp)
+    hyp = np.concatenate([[0.6 + rng.random(), 0.5 + rng.random(), 0.5 + rng.random(), 0.05 + 0.1 * rng.random()],
+                          ls(1), ls(d), ls(d)])
+    return dict(x1=x1, f1=0.5 * rng.standard_normal(n1), x2=x2, f2=rng.standard_normal(nbase2 * xdiv), hyp=hyp)
+
+
+def gram_hp(kind, c, xdiv):
+    """(K, sum_t (2 + |arg_t|) |term_t|, knn) in longdouble: rows = x1, columns = x2 rows replicated xdiv times."""
+    assert HAVE_LONGDOUBLE
+    x1, x2, hyp = ld(c["x1"]), ld(c["x2"]), ld(c["hyp"])
+    d = x1.shape[1]
+    half = ld(0.5)
+
+    def arg(a, b, ls):
+        t = (a[:, None, :] - b[None, :, :]) / ls
+        return half * (t * t).sum(-1)
+
+    if kind == 0:
+        a1 = np.repeat(arg(x1, x2, hyp[1:1 + d]), xdiv, axis=1)
+        K = hyp[0] * np.exp(-a1)
+        return K, (2 + a1) * np.abs(K), np.full(K.shape[1], hyp[0])
+    a1_, af_, nu, a2_, lsf = hyp[:5]
+    f1, f2 = ld(c["f1"]), ld(c["f2"])
+    g1 = np.repeat(arg(x1, x2, hyp[5:5 + d]), xdiv, axis=1)
+    g2 = np.repeat(arg(x1, x2, hyp[5 + d:5 + 2 * d]), xdiv, axis=1)
+    gf = half * ((f1[:, None] - f2[None, :]) / lsf) ** 2
+    T1 = a1_ * np.exp(-g1) * nu * f1[:, None] * f2[None, :]
+    T2 = a1_ * np.exp(-(g1 + gf)) * af_
+    T3 = a2_ * np.exp(-g2)
+    W = (2 + g1) * np.abs(T1) + (2 + g1 + gf) * np.abs(T2) + (2 + g2) * np.abs(T3)
+    return T1 + T2 + T3, W, a1_ * (nu * f2 * f2 + af_) + a2_
+
+
+def gram_violations(got, K, W, c=None):
+    """Elements outside the bound: c 2^-53 W where the reference is >= 1e-290, else |got - ref| <= 1e-300.  Returns
+    (count, worst ratio err / (2^-53 W) over the regular elements)."""
+    c = GRAM_C if c is None else c
+    err = np.abs(ld(got) - K)
+    tiny = np.abs(K) < ld(1e-290)
+    ratio = np.where(tiny, 0, err / np.where(tiny, 1, ld(U) * W))
+    bad = np.where(tiny, err > ld(1e-300), ratio > c)
+    return int(bad.sum()), float(ratio.max()) if ratio.size else 0.0
+
+
+# ---- fused ELBO (variational_elbo_mf.py:24-51; include/mobocmf_hip.h, mobocmf_elbo_forward)
+LOG_2PI = ld(2) * np.arctan(ld(1)) * 4
+LOG_2PI = np.log(LOG_2PI)
+
+
+def elbo_hp(layers, y, fid, kls, scale, g_elbo, g_skl):
+    """layers[l] = None | dict(mean, var (B*div each), raw, lo, hi, div, rows).  Returns a dict of longdouble references:
+    out3, abs3 (sum of |terms| behind out3[0] / out3[1]), n_terms, g_mean[l], g_var[l] (NaN beyond the prefix), g_raw[l],
+    g_raw_abs[l], n_raw[l], g_kl."""
+    y, fid = ld(y), np.asarray(fid)
+    data, dabs, n = ld(0), ld(0), 0
+    ge = ld(0 if g_elbo is None else g_elbo)
+    gs = ld(0 if g_skl is None else g_skl)
+    out = dict(g_mean=[], g_var=[], g_raw=[], g_raw_abs=[], n_raw=[])
+    for l, lay in enumerate(layers):
+        if lay is None:
+            for k in ("g_mean", "g_var", "g_raw", "g_raw_abs", "n_raw"):
+                out[k].append(None)
+            continue
+        div, rows = lay["div"], lay["rows"]
+        lo, hi, raw = ld(lay["lo"]), ld(lay["hi"]), ld(lay["raw"])
+        sg = 1 / (1 + np.exp(-raw))
+        tau = lo + (hi - lo) * sg if hi > lo else raw
+        chain = (hi - lo) * sg * (1 - sg) if hi > lo else ld(1)
+        nn = rows * div
+        mean, var = ld(lay["mean"][:nn]), ld(lay["var"][:nn])
+        b = np.arange(nn) // div
+        mask = fid[b] == float(l)
+        dlt = y[b] - mean
+        term = np.where(mask, -ld(0.5) * ((dlt * dlt + var) / tau + np.log(tau) + LOG_2PI), 0) / div
+        data += term.sum()
+        dabs += np.abs(term).sum()
+        n += int(mask.sum())
+        gm = np.full(lay["mean"].shape[0], np.nan, np.longdouble)
+        gv = gm.copy()
+        gm[:nn] = np.where(mask, ge / div * dlt / tau, 0)
+        gv[:nn] = np.where(mask, -ld(0.5) * ge / div / tau, 0)
+        st = np.where(mask, ld(0.5) * ((dlt * dlt + var) / (tau * tau) - 1 / tau), 0) / div * ge * chain
+        sa = np.where(mask, ld(0.5) * ((dlt * dlt + var) / (tau * tau) + 1 / tau), 0) / div * np.abs(ge) * np.abs(chain)
+        out["g_mean"].append(gm)
+        out["g_var"].append(gv)
+        out["g_raw"].append(st.sum())
+        out["g_raw_abs"].append(sa.sum())
+        out["n_raw"].append(int(mask.sum()))
+    kl = sum((ld(k) for k in kls), ld(0))
+    kabs = sum((abs(ld(k)) for k in kls), ld(0))
+    sc = ld(scale)
+    out["out3"] = np.array([data - sc * kl, sc * kl, -(data - sc * kl)], np.longdouble)
+    out["abs3"] = np.array([dabs + abs(sc) * kabs, abs(sc) * kabs, dabs + abs(sc) * kabs], np.longdouble)
+    out["n_terms"] = n + len(kls)
+    out["g_kl"] = sc * (gs - ge)
+    out["g_kl_abs"] = abs(sc) * (abs(gs) + abs(ge))
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ direct C-ABI callers
+def lib():
+    from mobocmf_amd import _lib
+    return _lib.require_device()
+
+
+def make_tuning(**kw):
+    """An explicit mobocmf_tuning: the compiled-in defaults with ``kw`` on top."""
+    from mobocmf_amd import _lib
+    t = _lib.Tuning()
+    _lib.check(_lib.load().mobocmf_tuning_init(ctypes.byref(t)), "mobocmf_tuning_init")
+    for k, v in kw.items():
+        assert k in _lib.Tuning.KNOBS, k
+        setattr(t, k, int(v))
+    return t
+
+
+def _p(t):
+    return ctypes.c_void_p(0 if t is None else t.data_ptr())
+
+
+def _stream():
+    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+class Strided:
+    """A rows x width device matrix inside a NaN-filled backing store: leading dimension ``ldim`` >= width (the columns
+    width..ldim are slack) and ``offset`` doubles in front of the base pointer (offset 2: a base that is only 16-byte
+    aligned).  ``slack_untouched()``: every slack double is still NaN -- no stray write."""
+
+    def __init__(self, rows, width, pad=0, offset=0, fill=None, dtype=torch.float64, device="cuda"):
+        self.rows, self.width, self.ld, self.offset = rows, width, width + pad, offset
+        self.back = torch.full((offset + rows * self.ld,), NAN, dtype=dtype, device=device)
+        self.full = self.back[offset:].view(rows, self.ld)
+        self.view = self.full[:, :width]
+        self.mask = torch.ones(self.back.shape, dtype=torch.bool, device=device)
+        self.mask[offset:].view(rows, self.ld)[:, :width] = False
+        if fill is not None:
+            self.set(fill)
+
+    def set(self, a):
+        self.view.copy_(torch.as_tensor(np.ascontiguousarray(a), dtype=torch.float64).to(self.view.device))
+        return self
+
+    def poison(self):
+        self.back.fill_(NAN)
+        return self
+
+    def slack_untouched(self):
+        return bool(torch.isnan(self.back[self.mask]).all())
+
+    @property
+    def ptr(self):
+        return ctypes.c_void_p(self.view.data_ptr())
+
+
+def gemm(A, B, C, Mr, Nc, Kd, tri=0, trans_b=0, alpha=1.0, accumulate=0, tune=None, check=True):
+    """mobocmf_gemm_f64 on Strided operands, pointers and leading dimensions as they are (check=False: the status is
+    returned, not raised)."""
+    from mobocmf_amd import _lib
+    rc = lib().mobocmf_gemm_f64(tri, int(trans_b), Mr, Nc, Kd, A.ptr, A.ld, B.ptr, B.ld, C.ptr, C.ld, float(alpha),
+                                int(accumulate), ctypes.byref(tune) if tune is not None else None, _stream())
+    if check:
+        _lib.check(rc, "mobocmf_gemm_f64")
+    return rc
+
+
+def colstat_rows(tri, Mr, Nc, Kd, tune):
+    from mobocmf_amd import _lib
+    rows = ctypes.c_int32()
+    _lib.check(lib().mobocmf_gemm_colstat_rows(tri, Mr, Nc, Kd, ctypes.byref(tune), ctypes.byref(rows)), "colstat_rows")
+    return rows.value
+
+
+def gemm_epilogue(A, B, C, Mr, Nc, Kd, tri, epi, alpha=1.0, stream_out=0, colsq=None, coldot=None, avec=None, bscale=None,
+                  gmu=None, cgv=None, Aaux=None, rowdot=None, colact=None, tune=None):
+    """mobocmf_gemm_f64_epilogue; Aaux shares C's leading dimension (a Strided of C's layout)."""
+    from mobocmf_amd import _lib
+    assert Aaux is None or Aaux.ld == C.ld
+    rc = lib().mobocmf_gemm_f64_epilogue(tri, epi, Mr, Nc, Kd, A.ptr, A.ld, B.ptr, B.ld, C.ptr, C.ld, float(alpha),
+                                         int(stream_out), _p(colsq), _p(coldot), _p(avec), _p(bscale), _p(gmu), _p(cgv),
+                                         Aaux.ptr if Aaux is not None else None, _p(rowdot), _p(colact),
+                                         ctypes.byref(tune) if tune is not None else None, _stream())
+    _lib.check(rc, "mobocmf_gemm_f64_epilogue")
+
+
+def syrk(A, w, H, Mr, Kd, kact=None, tune=None):
+    """mobocmf_syrk_weighted_f64 with a NaN-filled workspace of exactly the reported size."""
+    from mobocmf_amd import _lib
+    nb = ctypes.c_size_t()
+    tp = ctypes.byref(tune) if tune is not None else None
+    _lib.check(lib().mobocmf_syrk_workspace_bytes(Mr, Kd, tp, ctypes.byref(nb)), "mobocmf_syrk_workspace_bytes")
+    ws = torch.full((max(nb.value // 8, 1),), NAN, dtype=torch.float64, device=H.device)
+    rc = lib().mobocmf_syrk_weighted_f64(Mr, Kd, A.ptr, A.ld, _p(w), _p(H), _p(ws), nb.value, _p(kact), tp, _stream())
+    _lib.check(rc, "mobocmf_syrk_weighted_f64")
+
+
+def gram_rep(kind, d, x1, f1, n1, x2, f2, nbase2, xdiv, hyp, K, ldk, knn=None):
+    """mobocmf_gram_forward_rep with the pointers as given (f2 may be a view that is only 8-byte aligned)."""
+    from mobocmf_amd import _lib
+    rc = lib().mobocmf_gram_forward_rep(kind, d, _p(x1), _p(f1), n1, _p(x2), _p(f2), nbase2, xdiv, _p(hyp), _p(K), ldk,
+                                        _p(knn), _stream())
+    _lib.check(rc, "mobocmf_gram_forward_rep")
+
+
+def _tab(ts):
+    return (ctypes.c_void_p * max(len(ts), 1))(*[0 if t is None else t.data_ptr() for t in ts])
+
+
+def _elbo_tables(layers, B):
+    L = len(layers)
+    get = lambda k, dflt: [dflt if lay is None else lay[k] for lay in layers]
+    return (L, (ctypes.c_int32 * L)(*get("div", 1)), (ctypes.c_double * L)(*get("lo", 0.0)),
+            (ctypes.c_double * L)(*get("hi", 0.0)), (ctypes.c_int64 * L)(*get("rows", B)))
+
+
+def elbo_forward(layers, y, fid, kls, scale):
+    """mobocmf_elbo_forward; layers[l] = None | dict(mean, var, raw: device tensors; div, lo, hi, rows).  Returns out3."""
+    from mobocmf_amd import _lib
+    B = y.numel()
+    L, div, lo, hi, rows = _elbo_tables(layers, B)
+    T = lambda k: _tab([None if lay is None else lay[k] for lay in layers])
+    out = torch.full((3,), NAN, dtype=torch.float64, device=y.device)
+    scratch = torch.full((8 * 512,), NAN, dtype=torch.float64, device=y.device)
+    rc = lib().mobocmf_elbo_forward(L, T("mean"), T("var"), div, T("raw"), lo, hi, _p(y), _p(fid), B, rows, len(kls),
+                                    _tab(kls) if kls else None, float(scale), _p(out), _p(scratch), scratch.numel() * 8,
+                                    _stream())
+    _lib.check(rc, "mobocmf_elbo_forward")
+    return out
+
+
+def elbo_backward(layers, y, fid, scale, g_elbo, g_skl):
+    """mobocmf_elbo_backward into NaN-filled gradient buffers of B * div entries per layer.
+    Returns (g_mean, g_var, g_raw lists, g_kl)."""
+    from mobocmf_amd import _lib
+    B = y.numel()
+    L, div, lo, hi, rows = _elbo_tables(layers, B)
+    T = lambda k: _tab([None if lay is None else lay[k] for lay in layers])
+    new = lambda lay, n: None if lay is None else torch.full((n,), NAN, dtype=torch.float64, device=y.device)
+    gm = [new(lay, 0 if lay is None else lay["mean"].numel()) for lay in layers]
+    gv = [new(lay, 0 if lay is None else lay["mean"].numel()) for lay in layers]
+    gr = [new(lay, 1) for lay in layers]
+    gkl = torch.full((1,), NAN, dtype=torch.float64, device=y.device)
+    scratch = torch.full((8 * 512,), NAN, dtype=torch.float64, device=y.device)
+    rc = lib().mobocmf_elbo_backward(L, T("mean"), T("var"), div, T("raw"), lo, hi, _p(y), _p(fid), B, rows, float(scale),
+                                     _p(g_elbo), _p(g_skl), _tab(gm), _tab(gv), _tab(gr), _p(gkl), _p(scratch),
+                                     scratch.numel() * 8, _stream())
+    _lib.check(rc, "mobocmf_elbo_backward")
+    return gm, gv, gr, gkl
