@@ -805,6 +805,55 @@ int mobocmf_natgrad_step(int32_t n, int32_t M, double* const* m, double* const* 
                          int64_t* step_count, int32_t* const* skipped, int32_t* const* info, void* workspace, size_t bytes,
                          const mobocmf_tuning* tuning, mobocmf_stream_t stream);
 
+/* ---- The same update for SMALL layers (M <= MOBOCMF_NATGRAD_SMALL_MAX_M), the sizes of the one-launch steps above: ONE launch
+ * moves every layer of the array, one workgroup per layer, and M may differ from layer to layer (M <= 32: plain FP64 in LDS;
+ * 32 < M <= 128: 16 x 16 tiles on v_mfma_f64_16x16x4_f64).  Meant as the second launch of a step whose first launch --
+ * mobocmf_tiny_elbo_step / mobocmf_coop_elbo_step with `grad` set and the trainable bits 7 and 8 of the layer cleared -- left
+ * d(-ELBO) / d m and / d L_S in its flat gradient: g_m and g_LS then point into that array.
+ *   Algebra, schedule and failure rule are mobocmf_natgrad_step's: L_new = L_S T with T T^T = (I + 2 gamma_t scale Psi)^-1,
+ *   m_new = m - gamma_t scale L_new L_new^T g_m, gamma_t = min(gamma, gamma_init (gamma / gamma_init)^(t / warmup_steps)).  Here
+ *   EVERY layer has its own counter t = step_count[0] (device int64), read by its workgroup at entry and incremented at exit.
+ *   A non-positive or non-finite pivot of J (I + 2 gamma_t scale Psi) J leaves m and L_S bitwise unchanged, writes the 1-based
+ *   pivot to info[0] and increments skipped[0] (caller-zeroed); the counter advances all the same.  info[0] = 0 otherwise.
+ *   Of L_S and g_LS (row-major, ld M) only the lower triangle is read; only the lower triangle of L_S is written; the diagonal
+ *   signs of L_S are kept.
+ *   Guard (all optional): guard_info / n_guard_info -- the info words of the launch that produced the gradients;
+ *   guard_status -- the low 32 bits of that launch's in-launch status word (sync_words of mobocmf_coop_elbo_step, status of
+ *   mobocmf_tiny_coupling); guard_loss -- its out[2].  If any of the words is non-zero or the loss is not finite, NOTHING of
+ *   the layer is written -- m, L_S, step_count, skipped and info stay bitwise -- so that nothing commits parameters after a
+ *   failed factorisation or an abandoned in-launch wait of the producing launch (mobocmf_check_info).
+ *   work: mobocmf_natgrad_small_work_bytes(M) bytes of device memory owned by the layer (0 bytes, and NULL allowed, for
+ *   M <= 32).  Two layers of one launch share nothing they write.
+ * The kernel reads the records from DEVICE memory (`dev_layers`: the caller uploads the array once); `host_layers` is the same
+ * array in host memory, used for validation and launch geometry only.  The launch waits for no other workgroup and has no
+ * in-launch wait contract of its own; no atomics, fixed summation orders (two calls on the same inputs are bitwise equal);
+ * nothing is read on the host: capturable.  The library keeps no state between calls.
+ * MOBOCMF_BAD_ARG (host-visible, before any HIP call): host_layers or dev_layers NULL, n_layers < 1, and for any layer an M
+ * outside 1..MOBOCMF_NATGRAD_SMALL_MAX_M, a NULL m, L_S, g_m, g_LS, step_count, skipped or info, a NULL work with M > 32, a
+ * negative n_guard_info or a NULL guard_info with n_guard_info > 0, a scale that is not positive and finite; gamma or
+ * gamma_init not positive and finite, gamma_init > gamma, warmup_steps < 0. */
+#define MOBOCMF_NATGRAD_SMALL_MAX_M 128
+typedef struct mobocmf_natgrad_small_layer {
+    int32_t M;
+    int32_t n_guard_info;                    /* words at guard_info (0: none) */
+    double* m;                               /* M */
+    double* L_S;                             /* M x M row-major, lower triangle used */
+    const double* g_m;                       /* M: d loss / d m */
+    const double* g_LS;                      /* M x M row-major, lower triangle used: d loss / d L_S */
+    double scale;                            /* what turns the loss into -ELBO (mobocmf_natgrad_step) */
+    int64_t* step_count;                     /* this layer's gamma-schedule counter */
+    int32_t* skipped;                        /* one word, incremented when the step is skipped */
+    int32_t* info;                           /* one word: 0 or the failed pivot */
+    const int32_t* guard_info;               /* the producing launch's info words (may be NULL) */
+    const int32_t* guard_status;             /* its in-launch status word (may be NULL) */
+    const double* guard_loss;                /* its out[2] (may be NULL) */
+    double* work;                            /* mobocmf_natgrad_small_work_bytes */
+} mobocmf_natgrad_small_layer;
+int mobocmf_natgrad_small_work_bytes(int32_t M, size_t* bytes);
+int mobocmf_natgrad_small_step(const mobocmf_natgrad_small_layer* host_layers, const mobocmf_natgrad_small_layer* dev_layers,
+                               int32_t n_layers, double gamma, double gamma_init, int32_t warmup_steps,
+                               mobocmf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -72,6 +72,15 @@ class TinyCoupling(ctypes.Structure):
                 ("reserved", ctypes.c_int32)]
 
 
+class NatgradSmallLayer(ctypes.Structure):
+    """mobocmf_natgrad_small_layer: one layer of mobocmf_natgrad_small_step (the kernel reads the array from DEVICE memory)."""
+    _fields_ = [("M", ctypes.c_int32), ("n_guard_info", ctypes.c_int32), ("m", ctypes.c_void_p), ("L_S", ctypes.c_void_p),
+                ("g_m", ctypes.c_void_p), ("g_LS", ctypes.c_void_p), ("scale", ctypes.c_double),
+                ("step_count", ctypes.c_void_p), ("skipped", ctypes.c_void_p), ("info", ctypes.c_void_p),
+                ("guard_info", ctypes.c_void_p), ("guard_status", ctypes.c_void_p), ("guard_loss", ctypes.c_void_p),
+                ("work", ctypes.c_void_p)]
+
+
 RFF_MAX_LAYERS = 3        # MOBOCMF_RFF_MAX_LAYERS
 
 
@@ -187,8 +196,11 @@ SYMBOLS = {
     "mobocmf_check_info": [_P, ctypes.POINTER(_I32), _P],
     "mobocmf_natgrad_workspace_bytes": [_I32, _I32, ctypes.POINTER(_SZ)],
     "mobocmf_natgrad_step": [_I32, _I32, _P, _P, _P, _P, _D, _D, _I32, _D, _P, _P, _P, _P, _SZ, ctypes.POINTER(Tuning), _P],
+    "mobocmf_natgrad_small_work_bytes": [_I32, ctypes.POINTER(_SZ)],
+    "mobocmf_natgrad_small_step": [_P, _P, _I32, _D, _D, _I32, _P],
 }
 NATGRAD_MAX_M, NATGRAD_MAX_LAYERS = 1024, 4      # MOBOCMF_NATGRAD_MAX_M, layers per mobocmf_natgrad_step call
+NATGRAD_SMALL_MAX_M = 128                        # MOBOCMF_NATGRAD_SMALL_MAX_M
 MAX_D, MAX_XDIV = 32, 48        # MOBOCMF_MAX_D / MOBOCMF_MAX_XDIV of include/mobocmf_hip.h
 PARETO_MAX_K, HV_MAX_K = 16, 5   # MOBOCMF_PARETO_MAX_K / MOBOCMF_HV_MAX_K
 HV_MAX_POINTS = {1: 65536, 2: 65536, 3: 65536, 4: 1024, 5: 256}   # the work bound of mobocmf_hypervolume

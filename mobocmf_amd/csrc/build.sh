@@ -12,8 +12,8 @@ force=0
 ccver=$($HIPCC --version 2>/dev/null | sha256sum | cut -c1-16)
 objs=""
 pids=""
-for f in gemm_f64 chol gram elementwise rff rff_opt pareto inducing minibatch natgrad tiny_step coop_step api; do
-  want=$( (echo "$ccver $FLAGS"; cat $f.hip common.h inlaunch.h small_step_common.h tile16.h minibatch_perm.h rff_desc.h ../../include/mobocmf_hip.h) | sha256sum | cut -c1-32)
+for f in gemm_f64 chol gram elementwise rff rff_opt pareto inducing minibatch natgrad natgrad_small tiny_step coop_step api; do
+  want=$( (echo "$ccver $FLAGS"; cat $f.hip common.h inlaunch.h small_step_common.h tile16.h natgrad_schedule.h minibatch_perm.h rff_desc.h ../../include/mobocmf_hip.h) | sha256sum | cut -c1-32)
   have=$(cat $f.o.stamp 2>/dev/null || true)
   if [ $force = 1 ] || [ ! -f $f.o ] || [ "$want" != "$have" ]; then
     rm -f $f.o $f.o.stamp           # a failed compile must not leave a stale object for the link step

@@ -10,6 +10,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "natgrad_schedule.h"
 
 int launch_potrf_z(double* A, int64_t ld, int Mp, int M, double* Dinv, double* Ld, int32_t* const* info, int nz, int64_t zs,
                    double* zero0, double* zero1, void* sync, int* inverse_done, hipStream_t s);
@@ -36,14 +37,6 @@ struct NgTensors {
     int32_t* skipped[MAX_ZL];
     const int32_t* info[MAX_ZL];
 };
-
-// gamma_t = min(gamma, gamma_init rho^t), rho = (gamma / gamma_init)^(1 / warmup): as gamma_init exp(t / warmup log(gamma /
-// gamma_init)), whose rounding error does not grow with t
-__device__ __forceinline__ double gamma_at(int64_t t, double gamma, double gamma_init, double log_ratio, int warmup) {
-    if (warmup <= 0 || t >= warmup) return gamma;
-    if (t < 0) t = 0;
-    return fmin(gamma, gamma_init * exp((double)t / (double)warmup * log_ratio));
-}
 
 // LSp = tril(L_S) zero-padded to Mp x Mp, LST its transpose, Gp = scale tril(g_LS) padded, gp = scale g_m padded
 __global__ void natgrad_pad_kernel(NgTensors t, int M, int Mp, double scale, double* LSp, double* LST, double* Gp, double* gp,

@@ -1386,6 +1386,88 @@ class FusedNatGradAdam:
         return skipped[:self.num_layers]
 
 
+class NatGradSmallLayers:
+    """The record array of ``natgrad_small_step`` (mobocmf_natgrad_small_layer), built and uploaded once.  ``layers``: one dict
+    per layer with the float64 GPU tensors ``m`` [M], ``L_S`` [M x M], ``g_m`` [M], ``g_LS`` [M x M] (contiguous; views into a
+    flat gradient are fine), ``scale`` (default 1), and optionally ``step_count`` (one int64), ``skipped``, ``info`` (one int32
+    each) -- where a layer gives none of the three, words of the table's own ``natgrad_steps`` / ``skipped`` / ``info``
+    tensors, which exist only then (None when every layer brings its words) -- and the guard:
+    ``guard_info`` (int32 tensor, every word of it), ``guard_status`` (the producing launch's status word, int32 or int64),
+    ``guard_loss`` (one float64).  The table owns the layers' ``work`` buffers and keeps every tensor alive."""
+
+    def __init__(self, layers):
+        lib = _lib.require_device()
+        n = len(layers)
+        if n < 1:
+            raise _lib.MobocmfError("natgrad_small_step: at least one layer")
+        dev = layers[0]["m"].device
+        self.device = dev
+        self.natgrad_steps = self.words = self.skipped = self.info = None
+        if not all("step_count" in ly and "skipped" in ly and "info" in ly for ly in layers):
+            self.natgrad_steps = torch.zeros(n, dtype=torch.int64, device=dev)
+            self.words = torch.zeros(2, n, dtype=torch.int32, device=dev)      # one host copy reads both rows
+            self.skipped, self.info = self.words[0], self.words[1]
+        self.host = (_lib.NatgradSmallLayer * n)()
+        self._keep = []
+        for z, ly in enumerate(layers):
+            m, L, gm, gL = ly["m"], ly["L_S"], ly["g_m"], ly["g_LS"]
+            M = m.numel()
+            for t in (m, L, gm, gL):
+                if not t.is_cuda or t.dtype != torch.float64 or not t.is_contiguous():
+                    raise _lib.MobocmfError("natgrad_small_step: contiguous float64 GPU tensors only (there is no CPU fallback)")
+            if not (1 <= M <= _lib.NATGRAD_SMALL_MAX_M):
+                raise _lib.MobocmfError("natgrad_small_step: 1 <= M <= %d (got %d)" % (_lib.NATGRAD_SMALL_MAX_M, M))
+            if L.numel() != M * M or gm.numel() != M or gL.numel() != M * M:
+                raise _lib.MobocmfError("natgrad_small_step: m [M], L_S [M x M], g_m [M], g_LS [M x M] per layer")
+            step = ly["step_count"] if "step_count" in ly else self.natgrad_steps[z:z + 1]
+            skipped = ly["skipped"] if "skipped" in ly else self.skipped[z:z + 1]
+            info = ly["info"] if "info" in ly else self.info[z:z + 1]
+            if step.dtype != torch.int64 or step.numel() != 1 or not step.is_cuda:
+                raise _lib.MobocmfError("natgrad_small_step: step_count is one int64 on the GPU per layer")
+            for w in (skipped, info):
+                if w.dtype != torch.int32 or w.numel() != 1 or not w.is_cuda:
+                    raise _lib.MobocmfError("natgrad_small_step: skipped and info are one int32 on the GPU per layer")
+            R = self.host[z]
+            R.M, R.scale = M, float(ly.get("scale", 1.0))
+            R.m, R.L_S, R.g_m, R.g_LS = m.data_ptr(), L.data_ptr(), gm.data_ptr(), gL.data_ptr()
+            R.step_count, R.skipped, R.info = step.data_ptr(), skipped.data_ptr(), info.data_ptr()
+            gi, gst, gl = ly.get("guard_info"), ly.get("guard_status"), ly.get("guard_loss")
+            if gi is not None:
+                if gi.dtype != torch.int32 or not gi.is_cuda or not gi.is_contiguous():
+                    raise _lib.MobocmfError("natgrad_small_step: guard_info is a contiguous int32 GPU tensor")
+                R.guard_info, R.n_guard_info = gi.data_ptr(), gi.numel()
+            if gst is not None:
+                if gst.dtype not in (torch.int32, torch.int64) or gst.numel() != 1 or not gst.is_cuda:
+                    raise _lib.MobocmfError("natgrad_small_step: guard_status is one int32 / int64 word on the GPU")
+                R.guard_status = gst.data_ptr()
+            if gl is not None:
+                if gl.dtype != torch.float64 or gl.numel() != 1 or not gl.is_cuda:
+                    raise _lib.MobocmfError("natgrad_small_step: guard_loss is one float64 on the GPU")
+                R.guard_loss = gl.data_ptr()
+            wb = ctypes.c_size_t()
+            _lib.check(lib.mobocmf_natgrad_small_work_bytes(M, ctypes.byref(wb)), "mobocmf_natgrad_small_work_bytes")
+            work = None
+            if wb.value:
+                work = torch.zeros(wb.value // 8, dtype=torch.float64, device=dev)
+                R.work = work.data_ptr()
+            self._keep += [m, L, gm, gL, step, skipped, info, gi, gst, gl, work]
+        self.n = n
+        self._dev_table = torch.frombuffer(bytearray(bytes(self.host)), dtype=torch.uint8).to(dev)
+
+
+def natgrad_small_step(layers, gamma, gamma_init, warmup_steps, stream=None):
+    """mobocmf_natgrad_small_step: the natural-gradient update of every layer of ``layers`` (a ``NatGradSmallLayers``, or the list
+    of dicts it is built from) in ONE launch, one workgroup per layer, M <= 128 and free to differ between the layers; each layer
+    has its own gamma-schedule counter.  Only enqueues (on ``stream``, default the current one): capturable.  Returns the table."""
+    lib = _lib.require_device()
+    table = layers if isinstance(layers, NatGradSmallLayers) else NatGradSmallLayers(layers)
+    st = _stream() if stream is None else ctypes.c_void_p(stream.cuda_stream)
+    _lib.check(lib.mobocmf_natgrad_small_step(ctypes.cast(table.host, ctypes.c_void_p), ctypes.c_void_p(table._dev_table.data_ptr()),
+                                              table.n, float(gamma), float(gamma_init), int(warmup_steps), st),
+               "mobocmf_natgrad_small_step")
+    return table
+
+
 def check_info(info):
     """Synchronising: raises if the last Cholesky reported a non-positive pivot."""
     lib = _lib.require_device()

@@ -144,14 +144,19 @@ class BlackBoxMFDGPFitter:
     def __init__(self, num_fidelities, batch_size, lr_1=0.003, lr_2=0.001, num_epochs_1=5000, num_epochs_2=15000,
                  pareto_set_size=50, opt_grid_size=1000, eps=1e-8, decoupled_evals=False,
                  type_lengthscale=TL.MEDIAN, device="cuda", pareto_refine="slsqp", variational_optimizer="adam",
-                 natgrad_gamma=0.1, natgrad_gamma_init=1e-4, natgrad_warmup_steps=100, **model_kwargs):
+                 natgrad_gamma=0.1, natgrad_gamma_init=1e-4, natgrad_warmup_steps=100, natgrad_one_launch=False,
+                 **model_kwargs):
         if pareto_refine not in ("slsqp", "device"):
             raise ValueError("pareto_refine must be 'slsqp' or 'device' (got %r)" % (pareto_refine,))
         if variational_optimizer not in ("adam", "natgrad"):
             raise ValueError("variational_optimizer must be 'adam' or 'natgrad' (got %r)" % (variational_optimizer,))
+        if natgrad_one_launch and variational_optimizer != "natgrad":
+            raise ValueError("natgrad_one_launch=True needs variational_optimizer='natgrad' (got %r)" % (variational_optimizer,))
         # "natgrad": q(u) of every layer moves by natural gradients inside the captured layer-path steps (both training phases
-        # and the conditioned fit), Adam keeps the other parameters; the one-launch steps are not taken
+        # and the conditioned fit), Adam keeps the other parameters; the one-launch steps are taken only with
+        # natgrad_one_launch=True (their step plus one natural-gradient launch for all layers, util/tiny_step.py)
         self.variational_optimizer = variational_optimizer
+        self.natgrad_one_launch = bool(natgrad_one_launch)
         self.natgrad_gamma, self.natgrad_gamma_init = natgrad_gamma, natgrad_gamma_init
         self.natgrad_warmup_steps = natgrad_warmup_steps
         self.pareto_refine = pareto_refine      # MOOP's refine: host SLSQP | the one-launch refinement on the GPU
@@ -215,6 +220,10 @@ class BlackBoxMFDGPFitter:
 
     def _natgrad(self):
         return getattr(self, "variational_optimizer", "adam") == "natgrad"
+
+    def _one_launch_allowed(self):
+        """The one-launch steps are tried first: always with Adam, with natural gradients only on request."""
+        return not self._natgrad() or getattr(self, "natgrad_one_launch", False)
 
     def _optimizer_kwargs(self):
         """The captured steps' optimiser keywords."""
@@ -294,7 +303,9 @@ class BlackBoxMFDGPFitter:
         The rows are shuffled once (see the module docstring): the step runs GPyTorch's general branch, as the
         reference's shuffled batches do."""
         # the reference's own sizes (M = N = tens of points): every surrogate's whole step in ONE launch per epoch
-        done, tiny = (0, None) if self._natgrad() else self._train_mfdgp_tiny(fix_variational_hypers, num_epochs, lr)
+        done, tiny = (0, None)
+        if self._one_launch_allowed():
+            done, tiny = self._train_mfdgp_tiny(fix_variational_hypers, num_epochs, lr)
         if done >= num_epochs:
             return
         num_epochs -= done
@@ -346,7 +357,8 @@ class BlackBoxMFDGPFitter:
             return 0, None
         dev = data[0][0].device
         step = cls([h.mfdgp for _, _, h in hs], [h.num_data for _, _, h in hs], [t[0] for t in data],
-                   [t[1] for t in data], [t[2] for t in data], lr=lr, stream=self._stream_for(0, dev))
+                   [t[1] for t in data], [t[2] for t in data], lr=lr, stream=self._stream_for(0, dev),
+                   **self._optimizer_kwargs())
         step.stream.wait_stream(torch.cuda.current_stream(dev))
 
         def report(i, _, step):
@@ -725,7 +737,7 @@ class BlackBoxMFDGPFitter:
             raise ValueError("variational_optimizer='natgrad' needs batch_size >= number of training points in the conditioned "
                              "fit (mini-batches come from a host-side loader)")
         tiny = None
-        if use_graphs and self.use_tiny_step and parallel.world()[1] == 1 and not self._natgrad():
+        if use_graphs and self.use_tiny_step and parallel.world()[1] == 1 and self._one_launch_allowed():
             # the reference's own sizes: the whole iteration in 3 + n_con launches (util/tiny_step.py)
             done, tiny = self._train_conditioned_tiny(num_iters)
             num_iters -= done
@@ -751,7 +763,7 @@ class BlackBoxMFDGPFitter:
         # M <= 32 in one workgroup per surrogate, M <= 128 in several
         for cls in (tiny_step.TinyConditionedStep, coop_step.CoopConditionedStep):
             try:
-                step = cls(self, lr=self.lr_2, stream=self._stream_for(0, dev))
+                step = cls(self, lr=self.lr_2, stream=self._stream_for(0, dev), **self._optimizer_kwargs())
                 break
             except _lib.MobocmfError:
                 continue

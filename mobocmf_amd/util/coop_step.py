@@ -77,7 +77,7 @@ class CoopELBOStep(_CoopLaunch, TS.TinyELBOStep):
 class CoopConditionedStep(_CoopLaunch, TS.TinyConditionedStep):
     """One iteration of the conditioned training in ONE launch (mode 4), or forward-only launch + factor launches + step launch."""
 
-    def _issue(self):
+    def _issue_step(self):
         if self.one_launch and self.T <= 256:
             try:
                 self._launch(4)

@@ -130,12 +130,26 @@ class TinyELBOStep:
     as of the last step (before its update)."""
 
     def __init__(self, models, num_data, xs, ys, fids, lr, betas=(0.9, 0.999), eps=1e-8, stream=None, fixed_eps=None,
-                 want_grad=False, prepared=None, force=False):
+                 want_grad=False, prepared=None, force=False, variational_optimizer="adam", natgrad_gamma=0.1,
+                 natgrad_gamma_init=1e-4, natgrad_warmup_steps=100):
         """``force``: take every size the kernel accepts, also those where the layer path is faster (tests, sweeps).
+        ``variational_optimizer="natgrad"``: q(u) of every layer whose ``variational_mean`` AND ``chol_variational_covar`` both
+        require a gradient moves by natural gradients (schedule ``natgrad_gamma`` / ``natgrad_gamma_init`` /
+        ``natgrad_warmup_steps`` as ``GraphedELBOStep``): the one-launch step leaves those two tensors alone (trainable bits
+        7 and 8 cleared) and writes its flat gradient, a second launch (mobocmf_natgrad_small_step, one workgroup per layer)
+        moves them; Adam keeps every other parameter, and a layer with either tensor frozen keeps today's path.
         ``prepared`` (TinyConditionedStep): per model a dict with the rows ALREADY in the kernel's order and the optional
         fields of mobocmf_tiny_model -- x, y, fid, rows, row_weight, kl_scale, seeds (bool), rand (row0, rows), xrng, eps
         (per layer, prefix columns)."""
         lib = _lib.require_device()
+        if variational_optimizer not in ("adam", "natgrad"):
+            raise ValueError("variational_optimizer must be 'adam' or 'natgrad' (got %r)" % (variational_optimizer,))
+        self.variational_optimizer = variational_optimizer
+        self.natgrad_gamma, self.natgrad_gamma_init = float(natgrad_gamma), float(natgrad_gamma_init)
+        self.natgrad_warmup_steps = int(natgrad_warmup_steps)
+        if variational_optimizer == "natgrad" and not (0.0 < self.natgrad_gamma_init <= self.natgrad_gamma
+                                                       and self.natgrad_warmup_steps >= 0):
+            raise ValueError("%s: 0 < natgrad_gamma_init <= natgrad_gamma and natgrad_warmup_steps >= 0" % type(self).__name__)
         self.models = list(models)
         n = len(self.models)
         dev = (xs[0] if prepared is None else prepared[0]["x"]).device
@@ -150,6 +164,9 @@ class TinyELBOStep:
         self._keep = []          # tensors the descriptors point at
         self.exp_avg, self.exp_avg_sq, self.grads, self._work = [], [], [], []
         self._segments = []      # per model: [(parameter tensor, flat offset, length)]
+        self._gflat = {}         # model -> the flat gradient its launches write (want_grad, or a natural-gradient layer)
+        self._natural = []       # layers moved by natural gradients: (model, layer, word, M, flat offset of m, of L_S, scale)
+        self.num_layers = 0      # layers of all models: one word each in natgrad_steps / skipped / natgrad_info
         self.top_moments, self.seeds, self.x_rows = [], [], []      # prepared models: (2, ncol_top) tensors, the x array
         for i, model in enumerate(self.models):
             prep = None if prepared is None else prepared[i]
@@ -206,8 +223,15 @@ class TinyELBOStep:
                     tr |= int(p.requires_grad) << s
                     segs.append((p, off, p.numel()))
                     off += p.numel()
+                natural = variational_optimizer == "natgrad" and vd.variational_mean.requires_grad and \
+                    vd.chol_variational_covar.requires_grad
+                if natural:      # (scale: what turns the launch's loss into -ELBO -- the inverse of kl_scale)
+                    Ml = vd.variational_mean.numel()
+                    self._natural.append((i, l, self.num_layers, Ml, off, off + Ml,
+                                          1.0 if prep is not None else float(num_data[i]) / N))
+                self.num_layers += 1
                 for bit, p in ((7, vd.variational_mean), (8, vd.chol_variational_covar)):
-                    tr |= int(p.requires_grad) << bit
+                    tr |= int(p.requires_grad and not natural) << bit
                     segs.append((p, off, p.numel()))
                     off += p.numel()
                 T.m[l], T.L_S[l] = vd.variational_mean.data_ptr(), vd.chol_variational_covar.data_ptr()
@@ -250,15 +274,57 @@ class TinyELBOStep:
             T.steps_done = self.steps_done[i:i + 1].data_ptr()
             T.out = self.losses[i].data_ptr()
             T.info = self.infos[i].data_ptr()
-            if want_grad:
+            if want_grad or any(k[0] == i for k in self._natural):
                 gflat = torch.zeros(off, dtype=torch.float64, device=dev)
-                self.grads.append(gflat)
+                if want_grad:
+                    self.grads.append(gflat)
+                self._gflat[i] = gflat
                 T.grad = gflat.data_ptr()
             self._segments.append(segs)
         raw = bytes(self.host)
         self._dev_table = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(dev)
         self._snap = None
+        self._setup_natgrad()
         self._order_after_setup()
+
+    def _setup_natgrad(self):
+        """The records of the second launch (functional.NatGradSmallLayers): every natural-gradient layer's m / L_S, their
+        segments of the model's flat gradient, its own schedule counter, and as guard the producing launch's info words, its
+        in-launch status word (where the kernel has one) and its loss."""
+        dev = self.device
+        self.skipped = [0] * self.num_layers      # per layer, as of the last check()
+        self._natgrad_table = self.natgrad_steps = self.natgrad_words = self.natgrad_skipped = self.natgrad_info = None
+        if not self._natural:      # (the default path allocates nothing for this)
+            return
+        self.natgrad_steps = torch.zeros(self.num_layers, dtype=torch.int64, device=dev)
+        self.natgrad_words = torch.zeros(2, self.num_layers, dtype=torch.int32, device=dev)      # one host copy reads both rows
+        self.natgrad_skipped, self.natgrad_info = self.natgrad_words[0], self.natgrad_words[1]
+        sync = self.in_launch_sync()
+        status = None if sync is None else sync.words[sync.status_index:sync.status_index + 1]
+        recs = []
+        for i, l, w, M, om, oL, scale in self._natural:
+            vd = self.models[i]._layers()[l].variational_strategy._variational_distribution
+            g = self._gflat[i]
+            recs.append(dict(m=vd.variational_mean.data, L_S=vd.chol_variational_covar.data, g_m=g[om:om + M],
+                             g_LS=g[oL:oL + M * M], scale=scale, step_count=self.natgrad_steps[w:w + 1],
+                             skipped=self.natgrad_skipped[w:w + 1], info=self.natgrad_info[w:w + 1],
+                             guard_info=self.infos[i], guard_status=status, guard_loss=self.losses[i, 2:3]))
+        self._natgrad_table = F.NatGradSmallLayers(recs)
+
+    def _natgrad_launch(self):
+        """The second launch of a step: moves (m, L_S) of the natural-gradient layers from the flat gradients the step's launch
+        has just written; on ``self.stream``, nothing in between."""
+        if self._natgrad_table is not None:
+            F.natgrad_small_step(self._natgrad_table, self.natgrad_gamma, self.natgrad_gamma_init, self.natgrad_warmup_steps,
+                                 stream=self.stream)
+
+    def skipped_steps(self):
+        """Synchronising (one device-to-host copy): per layer, in the order of the models' layers, how many natural-gradient
+        steps left it unchanged because I + 2 gamma Psi was not positive definite."""
+        self.stream.synchronize()
+        if self._natgrad_table is not None:
+            self.skipped = self.natgrad_words[0].cpu().tolist()
+        return list(self.skipped)
 
     def _order_after_setup(self):
         """Everything above was allocated, zero-filled and uploaded on the CURRENT stream; the launches run on ``self.stream``.
@@ -285,6 +351,7 @@ class TinyELBOStep:
     def step(self):
         """Enqueues one step of every model on ``self.stream``."""
         self._launch(1)
+        self._natgrad_launch()
         return self.losses
 
     def gradients(self):
@@ -333,12 +400,16 @@ class TinyELBOStep:
             raise NotPSDError("K_mm not positive definite in model %d layer %d (pivot %d)" % (i, l, code))
         if not bool(torch.isfinite(self.losses).all()):
             raise FloatingPointError("non-finite ELBO")
+        if self._natgrad_table is not None:      # (the natural-gradient launch waits for nothing: its info is 0 or a pivot)
+            self.skipped = self.natgrad_words[0].cpu().tolist()
 
     def snapshot(self):
         with torch.cuda.stream(self.stream):
             self._snap = ([p.detach().clone() for m in self.models for p in m.parameters()],
                           [t.clone() for t in self.exp_avg], [t.clone() for t in self.exp_avg_sq], self.steps_done.clone(),
                           [l._rng(self.device).clone() for m in self.models for l in m._layers()])
+            if self._natgrad_table is not None:
+                self._snap_natgrad = (self.natgrad_steps.clone(), self.natgrad_words.clone())
 
     def restore(self):
         """Back to the last snapshot (parameters, optimiser state, eps streams); the in-launch counters and status start afresh."""
@@ -357,6 +428,9 @@ class TinyELBOStep:
             self.steps_done.copy_(steps)
             for layer, s0 in zip([l for m in self.models for l in m._layers()], rngs):
                 layer._rng(self.device).copy_(s0)
+            if self._natgrad_table is not None:
+                self.natgrad_steps.copy_(self._snap_natgrad[0])
+                self.natgrad_words.copy_(self._snap_natgrad[1])
 
     def close(self):
         """The end of this step's part of a training phase (finished, or rolled back for the layer path to continue): the
@@ -375,6 +449,12 @@ class TinyELBOStep:
                     optimizer.state[k]["exp_avg"].copy_(self.exp_avg[i][off:off + n].reshape(p.shape))
                     optimizer.state[k]["exp_avg_sq"].copy_(self.exp_avg_sq[i][off:off + n].reshape(p.shape))
             optimizer.steps_done.copy_(self.steps_done[i])
+            ng = getattr(optimizer, "natgrad_steps", None)
+            if ng is not None and self._natgrad_table is not None:
+                # a FusedNatGradAdam continues the gamma schedule where model i's layers stood (they advance together)
+                mine = [w for k, _, w, _, _, _, _ in self._natural if k == i]
+                if mine:
+                    ng.copy_(self.natgrad_steps[mine[0]].expand_as(ng))
 
 
 def _ptrs(vals):
@@ -393,7 +473,8 @@ class TinyConditionedStep(TinyELBOStep):
     KL weight 1: -elbo / B * num_data, :281-303).  One sample per row (the reference's S = 1)."""
 
     def __init__(self, fitter, lr, betas=(0.9, 0.999), eps=1e-8, stream=None, n_tilde=10, fixed_x_tilde=None, fixed_eps=None,
-                 want_grad=False):
+                 want_grad=False, variational_optimizer="adam", natgrad_gamma=0.1, natgrad_gamma_init=1e-4,
+                 natgrad_warmup_steps=100):
         hs = fitter._handlers()
         dev = fitter.pareto_set.device
         P, d = fitter.pareto_set.shape
@@ -434,7 +515,9 @@ class TinyConditionedStep(TinyELBOStep):
                 kl_scale=1.0, seeds=True, seed_scale=-1.0, xrng=self.xrng, rand=(P, Tn), eps=e))
         self._roles = [(0 if tag == "OBJ" else 1) for tag, _, _ in hs]
         super().__init__([h.mfdgp for _, _, h in hs], None, None, None, None, lr, betas=betas, eps=eps, stream=stream,
-                         want_grad=want_grad, prepared=prepared)
+                         want_grad=want_grad, prepared=prepared, variational_optimizer=variational_optimizer,
+                         natgrad_gamma=natgrad_gamma, natgrad_gamma_init=natgrad_gamma_init,
+                         natgrad_warmup_steps=natgrad_warmup_steps)
         # the factor launches: pointer tables into the models' top-layer moments / seed arrays, built once
         obj = [k for k, (tag, _, _) in enumerate(hs) if tag == "OBJ"]
         con = [k for k, (tag, _, _) in enumerate(hs) if tag == "CON"]
@@ -505,6 +588,11 @@ class TinyConditionedStep(TinyELBOStep):
         self._graph = g
 
     def _issue(self):
+        """The launches of one iteration, the natural-gradient launch (if any) last: a captured graph replays them all."""
+        self._issue_step()
+        self._natgrad_launch()
+
+    def _issue_step(self):
         if self.one_launch and self.T <= 256 and len(self.models) <= 64:
             try:
                 self._launch(4)
