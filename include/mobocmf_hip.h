@@ -573,13 +573,18 @@ int mobocmf_scalar_combine(int32_t n, const double* const* x, const double* coef
  *   Flat layout of grad / adam_m / adam_v (mobocmf_tiny_flat_len doubles): per layer [packed hyper-parameters | m | L_S], then
  *     raw_noise of every layer.  grad (optional) receives d(-ELBO)/d(raw parameters) of the step.
  *   out[0] = ELBO, out[1] = scaled KL, out[2] = -ELBO (before the update); info[l] = 0 or the failed Cholesky pivot (1-based).
- * do_update = 0: gradients only (no parameter, optimiser or rng-counter write); 1: the step; 2: forward only (out, top_mean /
- * top_var; draws the random rows of x) -- a conditioned iteration is mode 2, the factor launches on top_mean / top_var, mode 1;
- * 3: input gradients (the parameters are constants -- acquisition search, JESMOC_MFDGP.py:38-52): `grad` receives d / d x
- * (N x d) of <seed_gmean, top mean> + <seed_gvar, top var> (times seed_scale) and nothing else is written -- predictive
- * moments of fitted models are mode 2 with branch = 1, eps[l] = the layer's fixed samples tiled over the test points;
- * 4: mode 1 with the factor terms of the conditioned loss formed INSIDE the launch (mobocmf_tiny_coupling: ONE launch per
- * conditioned iteration instead of mode 2 + factor launches + mode 1). */
+ * do_update is one of the MOBOCMF_STEP_* modes below.  GRADIENTS: gradients only (no parameter, optimiser or rng-counter
+ * write); UPDATE: the step; FORWARD: forward only (out, top_mean / top_var; draws the random rows of x) -- a conditioned
+ * iteration is FORWARD, the factor launches on top_mean / top_var, UPDATE; INPUT_GRADIENTS: the parameters are constants
+ * (acquisition search, JESMOC_MFDGP.py:38-52): `grad` receives d / d x (N x d) of <seed_gmean, top mean> + <seed_gvar, top var>
+ * (times seed_scale) and nothing else is written -- predictive moments of fitted models are FORWARD with branch = 1, eps[l] =
+ * the layer's fixed samples tiled over the test points; COUPLED: UPDATE with the factor terms of the conditioned loss formed
+ * INSIDE the launch (mobocmf_tiny_coupling: ONE launch per conditioned iteration instead of FORWARD + factor launches + UPDATE). */
+#define MOBOCMF_STEP_GRADIENTS 0
+#define MOBOCMF_STEP_UPDATE 1
+#define MOBOCMF_STEP_FORWARD 2
+#define MOBOCMF_STEP_INPUT_GRADIENTS 3
+#define MOBOCMF_STEP_COUPLED 4
 #define MOBOCMF_TINY_MAX_LAYERS 3
 #define MOBOCMF_TINY_MAX_M 32
 #define MOBOCMF_TINY_MAX_D 8
@@ -616,14 +621,14 @@ typedef struct mobocmf_tiny_model {
      * mobocmf_cond_factors_forward) entering at the top layer's columns. */
     const double* row_weight;                /* N (NULL: 1) */
     const double* seed_gmean;                /* rows[L-1] * S: d(outside term) / d mean of the top layer's columns (NULL: none;
-                                              * mode 4 WRITES both arrays itself before its backward reads them) */
+                                              * MOBOCMF_STEP_COUPLED WRITES both arrays itself before its backward reads them) */
     const double* seed_gvar;
     double seed_scale;                       /* the outside term's coefficient in the loss (the fitter's -1) */
     double* top_mean;                        /* rows[L-1] * S: the top layer's moments, written by every mode (NULL: not) */
     double* top_var;
-    int64_t* xrng;                           /* {seed, calls}: modes 2 / 4 draw rows [rand_row0, rand_row0 + rand_rows) of x from */
-    int32_t rand_row0, rand_rows;            /* U(0,1) (the x~ of :276; x must be writable); modes 1 / 4 of model 0 advance calls */
-    /* mode 4 (the whole conditioned iteration in ONE launch with an in-launch barrier): what couples the models, and this model's part in it */
+    int64_t* xrng;                           /* {seed, calls}: FORWARD / COUPLED draw rows [rand_row0, rand_row0 + rand_rows) of x from */
+    int32_t rand_row0, rand_rows;            /* U(0,1) (the x~ of :276; x must be writable); UPDATE / COUPLED of model 0 advance calls */
+    /* MOBOCMF_STEP_COUPLED (the whole conditioned iteration in ONE launch with an in-launch barrier): what couples the models, and this model's part in it */
     const struct mobocmf_tiny_coupling* coupling;
     int32_t role, role_index;                /* 0: objective role_index of the coupling, 1: constraint role_index */
 } mobocmf_tiny_model;
@@ -662,20 +667,20 @@ int mobocmf_tiny_elbo_step(const mobocmf_tiny_model* host_models, const mobocmf_
  * phases separated by an in-launch barrier of the surrogate's workgroups (arrival counter + agent-scope fences); every product
  * runs on v_mfma_f64_16x16x4_f64.  Same descriptor (mobocmf_tiny_model; M <= MOBOCMF_COOP_MAX_M, d <= 8, L <= 3), same flat
  * layout of grad / adam_m / adam_v (mobocmf_tiny_flat_len), same draws, same results as the layer path up to summation order;
- * `work` is sized by mobocmf_coop_work_bytes.  do_update: 0 gradients only | 1 the step | 2 forward only | 3 input gradients
- * (as mobocmf_tiny_elbo_step's mode 3: `grad` <- N x d, d/dx of <seed_gmean, top mean> + <seed_gvar, top var>; needs `grad`
- * and the seeds; nothing else is written) | 4 the conditioned iteration in one launch (mobocmf_tiny_coupling with n_models = the models of the launch; the barrier of its record is not
+ * `work` is sized by mobocmf_coop_work_bytes.  do_update: MOBOCMF_STEP_GRADIENTS | UPDATE | FORWARD | INPUT_GRADIENTS
+ * (as mobocmf_tiny_elbo_step's: `grad` <- N x d, d/dx of <seed_gmean, top mean> + <seed_gvar, top var>; needs `grad`
+ * and the seeds; nothing else is written) | COUPLED, the conditioned iteration in one launch (mobocmf_tiny_coupling with n_models = the models of the launch; the barrier of its record is not
  * used: the whole grid meets on the launch's own sync words).
  * wgs_per_model: workgroups sharing one surrogate, 1..64, or 0 = chosen from the widest phase (at most 32); *wgs_used (may be
  * NULL) receives the choice.  Every workgroup of the launch must be resident at once (n_models * wgs_per_model <= what the
  * device holds of this kernel: checked, MOBOCMF_BAD_ARG otherwise -- an ordinary launch, not a cooperative one, so that it can
  * be captured into a graph).  sync_words: 16 * (n_models + 1) device int64 -- monotonic arrival counters (a group of words
  * serves one launch at a time, always with the same wgs_per_model and n_models) and, at word 16 * n_models + 1, the status
- * word of the in-launch wait contract (mobocmf_check_info; bit 0 a wait gave up, bit 1 mode 4 did not match its coupling
+ * word of the in-launch wait contract (mobocmf_check_info; bit 0 a wait gave up, bit 1 MOBOCMF_STEP_COUPLED did not match its coupling
  * record).  The caller zeroes the block once before the first launch and again only after reading a non-zero status; a
  * workgroup that gives up also sets info[0] = -1 and out[2] = NaN. */
 #define MOBOCMF_COOP_MAX_M 128
-/* OR'd into do_update 2 or 3 of mobocmf_coop_elbo_step: the parameters are the ones of an earlier launch on the same `work`
+/* OR'd into MOBOCMF_STEP_FORWARD or MOBOCMF_STEP_INPUT_GRADIENTS of mobocmf_coop_elbo_step: the parameters are the ones of an earlier launch on the same `work`
  * (an acquisition search against fitted models, JESMOC_MFDGP.py:137-184): K_mm, its Cholesky and inverse, U, a and the KL stay as
  * that launch left them and are not formed again (35-65 us of a ~140 us launch).  The caller vouches for it. */
 #define MOBOCMF_STEP_CHAIN_VALID 16
@@ -769,7 +774,7 @@ int mobocmf_syrk_weighted_f64(int32_t Mr, int64_t Kd, const double* A, int64_t l
  * were not resident together: the results of that call are invalid, repeat it with less concurrent work or with the
  * launch-per-step form).
  * The in-launch wait contract of the one-launch forms (the one-launch Cholesky, mobocmf_tuning.potrf_cols = 0; the cooperative
- * step; mode 4 of mobocmf_tiny_elbo_step): they are ordinary launches whose workgroups wait for each other, so the host checks
+ * step; MOBOCMF_STEP_COUPLED of mobocmf_tiny_elbo_step): they are ordinary launches whose workgroups wait for each other, so the host checks
  * that all of them are resident at once, and every wait is bounded by 1 s of the device's wall clock.  A give-up is reported
  * only by an atomic OR into a status word, which no later workgroup or launch clears, and every wait releases only while that
  * word is zero.  Where the counters persist across launches (sync_words of mobocmf_coop_elbo_step, the barrier / status of

@@ -40,6 +40,8 @@ class LayerDesc(ctypes.Structure):
 
 TINY_MAX_LAYERS, TINY_MAX_M, TINY_MAX_D = 3, 32, 8      # MOBOCMF_TINY_MAX_* of include/mobocmf_hip.h
 COOP_MAX_M = 128                                         # MOBOCMF_COOP_MAX_M
+# MOBOCMF_STEP_*: do_update of mobocmf_tiny_elbo_step / mobocmf_coop_elbo_step
+STEP_GRADIENTS, STEP_UPDATE, STEP_FORWARD, STEP_INPUT_GRADIENTS, STEP_COUPLED = range(5)
 STEP_CHAIN_VALID = 16                                    # MOBOCMF_STEP_CHAIN_VALID
 
 

@@ -18,9 +18,9 @@
 //     backward's products), operands read from L2 in k-major form (4 rows x 128 contiguous bytes per load instruction), which
 //     is why L^-1, U are kept in both orientations.
 // Rows ordered by descending fidelity, layer l on the first rows[l] of them, as the one-workgroup kernel.
-// Modes (do_update): 0 gradients only, 1 the step, 2 forward only, 3 input gradients (acquisition search: `grad` <- d/dx of the
-// seeded top-layer moments, nothing else written), 4 the conditioned iteration in one launch (all models'
-// workgroups meet once more after the forward and form the theta / omega factor gradients, as tiny_step.hip's mode 4).
+// Modes (do_update, MOBOCMF_STEP_*): GRADIENTS only, UPDATE (the step), FORWARD only, INPUT_GRADIENTS (acquisition search:
+// `grad` <- d/dx of the seeded top-layer moments, nothing else written), COUPLED: the conditioned iteration in one launch (all models'
+// workgroups meet once more after the forward and form the theta / omega factor gradients, as tiny_step.hip's MOBOCMF_STEP_COUPLED).
 
 #include "common.h"
 #include "inlaunch.h"
@@ -338,7 +338,7 @@ PHASE_FN void ph_setup() {
         if (tid - 128 < g.ntri) tile_of_slow(tid - 128, ti, tj);
         tmap[tid - 128] = (ti << 4) | tj;
     }
-    if (tid == CT - 1 && (do_update == 1 || do_update == 4)) {
+    if (tid == CT - 1 && (do_update == MOBOCMF_STEP_UPDATE || do_update == MOBOCMF_STEP_COUPLED)) {
         const double step = (double)(md.steps_done[0] + 1);
         sc[12] = 1.0 - pow(b1, step);
         sc[13] = sqrt(1.0 - pow(b2, step));
@@ -348,7 +348,7 @@ PHASE_FN void ph_setup() {
         sc[tid] = hi > lo ? lo + (hi - lo) / (1.0 + exp(-r)) : r;
         sc[8 + tid] = log(sc[tid]);
     }
-    if ((do_update == 2 || do_update == 4) && md.xrng && md.rand_rows > 0 && wj == 0) {
+    if ((do_update == MOBOCMF_STEP_FORWARD || do_update == MOBOCMF_STEP_COUPLED) && md.xrng && md.rand_rows > 0 && wj == 0) {
         // the x~ of this iteration (blackbox_mfdgp_fitter.py:276): every model of the launch draws the SAME points
         const uint64_t seed = (uint64_t)md.xrng[0], call = (uint64_t)md.xrng[1];
         double* xw = const_cast<double*>(md.x) + (int64_t)md.rand_row0 * d;
@@ -835,7 +835,7 @@ PHASE_FN void ph_syrk(int lh) {
         }
 }
 
-// INGRAD: mode 3 (input gradients; a compile-time variant so that the training step's code is what it was without it)
+// INGRAD: MOBOCMF_STEP_INPUT_GRADIENTS (a compile-time variant so that the training step's code is what it was without it)
 template <bool INGRAD>
 PHASE_FN void ph_backward(int l_in) {
     CTX_LOCALS;
@@ -1050,7 +1050,7 @@ PHASE_FN void ph_backward(int l_in) {
         CSTAMP(20 + l_in);
 }
 
-// mode 3, last phase: d/dx of a base row = the sum over the layers that hold the row and over its sample columns
+// MOBOCMF_STEP_INPUT_GRADIENTS, last phase: d/dx of a base row = the sum over the layers that hold the row and over its sample columns
 PHASE_FN void ph_dx() {
     CTX_LOCALS;
     gwd out = GW(md.grad);
@@ -1429,7 +1429,7 @@ PHASE_FN void ph_adam() {
     // per thread at a time: their loads are in flight together.
     {
         const double bc1 = sc[12], bc2s = sc[13];
-        const bool upd = do_update == 1 || do_update == 4;
+        const bool upd = do_update == MOBOCMF_STEP_UPDATE || do_update == MOBOCMF_STEP_COUPLED;
         const int flat = (int)g.flat_len;
         auto grad_of = [&](int e) -> double {
             if (e >= (int)g.flat_noise) {
@@ -1509,7 +1509,7 @@ PHASE_FN void ph_adam() {
 // the barrier of the surrogate's k workgroups (inlaunch.h il_barrier; a give-up is in the launch's status word gcnt[1])
 #define MODEL_BARRIER(id) do { CSTAMP(id); if (!il_barrier<2>(cx->mcnt, (unsigned)k, (unsigned*)(cx->gcnt + 1), wait_ticks, (int*)(sc + 30))) { if (tid == 0) { md.info[0] = -1; md.out[2] = __builtin_nan(""); } return; } CSTAMP(99); } while (0)
 
-// PREDICT: the instantiation for an acquisition search (mode 3, and mode 2 with MOBOCMF_STEP_CHAIN_VALID) -- a kernel of its own, so
+// PREDICT: the instantiation for an acquisition search (INPUT_GRADIENTS, and FORWARD with MOBOCMF_STEP_CHAIN_VALID) -- a kernel of its own, so
 // that the training step's kernel carries none of its code (with the input-gradient phases inlined into ONE kernel the training
 // step lost ~1.5 %: 316.5 -> 321.5 us at C2)
 template <bool PREDICT>
@@ -1561,7 +1561,7 @@ __global__ __launch_bounds__(CT) void coop_step_kernel(const mobocmf_tiny_model*
         MODEL_BARRIER(10 + l);
     }
     ph_elbo();
-    if (do_update == 2) return;
+    if (do_update == MOBOCMF_STEP_FORWARD) return;
     if constexpr (PREDICT) {      // input gradients: the backward column phases only, then the rows' sums
         for (int l = L - 1; l >= 0; --l) {
             ph_backward<true>(l);
@@ -1570,7 +1570,7 @@ __global__ __launch_bounds__(CT) void coop_step_kernel(const mobocmf_tiny_model*
         ph_dx();
         return;
     } else {
-    if (do_update == 4) {
+    if (do_update == MOBOCMF_STEP_COUPLED) {
         if (!ph_couple(wait_ticks)) return;
         MODEL_BARRIER(15);
     }
@@ -1609,33 +1609,12 @@ size_t coop_lds_bytes(int Mp) {
     return (common + (chain > col ? chain : col)) * sizeof(double);
 }
 
-bool coop_valid_model(const mobocmf_tiny_model& m) {
-    if (m.L < 1 || m.L > TLM || m.M < 1 || m.M > CMAXM || m.d < 1 || m.d > DBT || m.S < 1 || m.N < 1) return false;
-    if (m.rows[0] != m.N) return false;
-    for (int l = 0; l < m.L; ++l) {
-        if (m.rows[l] < 1 || (l && m.rows[l] > m.rows[l - 1])) return false;
-        if ((int64_t)m.rows[l] * m.S > (1 << 20)) return false;
-        const int ns = l == 0 ? 2 : 7;
-        for (int s = 0; s < ns; ++s)
-            if (!m.raw[l][s]) return false;
-        if (!m.m[l] || !m.L_S[l] || !m.raw_noise[l]) return false;
-        if (l && !m.eps[l] && !m.rng[l]) return false;
-    }
-    if ((m.seed_gmean == nullptr) != (m.seed_gvar == nullptr) || (m.top_mean == nullptr) != (m.top_var == nullptr)) return false;
-    if (m.xrng && (m.rand_row0 < 0 || m.rand_rows < 0 || m.rand_row0 + m.rand_rows > m.N)) return false;
-    if (m.branch != 0 && m.branch != 1) return false;
-    return m.x && m.y && m.fid && m.Zx && m.adam_m && m.adam_v && m.steps_done && m.work && m.out && m.info;
-}
-
 }  // namespace
 
 extern "C" {
 
 int mobocmf_coop_work_bytes(const mobocmf_tiny_model* model, size_t* bytes) {
-    if (!model || !bytes || model->L < 1 || model->L > TLM || model->M < 1 || model->M > CMAXM || model->d < 1 || model->S < 1)
-        return MOBOCMF_BAD_ARG;
-    for (int l = 0; l < model->L; ++l)
-        if (model->rows[l] < 1) return MOBOCMF_BAD_ARG;
+    if (!bytes || !sizable_model(model) || model->M > CMAXM) return MOBOCMF_BAD_ARG;
     CGeom g;
     cgeom_of(*model, g);
     size_t n = (size_t)g.work_len;
@@ -1653,17 +1632,16 @@ int mobocmf_coop_elbo_step(const mobocmf_tiny_model* host_models, const mobocmf_
         return MOBOCMF_BAD_ARG;
     const int chain_valid = do_update & MOBOCMF_STEP_CHAIN_VALID;
     do_update &= ~MOBOCMF_STEP_CHAIN_VALID;
-    if (do_update < 0 || do_update > 4 || (chain_valid && do_update != 2 && do_update != 3)) return MOBOCMF_BAD_ARG;
+    if (do_update < MOBOCMF_STEP_GRADIENTS || do_update > MOBOCMF_STEP_COUPLED ||
+        (chain_valid && do_update != MOBOCMF_STEP_FORWARD && do_update != MOBOCMF_STEP_INPUT_GRADIENTS))
+        return MOBOCMF_BAD_ARG;
     int mpmax = 0, want = 1;
     for (int i = 0; i < n_models; ++i) {
         const mobocmf_tiny_model& m = host_models[i];
-        if (!coop_valid_model(m)) return MOBOCMF_BAD_ARG;
-        if (do_update == 4) {
-            if (!m.coupling || m.S != 1 || !m.seed_gmean || !m.top_mean || m.role < 0 || m.role > 1 || m.role_index < 0 ||
-                m.role_index > 7 || m.coupling != host_models[0].coupling)
-                return MOBOCMF_BAD_ARG;
-        }
-        if (do_update == 3 && (!m.grad || !m.seed_gmean)) return MOBOCMF_BAD_ARG;      // (grad receives N x d input gradients)
+        if (!valid_model(m, CMAXM)) return MOBOCMF_BAD_ARG;
+        if (do_update == MOBOCMF_STEP_COUPLED && !valid_coupled_model(m, host_models[0])) return MOBOCMF_BAD_ARG;
+        // (grad receives N x d input gradients)
+        if (do_update == MOBOCMF_STEP_INPUT_GRADIENTS && (!m.grad || !m.seed_gmean)) return MOBOCMF_BAD_ARG;
         CGeom g;
         cgeom_of(m, g);
         if (g.Mp > mpmax) mpmax = g.Mp;
@@ -1676,7 +1654,7 @@ int mobocmf_coop_elbo_step(const mobocmf_tiny_model* host_models, const mobocmf_
         if (g.work_len >= ((int64_t)1 << 31)) return MOBOCMF_BAD_ARG;      // (workspace offsets are formed in 32 bits)
     }
     const size_t shm = coop_lds_bytes(mpmax);
-    const bool predict = do_update == 3 || chain_valid;
+    const bool predict = do_update == MOBOCMF_STEP_INPUT_GRADIENTS || chain_valid;
     const void* kfn = predict ? (const void*)coop_step_kernel<true> : (const void*)coop_step_kernel<false>;
     // every workgroup of the launch waits for its peers inside the launch: all of them must be resident at once
     IlGuard gd;

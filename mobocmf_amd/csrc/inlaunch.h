@@ -1,5 +1,5 @@
 // Waits between the workgroups of ONE ordinary launch (internal): the one-launch Cholesky (chol.hip potrf_coop_kernel), the
-// cooperative step (coop_step.hip) and the conditioned iteration of the one-workgroup kernel (tiny_step.hip, mode 4).
+// cooperative step (coop_step.hip) and the conditioned iteration of the one-workgroup kernel (tiny_step.hip, MOBOCMF_STEP_COUPLED).
 // The contract (include/mobocmf_hip.h, mobocmf_check_info):
 //  - the host checks that every workgroup of the launch is resident at once (il_guard); every wait is still bounded, by
 //    IL_WAIT_SECONDS of wall clock (the tick count is a kernel argument, il_guard's wait_ticks);

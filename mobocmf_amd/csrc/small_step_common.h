@@ -1,6 +1,7 @@
 // Device helpers shared by the one-launch steps of small surrogates (tiny_step.hip: one workgroup per surrogate, M <= 32;
 // coop_step.hip: several workgroups per surrogate, M <= 128): wavefront / workgroup reductions, the layer kernels' covariance
-// function with its gradient terms (gram.hip), and the theta / omega factor gradients of the conditioned iteration.
+// function with its gradient terms (gram.hip), the theta / omega factor gradients of the conditioned iteration, and
+// the descriptor checks both entry points make on the host before a launch.
 // Internal; every including file gets its own copies (anonymous namespace).
 #pragma once
 #include "common.h"
@@ -13,7 +14,7 @@ constexpr int DBT = MOBOCMF_TINY_MAX_D;          // x columns of a staged induci
 constexpr int ZW = DBT + 1;                      // + the f column
 constexpr int HS = 5 + 2 * DBT;                  // packed hyper-parameters of a layer, at most
 constexpr int NVEC = 11;                         // per-column vectors of a layer kept in `work`
-constexpr int64_t CPL_DOUBLES = 256 * 17;           // scratch of coupling_seeds (mode 4)
+constexpr int64_t CPL_DOUBLES = 256 * 17;           // scratch of coupling_seeds (MOBOCMF_STEP_COUPLED)
 constexpr int NSEG = 32;                         // parameter tensors of a model, at most (3 layers x 9 + 3 noise)
 constexpr double MINV = 1e-10;                   // gpytorch.settings.min_variance (float64)
 constexpr double LOG2PI = 1.8378770664093453;
@@ -160,8 +161,8 @@ __device__ __forceinline__ double peer(const double* p) {
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// Mode 4, after the grid barrier: the factor gradients of THIS model (blackbox_mfdgp_fitter.py:227-243; the algebra of
-// elementwise.hip cond_factors_kernel) into its seed arrays -- zero on the batch columns, the theta factors on a constraint's
+// MOBOCMF_STEP_COUPLED, after the grid barrier: the factor gradients of THIS model (blackbox_mfdgp_fitter.py:227-243; the algebra
+// of elementwise.hip cond_factors_kernel) into its seed arrays -- zero on the batch columns, the theta factors on a constraint's
 // Pareto columns, the omega factors (all models' moments at x~) on the x~ columns.  part: >= 256 * (1 + 2 n_obj) doubles of
 // workgroup scratch.  NT threads; all of them call it.
 template <int NT>
@@ -170,7 +171,7 @@ __device__ __forceinline__ void coupling_seeds(const mobocmf_tiny_model* models,
     const mobocmf_tiny_coupling& cp = *md.coupling;
     const int tid = threadIdx.x, P = cp.P, T = cp.T, no = cp.n_obj, nc = cp.n_con;
     const int stride = 1 + 2 * no;
-    double* sgm = const_cast<double*>(md.seed_gmean);      // (inputs of modes 1 / 3; in mode 4 the launch fills them itself)
+    double* sgm = const_cast<double*>(md.seed_gmean);      // (inputs of UPDATE / INPUT_GRADIENTS; COUPLED fills them itself)
     double* sgv = const_cast<double*>(md.seed_gvar);
     for (int c = tid; c < ncol_top; c += NT) { sgm[c] = 0.0; sgv[c] = 0.0; }
     // ---- omega: sum_p over the Pareto points, split among NG thread groups per point t (T <= NT)
@@ -286,5 +287,38 @@ __device__ __forceinline__ void coupling_seeds(const mobocmf_tiny_model* models,
 }
 
 __device__ __forceinline__ int seg_len(int l, int s, int d) { return l == 0 ? (s == 0 ? 1 : d) : (s < 5 ? 1 : d); }
+
+// ---- the host side of both entry points: what is checked before a launch
+// a descriptor whose sizes a work_bytes query can read
+inline bool sizable_model(const mobocmf_tiny_model* m) {
+    if (!m || m->L < 1 || m->L > TLM || m->M < 1 || m->d < 1 || m->S < 1) return false;
+    for (int l = 0; l < m->L; ++l)
+        if (m->rows[l] < 1) return false;
+    return true;
+}
+// a descriptor a launch may read (max_m: the kernel's limit on the inducing points)
+inline bool valid_model(const mobocmf_tiny_model& m, int max_m) {
+    if (m.L < 1 || m.L > TLM || m.M < 1 || m.M > max_m || m.d < 1 || m.d > DBT || m.S < 1 || m.N < 1) return false;
+    if (m.rows[0] != m.N) return false;
+    for (int l = 0; l < m.L; ++l) {
+        if (m.rows[l] < 1 || (l && m.rows[l] > m.rows[l - 1])) return false;
+        if ((int64_t)m.rows[l] * m.S > (1 << 20)) return false;
+        const int ns = l == 0 ? 2 : 7;
+        for (int s = 0; s < ns; ++s)
+            if (!m.raw[l][s]) return false;
+        if (!m.m[l] || !m.L_S[l] || !m.raw_noise[l]) return false;
+        if (l && !m.eps[l] && !m.rng[l]) return false;
+    }
+    if ((m.seed_gmean == nullptr) != (m.seed_gvar == nullptr) || (m.top_mean == nullptr) != (m.top_var == nullptr)) return false;
+    if (m.xrng && (m.rand_row0 < 0 || m.rand_rows < 0 || m.rand_row0 + m.rand_rows > m.N)) return false;
+    if (m.branch != 0 && m.branch != 1) return false;
+    return m.x && m.y && m.fid && m.Zx && m.adam_m && m.adam_v && m.steps_done && m.work && m.out && m.info;
+}
+// ... and what MOBOCMF_STEP_COUPLED needs of it besides: S = 1, seeds and top moments present, a role, the coupling record of
+// the launch's first model (the record itself is checked in depth by the caller's binding)
+inline bool valid_coupled_model(const mobocmf_tiny_model& m, const mobocmf_tiny_model& first) {
+    return m.coupling && m.S == 1 && m.seed_gmean && m.top_mean && m.role >= 0 && m.role <= 1 && m.role_index >= 0 &&
+           m.role_index <= 7 && m.coupling == first.coupling;
+}
 
 }  // namespace

@@ -10,9 +10,9 @@
 // state of every layer lives in LDS; the M x N' panels join it there when they fit, else they live in `work` (a workgroup
 // reads its own global writes after a barrier: one CU, one L1).  Only the Cholesky + triangular inverse is serial: one wavefront per layer, the matrix row-per-lane in
 // registers, pivots and multipliers broadcast by v_readlane (no LDS round trip, no barrier), the layers side by side.
-// Modes (do_update): 0 gradients only, 1 the step, 2 forward only (acquisition moments; the first launch of a three-launch
-// conditioned iteration), 3 input gradients (acquisition search), 4 the conditioned iteration in one launch (the models'
-// workgroups meet at an arrival counter after their forward and form the theta / omega factor gradients themselves).
+// Modes (do_update, MOBOCMF_STEP_*): GRADIENTS only, UPDATE (the step), FORWARD only (acquisition moments; the first launch of
+// a three-launch conditioned iteration), INPUT_GRADIENTS (acquisition search), COUPLED: the conditioned iteration in one launch
+// (the models' workgroups meet at an arrival counter after their forward and form the theta / omega factor gradients themselves).
 
 #include "common.h"
 #include "inlaunch.h"
@@ -49,9 +49,9 @@ __host__ __device__ inline void geom_of(const mobocmf_tiny_model& md, Geom& g) {
         wo += (int64_t)g.ncol[l] * (2 * md.M + NVEC);
     }
     g.scratch_off = wo;
-    g.srows = md.M > DBT ? md.M : DBT;      // rows of a scratch panel (mode 3 keeps DBT values per column in one)
+    g.srows = md.M > DBT ? md.M : DBT;      // rows of a scratch panel (MOBOCMF_STEP_INPUT_GRADIENTS keeps DBT values per column in one)
     g.pool_len = wo + 3 * (int64_t)g.srows * g.ncmax;
-    g.cpl_off = g.pool_base + g.pool_len;      // mode 4: partial sums of the factor terms, 256 x (1 + 2 x 8) doubles
+    g.cpl_off = g.pool_base + g.pool_len;      // MOBOCMF_STEP_COUPLED: partial sums of the factor terms, 256 x (1 + 2 x 8) doubles
     g.work_len = g.cpl_off + CPL_DOUBLES;
 #ifdef TINY_STAMPS
     g.work_len += 128;      // phase stamps (tools/tiny_stamps.py): the last 128 doubles of `work`
@@ -189,9 +189,9 @@ __global__ __launch_bounds__(TT) void tiny_step_kernel(const mobocmf_tiny_model*
         W0[l * MS + i * LD + j] = j <= i ? md.L_S[l][i * M + j] : 0.0;
     }
     for (int e = tid; e < L * M; e += TT) mst[(e / M) * MR + e % M] = md.m[e / M][e % M];
-    if (do_update == 3)
+    if (do_update == MOBOCMF_STEP_INPUT_GRADIENTS)
         for (int e = tid; e < md.N * d; e += TT) md.grad[e] = 0.0;
-    if ((do_update == 2 || do_update == 4) && md.xrng && md.rand_rows > 0) {
+    if ((do_update == MOBOCMF_STEP_FORWARD || do_update == MOBOCMF_STEP_COUPLED) && md.xrng && md.rand_rows > 0) {
         // the x~ of this iteration (:276): every model of the launch draws the SAME points from the shared stream
         const uint64_t seed = (uint64_t)md.xrng[0], call = (uint64_t)md.xrng[1];
         double* xw = const_cast<double*>(md.x) + (int64_t)md.rand_row0 * d;
@@ -219,7 +219,8 @@ __global__ __launch_bounds__(TT) void tiny_step_kernel(const mobocmf_tiny_model*
         seg_ptr[k] = ptr;
         seg_end[k] = end;
     }
-    if (tid == TT - 1 && (do_update == 1 || do_update == 4)) {      // Adam's bias corrections (two pow calls): once, off the critical path
+    // Adam's bias corrections (two pow calls): once, off the critical path
+    if (tid == TT - 1 && (do_update == MOBOCMF_STEP_UPDATE || do_update == MOBOCMF_STEP_COUPLED)) {
         const double step = (double)(md.steps_done[0] + 1);
         sc[12] = 1.0 - pow(b1, step);
         sc[13] = sqrt(1.0 - pow(b2, step));
@@ -385,8 +386,8 @@ __global__ __launch_bounds__(TT) void tiny_step_kernel(const mobocmf_tiny_model*
         }
     }
 
-    if (do_update == 2) return;
-    if (do_update == 4) {
+    if (do_update == MOBOCMF_STEP_FORWARD) return;
+    if (do_update == MOBOCMF_STEP_COUPLED) {
         // the conditioned iteration in one launch: every model's top-layer moments are published, the grid meets, every
         // workgroup forms the theta / omega factor gradients of its own model (its own moments it reads back from L1 / LDS
         // order; the others' with agent-scope loads)
@@ -398,7 +399,7 @@ __global__ __launch_bounds__(TT) void tiny_step_kernel(const mobocmf_tiny_model*
         // hanging the device, and every later barrier fails at its first poll until the host clears the record.  This is an ORDINARY launch, not a
         // cooperative one (hipLaunchCooperativeKernel + grid.sync() does the same job with a 23 us dispatch gap per launch
         // and cannot be captured into a graph): co-residency is checked on the host against the device's occupancy for this
-        // kernel and LDS size (mobocmf_tiny_elbo_step refuses mode 4 otherwise).
+        // kernel and LDS size (mobocmf_tiny_elbo_step refuses MOBOCMF_STEP_COUPLED otherwise).
         // A launch whose shape does not match the record (another n_models than the record was made for: the arrival counter
         // would no longer be a multiple of the grid at launch start; T outside what coupling_seeds divides by) stops HERE, in
         // every workgroup alike, before anyone arrives: nothing hangs, nothing is updated, the sticky status word says why.
@@ -496,7 +497,7 @@ __global__ __launch_bounds__(TT) void tiny_step_kernel(const mobocmf_tiny_model*
         }
         __syncthreads();
         STAMP();
-        if (do_update == 3) {
+        if (do_update == MOBOCMF_STEP_INPUT_GRADIENTS) {
             // input gradients only (the parameters are constants: acquisition search): per column d loss / d f, handed to
             // the layer below, and d loss / d x, summed over the row's columns into grad[b][k]
             for (int c = tid; c < nc; c += TT) {
@@ -737,7 +738,7 @@ __global__ __launch_bounds__(TT) void tiny_step_kernel(const mobocmf_tiny_model*
         STAMP();
     }
 
-    if (do_update == 3) return;
+    if (do_update == MOBOCMF_STEP_INPUT_GRADIENTS) return;
     // ---- raw-parameter gradients into the flat vector (g_LS is there already)
     for (int e = tid; e < L * HS; e += TT) {
         const int l = e / HS, t = e % HS;
@@ -754,7 +755,7 @@ __global__ __launch_bounds__(TT) void tiny_step_kernel(const mobocmf_tiny_model*
     STAMP();
     if (md.grad)
         for (int64_t e = tid; e < g.flat_len; e += TT) md.grad[e] = gflat[e];
-    if (!do_update) return;
+    if (do_update == MOBOCMF_STEP_GRADIENTS) return;
     // ---- Adam (torch.optim.Adam: p -= (lr / bc1) m / (sqrt(v) / sqrt(bc2) + eps)), every trainable tensor
     {
         const int64_t step = md.steps_done[0] + 1;
@@ -794,24 +795,6 @@ size_t lds_bytes(int MR) {
     return n * sizeof(double);
 }
 
-bool valid_model(const mobocmf_tiny_model& m) {
-    if (m.L < 1 || m.L > TLM || m.M < 1 || m.M > MOBOCMF_TINY_MAX_M || m.d < 1 || m.d > DBT || m.S < 1 || m.N < 1) return false;
-    if (m.rows[0] != m.N) return false;
-    for (int l = 0; l < m.L; ++l) {
-        if (m.rows[l] < 1 || (l && m.rows[l] > m.rows[l - 1])) return false;
-        if ((int64_t)m.rows[l] * m.S > (1 << 20)) return false;
-        const int ns = l == 0 ? 2 : 7;
-        for (int s = 0; s < ns; ++s)
-            if (!m.raw[l][s]) return false;
-        if (!m.m[l] || !m.L_S[l] || !m.raw_noise[l]) return false;
-        if (l && !m.eps[l] && !m.rng[l]) return false;
-    }
-    if ((m.seed_gmean == nullptr) != (m.seed_gvar == nullptr) || (m.top_mean == nullptr) != (m.top_var == nullptr)) return false;
-    if (m.xrng && (m.rand_row0 < 0 || m.rand_rows < 0 || m.rand_row0 + m.rand_rows > m.N)) return false;
-    if (m.branch != 0 && m.branch != 1) return false;
-    return m.x && m.y && m.fid && m.Zx && m.adam_m && m.adam_v && m.steps_done && m.work && m.out && m.info;
-}
-
 }  // namespace
 
 extern "C" {
@@ -825,9 +808,7 @@ int mobocmf_tiny_flat_len(const mobocmf_tiny_model* model, int64_t* len) {
 }
 
 int mobocmf_tiny_work_bytes(const mobocmf_tiny_model* model, size_t* bytes) {
-    if (!model || !bytes || model->L < 1 || model->L > TLM || model->M < 1 || model->d < 1 || model->S < 1) return MOBOCMF_BAD_ARG;
-    for (int l = 0; l < model->L; ++l)
-        if (model->rows[l] < 1) return MOBOCMF_BAD_ARG;
+    if (!bytes || !sizable_model(model)) return MOBOCMF_BAD_ARG;
     Geom g;
     geom_of(*model, g);
     *bytes = (size_t)g.work_len * sizeof(double);
@@ -836,21 +817,19 @@ int mobocmf_tiny_work_bytes(const mobocmf_tiny_model* model, size_t* bytes) {
 
 int mobocmf_tiny_elbo_step(const mobocmf_tiny_model* host_models, const mobocmf_tiny_model* dev_models, int32_t n_models,
                            double lr, double beta1, double beta2, double eps, int32_t do_update, mobocmf_stream_t stream) {
-    if (!host_models || !dev_models || n_models < 1 || n_models > 65535 || do_update < 0 || do_update > 4) return MOBOCMF_BAD_ARG;
+    if (!host_models || !dev_models || n_models < 1 || n_models > 65535 || do_update < MOBOCMF_STEP_GRADIENTS ||
+        do_update > MOBOCMF_STEP_COUPLED)
+        return MOBOCMF_BAD_ARG;
     int mmax = 0;
     int64_t pmax = 0;
     int cmax = 0;
     for (int i = 0; i < n_models; ++i) {
-        if (!valid_model(host_models[i]) || (do_update == 3 && !host_models[i].grad)) return MOBOCMF_BAD_ARG;
-        if (do_update == 4) {      // S = 1, seeds and top moments present, a coupling (checked in depth by the caller's binding)
-            const mobocmf_tiny_model& m = host_models[i];
-            if (!m.coupling || m.S != 1 || !m.seed_gmean || !m.top_mean || m.role < 0 || m.role > 1 || m.role_index < 0 ||
-                m.role_index > 7 || m.coupling != host_models[0].coupling)
-                return MOBOCMF_BAD_ARG;
-        }
-        if (host_models[i].M > mmax) mmax = host_models[i].M;
+        const mobocmf_tiny_model& m = host_models[i];
+        if (!valid_model(m, MOBOCMF_TINY_MAX_M) || (do_update == MOBOCMF_STEP_INPUT_GRADIENTS && !m.grad)) return MOBOCMF_BAD_ARG;
+        if (do_update == MOBOCMF_STEP_COUPLED && !valid_coupled_model(m, host_models[0])) return MOBOCMF_BAD_ARG;
+        if (m.M > mmax) mmax = m.M;
         Geom g;
-        geom_of(host_models[i], g);
+        geom_of(m, g);
         if (g.pool_len > pmax) pmax = g.pool_len;
         if (g.ncmax > cmax) cmax = g.ncmax;
     }
@@ -865,13 +844,13 @@ int mobocmf_tiny_elbo_step(const mobocmf_tiny_model* host_models, const mobocmf_
     const bool wide = (int64_t)mmax * cmax > 2 * 256;
     const void* fn = MR == 16 ? (wide ? (const void*)tiny_step_kernel<16, 512> : (const void*)tiny_step_kernel<16, 256>)
                               : (wide ? (const void*)tiny_step_kernel<32, 512> : (const void*)tiny_step_kernel<32, 256>);
-    // mode 4's in-launch barrier needs every workgroup of the launch resident at once: bound the grid by what THIS device holds
+    // COUPLED's in-launch barrier needs every workgroup of the launch resident at once: bound the grid by what THIS device holds
     // of this kernel with this much LDS (a partitioned or smaller device holds fewer; MOBOCMF_BAD_ARG sends the caller to the
     // three-launch form).  The guard also sets the dynamic-LDS attribute beyond 64 KB; the other launches need neither.
     IlGuard gd = {0, 0};
-    if (do_update == 4 || shm > 64 * 1024)
+    if (do_update == MOBOCMF_STEP_COUPLED || shm > 64 * 1024)
         if (const int rc = il_guard(fn, wide ? 512 : 256, shm, (int)LDS_BUDGET, gd)) return rc;
-    if (do_update == 4 && (n_models > 64 || (int64_t)n_models > gd.resident)) return MOBOCMF_BAD_ARG;
+    if (do_update == MOBOCMF_STEP_COUPLED && (n_models > 64 || (int64_t)n_models > gd.resident)) return MOBOCMF_BAD_ARG;
 #define LAUNCH(MR_, TT_)                                                                                              \
     hipLaunchKernelGGL((tiny_step_kernel<MR_, TT_>), dim3((unsigned)n_models), dim3(TT_), shm, s, dev_models, lr, beta1, \
                        beta2, eps, do_update, pool_in_lds, gd.wait_ticks)

@@ -6,25 +6,23 @@ mfdgp.py:295-298); the one-workgroup kernel (util/tiny_step.py) covers M <= 32, 
 ``CoopELBOStep`` has the surface of ``TinyELBOStep`` / ``GraphedELBOStep`` that the fitter's loop uses (step / check / snapshot /
 restore / losses / export_adam_state); ``CoopConditionedStep`` is the conditioned iteration (blackbox_mfdgp_fitter.py:245-354).
 """
-import ctypes
-
-import torch
-
 from .. import _lib
-from .. import functional as F
 from . import tiny_step as TS
 
-MAX_COLUMNS = 16384      # rows[l] * S per layer this binding accepts
+MAX_COLUMNS = 16384              # rows[l] * S per layer this binding accepts
+MAX_PREDICT_COLUMNS = 4096       # T * S per layer beyond which the layer path (frozen chains) is the better search engine
+MAX_WORTHWHILE_COLUMNS = 2048    # summed over the layers: beyond, the layer path's grid-filling launches win (tools/coop_sweep.py)
+
+# several workgroups per surrogate (csrc/coop_step.hip); a coupled launch takes as many models as the device keeps resident
+COOP = TS.Kernel("mobocmf_coop_elbo_step", "mobocmf_coop_work_bytes", _lib.COOP_MAX_M, MAX_COLUMNS, MAX_PREDICT_COLUMNS, None,
+                 cooperative=True)
 
 
 def eligible(model, x, fidelities):
     """The structural limits of the cooperative kernel: <= 3 layers sharing one set of <= 128 inducing inputs, d <= 8, softplus /
     Interval constraints, float64 parameters on the GPU (``tiny_step.eligible`` with this kernel's limits; no speed rule: the
     launch beats the layer path's ~57 launches per step wherever it applies)."""
-    return TS.eligible(model, x, fidelities, speed_rule=False, max_m=_lib.COOP_MAX_M, max_columns=MAX_COLUMNS)
-
-
-MAX_WORTHWHILE_COLUMNS = 2048      # summed over the layers: beyond, the layer path's grid-filling launches win (tools/coop_sweep.py)
+    return TS.eligible(model, x, fidelities, speed_rule=False, kernel=COOP)
 
 
 def worthwhile(model, x, fidelities):
@@ -33,98 +31,35 @@ def worthwhile(model, x, fidelities):
     the gate is the number of columns)."""
     if not eligible(model, x, fidelities):
         return False
-    L = len(model._layers())
     S = model.num_samples_for_training
-    fidv = fidelities.reshape(-1)
-    cols = sum(int((fidv >= l).sum()) * (S if l else 1) for l in range(L))
-    return cols <= MAX_WORTHWHILE_COLUMNS
-
-
-class _CoopLaunch:
-    """The launch of mobocmf_coop_elbo_step for the descriptor table a Tiny* step object built."""
-    _work_bytes_fn = "mobocmf_coop_work_bytes"
-    wgs_per_model = 0      # 0: chosen by the library from the widest phase
-
-    @staticmethod
-    def _eligible(model, x, fid, force):
-        return eligible(model, x, fid)
-
-    @staticmethod
-    def _eligible_conditioned(model, x, fid):
-        return eligible(model, x, fid)
-
-    def _new_sync(self):
-        # per model 16 words (its arrival counter first), then the grid's counter and the launch's status word
-        n = len(self.models)
-        return F.InLaunchSync(torch.zeros(16 * (n + 1), dtype=torch.int64, device=self.device), 16 * n + 1, self.stream)
-
-    def _launch(self, mode):
-        lib = _lib.require_device()
-        used = ctypes.c_int32(0)
-        _lib.check(lib.mobocmf_coop_elbo_step(ctypes.cast(self.host, ctypes.c_void_p), ctypes.c_void_p(self._dev_table.data_ptr()),
-                                              len(self.models), int(self.wgs_per_model),
-                                              ctypes.c_void_p(self.in_launch_sync().ptr(0)),
-                                              self.lr, self.betas[0], self.betas[1], self.eps, int(mode), ctypes.byref(used),
-                                              ctypes.c_void_p(self.stream.cuda_stream)),
-                   "mobocmf_coop_elbo_step")
-        self.wgs_used = used.value
-
-
-class CoopELBOStep(_CoopLaunch, TS.TinyELBOStep):
-    """``step()`` == one full-batch ELBO step of EVERY model of the group, one launch (see ``TinyELBOStep`` for the arguments)."""
-
-
-class CoopConditionedStep(_CoopLaunch, TS.TinyConditionedStep):
-    """One iteration of the conditioned training in ONE launch (mode 4), or forward-only launch + factor launches + step launch."""
-
-    def _issue_step(self):
-        if self.one_launch and self.T <= 256:
-            try:
-                self._launch(4)
-                return
-            except _lib.MobocmfError:
-                self.one_launch = False
-        self._launch(2)
-        self._factors()
-        self._launch(1)
-
-
-MAX_PREDICT_COLUMNS = 4096      # T * S per layer beyond which the layer path (frozen chains) is the better search engine
+    rows = TS.rows_per_layer(fidelities, len(model._layers()))
+    return sum(r * (S if l else 1) for l, r in enumerate(rows)) <= MAX_WORTHWHILE_COLUMNS
 
 
 def fits_predict(model, fidelity, T, d):
     """``tiny_step.fits_predict`` with the cooperative kernel's limits (M <= 128) and its column bound."""
-    S = model.num_samples_for_acquisition if fidelity > 0 else 1
-    return T * S <= MAX_PREDICT_COLUMNS and TS.fits_predict(model, fidelity, T, d, speed_rule=False, max_m=_lib.COOP_MAX_M)
+    return TS.fits_predict(model, fidelity, T, d, speed_rule=False, kernel=COOP)
 
 
-class CoopPredictGroup(_CoopLaunch, TS.TinyPredictGroup):
+class CoopELBOStep(TS.TinyELBOStep):
+    """``step()`` == one full-batch ELBO step of EVERY model of the group, one launch (see ``TinyELBOStep`` for the arguments)."""
+    kernel = COOP
+
+
+class CoopConditionedStep(TS.TinyConditionedStep):
+    """One iteration of the conditioned training in ONE launch (STEP_COUPLED), or forward-only launch + factor launches + step
+    launch."""
+    kernel = COOP
+
+
+class CoopPredictGroup(TS.TinyPredictGroup):
     """``TinyPredictGroup`` for mid-size models (32 < M <= 128): predictive moments of several fitted models at the same T test
-    points in ONE cooperative launch (mode 2), their gradient w.r.t. the test points in one more (mode 3) -- the acquisition
-    search of the reference's later BO iterations (JESMOC_MFDGP.py:137-184 against M = N = 33 ... 75 surrogates).  A give-up of
-    an in-launch wait is reported by ``thaw()``, at the end of the search."""
-    _work_bytes_fn = "mobocmf_coop_work_bytes"
-    wgs_per_model = 0
-    lr, betas, eps = 0.0, (0.9, 0.999), 1e-8      # (no update in modes 2 / 3)
+    points in ONE cooperative launch (STEP_FORWARD), their gradient w.r.t. the test points in one more (STEP_INPUT_GRADIENTS) --
+    the acquisition search of the reference's later BO iterations (JESMOC_MFDGP.py:137-184 against M = N = 33 ... 75
+    surrogates).  A give-up of an in-launch wait is reported by ``thaw()``, at the end of the search."""
+    kernel = COOP
     _frozen = False            # inside freeze() ... thaw(): the models' parameters do not change between launches
     _chain_ready = False       # ... and a launch since freeze() has left their chains (L^-1, U, a) in the workspaces
-
-    @property
-    def stream(self):
-        return torch.cuda.current_stream(self.device)
-
-    def _order_after_setup(self):
-        pass      # (the words are zero-filled on the stream the launches run on)
-
-    def _new_sync(self):
-        n = len(self.models)
-        return F.InLaunchSync(torch.zeros(16 * (n + 1), dtype=torch.int64, device=self.device), 16 * n + 1)
-
-    in_launch_sync = TS.TinyELBOStep.in_launch_sync
-
-    @staticmethod
-    def _fits(model, fidelity, T, d):
-        return fits_predict(model, fidelity, T, d)
 
     def freeze(self):
         """The parameters are constants until ``thaw()`` (an acquisition search, JESMOC_MFDGP._optimize): the first launch
@@ -142,6 +77,6 @@ class CoopPredictGroup(_CoopLaunch, TS.TinyPredictGroup):
 
     def _launch(self, mode):
         if self._frozen and self._chain_ready:
-            mode = int(mode) | _lib.STEP_CHAIN_VALID
+            mode |= _lib.STEP_CHAIN_VALID
         super()._launch(mode)
         self._chain_ready = self._frozen

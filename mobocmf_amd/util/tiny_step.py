@@ -15,7 +15,6 @@ from .. import _lib
 from .. import functional as F
 from .. import gp
 
-MAX_COLUMNS = 1024      # rows[l] * S per layer: hard limit of this binding
 LAYER_PATH_US = 240.0   # what a step of a small surrogate costs through the layer entry points (HIP-graph replay, MI355X)
 
 
@@ -26,41 +25,88 @@ def estimated_us(M, columns):
     return 20.0 + 0.15 * M * M + (M * M / 900.0) * float(sum(columns))
 
 
+class Kernel:
+    """The kernel a step object or a predict group drives: its limits, its entry points, the words of its in-launch waits and
+    its launch.  ``max_columns`` / ``max_predict_columns``: rows[l] * S per layer this binding accepts for training / for
+    prediction; ``max_coupled_models``: models of one MOBOCMF_STEP_COUPLED launch (None: what the device keeps resident)."""
+
+    def __init__(self, entry, work_bytes_fn, max_m, max_columns, max_predict_columns, max_coupled_models, cooperative):
+        self.entry, self.work_bytes_fn = entry, work_bytes_fn
+        self.max_m, self.max_columns, self.max_predict_columns = max_m, max_columns, max_predict_columns
+        self.max_coupled_models, self.cooperative = max_coupled_models, cooperative
+
+    def sync_words(self, n, coupled):
+        """(int64 words, index of the status word) of the in-launch waits of a group of n models; None: the launches wait
+        for nothing."""
+        if self.cooperative:      # per model 16 words (its arrival counter first), then the grid's counter and the status word
+            return 16 * (n + 1), 16 * n + 1
+        return (2, 1) if coupled else None      # the coupling record's arrival counter and its status word
+
+    def launch(self, group, mode, lr, beta1, beta2, eps):
+        """Enqueues one launch over ``group``'s descriptor table on its stream (None: the current one).  The cooperative kernel
+        runs ``group.wgs_per_model`` workgroups per model (0: chosen by the library from the widest phase) and leaves what it
+        ran with in ``group.wgs_used``."""
+        fn = getattr(_lib.require_device(), self.entry)
+        host, table = ctypes.cast(group.host, ctypes.c_void_p), ctypes.c_void_p(group._dev_table.data_ptr())
+        stream = group.stream if group.stream is not None else torch.cuda.current_stream(group.device)
+        stream = ctypes.c_void_p(stream.cuda_stream)
+        if not self.cooperative:
+            _lib.check(fn(host, table, len(group.models), lr, beta1, beta2, eps, int(mode), stream), self.entry)
+            return
+        used = ctypes.c_int32(0)
+        _lib.check(fn(host, table, len(group.models), int(group.wgs_per_model), ctypes.c_void_p(group.in_launch_sync().ptr(0)),
+                      lr, beta1, beta2, eps, int(mode), ctypes.byref(used), stream), self.entry)
+        group.wgs_used = used.value
+
+
+# one workgroup per surrogate (csrc/tiny_step.hip)
+TINY = Kernel("mobocmf_tiny_elbo_step", "mobocmf_tiny_work_bytes", _lib.TINY_MAX_M, 1024, 4096, 64, cooperative=False)
+
+
 def _hyper_params(layer):
     return [getattr(m, n) for m, n in gp._hyper_sources(layer.covar_module, layer.kind)]
 
 
-def fits_predict(model, fidelity, T, d, speed_rule=True, max_m=None):
-    """True when ``model``'s predictive moments at T test points up to layer ``fidelity`` fit the one-launch kernel (the
-    structural limits of ``eligible``; the training flags do not matter: prediction runs the eval branch).  ``max_m``: the
-    inducing-point limit of the kernel asked about (default: the one-workgroup kernel's)."""
+def _likelihood(model, l):
+    return getattr(model, model.name_hidden_layer_likelihood + str(l))
+
+
+def rows_per_layer(fidelities, L):
+    """Layer l runs on the rows of fidelity >= l."""
+    fidv = fidelities.reshape(-1)
+    return [int((fidv >= l).sum()) for l in range(L)]
+
+
+def structure_fits(model, L, d, max_m, training, on_gpu=True):
+    """The structural limits both kernels share, for the first ``L`` layers of ``model`` (None: all) on d input columns: <= 3 of the
+    expected kinds sharing one jitter and one set of <= ``max_m`` inducing inputs (Z~_l = [Z_x, m_{l-1}]), d <= 8, softplus /
+    Interval constraints, float64 contiguous parameters (``on_gpu``: on the GPU); ``training``: model and layers in training
+    mode (prediction runs the eval branch whatever the flags say)."""
     try:
-        layers = model._layers()[:fidelity + 1]
+        layers = model._layers() if L is None else model._layers()[:L]
         if not (1 <= len(layers) <= _lib.TINY_MAX_LAYERS) or model.use_only_highest_fidelity or not (1 <= d <= _lib.TINY_MAX_D):
+            return False
+        if training and model._eval_mode:
             return False
         Z0 = layers[0].variational_strategy._inducing_points
         M = Z0.shape[0]
-        if not (1 <= M <= (max_m or _lib.TINY_MAX_M)) or Z0.shape[1] != d or not Z0.is_cuda:
-            return False
-        S = model.num_samples_for_acquisition
-        cols = [T] + [T * S] * (len(layers) - 1)
-        if max(cols) > MAX_COLUMNS * 4 or (speed_rule and estimated_us(M, cols) > LAYER_PATH_US):
+        if not (1 <= M <= max_m) or Z0.shape[1] != d or (on_gpu and not Z0.is_cuda):
             return False
         jit = layers[0].variational_strategy.jitter_val
         for l, layer in enumerate(layers):
             vs = layer.variational_strategy
             vd = vs._variational_distribution
             Zl = vs._inducing_points
-            if layer.kind != (0 if l == 0 else 1) or vs.jitter_val != jit or Zl.shape[0] != M:
+            if layer.kind != (0 if l == 0 else 1) or vs.jitter_val != jit or Zl.shape[0] != M or (training and not layer.training):
                 return False
-            if l and (not torch.equal(Zl[:, :-1], Z0) or layer.samples.numel() != S):
+            if l and not torch.equal(Zl[:, :-1], Z0):      # layers >= 1 share Z_x; their f column is m_{l-1} (F9)
                 return False
-            lik = getattr(model, model.name_hidden_layer_likelihood + str(l))
+            lik = _likelihood(model, l)
             c = lik.raw_noise_constraint
             if type(c) is not gp.Interval or not (c.upper_bound > c.lower_bound) or c.upper_bound == float("inf"):
                 return False
             ps = _hyper_params(layer) + [vd.variational_mean, vd.chol_variational_covar, lik.raw_noise]
-            if not all(p.is_cuda and p.dtype == torch.float64 and p.is_contiguous() for p in ps):
+            if not all((p.is_cuda or not on_gpu) and p.dtype == torch.float64 and p.is_contiguous() for p in ps):
                 return False
             if not all(type(getattr(m, n + "_constraint")) is gp.Positive
                        for m, n in gp._hyper_sources(layer.covar_module, layer.kind)):
@@ -70,59 +116,183 @@ def fits_predict(model, fidelity, T, d, speed_rule=True, max_m=None):
         return False
 
 
-def eligible(model, x, fidelities, speed_rule=True, max_m=None, max_columns=None):
-    """(``max_m`` / ``max_columns``: the limits of the kernel asked about; default: the one-workgroup kernel's.)  True when ``model`` on the batch ``x`` fits the one-launch step: <= 3 layers sharing one set of <= 32 inducing inputs
-    (Z~_l = [Z_x, m_{l-1}]), d <= 8, softplus / Interval constraints, float64 parameters on the GPU, every fidelity's
-    prefix non-empty -- and, with ``speed_rule``, small enough for one workgroup to beat the layer path (estimated_us)."""
+def fits_predict(model, fidelity, T, d, speed_rule=True, kernel=TINY):
+    """True when ``model``'s predictive moments at T test points up to layer ``fidelity`` fit the one-launch kernel
+    (``structure_fits``; the training flags do not matter), every layer has the model's number of fixed samples and the
+    columns are within the kernel's limit -- and, with ``speed_rule``, few enough for one workgroup to beat the layer path."""
     try:
+        if not structure_fits(model, fidelity + 1, d, kernel.max_m, training=False):
+            return False
+        layers = model._layers()[:fidelity + 1]
+        S = model.num_samples_for_acquisition
+        cols = [T] + [T * S] * (len(layers) - 1)
+        if max(cols) > kernel.max_predict_columns or any(layer.samples.numel() != S for layer in layers[1:]):
+            return False
+        M = layers[0].variational_strategy._inducing_points.shape[0]
+        return not (speed_rule and estimated_us(M, cols) > LAYER_PATH_US)
+    except AttributeError:
+        return False
+
+
+def eligible(model, x, fidelities, speed_rule=True, kernel=TINY):
+    """True when ``model`` on the batch ``x`` fits the one-launch step of ``kernel``: ``structure_fits`` in training mode, fixed
+    inducing inputs, float64 data on the GPU, rows[l] * S within the kernel's limit, every fidelity's prefix non-empty -- and,
+    with ``speed_rule``, small enough for one workgroup to beat the layer path (estimated_us)."""
+    try:
+        if not x.is_cuda or x.dtype != torch.float64 or x.dim() != 2:
+            return False
+        if not structure_fits(model, None, x.shape[1], kernel.max_m, training=True):
+            return False
         layers = model._layers()
-        L = len(layers)
-        if not (1 <= L <= _lib.TINY_MAX_LAYERS) or model.use_only_highest_fidelity or model._eval_mode:
-            return False
-        if not x.is_cuda or x.dtype != torch.float64 or x.dim() != 2 or not (1 <= x.shape[1] <= _lib.TINY_MAX_D):
-            return False
-        Z0 = layers[0].variational_strategy._inducing_points
-        M = Z0.shape[0]
-        if not (1 <= M <= (max_m or _lib.TINY_MAX_M)) or Z0.requires_grad or Z0.shape[1] != x.shape[1]:
+        if any(layer.variational_strategy._inducing_points.requires_grad for layer in layers):
             return False
         S = model.num_samples_for_training
-        fidv = fidelities.reshape(-1)
-        N = fidv.numel()
-        if N != x.shape[0] or N * max(S, 1) > (max_columns or MAX_COLUMNS):
+        N = fidelities.numel()
+        if N != x.shape[0] or N * max(S, 1) > kernel.max_columns:
             return False
-        counts = [int((fidv >= l).sum()) for l in range(L)]
+        counts = rows_per_layer(fidelities, len(layers))
         if counts[0] != N or counts[-1] < 1:
             return False
-        if speed_rule and estimated_us(M, [c * (S if l else 1) for l, c in enumerate(counts)]) > LAYER_PATH_US:
-            return False
-        jit = layers[0].variational_strategy.jitter_val
-        for l, layer in enumerate(layers):
-            vs = layer.variational_strategy
-            vd = vs._variational_distribution
-            if layer.kind != (0 if l == 0 else 1) or vs.jitter_val != jit or not layer.training:
-                return False
-            Zl = vs._inducing_points
-            if Zl.requires_grad or Zl.shape[0] != M:
-                return False
-            if l and not torch.equal(Zl[:, :-1], Z0):      # layers >= 1 share Z_x; their f column is m_{l-1} (F9)
-                return False
-            ps = _hyper_params(layer) + [vd.variational_mean, vd.chol_variational_covar]
-            lik = getattr(model, model.name_hidden_layer_likelihood + str(l))
-            c = lik.raw_noise_constraint
-            if type(c) is not gp.Interval or not (c.upper_bound > c.lower_bound) or c.upper_bound == float("inf"):
-                return False
-            ps.append(lik.raw_noise)
-            if not all(p.is_cuda and p.dtype == torch.float64 and p.is_contiguous() for p in ps):
-                return False
-            if not all(type(getattr(m, n + "_constraint")) is gp.Positive
-                       for m, n in gp._hyper_sources(layer.covar_module, layer.kind)):
-                return False
-        return True
+        M = layers[0].variational_strategy._inducing_points.shape[0]
+        return not (speed_rule and estimated_us(M, [c * (S if l else 1) for l, c in enumerate(counts)]) > LAYER_PATH_US)
     except AttributeError:
         return False
 
 
-class TinyELBOStep:
+class Descriptor:
+    """Fills one mobocmf_tiny_model record ``rec`` for the first ``L`` layers of ``model``: the header, per layer the raw
+    parameters, m, L_S, the noise parameter with its bounds, Z_x, the jitter and the eps / rng pointers.  ``segments``: the flat
+    vector of grad / adam_m / adam_v as [(parameter, offset, length)], checked against mobocmf_tiny_flat_len.  Everything up to
+    ``allocate`` runs on whatever device the model is on (the library's size queries are host code)."""
+
+    def __init__(self, rec, model, L, d, S, rows, kl_scale, eps=None, natgrad=False, branch=0):
+        """``rows[l]``: the rows of layer l; ``eps[l]``: given draws of layer l >= 1 (None: the layer's rng stream);
+        ``natgrad``: q(u) of every layer whose m AND L_S both require a gradient is moved by the natural-gradient launch --
+        ``natural`` lists them as (layer, M, flat offset of m, of L_S) and their trainable bits 7 and 8 are cleared."""
+        self.rec, self.model, self.layers = rec, model, model._layers()[:L]
+        self.keep, self.segments, self.natural, self.eps = [], [], [], [None] * L
+        Z0 = self.layers[0].variational_strategy._inducing_points
+        rec.L, rec.M, rec.d, rec.S, rec.N = L, Z0.shape[0], d, S, rows[0]
+        rec.branch, rec.kl_scale, rec.jitter = branch, kl_scale, self.layers[0].variational_strategy.jitter_val
+        Zx = Z0.detach().contiguous()
+        rec.Zx = Zx.data_ptr()
+        self.keep.append(Zx)
+        off = 0
+        for l, layer in enumerate(self.layers):
+            vd = layer.variational_strategy._variational_distribution
+            lik = _likelihood(model, l)
+            rec.rows[l] = rows[l]
+            tr = 0
+            for s, p in enumerate(_hyper_params(layer)):
+                rec.raw[l][s] = p.data_ptr()
+                tr |= int(p.requires_grad) << s
+                self.segments.append((p, off, p.numel()))
+                off += p.numel()
+            natural = natgrad and vd.variational_mean.requires_grad and vd.chol_variational_covar.requires_grad
+            if natural:
+                Ml = vd.variational_mean.numel()
+                self.natural.append((l, Ml, off, off + Ml))
+            for bit, p in ((7, vd.variational_mean), (8, vd.chol_variational_covar)):
+                tr |= int(p.requires_grad and not natural) << bit
+                self.segments.append((p, off, p.numel()))
+                off += p.numel()
+            rec.m[l], rec.L_S[l] = vd.variational_mean.data_ptr(), vd.chol_variational_covar.data_ptr()
+            # (the eval branch never updates: its record keeps the bits 0)
+            rec.trainable[l] = 0 if branch else tr | int(lik.raw_noise.requires_grad) << 9
+            rec.raw_noise[l] = lik.raw_noise.data_ptr()
+            rec.noise_lo[l], rec.noise_hi[l] = lik.raw_noise_constraint.lower_bound, lik.raw_noise_constraint.upper_bound
+            if l and eps is not None and eps[l] is not None:
+                self.set_eps(l, eps[l])
+            elif l:
+                rng = layer._rng(Zx.device)
+                rec.rng[l] = rng.data_ptr()
+                self.keep.append(rng)
+        for l in range(L):
+            self.segments.append((_likelihood(model, l).raw_noise, off + l, 1))
+        self.flat_len = off + L
+        flat = ctypes.c_int64()
+        _lib.check(_lib.load().mobocmf_tiny_flat_len(ctypes.byref(rec), ctypes.byref(flat)), "mobocmf_tiny_flat_len")
+        assert flat.value == self.flat_len, (flat.value, self.flat_len)
+
+    def set_eps(self, l, e):
+        self.eps[l] = e
+        self.rec.eps[l] = e.data_ptr()
+        self.keep.append(e)
+
+    @classmethod
+    def for_training(cls, rec, model, d, fidelities, num_data, natgrad=False):
+        """The full-batch ELBO step on rows ordered by descending fidelity: kl_scale = N / num_data."""
+        L = len(model._layers())
+        rows = rows_per_layer(fidelities, L)
+        return cls(rec, model, L, d, model.num_samples_for_training, rows, rows[0] / float(num_data), natgrad=natgrad)
+
+    @classmethod
+    def for_prediction(cls, rec, model, fidelity, n_test, d):
+        """The eval branch at ``n_test`` points up to layer ``fidelity``: eval_mode's draws are the layers' fixed samples, tiled
+        over the test points (mfdgp_hidden_layer.py:263-270); no row is scored."""
+        L = fidelity + 1
+        eps = [None] + [layer.samples.reshape(-1).to(torch.float64).repeat(n_test).contiguous() for layer in model._layers()[1:L]]
+        return cls(rec, model, L, d, model.num_samples_for_acquisition if L > 1 else 1, [n_test] * L, 0.0, eps=eps, branch=1)
+
+    def allocate(self, kernel, dev):
+        """Sizes and allocates the workspace of ``kernel`` for this record.  MOBOCMF_POISON (as functional._scratch): NaN-filled,
+        so a read of anything the launch did not write shows."""
+        wb = ctypes.c_size_t()
+        _lib.check(getattr(_lib.load(), kernel.work_bytes_fn)(ctypes.byref(self.rec), ctypes.byref(wb)), kernel.work_bytes_fn)
+        work = torch.full((wb.value // 8,), float("nan") if os.environ.get("MOBOCMF_POISON") else 0.0,
+                          dtype=torch.float64, device=dev)
+        self.rec.work = work.data_ptr()
+        return work
+
+
+class _OneLaunchGroup:
+    """What the step objects and the predict groups share: the descriptor table of their models in host and device memory,
+    the tensors it points at, the words of the in-launch waits and the launch of ``kernel``."""
+    kernel = TINY
+    coupled = False        # the launches meet at the barrier of a coupling record (the conditioned step)
+    stream = None          # the launches' stream; None: the current one
+    wgs_per_model = 0      # the cooperative kernel's workgroups per model; 0: chosen by the library from the widest phase
+
+    def _new_table(self, models, dev):
+        self.models, self.device = list(models), dev
+        self.host = (_lib.TinyModel * len(self.models))()
+        self._keep = []          # tensors the descriptors point at
+
+    def _upload(self):
+        """The table as the kernels read it.  It and everything it points at was allocated, zero-filled and uploaded on the
+        CURRENT stream: the launches on ``self.stream`` come after."""
+        self._dev_table = torch.frombuffer(bytearray(bytes(self.host)), dtype=torch.uint8).to(self.device)
+        self._order_after_setup()
+
+    def _order_after_setup(self):
+        """Without this edge a fill kernel could still be pending when the first launch starts (found with a cooperative launch
+        whose arrival counters were zeroed under it: tools/coop_concurrency_probe.py)."""
+        if self.stream is not None:
+            self.stream.wait_stream(torch.cuda.current_stream(self.device))
+
+    def in_launch_sync(self):
+        """The counters and status word of the launches' in-launch waits (functional.InLaunchSync), made on first use; None
+        for a kernel without such waits."""
+        sync = self.__dict__.get("sync")
+        if sync is None:
+            sync = self.sync = self._new_sync()
+            if sync is not None:
+                self._order_after_setup()      # (zero-filled on the current stream)
+        return sync
+
+    def _new_sync(self):
+        layout = self.kernel.sync_words(len(self.models), self.coupled)
+        if layout is None:
+            return None
+        return F.InLaunchSync(torch.zeros(layout[0], dtype=torch.int64, device=self.device), layout[1], self.stream)
+
+    def _launch(self, mode):
+        """mode: _lib.STEP_* (do_update of mobocmf_tiny_elbo_step / mobocmf_coop_elbo_step); no update in the forward-only and
+        input-gradient modes, so Adam's settings do not matter here."""
+        self.kernel.launch(self, mode, 0.0, 0.9, 0.999, 1e-8)
+
+
+class TinyELBOStep(_OneLaunchGroup):
     """``step()`` == one full-batch ELBO step of EVERY model of the group, one launch.  ``models[i]`` trains on
     ``(xs[i], ys[i], fids[i])`` (y: (N, 1) or (N,); fidelities as the ELBO takes them).  The rows are ordered once by
     descending fidelity (``row_order[i]``; a full-batch ELBO is a sum over rows) and layer l runs on the rows of fidelity
@@ -141,7 +311,7 @@ class TinyELBOStep:
         ``prepared`` (TinyConditionedStep): per model a dict with the rows ALREADY in the kernel's order and the optional
         fields of mobocmf_tiny_model -- x, y, fid, rows, row_weight, kl_scale, seeds (bool), rand (row0, rows), xrng, eps
         (per layer, prefix columns)."""
-        lib = _lib.require_device()
+        _lib.require_device()
         if variational_optimizer not in ("adam", "natgrad"):
             raise ValueError("variational_optimizer must be 'adam' or 'natgrad' (got %r)" % (variational_optimizer,))
         self.variational_optimizer = variational_optimizer
@@ -150,49 +320,53 @@ class TinyELBOStep:
         if variational_optimizer == "natgrad" and not (0.0 < self.natgrad_gamma_init <= self.natgrad_gamma
                                                        and self.natgrad_warmup_steps >= 0):
             raise ValueError("%s: 0 < natgrad_gamma_init <= natgrad_gamma and natgrad_warmup_steps >= 0" % type(self).__name__)
-        self.models = list(models)
-        n = len(self.models)
         dev = (xs[0] if prepared is None else prepared[0]["x"]).device
-        self.device = dev
+        self._new_table(models, dev)
+        n = len(self.models)
         self.lr, self.betas, self.eps = float(lr), (float(betas[0]), float(betas[1])), float(eps)
         self.stream = stream if stream is not None else torch.cuda.Stream(device=dev)
-        self.host = (_lib.TinyModel * n)()
         self.losses = torch.zeros(n, 3, dtype=torch.float64, device=dev)
         self.infos = torch.zeros(n, _lib.TINY_MAX_LAYERS, dtype=torch.int32, device=dev)
         self.steps_done = torch.zeros(n, dtype=torch.int64, device=dev)
         self.row_order, self.layer_rows = [], []
-        self._keep = []          # tensors the descriptors point at
         self.exp_avg, self.exp_avg_sq, self.grads, self._work = [], [], [], []
         self._segments = []      # per model: [(parameter tensor, flat offset, length)]
         self._gflat = {}         # model -> the flat gradient its launches write (want_grad, or a natural-gradient layer)
         self._natural = []       # layers moved by natural gradients: (model, layer, word, M, flat offset of m, of L_S, scale)
         self.num_layers = 0      # layers of all models: one word each in natgrad_steps / skipped / natgrad_info
         self.top_moments, self.seeds, self.x_rows = [], [], []      # prepared models: (2, ncol_top) tensors, the x array
+        natgrad = variational_optimizer == "natgrad"
         for i, model in enumerate(self.models):
             prep = None if prepared is None else prepared[i]
             x, y, fid = (xs[i], ys[i], fids[i]) if prep is None else (prep["x"], prep["y"], prep["fid"])
-            if not self._eligible(model, x, fid, force):
+            if not eligible(model, x, fid, speed_rule=not force and not self.kernel.cooperative, kernel=self.kernel):
                 raise _lib.MobocmfError("%s: model %d does not fit the one-launch step (see eligible())" % (type(self).__name__, i))
-            layers = model._layers()
-            L, S = len(layers), model.num_samples_for_training
+            L, S = len(model._layers()), model.num_samples_for_training
             fidv = fid.reshape(-1).to(torch.float64)
             N = fidv.numel()
+            T = self.host[i]
             if prep is None:
-                counts = [int((fidv >= l).sum()) for l in range(L)]
+                desc = Descriptor.for_training(T, model, x.shape[1], fidv, num_data[i], natgrad)
                 order = torch.argsort(fidv, descending=True, stable=True)
                 xo, yo, fo = x[order].contiguous(), y.reshape(-1)[order].to(torch.float64).contiguous(), fidv[order].contiguous()
+                given = None if fixed_eps is None else fixed_eps[i]
             else:
-                counts, order = [int(r) for r in prep["rows"]], None
+                desc = Descriptor(T, model, L, x.shape[1], S, [int(r) for r in prep["rows"]], float(prep["kl_scale"]),
+                                  natgrad=natgrad)
+                order = None
                 xo, yo, fo = x.contiguous(), y.reshape(-1).to(torch.float64).contiguous(), fidv.contiguous()
+                given = prep.get("eps")
+            counts = list(T.rows[:L])
             self.row_order.append(order)
             self.layer_rows.append(counts)
-            T = self.host[i]
-            T.L, T.M, T.d, T.S, T.N = L, layers[0].variational_strategy._inducing_points.shape[0], x.shape[1], S, N
-            Zx = layers[0].variational_strategy._inducing_points.detach().contiguous()
-            T.x, T.y, T.fid, T.Zx = xo.data_ptr(), yo.data_ptr(), fo.data_ptr(), Zx.data_ptr()
-            self._keep += [xo, yo, fo, Zx]
-            T.kl_scale = N / float(num_data[i]) if prep is None else float(prep["kl_scale"])
-            T.jitter = layers[0].variational_strategy.jitter_val
+            T.x, T.y, T.fid = xo.data_ptr(), yo.data_ptr(), fo.data_ptr()
+            self._keep += [xo, yo, fo]
+            for l in range(1, L):
+                e = None if given is None else given[l]
+                if e is not None and order is not None:      # given for the batch as passed in (N * S values): follow the rows
+                    e = e.reshape(N, S)[order]
+                if e is not None:
+                    desc.set_eps(l, e.reshape(-1)[:counts[l] * S].contiguous())
             if prep is not None:
                 ntop = counts[-1] * (S if L > 1 else 1)
                 if prep.get("row_weight") is not None:
@@ -211,81 +385,29 @@ class TinyELBOStep:
                     T.rand_row0, T.rand_rows = prep["rand"]
                     self._keep.append(prep["xrng"])
                 self.x_rows.append(xo)
-            segs = []
-            off = 0
-            for l, layer in enumerate(layers):
-                vd = layer.variational_strategy._variational_distribution
-                lik = getattr(model, model.name_hidden_layer_likelihood + str(l))
-                T.rows[l] = counts[l]
-                tr = 0
-                for s, p in enumerate(_hyper_params(layer)):
-                    T.raw[l][s] = p.data_ptr()
-                    tr |= int(p.requires_grad) << s
-                    segs.append((p, off, p.numel()))
-                    off += p.numel()
-                natural = variational_optimizer == "natgrad" and vd.variational_mean.requires_grad and \
-                    vd.chol_variational_covar.requires_grad
-                if natural:      # (scale: what turns the launch's loss into -ELBO -- the inverse of kl_scale)
-                    Ml = vd.variational_mean.numel()
-                    self._natural.append((i, l, self.num_layers, Ml, off, off + Ml,
-                                          1.0 if prep is not None else float(num_data[i]) / N))
-                self.num_layers += 1
-                for bit, p in ((7, vd.variational_mean), (8, vd.chol_variational_covar)):
-                    tr |= int(p.requires_grad and not natural) << bit
-                    segs.append((p, off, p.numel()))
-                    off += p.numel()
-                T.m[l], T.L_S[l] = vd.variational_mean.data_ptr(), vd.chol_variational_covar.data_ptr()
-                tr |= int(lik.raw_noise.requires_grad) << 9
-                T.trainable[l] = tr
-                T.raw_noise[l] = lik.raw_noise.data_ptr()
-                T.noise_lo[l], T.noise_hi[l] = lik.raw_noise_constraint.lower_bound, lik.raw_noise_constraint.upper_bound
-                if l:
-                    if prep is not None:
-                        e = None if prep.get("eps") is None else prep["eps"][l]
-                        if e is not None:
-                            e = e.reshape(-1)[:counts[l] * S].contiguous()
-                    else:
-                        e = None if fixed_eps is None or fixed_eps[i] is None else fixed_eps[i][l]
-                        if e is not None:      # given for the batch as passed in (N * S values): follow the rows
-                            e = e.reshape(N, S)[order][:counts[l]].reshape(-1).contiguous()
-                    if e is not None:
-                        T.eps[l] = e.data_ptr()
-                        self._keep.append(e)
-                    rng = layer._rng(dev)
-                    T.rng[l] = rng.data_ptr()
-                    self._keep.append(rng)
-            for l in range(L):
-                lik = getattr(model, model.name_hidden_layer_likelihood + str(l))
-                segs.append((lik.raw_noise, off, 1))
-                off += 1
-            flat = ctypes.c_int64()
-            _lib.check(lib.mobocmf_tiny_flat_len(ctypes.byref(T), ctypes.byref(flat)), "mobocmf_tiny_flat_len")
-            assert flat.value == off, (flat.value, off)
-            wb = ctypes.c_size_t()
-            _lib.check(getattr(lib, self._work_bytes_fn)(ctypes.byref(T), ctypes.byref(wb)), self._work_bytes_fn)
-            # MOBOCMF_POISON (as functional._scratch): NaN-filled workspace, so a read of anything the launch did not write shows
-            work = torch.full((wb.value // 8,), float("nan") if os.environ.get("MOBOCMF_POISON") else 0.0,
-                              dtype=torch.float64, device=dev)
-            ea, eq = torch.zeros(off, dtype=torch.float64, device=dev), torch.zeros(off, dtype=torch.float64, device=dev)
-            self._work.append(work)
+            # (scale: what turns the launch's loss into -ELBO -- the inverse of kl_scale)
+            scale = 1.0 if prep is not None else float(num_data[i]) / N
+            self._natural += [(i, l, self.num_layers + l, Ml, om, oL, scale) for l, Ml, om, oL in desc.natural]
+            self.num_layers += L
+            self._keep += desc.keep
+            self._segments.append(desc.segments)
+            self._work.append(desc.allocate(self.kernel, dev))
+            ea, eq = (torch.zeros(desc.flat_len, dtype=torch.float64, device=dev) for _ in range(2))
             self.exp_avg.append(ea)
             self.exp_avg_sq.append(eq)
-            T.work, T.adam_m, T.adam_v = work.data_ptr(), ea.data_ptr(), eq.data_ptr()
+            T.adam_m, T.adam_v = ea.data_ptr(), eq.data_ptr()
             T.steps_done = self.steps_done[i:i + 1].data_ptr()
             T.out = self.losses[i].data_ptr()
             T.info = self.infos[i].data_ptr()
-            if want_grad or any(k[0] == i for k in self._natural):
-                gflat = torch.zeros(off, dtype=torch.float64, device=dev)
+            if want_grad or desc.natural:
+                gflat = torch.zeros(desc.flat_len, dtype=torch.float64, device=dev)
                 if want_grad:
                     self.grads.append(gflat)
                 self._gflat[i] = gflat
                 T.grad = gflat.data_ptr()
-            self._segments.append(segs)
-        raw = bytes(self.host)
-        self._dev_table = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(dev)
         self._snap = None
         self._setup_natgrad()
-        self._order_after_setup()
+        self._upload()
 
     def _setup_natgrad(self):
         """The records of the second launch (functional.NatGradSmallLayers): every natural-gradient layer's m / L_S, their
@@ -326,31 +448,13 @@ class TinyELBOStep:
             self.skipped = self.natgrad_words[0].cpu().tolist()
         return list(self.skipped)
 
-    def _order_after_setup(self):
-        """Everything above was allocated, zero-filled and uploaded on the CURRENT stream; the launches run on ``self.stream``.
-        Without this edge a fill kernel could still be pending when the first launch starts (found with a cooperative launch
-        whose arrival counters were zeroed under it: tools/coop_concurrency_probe.py)."""
-        self.stream.wait_stream(torch.cuda.current_stream(self.device))
-
-    # ------------------------------------------------------------------ the kernel this class drives
-    _work_bytes_fn = "mobocmf_tiny_work_bytes"
-
-    @staticmethod
-    def _eligible(model, x, fid, force):
-        return eligible(model, x, fid, speed_rule=not force)
-
     # ------------------------------------------------------------------ the step
     def _launch(self, mode):
-        """mode: 0 gradients only, 1 the step, 2 forward only (mobocmf_tiny_elbo_step's do_update)."""
-        lib = _lib.require_device()
-        _lib.check(lib.mobocmf_tiny_elbo_step(ctypes.cast(self.host, ctypes.c_void_p), ctypes.c_void_p(self._dev_table.data_ptr()),
-                                              len(self.models), self.lr, self.betas[0], self.betas[1], self.eps,
-                                              int(mode), ctypes.c_void_p(self.stream.cuda_stream)),
-                   "mobocmf_tiny_elbo_step")
+        self.kernel.launch(self, mode, self.lr, self.betas[0], self.betas[1], self.eps)
 
     def step(self):
         """Enqueues one step of every model on ``self.stream``."""
-        self._launch(1)
+        self._launch(_lib.STEP_UPDATE)
         self._natgrad_launch()
         return self.losses
 
@@ -358,7 +462,7 @@ class TinyELBOStep:
         """-ELBO and its raw-parameter gradients at the current parameters, no update (``want_grad=True``): per model a dict
         parameter -> gradient tensor of its shape."""
         assert self.grads, "construct with want_grad=True"
-        self._launch(0)
+        self._launch(_lib.STEP_GRADIENTS)
         self.stream.synchronize()
         return [{p: self.grads[i][off:off + n].reshape(p.shape) for p, off, n in segs} for i, segs in enumerate(self._segments)]
 
@@ -371,19 +475,6 @@ class TinyELBOStep:
         return self.losses[:, 1]
 
     # ------------------------------------------------------------------ verdicts / roll-back (as GraphedELBOStep)
-    def in_launch_sync(self):
-        """The counters and status word of the launches' in-launch waits (functional.InLaunchSync), made on first use; None
-        for a kernel without such waits."""
-        sync = self.__dict__.get("sync")
-        if sync is None:
-            sync = self.sync = self._new_sync()
-            if sync is not None:
-                self._order_after_setup()      # (zero-filled on the current stream)
-        return sync
-
-    def _new_sync(self):
-        return None
-
     def check(self):
         """Synchronising: raises if a launch since the last check gave up an in-launch wait (functional.InLaunchWaitAbandoned),
         a Cholesky of the last step failed or a loss is not finite."""
@@ -463,7 +554,7 @@ def _ptrs(vals):
 
 class TinyConditionedStep(TinyELBOStep):
     """One iteration of the conditioned training (blackbox_mfdgp_fitter.py:245-354: fresh x~ ~ U[0,1]^(n_tilde x d), the joint
-    loss over ALL surrogates, one Adam) in ONE launch instead of ~180 (mobocmf_tiny_elbo_step mode 4: every model on [Pareto
+    loss over ALL surrogates, one Adam) in ONE launch instead of ~180 (mobocmf_tiny_elbo_step MOBOCMF_STEP_COUPLED: every model on [Pareto
     set | x~ | its batch], x~ drawn in the launch; after the forward the models' workgroups meet at a barrier and each forms
     the theta / omega factor gradients of its model from all models' top-layer moments), or, ``one_launch = False``, in
     3 + n_con: forward-only launch, mobocmf_cond_factors_forward for the theta factors of every constraint and for the omega
@@ -548,7 +639,7 @@ class TinyConditionedStep(TinyELBOStep):
         self._setup_coupling(front, thr, log_e, log_1me)
 
     def _setup_coupling(self, front, thr, log_e, log_1me):
-        """mobocmf_tiny_coupling for the one-launch iteration (mode 4) and every model's role in it; the descriptor table is
+        """mobocmf_tiny_coupling for the one-launch iteration (STEP_COUPLED) and every model's role in it; the descriptor table is
         uploaded again with those fields set."""
         cp = _lib.TinyCoupling()
         cp.n_obj, cp.n_con, cp.P, cp.T = len(self._obj), len(self._con), self.P, self.T
@@ -566,8 +657,7 @@ class TinyConditionedStep(TinyELBOStep):
         self._coupling = torch.frombuffer(bytearray(bytes(cp)), dtype=torch.uint8).to(self.device)
         for k in range(len(self.models)):
             self.host[k].coupling = self._coupling.data_ptr()
-        self._dev_table = torch.frombuffer(bytearray(bytes(self.host)), dtype=torch.uint8).to(self.device)
-        self._order_after_setup()
+        self._upload()
 
     def _factors(self):
         lib = _lib.require_device()
@@ -575,9 +665,10 @@ class TinyConditionedStep(TinyELBOStep):
         for a in self._theta + [self._omega]:
             _lib.check(lib.mobocmf_cond_factors_forward(*a, st), "mobocmf_cond_factors_forward")
 
+    coupled = True
     use_graph = True      # the iteration's launch(es) replayed from one HIP graph
-    one_launch = True     # the whole iteration as ONE launch (mode 4: the factor terms formed inside, after an in-launch barrier
-    #                       of the models' workgroups); False: forward-only launch + factor launches + step launch
+    one_launch = True     # the whole iteration as ONE launch (STEP_COUPLED: the factor terms formed inside, after an in-launch
+    #                       barrier of the models' workgroups); False: forward-only launch + factor launches + step launch
 
     def _capture(self):
         """The launch(es) of an iteration captured once: every argument is static (pointers, sizes, the learning rate), x~ and
@@ -593,17 +684,18 @@ class TinyConditionedStep(TinyELBOStep):
         self._natgrad_launch()
 
     def _issue_step(self):
-        if self.one_launch and self.T <= 256 and len(self.models) <= 64:
+        most = self.kernel.max_coupled_models
+        if self.one_launch and self.T <= 256 and (most is None or len(self.models) <= most):
             try:
-                self._launch(4)
+                self._launch(_lib.STEP_COUPLED)
                 return
             except _lib.MobocmfError:
                 # refused (MOBOCMF_BAD_ARG: more models than this device keeps resident at once -- the in-launch barrier
                 # needs them all): nothing was enqueued; the three-launch form has no such requirement
                 self.one_launch = False
-        self._launch(2)
+        self._launch(_lib.STEP_FORWARD)
         self._factors()
-        self._launch(1)
+        self._launch(_lib.STEP_UPDATE)
 
     def step(self):
         if self.use_graph:
@@ -617,9 +709,9 @@ class TinyConditionedStep(TinyELBOStep):
 
     def gradients(self):
         assert self.grads, "construct with want_grad=True"
-        self._launch(2)
+        self._launch(_lib.STEP_FORWARD)
         self._factors()
-        self._launch(0)
+        self._launch(_lib.STEP_GRADIENTS)
         self.stream.synchronize()
         return [{p: self.grads[i][off:off + n].reshape(p.shape) for p, off, n in segs} for i, segs in enumerate(self._segments)]
 
@@ -635,9 +727,6 @@ class TinyConditionedStep(TinyELBOStep):
     def snapshot(self):
         super().snapshot()
         self._snap = self._snap + (None if self.xrng is None else self.xrng.clone(),)
-
-    def _new_sync(self):
-        return F.InLaunchSync(torch.zeros(2, dtype=torch.int64, device=self.device), 1, self.stream)
 
     @property
     def _barrier(self):
@@ -667,7 +756,7 @@ class _TinyMomentsFn(torch.autograd.Function):
         ctx.group = group
         ctx.save_for_backward(X.detach())
         group.x.copy_(X.detach().reshape(group.T, group.d))
-        group._launch(2)
+        group._launch(_lib.STEP_FORWARD)
         return group.moments.clone()
 
     @staticmethod
@@ -676,94 +765,58 @@ class _TinyMomentsFn(torch.autograd.Function):
         (X,) = ctx.saved_tensors
         group.x.copy_(X.reshape(group.T, group.d))      # (another evaluation may have used the group since the forward)
         group.seeds.copy_(g)
-        group._launch(3)
+        group._launch(_lib.STEP_INPUT_GRADIENTS)
         return None, group.gx.sum(0).reshape(X.shape)
 
 
-class TinyPredictGroup:
+class TinyPredictGroup(_OneLaunchGroup):
     """Predictive moments of SEVERAL fitted small models at the same T test points (eval branch, the layers' fixed
     ``samples``: MFDGP.predict_for_acquisition, mfdgp.py:237-262) in ONE launch -- mobocmf_tiny_elbo_step in its forward-only
-    mode -- and their gradient w.r.t. the test points in one more (mode 3): what an acquisition search evaluates hundreds of
-    times against constant parameters (JESMOC_MFDGP.py:137-184).  ``moments_at(X)`` -> (n_models, 2, T * S) (T for
+    mode -- and their gradient w.r.t. the test points in one more (STEP_INPUT_GRADIENTS): what an acquisition search evaluates
+    hundreds of times against constant parameters (JESMOC_MFDGP.py:137-184).  ``moments_at(X)`` -> (n_models, 2, T * S) (T for
     fidelity 0): mean and variance of the top layer's columns, WITHOUT the likelihood noise; differentiable w.r.t. X."""
 
-    _work_bytes_fn = "mobocmf_tiny_work_bytes"
-
-    @staticmethod
-    def _fits(model, fidelity, T, d):
-        return fits_predict(model, fidelity, T, d, speed_rule=False)
-
     def __init__(self, models, fidelity, T, d, stream=None):
-        lib = _lib.require_device()
-        self.models, self.fidelity, self.T, self.d = list(models), fidelity, int(T), int(d)
-        n = len(self.models)
-        dev = next(self.models[0].parameters()).device
-        self.device = dev
-        L = fidelity + 1
-        self.S = self.models[0].num_samples_for_acquisition if L > 1 else 1
+        _lib.require_device()
+        models = list(models)
+        dev = next(models[0].parameters()).device
+        self._new_table(models, dev)
+        self.fidelity, self.T, self.d = fidelity, int(T), int(d)
+        n, L = len(models), fidelity + 1
+        self.S = models[0].num_samples_for_acquisition if L > 1 else 1
         ncol = self.T * self.S
         self.x = torch.zeros(self.T, d, dtype=torch.float64, device=dev)
         self.moments = torch.zeros(n, 2, ncol, dtype=torch.float64, device=dev)
         self.seeds = torch.zeros(n, 2, ncol, dtype=torch.float64, device=dev)
         self.gx = torch.zeros(n, self.T, d, dtype=torch.float64, device=dev)
-        self.host = (_lib.TinyModel * n)()
-        self._keep = []
         zrow = torch.zeros(self.T, dtype=torch.float64, device=dev)
         nofid = torch.full((self.T,), -1.0, dtype=torch.float64, device=dev)      # no row is scored: moments only
         self._keep += [zrow, nofid]
-        for i, model in enumerate(self.models):
-            if not self._fits(model, fidelity, self.T, d) or \
+        for i, model in enumerate(models):
+            if not fits_predict(model, fidelity, self.T, d, speed_rule=False, kernel=self.kernel) or \
                     (L > 1 and model.num_samples_for_acquisition != self.S):
-                raise _lib.MobocmfError("TinyPredictGroup: model %d does not fit the one-launch kernel" % i)
-            layers = model._layers()[:L]
+                raise _lib.MobocmfError("%s: model %d does not fit the one-launch kernel" % (type(self).__name__, i))
             Tm = self.host[i]
-            Tm.L, Tm.M, Tm.d, Tm.S, Tm.N = L, layers[0].variational_strategy._inducing_points.shape[0], d, self.S, self.T
-            Tm.branch = 1
-            Zx = layers[0].variational_strategy._inducing_points.detach().contiguous()
-            Tm.x, Tm.y, Tm.fid, Tm.Zx = self.x.data_ptr(), zrow.data_ptr(), nofid.data_ptr(), Zx.data_ptr()
-            Tm.kl_scale, Tm.jitter = 0.0, layers[0].variational_strategy.jitter_val
-            self._keep.append(Zx)
-            for l, layer in enumerate(layers):
-                vd = layer.variational_strategy._variational_distribution
-                lik = getattr(model, model.name_hidden_layer_likelihood + str(l))
-                Tm.rows[l] = self.T
-                for s, p in enumerate(_hyper_params(layer)):
-                    Tm.raw[l][s] = p.data_ptr()
-                Tm.m[l], Tm.L_S[l] = vd.variational_mean.data_ptr(), vd.chol_variational_covar.data_ptr()
-                Tm.raw_noise[l] = lik.raw_noise.data_ptr()
-                Tm.noise_lo[l], Tm.noise_hi[l] = lik.raw_noise_constraint.lower_bound, lik.raw_noise_constraint.upper_bound
-                if l:      # eval_mode's draws: the layer's fixed samples, tiled over the test points (mfdgp_hidden_layer.py:263-270)
-                    e = layer.samples.reshape(-1).to(torch.float64).repeat(self.T).contiguous()
-                    Tm.eps[l] = e.data_ptr()
-                    self._keep.append(e)
-            flat, wb = ctypes.c_int64(), ctypes.c_size_t()
-            _lib.check(lib.mobocmf_tiny_flat_len(ctypes.byref(Tm), ctypes.byref(flat)), "mobocmf_tiny_flat_len")
-            _lib.check(getattr(lib, self._work_bytes_fn)(ctypes.byref(Tm), ctypes.byref(wb)), self._work_bytes_fn)
-            work = torch.zeros(wb.value // 8, dtype=torch.float64, device=dev)
-            dummy = torch.zeros(2, flat.value, dtype=torch.float64, device=dev)      # (never written: modes 2 / 3 only)
+            desc = Descriptor.for_prediction(Tm, model, fidelity, self.T, d)
+            Tm.x, Tm.y, Tm.fid = self.x.data_ptr(), zrow.data_ptr(), nofid.data_ptr()
+            work = desc.allocate(self.kernel, dev)
+            dummy = torch.zeros(2, desc.flat_len, dtype=torch.float64, device=dev)      # (never written: no update here)
             misc = torch.zeros(8, dtype=torch.int64, device=dev)
             out = torch.zeros(3, dtype=torch.float64, device=dev)
-            self._keep += [work, dummy, misc, out]
-            Tm.work, Tm.adam_m, Tm.adam_v = work.data_ptr(), dummy[0].data_ptr(), dummy[1].data_ptr()
+            self._keep += desc.keep + [work, dummy, misc, out]
+            Tm.adam_m, Tm.adam_v = dummy[0].data_ptr(), dummy[1].data_ptr()
             Tm.steps_done, Tm.info, Tm.out = misc.data_ptr(), misc[4:].data_ptr(), out.data_ptr()
             Tm.top_mean, Tm.top_var = self.moments[i, 0].data_ptr(), self.moments[i, 1].data_ptr()
             Tm.seed_gmean, Tm.seed_gvar, Tm.seed_scale = self.seeds[i, 0].data_ptr(), self.seeds[i, 1].data_ptr(), 1.0
             Tm.grad = self.gx[i].data_ptr()
-        self._dev_table = torch.frombuffer(bytearray(bytes(self.host)), dtype=torch.uint8).to(dev)
-
-    def _launch(self, mode):
-        lib = _lib.require_device()
-        _lib.check(lib.mobocmf_tiny_elbo_step(ctypes.cast(self.host, ctypes.c_void_p), ctypes.c_void_p(self._dev_table.data_ptr()),
-                                              len(self.models), 0.0, 0.9, 0.999, 1e-8, int(mode),
-                                              ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)),
-                   "mobocmf_tiny_elbo_step")
+        self._upload()
 
     def moments_at(self, X):
         X = X.reshape(self.T, self.d)
         if X.requires_grad and torch.is_grad_enabled():
             return _TinyMomentsFn.apply(self, X)
         self.x.copy_(X.detach())
-        self._launch(2)
+        self._launch(_lib.STEP_FORWARD)
         return self.moments.clone()
 
     def noise(self, refresh=False):

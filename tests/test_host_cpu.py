@@ -326,10 +326,11 @@ def test_tiny_step_descriptor_layout_and_argument_checks():
     arr = (_lib.TinyModel * 1)(T)
     host = ctypes.cast(arr, ctypes.c_void_p)
     step = lambda n, mode, h=host: lib.mobocmf_tiny_elbo_step(h, host, n, 1e-3, 0.9, 0.999, 1e-8, mode, None)
-    assert step(1, 1) == _lib.BAD_ARG              # no pointers set
-    assert step(0, 1) == _lib.BAD_ARG and step(1, 3) == _lib.BAD_ARG and step(1, 1, None) == _lib.BAD_ARG
+    assert step(1, _lib.STEP_UPDATE) == _lib.BAD_ARG              # no pointers set
+    assert step(0, _lib.STEP_UPDATE) == _lib.BAD_ARG and step(1, _lib.STEP_INPUT_GRADIENTS) == _lib.BAD_ARG
+    assert step(1, _lib.STEP_UPDATE, None) == _lib.BAD_ARG
     arr[0].M = 33                                  # beyond MOBOCMF_TINY_MAX_M
-    assert step(1, 1) == _lib.BAD_ARG
+    assert step(1, _lib.STEP_UPDATE) == _lib.BAD_ARG
 
 
 def test_coop_step_argument_checks_are_made_on_the_host():
@@ -358,16 +359,54 @@ def test_coop_step_argument_checks_are_made_on_the_host():
     host = ctypes.cast(arr, ctypes.c_void_p)
     sync = (ctypes.c_int64 * 32)()
     used = ctypes.c_int32(-7)
-    step = lambda n=1, wgs=0, mode=1, h=host, sw=sync: lib.mobocmf_coop_elbo_step(
+    step = lambda n=1, wgs=0, mode=_lib.STEP_UPDATE, h=host, sw=sync: lib.mobocmf_coop_elbo_step(
         h, host, n, wgs, ctypes.cast(sw, ctypes.c_void_p) if sw is not None else None, 1e-3, 0.9, 0.999, 1e-8, mode,
         ctypes.byref(used), None)
     assert step() == _lib.BAD_ARG                  # a descriptor without pointers
     assert step(n=0) == _lib.BAD_ARG and step(wgs=65) == _lib.BAD_ARG and step(wgs=-1) == _lib.BAD_ARG
     assert step(mode=5) == _lib.BAD_ARG and step(mode=-1) == _lib.BAD_ARG
     # MOBOCMF_STEP_CHAIN_VALID goes with the forward-only and the input-gradient mode only
-    for m in (0, 1, 4):
+    for m in (_lib.STEP_GRADIENTS, _lib.STEP_UPDATE, _lib.STEP_COUPLED):
         assert step(mode=m | _lib.STEP_CHAIN_VALID) == _lib.BAD_ARG, m
     assert step(h=None) == _lib.BAD_ARG and step(sw=None) == _lib.BAD_ARG
+    # a descriptor with EVERY pointer set (to host memory nobody reads: each call below is refused before a launch), which
+    # both entry points check with the same functions: the rows of a layer exceed those of the layer below; a coupled call
+    # whose role index is beyond the 8 objectives / constraints, or whose models do not share one coupling record
+    mem = (ctypes.c_double * 8)()
+    ptr = ctypes.addressof(mem)
+    G = _lib.TinyModel()
+    G.L, G.M, G.d, G.S, G.N = 2, 20, 2, 1, 30
+    G.rows[0], G.rows[1] = 30, 10
+    for name in ("x", "y", "fid", "Zx", "adam_m", "adam_v", "steps_done", "work", "grad", "out", "info", "seed_gmean",
+                 "seed_gvar", "top_mean", "top_var", "coupling"):
+        setattr(G, name, ptr)
+    for l in range(2):
+        G.m[l] = G.L_S[l] = G.raw_noise[l] = G.rng[l] = ptr
+        for s in range(7):
+            G.raw[l][s] = ptr
+    G.role, G.role_index = 1, 0
+
+    def refused(models, mode):
+        arr = (_lib.TinyModel * len(models))(*models)
+        h = ctypes.cast(arr, ctypes.c_void_p)
+        n = len(models)
+        return [lib.mobocmf_tiny_elbo_step(h, h, n, 1e-3, 0.9, 0.999, 1e-8, mode, None),
+                lib.mobocmf_coop_elbo_step(h, h, n, 0, ctypes.cast(sync, ctypes.c_void_p), 1e-3, 0.9, 0.999, 1e-8, mode,
+                                           ctypes.byref(used), None)] == [_lib.BAD_ARG] * 2
+
+    # control: G itself is a descriptor the size queries accept (a launch cannot be tried here), and each case below differs
+    # from G in ONE field
+    assert lib.mobocmf_tiny_work_bytes(ctypes.byref(G), ctypes.byref(wb)) == _lib.OK
+    assert lib.mobocmf_coop_work_bytes(ctypes.byref(G), ctypes.byref(wb)) == _lib.OK
+    B = _lib.TinyModel.from_buffer_copy(G)
+    B.rows[1] = 31
+    assert refused([B], _lib.STEP_UPDATE) and refused([B], _lib.STEP_COUPLED)
+    B = _lib.TinyModel.from_buffer_copy(G)
+    B.role_index = 8
+    assert refused([B], _lib.STEP_COUPLED) and refused([G, B], _lib.STEP_COUPLED)
+    B = _lib.TinyModel.from_buffer_copy(G)
+    B.coupling = ptr + 8
+    assert refused([G, B], _lib.STEP_COUPLED)
     assert used.value == -7                        # nothing was chosen, nothing launched
 
 

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """One-launch step (mobocmf_tiny_elbo_step) vs the layer path (HIP-graph replay) for ONE surrogate over the sizes the
-one-launch step accepts: where it stops paying (util/tiny_step.py MAX_COLUMNS).  Usage: python tools/tiny_sweep.py"""
+one-launch step accepts: where it stops paying (util/tiny_step.py TINY.max_columns).  Usage: python tools/tiny_sweep.py"""
 import os
 import sys
 import time
@@ -12,7 +12,7 @@ from mobocmf_amd.mlls import VariationalELBOMF  # noqa: E402
 from mobocmf_amd.util import synthetic, tiny_step  # noqa: E402
 from mobocmf_amd.util.graphed_step import GraphedELBOStep  # noqa: E402
 
-tiny_step.MAX_COLUMNS = 1 << 20
+tiny_step.TINY.max_columns = 1 << 20
 dev = torch.device("cuda")
 CASES = [(1, 2, 16, 16, 1), (1, 2, 16, 16, 4), (2, 2, 16, 64, 4), (2, 2, 16, 256, 2), (4, 2, 24, 24, 4), (4, 2, 32, 32, 1), (4, 2, 32, 64, 4), (4, 2, 32, 128, 4),
          (4, 2, 32, 256, 4), (4, 2, 32, 512, 4), (8, 3, 32, 256, 8), (8, 3, 32, 1024, 8)]
