@@ -34,7 +34,7 @@ def blackboxes():
 
 
 def run(epochs=300, cond_iters=200, acq_iters=50, n_low=14, n_high=6, grid=100, seed=0, device="cuda", verbose=True,
-        data=None, model_kwargs=None):
+        data=None, model_kwargs=None, acq_search="host"):
     rng = np.random.default_rng(seed)
     torch.manual_seed(seed)
     np.random.seed(seed)
@@ -56,7 +56,7 @@ def run(epochs=300, cond_iters=200, acq_iters=50, n_low=14, n_high=6, grid=100, 
     fitter.sample_and_store_pareto_solution()
     t.append(time.perf_counter())
     fitter.num_epochs_2 = cond_iters
-    acq = JESMOC_MFDGP(model=fitter, num_fidelities=2,
+    acq = JESMOC_MFDGP(model=fitter, num_fidelities=2, search=acq_search,
                        standard_bounds=torch.tensor([[0.0, 0.0], [1.0, 1.0]], dtype=torch.float64, device=device))
     torch.cuda.synchronize(); t.append(time.perf_counter())
     for f in range(2):

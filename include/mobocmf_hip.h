@@ -859,6 +859,52 @@ int mobocmf_natgrad_small_step(const mobocmf_natgrad_small_layer* host_layers, c
                                int32_t n_layers, double gamma, double gamma_init, int32_t warmup_steps,
                                mobocmf_stream_t stream);
 
+/* ---- The acquisition search on the device (csrc/acq_search.hip): the glue between the two one-launch model evaluations of an
+ * iterate (mobocmf_tiny_elbo_step / mobocmf_coop_elbo_step, MOBOCMF_STEP_FORWARD then MOBOCMF_STEP_INPUT_GRADIENTS, over a predict
+ * group whose models 2p / 2p + 1 are the unconditioned / conditioned surrogate of black-box p) and the selection of restarts and
+ * winner -- the loop of optimize_acqf at mobocmf/acquisition_functions/JESMOC_MFDGP.py:137-184 with no host in it.  Each entry
+ * point is ONE launch on `stream`, has no atomics and a fixed summation order (two calls on the same inputs are bitwise equal),
+ * allocates nothing, reads nothing on the host and keeps no state: capturable.  A bad argument is refused with MOBOCMF_BAD_ARG
+ * on the host, before any HIP call. */
+#define MOBOCMF_ACQ_MAX_PAIRS 32
+#define MOBOCMF_ACQ_MAX_COLUMNS (1 << 24) /* T * S */
+#define MOBOCMF_TOPK_MAX_K 64
+#define MOBOCMF_TOPK_MAX_N 4096
+
+/* JES of every test point from the group's raw top-layer moments (JESMOC_MFDGP.py:38-52 over mfdgp.py:237-262).
+ *   moments  (2 n_pairs, 2, T S): per model its means then its variances WITHOUT noise, column t S + s
+ *   noise    (2 n_pairs): the models' likelihood noise tau
+ *   per model and test point, mbar = (1/S) sum_s mu_s:  v = (1/S) sum_s (var_s + tau + mu_s^2) - mbar^2   (S = 1: var + tau)
+ *   acq[t] = sum_p 0.5 max(log v_{2p} - log v_{2p+1}, 0), summed in the order of p
+ * want_seeds = 1: seeds (the layout of moments) = d (sum_t acq[t]) / d (raw mean, raw variance):  d a / d v_u = 0.5 / v_u and
+ *   d a / d v_c = -0.5 / v_c where log v_u - log v_c >= 0, else 0 (equality passes, as torch.clamp's backward);
+ *   d v / d var_s = 1 / S;  d v / d mu_s = 2 (mu_s - mbar) / S.
+ * track = 1: wherever acq[t] > best_v[t] (strict; a NaN never wins) best_v[t] = acq[t] and row t of best_x (T x d) = row t of
+ *   the iterate x (T x d); the caller fills best_v with -inf before the first call.
+ * MOBOCMF_BAD_ARG: moments, noise or acq NULL; n_pairs outside 1..MOBOCMF_ACQ_MAX_PAIRS; T < 1; S < 1; T S >
+ * MOBOCMF_ACQ_MAX_COLUMNS; a flag other than 0 / 1; want_seeds with seeds NULL; track with x, best_v or best_x NULL or d
+ * outside 1..MOBOCMF_MAX_D. */
+int mobocmf_jes_group_forward(const double* moments, const double* noise, int32_t n_pairs, int32_t T, int32_t S,
+                              double* acq, int32_t want_seeds, double* seeds, int32_t track, const double* x, int32_t d,
+                              double* best_v, double* best_x, mobocmf_stream_t stream);
+
+/* One projected Adam ASCENT step on the iterate x (T x d): g[t][j] = -sum_i gx[i][t][j] over the n_models slices of the group's
+ * input gradients gx (n_models, T, d) in the order of i, then the update of mobocmf_adam_multi (the same expressions in the same
+ * order: with n_models = 1 the same bits) with the bias corrections of step steps_done[0] + 1, then x[t][j] clamped to
+ * [lo[j], hi[j]].  steps_done is ONE device int64 (completed steps); the launch is one workgroup and advances it itself.
+ * MOBOCMF_BAD_ARG: a NULL pointer; n_models outside 1..2 MOBOCMF_ACQ_MAX_PAIRS; T outside 1..MOBOCMF_TOPK_MAX_N; d outside
+ * 1..MOBOCMF_MAX_D. */
+int mobocmf_ascent_adam_step(double* x, const double* gx, int32_t n_models, int32_t T, int32_t d, const double* lo,
+                             const double* hi, double* exp_avg, double* exp_avg_sq, double lr, double beta1, double beta2,
+                             double eps, int64_t* steps_done, mobocmf_stream_t stream);
+
+/* The k largest of vals (n), in descending order, ties to the lower index, NaN after every number: out_vals (k), out_idx (k,
+ * int64) and, with x (n x d) given, the selected rows in out_x (k x d) (x and out_x both or neither; they must not overlap).
+ * MOBOCMF_BAD_ARG: vals, out_vals or out_idx NULL; k outside 1..MOBOCMF_TOPK_MAX_K; n < k; n > MOBOCMF_TOPK_MAX_N; only one of
+ * x / out_x given; with x, d outside 1..MOBOCMF_MAX_D. */
+int mobocmf_select_topk(const double* vals, int32_t n, int32_t k, const double* x, int32_t d, double* out_vals,
+                        int64_t* out_idx, double* out_x, mobocmf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -200,7 +200,11 @@ SYMBOLS = {
     "mobocmf_natgrad_step": [_I32, _I32, _P, _P, _P, _P, _D, _D, _I32, _D, _P, _P, _P, _P, _SZ, ctypes.POINTER(Tuning), _P],
     "mobocmf_natgrad_small_work_bytes": [_I32, ctypes.POINTER(_SZ)],
     "mobocmf_natgrad_small_step": [_P, _P, _I32, _D, _D, _I32, _P],
+    "mobocmf_jes_group_forward": [_P, _P, _I32, _I32, _I32, _P, _I32, _P, _I32, _P, _I32, _P, _P, _P],
+    "mobocmf_ascent_adam_step": [_P, _P, _I32, _I32, _I32, _P, _P, _P, _P, _D, _D, _D, _D, _P, _P],
+    "mobocmf_select_topk": [_P, _I32, _I32, _P, _I32, _P, _P, _P, _P],
 }
+ACQ_MAX_PAIRS, TOPK_MAX_K, TOPK_MAX_N = 32, 64, 4096      # MOBOCMF_ACQ_MAX_PAIRS / MOBOCMF_TOPK_MAX_K / MOBOCMF_TOPK_MAX_N
 NATGRAD_MAX_M, NATGRAD_MAX_LAYERS = 1024, 4      # MOBOCMF_NATGRAD_MAX_M, layers per mobocmf_natgrad_step call
 NATGRAD_SMALL_MAX_M = 128                        # MOBOCMF_NATGRAD_SMALL_MAX_M
 MAX_D, MAX_XDIV = 32, 48        # MOBOCMF_MAX_D / MOBOCMF_MAX_XDIV of include/mobocmf_hip.h

@@ -1,0 +1,189 @@
+// The device side of the acquisition search (JESMOC_MFDGP(search="device"), util/acq_search.py): what stands between the two
+// one-launch model evaluations of an iterate -- the JES value of every test point from the predict group's raw moments with its
+// gradient w.r.t. those moments and the best-iterate tracking, the projected Adam ascent step on the iterate -- and the
+// selection of the k best of n values (the restarts among the raw candidates, the winner among the restarts).
+//
+// All three are latency-bound glue on a few hundred to a few thousand doubles: each is ONE launch, has no atomics and sums in a
+// fixed order (two calls on the same inputs are bitwise equal), reads nothing on the host and keeps no state: capturable.
+#include "common.h"
+
+#define CHECK_LAUNCH() (hipGetLastError() == hipSuccess ? MOBOCMF_OK : MOBOCMF_HIP_ERROR)
+#define AS_BLOCK 256
+#define AS_JES_BLOCK 64        // test points per workgroup of the JES kernel (T = 200 raw candidates: four workgroups)
+#define AS_WAVE 64
+
+namespace {
+
+// v of one model at test point t (TinyPredictGroup.acquisition_moments): the moments over the S samples of mean_s, var_s + tau;
+// mbar: the mean over the samples (what the seeds need).
+__device__ __forceinline__ double as_model_v(const double* __restrict__ mean, const double* __restrict__ var, double tau,
+                                             int64_t c0, int S, double* mbar) {
+    if (S == 1) {
+        *mbar = mean[c0];
+        return var[c0] + tau;
+    }
+    double sm = 0.0, s2 = 0.0;
+    for (int s = 0; s < S; ++s) {
+        const double m = mean[c0 + s];
+        sm += m;
+        s2 += (var[c0 + s] + tau) + m * m;
+    }
+    sm /= S;
+    *mbar = sm;
+    return s2 / S - sm * sm;
+}
+
+__global__ void __launch_bounds__(AS_JES_BLOCK)
+jes_group_kernel(const double* __restrict__ moments, const double* __restrict__ noise, int n_pairs, int T, int S,
+                 double* __restrict__ acq, double* __restrict__ seeds, const double* __restrict__ x, int d,
+                 double* __restrict__ best_v, double* __restrict__ best_x) {
+    const int t = blockIdx.x * AS_JES_BLOCK + threadIdx.x;
+    if (t >= T) return;
+    const int64_t ncol = (int64_t)T * S, c0 = (int64_t)t * S;
+    const double inv_s = 1.0 / S;
+    double a = 0.0;
+    for (int p = 0; p < n_pairs; ++p) {
+        const double* mu_u = moments + (int64_t)(2 * p) * 2 * ncol;      // model 2p: (mean | variance), ncol each
+        const double* mu_c = mu_u + 2 * ncol;                            // model 2p + 1
+        double bar_u, bar_c;
+        const double vu = as_model_v(mu_u, mu_u + ncol, noise[2 * p], c0, S, &bar_u);
+        const double vc = as_model_v(mu_c, mu_c + ncol, noise[2 * p + 1], c0, S, &bar_c);
+        const double diff = log(vu) - log(vc);
+        a += 0.5 * (diff < 0.0 ? 0.0 : diff);      // (a NaN stays a NaN, as torch.clamp)
+        if (seeds) {
+            // torch.clamp's backward: the gradient passes where diff >= 0 (a NaN passes nothing)
+            const double gu = diff >= 0.0 ? 0.5 / vu : 0.0, gc = diff >= 0.0 ? -0.5 / vc : 0.0;
+            double* su = seeds + (int64_t)(2 * p) * 2 * ncol;
+            double* sc = su + 2 * ncol;
+            for (int s = 0; s < S; ++s) {
+                su[c0 + s] = gu * (2.0 * (mu_u[c0 + s] - bar_u) / S);
+                su[ncol + c0 + s] = gu * inv_s;
+                sc[c0 + s] = gc * (2.0 * (mu_c[c0 + s] - bar_c) / S);
+                sc[ncol + c0 + s] = gc * inv_s;
+            }
+        }
+    }
+    acq[t] = a;
+    if (best_v && a > best_v[t]) {      // strict; a NaN never wins
+        best_v[t] = a;
+        for (int j = 0; j < d; ++j) best_x[(int64_t)t * d + j] = x[(int64_t)t * d + j];
+    }
+}
+
+// One workgroup.  Every thread reads the step count, the workgroup meets, thread 0 advances it: no trailing launch.
+__global__ void __launch_bounds__(AS_BLOCK)
+ascent_adam_kernel(double* __restrict__ x, const double* __restrict__ gx, int n_models, int n, int d,
+                   const double* __restrict__ lo, const double* __restrict__ hi, double* __restrict__ m,
+                   double* __restrict__ v, double lr, double b1, double b2, double eps, int64_t* steps_done) {
+#pragma clang fp contract(off)      // (nothing below is fused but what is written as a fused operation)
+    const int64_t step = steps_done[0] + 1;
+    const double bc1 = 1.0 - pow(b1, (double)step), bc2s = sqrt(1.0 - pow(b2, (double)step));
+    for (int i = threadIdx.x; i < n; i += AS_BLOCK) {
+        double s = gx[i];
+        for (int k = 1; k < n_models; ++k) s += gx[(int64_t)k * n + i];
+        // From here on the arithmetic of adam_multi_kernel (elementwise.hip), bit for bit.  Which product of a sum of two the
+        // compiler fuses is its choice per kernel; the fused operations are therefore spelled out here as that kernel has
+        // them (m: the gradient's product fused onto the rounded b1 m; v: g * round((1 - b2) g) fused onto the rounded b2 v).
+        const double gi = -s;
+        const double mi = __builtin_fma(1.0 - b1, gi, b1 * m[i]);
+        const double vi = __builtin_fma(gi, (1.0 - b2) * gi, b2 * v[i]);
+        m[i] = mi;
+        v[i] = vi;
+        double xi = x[i];
+        xi -= (lr / bc1) * mi / (sqrt(vi) / bc2s + eps);
+        const double l = lo[i % d], h = hi[i % d];
+        xi = xi < l ? l : xi;           // (a NaN stays a NaN, as torch.clamp_)
+        xi = xi > h ? h : xi;
+        x[i] = xi;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) steps_done[0] = step;
+}
+
+// The order of the selection: larger value first, ties to the lower index, NaN after every number; index -1: no element.
+__device__ __forceinline__ bool as_before(double va, int ia, double vb, int ib) {
+    if (ia < 0 || ib < 0) return ib < 0 && ia >= 0;
+    const bool na = va != va, nb = vb != vb;
+    if (na != nb) return nb;
+    if (!na && va != vb) return va > vb;
+    return ia < ib;
+}
+
+// One workgroup, k rounds: every thread finds the first element (in the order above) of its share that comes strictly after
+// the element of the previous round, a butterfly picks the wavefront's, the wavefronts' four meet in LDS.
+__global__ void __launch_bounds__(AS_BLOCK)
+select_topk_kernel(const double* __restrict__ vals, int n, int k, const double* __restrict__ x, int d,
+                   double* __restrict__ out_vals, int64_t* __restrict__ out_idx, double* __restrict__ out_x) {
+    __shared__ double red_v[AS_BLOCK / AS_WAVE];
+    __shared__ int red_i[AS_BLOCK / AS_WAVE];
+    const int lane = threadIdx.x & (AS_WAVE - 1), wave = threadIdx.x / AS_WAVE;
+    double last_v = 0.0;
+    int last_i = -1;
+    for (int r = 0; r < k; ++r) {
+        double bv = 0.0;
+        int bi = -1;
+        for (int i = threadIdx.x; i < n; i += AS_BLOCK) {
+            const double vi = vals[i];
+            if (last_i >= 0 && !as_before(last_v, last_i, vi, i)) continue;      // picked in an earlier round
+            if (as_before(vi, i, bv, bi)) { bv = vi; bi = i; }
+        }
+#pragma unroll
+        for (int off = AS_WAVE / 2; off >= 1; off >>= 1) {
+            const double ov = __shfl_xor(bv, off, AS_WAVE);
+            const int oi = __shfl_xor(bi, off, AS_WAVE);
+            if (as_before(ov, oi, bv, bi)) { bv = ov; bi = oi; }
+        }
+        __syncthreads();                 // the readers of the previous round are done with red
+        if (lane == 0) { red_v[wave] = bv; red_i[wave] = bi; }
+        __syncthreads();
+        bv = red_v[0];
+        bi = red_i[0];
+#pragma unroll
+        for (int w = 1; w < AS_BLOCK / AS_WAVE; ++w)
+            if (as_before(red_v[w], red_i[w], bv, bi)) { bv = red_v[w]; bi = red_i[w]; }
+        last_v = bv;
+        last_i = bi;                     // (k <= n: every round finds one)
+        if (threadIdx.x == 0) { out_vals[r] = bv; out_idx[r] = bi; }
+        if (out_x && bi >= 0 && (int)threadIdx.x < d) out_x[(int64_t)r * d + threadIdx.x] = x[(int64_t)bi * d + threadIdx.x];
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int mobocmf_jes_group_forward(const double* moments, const double* noise, int32_t n_pairs, int32_t T, int32_t S,
+                              double* acq, int32_t want_seeds, double* seeds, int32_t track, const double* x, int32_t d,
+                              double* best_v, double* best_x, mobocmf_stream_t stream) {
+    if (!moments || !noise || !acq || n_pairs < 1 || n_pairs > MOBOCMF_ACQ_MAX_PAIRS || T < 1 || S < 1) return MOBOCMF_BAD_ARG;
+    if ((int64_t)T * S > MOBOCMF_ACQ_MAX_COLUMNS) return MOBOCMF_BAD_ARG;
+    if (want_seeds < 0 || want_seeds > 1 || track < 0 || track > 1 || (want_seeds && !seeds)) return MOBOCMF_BAD_ARG;
+    if (track && (!x || !best_v || !best_x || d < 1 || d > MOBOCMF_MAX_D)) return MOBOCMF_BAD_ARG;
+    hipLaunchKernelGGL(jes_group_kernel, dim3((unsigned)((T + AS_JES_BLOCK - 1) / AS_JES_BLOCK)), dim3(AS_JES_BLOCK), 0,
+                       (hipStream_t)stream, moments, noise, n_pairs, T, S, acq, want_seeds ? seeds : (double*)nullptr, x,
+                       track ? d : 0, track ? best_v : (double*)nullptr, best_x);
+    return CHECK_LAUNCH();
+}
+
+int mobocmf_ascent_adam_step(double* x, const double* gx, int32_t n_models, int32_t T, int32_t d, const double* lo,
+                             const double* hi, double* exp_avg, double* exp_avg_sq, double lr, double beta1, double beta2,
+                             double eps, int64_t* steps_done, mobocmf_stream_t stream) {
+    if (!x || !gx || !lo || !hi || !exp_avg || !exp_avg_sq || !steps_done) return MOBOCMF_BAD_ARG;
+    if (n_models < 1 || n_models > 2 * MOBOCMF_ACQ_MAX_PAIRS || T < 1 || T > MOBOCMF_TOPK_MAX_N || d < 1 || d > MOBOCMF_MAX_D)
+        return MOBOCMF_BAD_ARG;
+    hipLaunchKernelGGL(ascent_adam_kernel, dim3(1), dim3(AS_BLOCK), 0, (hipStream_t)stream, x, gx, n_models, T * d, d, lo, hi,
+                       exp_avg, exp_avg_sq, lr, beta1, beta2, eps, steps_done);
+    return CHECK_LAUNCH();
+}
+
+int mobocmf_select_topk(const double* vals, int32_t n, int32_t k, const double* x, int32_t d, double* out_vals,
+                        int64_t* out_idx, double* out_x, mobocmf_stream_t stream) {
+    if (!vals || !out_vals || !out_idx || k < 1 || k > MOBOCMF_TOPK_MAX_K || n < k || n > MOBOCMF_TOPK_MAX_N)
+        return MOBOCMF_BAD_ARG;
+    if ((x != nullptr) != (out_x != nullptr) || (x && (d < 1 || d > MOBOCMF_MAX_D))) return MOBOCMF_BAD_ARG;
+    hipLaunchKernelGGL(select_topk_kernel, dim3(1), dim3(AS_BLOCK), 0, (hipStream_t)stream, vals, n, k, x, x ? d : 0, out_vals,
+                       out_idx, out_x);
+    return CHECK_LAUNCH();
+}
+
+}  // extern "C"

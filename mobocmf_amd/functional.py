@@ -1468,6 +1468,47 @@ def natgrad_small_step(layers, gamma, gamma_init, warmup_steps, stream=None):
     return table
 
 
+def _on(stream):
+    return _stream() if stream is None else ctypes.c_void_p(stream.cuda_stream)
+
+
+def jes_group_forward(moments, noise, T, S, acq, seeds=None, x=None, best_v=None, best_x=None, stream=None):
+    """mobocmf_jes_group_forward: ``acq`` (T,) = the JES value of every test point from a predict group's raw ``moments``
+    (2 n_pairs, 2, T S) and ``noise`` (2 n_pairs,); ``seeds`` given: d acq.sum() / d moments written there; ``best_v`` (T,) /
+    ``best_x`` (T, d) given: updated from the iterate ``x`` (T, d) where acq[t] > best_v[t].  One launch, everything in place,
+    only enqueues (on ``stream``, default the current one): capturable."""
+    lib = _lib.require_device()
+    track = best_v is not None
+    _lib.check(lib.mobocmf_jes_group_forward(_ptr(moments), _ptr(noise), moments.shape[0] // 2, int(T), int(S), _ptr(acq),
+                                             int(seeds is not None), _ptr(seeds), int(track), _ptr(x),
+                                             x.shape[-1] if track else 0, _ptr(best_v), _ptr(best_x), _on(stream)),
+               "mobocmf_jes_group_forward")
+    return acq
+
+
+def ascent_adam_step(x, gx, lo, hi, exp_avg, exp_avg_sq, steps_done, lr, betas=(0.9, 0.999), eps=1e-8, stream=None):
+    """mobocmf_ascent_adam_step: one projected Adam ascent step on the iterate ``x`` (T, d), in place, along
+    -gx.sum(0) of the group's input gradients ``gx`` (n_models, T, d) -- FusedAdam's update, then the clamp to [lo, hi] (d,);
+    ``steps_done``: one device int64, advanced by the launch.  One launch, only enqueues: capturable."""
+    lib = _lib.require_device()
+    _lib.check(lib.mobocmf_ascent_adam_step(_ptr(x), _ptr(gx), gx.shape[0], x.shape[0], x.shape[1], _ptr(lo), _ptr(hi),
+                                            _ptr(exp_avg), _ptr(exp_avg_sq), float(lr), float(betas[0]), float(betas[1]),
+                                            float(eps), _ptr(steps_done), _on(stream)), "mobocmf_ascent_adam_step")
+    return x
+
+
+def select_topk(vals, k, out_vals, out_idx, x=None, out_x=None, stream=None):
+    """mobocmf_select_topk: the ``k`` largest of ``vals`` (n,) into ``out_vals`` (k,) / ``out_idx`` (k,, int64) in descending
+    order, ties to the lower index, NaN last; with ``x`` (n, d) the selected rows into ``out_x`` (k, d).  One launch, only
+    enqueues: capturable."""
+    lib = _lib.require_device()
+    if out_idx.dtype != torch.int64:
+        raise _lib.MobocmfError("select_topk: out_idx must be int64")
+    _lib.check(lib.mobocmf_select_topk(_ptr(vals), vals.numel(), int(k), _ptr(x), 0 if x is None else x.shape[-1],
+                                       _ptr(out_vals), _ptr(out_idx), _ptr(out_x), _on(stream)), "mobocmf_select_topk")
+    return out_vals, out_idx
+
+
 def check_info(info):
     """Synchronising: raises if the last Cholesky reported a non-positive pivot."""
     lib = _lib.require_device()

@@ -1,0 +1,163 @@
+"""The acquisition search with no host in the loop: ``JESMOC_MFDGP(search="device")``.
+
+``optimize_acqf_multistart`` (acquisition_functions/JESMOC_MFDGP.py) drives its ~200 iterates per fidelity from Python: around
+the two one-launch model evaluations of a predict group (util/tiny_step.py TinyPredictGroup, util/coop_step.py CoopPredictGroup)
+it issues a dozen element-wise framework kernels, three copies and an optimiser launch pair, and an evaluation costs more host
+time than device time.  ``DeviceAcqSearch`` keeps the same search on the GPU (csrc/acq_search.hip): one iterate is FOUR launches
+in stream order --
+
+    group STEP_FORWARD  ->  mobocmf_jes_group_forward (value, seeds, best iterate)  ->  group STEP_INPUT_GRADIENTS  ->
+    mobocmf_ascent_adam_step (the iterate IS the group's x buffer)
+
+-- captured once as a HIP graph (a single chain, no parallel branches) and replayed; nothing is read on the host until the
+caller fetches the winner.
+"""
+import torch
+
+from .. import _lib
+from .. import functional as F
+
+
+class DeviceAcqSearch:
+    """Projected-Adam multi-start ascent of the coupled JES acquisition over ``group`` -- a TinyPredictGroup / CoopPredictGroup
+    for T = ``num_restarts`` test points whose models 2p / 2p + 1 are the unconditioned / conditioned surrogate of black-box p
+    (JESMOC_MFDGP._tiny_group) -- inside the box ``bounds`` (2, d).  ``lr`` is scaled by mean(hi - lo) as the host loop does.
+
+    ``run(x0, maxiter)`` -> device tensors (candidate (1, d), value ()), WITHOUT synchronising: X_0 ... X_maxiter are each
+    scored once, the best iterate of every restart is kept, the best of those is returned.  The first iterate of a search runs
+    eagerly (a frozen CoopPredictGroup forms its chains there, so the replayed launches carry STEP_CHAIN_VALID); the others are
+    replays of the captured iterate(s).  A cooperative group is frozen by ``run``, and a cooperative raw-candidate group by
+    ``start_from_raw`` (``self.raw_group``); neither is thawed here, because ``thaw()`` reads the status word and that read
+    synchronises.  The caller thaws BOTH once it has fetched the result (``group.thaw()`` reports an abandoned in-launch
+    wait; JESMOC_MFDGP does it for every group it built): a group left frozen keeps chains of parameters that may since have
+    changed.  ``info_words()`` are the models' Cholesky verdicts."""
+    use_graph = True          # False: the same launches issued eagerly (tests, A/B)
+    iters_per_graph = 1       # iterates unrolled into one graph (DESIGN.md 5.6 on what tools/acq_search_bench.py reports)
+
+    def __init__(self, group, bounds, num_restarts, lr, betas=(0.9, 0.999), eps=1e-8):
+        _lib.require_device()
+        if group.T != int(num_restarts) or len(group.models) % 2:
+            raise _lib.MobocmfError("DeviceAcqSearch: a group of (uncond, cond) pairs built for T = num_restarts test points")
+        if not 1 <= len(group.models) // 2 <= _lib.ACQ_MAX_PAIRS:
+            raise _lib.MobocmfError("DeviceAcqSearch: 1..%d black-boxes per group" % _lib.ACQ_MAX_PAIRS)
+        dev, T, d = group.device, group.T, group.d
+        self.group, self.T, self.d = group, T, d
+        self.lo = bounds[0].detach().to(dev, torch.float64).contiguous()
+        self.hi = bounds[1].detach().to(dev, torch.float64).contiguous()
+        self.lr = float(lr) * float((bounds[1] - bounds[0]).mean())      # (construction only: the one host read of the bounds)
+        self.betas, self.eps = (float(betas[0]), float(betas[1])), float(eps)
+        z = lambda *shape: torch.zeros(*shape, dtype=torch.float64, device=dev)
+        self.noise = group.noise().detach().clone().contiguous()
+        self.acq, self.best_v, self.best_x = z(T), z(T), z(T, d)
+        self.exp_avg, self.exp_avg_sq = z(T, d), z(T, d)
+        self.steps_done = torch.zeros(1, dtype=torch.int64, device=dev)
+        self.win_v, self.win_i, self.cand = z(1), torch.zeros(1, dtype=torch.int64, device=dev), z(1, d)
+        self._graphs, self._raw = {}, {}
+        self._capture_stream = group.stream
+
+    # ------------------------------------------------------------------ the launches
+    def _score(self, seeds):
+        """The forward launch and the JES kernel on the group's current x: acq, the best iterate so far, optionally the seeds."""
+        g = self.group
+        g._launch(_lib.STEP_FORWARD)
+        F.jes_group_forward(g.moments, self.noise, self.T, g.S, self.acq, seeds=g.seeds if seeds else None, x=g.x,
+                            best_v=self.best_v, best_x=self.best_x, stream=g.stream)
+
+    def _iterate(self):
+        """One iterate: four launches (on the group's stream; None: the current one)."""
+        g = self.group
+        self._score(seeds=True)
+        g._launch(_lib.STEP_INPUT_GRADIENTS)
+        F.ascent_adam_step(g.x, g.gx, self.lo, self.hi, self.exp_avg, self.exp_avg_sq, self.steps_done, self.lr, self.betas,
+                           self.eps, stream=g.stream)
+
+    def _graph(self, n):
+        """``n`` iterates captured once (as TinyConditionedStep._capture): every argument is static and the step count lives on
+        the device, so a replay IS the next n iterates.  The capture pass itself executes nothing."""
+        if n not in self._graphs:
+            if self._capture_stream is None:
+                self._capture_stream = torch.cuda.Stream(device=self.group.device)
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g, stream=self._capture_stream, capture_error_mode="thread_local"):
+                for _ in range(n):
+                    self._iterate()
+            self._graphs[n] = g
+        return self._graphs[n]
+
+    def _stream_ctx(self):
+        s = self.group.stream
+        return torch.cuda.stream(s if s is not None else torch.cuda.current_stream(self.group.device))
+
+    # ------------------------------------------------------------------ the search
+    def start_from_raw(self, raw_group, Xraw):
+        """Scores the raw candidates ``Xraw`` (n, d) through ``raw_group`` -- the same models for T = n test points, or for
+        T = n / c: c equal chunks, one forward launch each, where n S columns are beyond the one-launch kernels' limit -- and
+        writes the ``num_restarts`` best rows straight into the search group's x.  Returns (raw values (n,), the restarts'
+        values, their indices): device tensors of this object, overwritten by the next call.  A cooperative ``raw_group`` is
+        left frozen (see the class docstring): the caller thaws it with the search group."""
+        n, Tc = Xraw.shape[0], raw_group.T
+        if n % Tc or len(raw_group.models) != len(self.group.models) or not self.T <= n <= _lib.TOPK_MAX_N:
+            raise _lib.MobocmfError("DeviceAcqSearch: the raw candidates in equal chunks of the raw group's T test points")
+        if (n, Tc) not in self._raw:
+            dev = self.group.device
+            self._raw[(n, Tc)] = (torch.zeros(n, dtype=torch.float64, device=dev), torch.zeros(self.T, dtype=torch.float64, device=dev),
+                                  torch.zeros(self.T, dtype=torch.int64, device=dev), raw_group.noise().detach().clone().contiguous(),
+                                  torch.zeros(n, self.d, dtype=torch.float64, device=dev))
+        vals, top_v, top_i, noise, xraw = self._raw[(n, Tc)]
+        self.raw_group, self.raw_values = raw_group, vals
+        if hasattr(raw_group, "freeze"):
+            raw_group.freeze()
+        xraw.copy_(Xraw.detach().reshape(n, self.d))
+        for c in range(n // Tc):
+            raw_group.x.copy_(xraw[c * Tc:(c + 1) * Tc])
+            raw_group._launch(_lib.STEP_FORWARD)
+            F.jes_group_forward(raw_group.moments, noise, Tc, raw_group.S, vals[c * Tc:(c + 1) * Tc], stream=raw_group.stream)
+        F.select_topk(vals, self.T, top_v, top_i, x=xraw, out_x=self.group.x, stream=self.group.stream)
+        return vals, top_v, top_i
+
+    def run(self, x0=None, maxiter=200):
+        """``x0`` (num_restarts, d): the starting points (None: what ``start_from_raw`` left in the group's x)."""
+        g = self.group
+        maxiter = int(maxiter)
+        with torch.no_grad(), self._stream_ctx():
+            if x0 is not None:
+                g.x.copy_(x0.detach().reshape(self.T, self.d))
+            self.best_v.fill_(float("-inf"))
+            self.exp_avg.zero_()
+            self.exp_avg_sq.zero_()
+            self.steps_done.zero_()
+            if hasattr(g, "freeze"):
+                g.freeze()
+            left = maxiter
+            if left > 0:
+                self._iterate()
+                left -= 1
+            if self.use_graph:
+                per = max(1, int(self.iters_per_graph))
+                for n, times in ((per, left // per), (1, left % per)):
+                    if times:
+                        graph = self._graph(n)
+                        for _ in range(times):
+                            graph.replay()
+            else:
+                for _ in range(left):
+                    self._iterate()
+            self._score(seeds=False)      # X_maxiter
+            F.select_topk(self.best_v, 1, self.win_v, self.win_i, x=self.best_x, out_x=self.cand, stream=g.stream)
+            return self.cand.clone(), self.win_v[0].clone()
+
+    def info_words(self):
+        """The Cholesky verdicts of the models of the search group and of the raw-candidate group last used (int32 words, 0:
+        fine) as one device tensor; no synchronisation."""
+        raw = self.__dict__.get("raw_group")
+        return torch.cat([w.reshape(-1) for g in (self.group, raw) if g is not None for w in g.info_words])
+
+
+def raise_on_info(words, what):
+    """``words``: HOST int32 info words of one-launch models (0: fine; > 0: the failed pivot; < 0: an abandoned in-launch wait)."""
+    from ..layers.mfdgp_hidden_layer import NotPSDError
+    bad = [int(v) for v in words.reshape(-1).tolist() if int(v) != 0]
+    if bad:
+        if bad[0] < 0:
+            raise F.InLaunchWaitAbandoned("%s: in-launch barrier abandoned (info %d)" % (what, bad[0]))
+        raise NotPSDError("%s: K_mm not positive definite (pivot %d)" % (what, bad[0]))

@@ -792,6 +792,7 @@ class TinyPredictGroup(_OneLaunchGroup):
         zrow = torch.zeros(self.T, dtype=torch.float64, device=dev)
         nofid = torch.full((self.T,), -1.0, dtype=torch.float64, device=dev)      # no row is scored: moments only
         self._keep += [zrow, nofid]
+        self.info_words = []      # per model the int32 words its launches leave their Cholesky verdicts in (0: fine)
         for i, model in enumerate(models):
             if not fits_predict(model, fidelity, self.T, d, speed_rule=False, kernel=self.kernel) or \
                     (L > 1 and model.num_samples_for_acquisition != self.S):
@@ -806,6 +807,7 @@ class TinyPredictGroup(_OneLaunchGroup):
             self._keep += desc.keep + [work, dummy, misc, out]
             Tm.adam_m, Tm.adam_v = dummy[0].data_ptr(), dummy[1].data_ptr()
             Tm.steps_done, Tm.info, Tm.out = misc.data_ptr(), misc[4:].data_ptr(), out.data_ptr()
+            self.info_words.append(misc[4:].view(torch.int32))
             Tm.top_mean, Tm.top_var = self.moments[i, 0].data_ptr(), self.moments[i, 1].data_ptr()
             Tm.seed_gmean, Tm.seed_gvar, Tm.seed_scale = self.seeds[i, 0].data_ptr(), self.seeds[i, 1].data_ptr(), 1.0
             Tm.grad = self.gx[i].data_ptr()
