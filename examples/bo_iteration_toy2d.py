@@ -5,7 +5,10 @@ step on the MI355X path -- the flow of examples/example_acquisition_mfdgp_toy_2d
   fit the unconditioned MFDGPs  ->  sample a Pareto solution (RFF posterior samples + MOOP)  ->  fit the conditioned
   MFDGPs (theta / omega factors)  ->  maximise the cost-weighted JES acquisition per fidelity  ->  next (x, fidelity).
 
-    python examples/bo_iteration_toy2d.py [--epochs 300] [--seed 0]
+    python examples/bo_iteration_toy2d.py [--epochs 300] [--seed 0] [--iters K [--warm-epochs E]]
+
+With ``--warm-epochs E`` every iteration after the first starts from the previous iteration's unconditioned fit
+(``warm_start="posterior"``: hyper-parameters, q(u) and noise carried over) and trains E epochs of phase 2 only.
 """
 import argparse
 import faulthandler
@@ -34,7 +37,12 @@ def blackboxes():
 
 
 def run(epochs=300, cond_iters=200, acq_iters=50, n_low=14, n_high=6, grid=100, seed=0, device="cuda", verbose=True,
-        data=None, model_kwargs=None, acq_search="host"):
+        data=None, model_kwargs=None, acq_search="host", previous=None, warm_epochs=None):
+    """``previous`` with ``warm_epochs``: a fitter holding the UNCONDITIONED fits of the same black-boxes on ``data`` without its
+    last rows -- the acquisition's ``blackbox_mfdgp_fitter_uncond`` of the last iteration (the fitter this function returns has
+    been trained conditioned since).  Every black-box is then initialised from its predecessor with ``warm_start="posterior"``,
+    there is no phase 1 and phase 2 runs ``warm_epochs`` epochs."""
+    warm = previous is not None and warm_epochs is not None
     rng = np.random.default_rng(seed)
     torch.manual_seed(seed)
     np.random.seed(seed)
@@ -43,13 +51,17 @@ def run(epochs=300, cond_iters=200, acq_iters=50, n_low=14, n_high=6, grid=100, 
         fid = np.concatenate([np.zeros(n_low), np.ones(n_high)])
     else:
         x, fid = data
-    fitter = BlackBoxMFDGPFitter(2, x.shape[0], num_epochs_1=epochs, num_epochs_2=epochs, pareto_set_size=10,
-                                 opt_grid_size=grid, type_lengthscale=TL.MEDIAN, device=device, **(model_kwargs or {}))
+    fitter = BlackBoxMFDGPFitter(2, x.shape[0], num_epochs_1=0 if warm else epochs,
+                                 num_epochs_2=warm_epochs if warm else epochs, pareto_set_size=10, opt_grid_size=grid,
+                                 type_lengthscale=TL.MEDIAN, device=device, **(model_kwargs or {}))
     fitter.verbose = False
     for name, (lo, hi, is_con) in blackboxes().items():
         y = np.where(fid == 0, lo(x), hi(x))
+        start = {}
+        if warm:
+            start = dict(previously_trained_model=previous.get_model(name, is_constraint=is_con), warm_start="posterior")
         fitter.initialize_mfdgp(torch.from_numpy(x), torch.from_numpy(y)[:, None], torch.from_numpy(fid)[:, None], name,
-                                is_constraint=is_con)
+                                is_constraint=is_con, **start)
     t = [time.perf_counter()]
     fitter.train_mfdgps()
     torch.cuda.synchronize(); t.append(time.perf_counter())
@@ -72,16 +84,20 @@ def run(epochs=300, cond_iters=200, acq_iters=50, n_low=14, n_high=6, grid=100, 
     return fitter, acq, cand, fidelity
 
 
-def loop(iters=3, seed=0, verbose=True, **kw):
+def loop(iters=3, seed=0, verbose=True, previous=None, warm_epochs=None, **kw):
     """``iters`` BO iterations as the reference's driver script runs them (toy_synthetic_2D_JESMOCMF.py:305-470): a fresh
-    fitter on the grown data set each time, the chosen point evaluated at the chosen fidelity for every black-box."""
+    fitter on the grown data set each time, the chosen point evaluated at the chosen fidelity for every black-box.
+    ``warm_epochs``: every iteration that has a predecessor (``previous``: one for the first iteration too) starts from its
+    unconditioned fit, see ``run``."""
     rng = np.random.default_rng(seed)
     x = rng.uniform(size=(20, 2))
     fid = np.concatenate([np.zeros(14), np.ones(6)])
     history = []
     for it in range(iters):
         t0 = time.perf_counter()
-        _, _, cand, fidelity = run(seed=seed + it, data=(x, fid), verbose=False, **kw)
+        _, acq, cand, fidelity = run(seed=seed + it, data=(x, fid), verbose=False, previous=previous,
+                                     warm_epochs=warm_epochs, **kw)
+        previous = acq.blackbox_mfdgp_fitter_uncond if warm_epochs is not None else None
         x = np.vstack([x, cand.detach().cpu().numpy()[None, :]])
         fid = np.concatenate([fid, [float(fidelity)]])
         history.append((cand.detach().cpu().numpy(), fidelity, time.perf_counter() - t0))
@@ -96,8 +112,12 @@ if __name__ == "__main__":
     ap.add_argument("--epochs", type=int, default=300)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--iters", type=int, default=1, help="number of BO iterations (1 = a single, verbose iteration)")
+    ap.add_argument("--warm-epochs", type=int, default=None,
+                    help="with --iters > 1: warm-start every iteration after the first and train this many phase-2 epochs")
     a = ap.parse_args()
+    if a.warm_epochs is not None and a.iters < 2:
+        ap.error("--warm-epochs needs --iters > 1: the first iteration has no predecessor to start from")
     if a.iters > 1:
-        loop(iters=a.iters, seed=a.seed, epochs=a.epochs)
+        loop(iters=a.iters, seed=a.seed, epochs=a.epochs, warm_epochs=a.warm_epochs)
     else:
         run(epochs=a.epochs, seed=a.seed)

@@ -13,8 +13,12 @@ reference point of the hypervolume is (1000, 1000), as there.
 ``--num-inducing M`` caps the inducing points of every surrogate at M; ``--inducing greedy`` then chooses them among the
 training rows by greedy conditional variance (``inducing_selection="greedy_variance"``) instead of taking the first M rows.
 
+``--warm-start`` starts every iteration after the first from the previous iteration's unconditioned fit
+(``warm_start="posterior"``) and trains ``--warm-epochs`` epochs of phase 2 only (default: ``--epochs``).  The new inducing
+inputs must extend the old ones, which all training rows and the first M rows do and a greedy re-selection in general does not.
+
     python examples/bo_loop_hv_toy2d.py [--iters 5] [--acq jes|random] [--epochs 300] [--seed 0] [--out .]
-                                        [--num-inducing M] [--inducing first|greedy]
+                                        [--num-inducing M] [--inducing first|greedy] [--warm-start [--warm-epochs E]]
 """
 import argparse
 import faulthandler
@@ -39,16 +43,21 @@ from mobocmf_amd.util.moop import MOOP  # noqa: E402
 REF_POINT = np.array([1000.0, 1000.0])
 
 
-def fit_only(x, fid, epochs, seed, device="cuda", model_kwargs=None):
+def fit_only(x, fid, epochs, seed, device="cuda", model_kwargs=None, previous=None, warm_epochs=None):
     """The unconditioned fit of bo_iteration_toy2d.run alone: what the random baseline recommends from."""
     torch.manual_seed(seed)
-    fitter = BlackBoxMFDGPFitter(2, x.shape[0], num_epochs_1=epochs, num_epochs_2=epochs, type_lengthscale=TL.MEDIAN,
-                                 device=device, **(model_kwargs or {}))
+    warm = previous is not None and warm_epochs is not None
+    fitter = BlackBoxMFDGPFitter(2, x.shape[0], num_epochs_1=0 if warm else epochs,
+                                 num_epochs_2=warm_epochs if warm else epochs, type_lengthscale=TL.MEDIAN, device=device,
+                                 **(model_kwargs or {}))
     fitter.verbose = False
     for name, (lo, hi, is_con) in blackboxes().items():
         y = np.where(fid == 0, lo(x), hi(x))
+        start = {}
+        if warm:
+            start = dict(previously_trained_model=previous.get_model(name, is_constraint=is_con), warm_start="posterior")
         fitter.initialize_mfdgp(torch.from_numpy(x), torch.from_numpy(y)[:, None], torch.from_numpy(fid)[:, None], name,
-                                is_constraint=is_con)
+                                is_constraint=is_con, **start)
     fitter.train_mfdgps()
     return fitter
 
@@ -72,8 +81,13 @@ def score(fitter, grid):
     return hv_iter, optimal_hv, float(feasible), num_ini - num_fini, num_fini, num_ini
 
 
-def loop_hv(iters=5, acq="jes", seed=0, out_dir=".", epochs=300, verbose=True, num_inducing=None, inducing="first", **kw):
-    """``iters`` BO iterations, each one scored and appended to ``out_dir``/hypervolumes.txt; returns the rows."""
+def loop_hv(iters=5, acq="jes", seed=0, out_dir=".", epochs=300, verbose=True, num_inducing=None, inducing="first",
+            warm_start=False, warm_epochs=None, **kw):
+    """``iters`` BO iterations, each one scored and appended to ``out_dir``/hypervolumes.txt; returns the rows.
+    ``warm_start``: every iteration after the first starts from the last one's unconditioned fit, ``warm_epochs`` epochs of
+    phase 2 (default: ``epochs``)."""
+    warm_epochs = (epochs if warm_epochs is None else warm_epochs) if warm_start else None
+    previous = None
     model_kwargs = {}
     if num_inducing is not None:
         model_kwargs = dict(num_inducing=num_inducing,
@@ -93,11 +107,14 @@ def loop_hv(iters=5, acq="jes", seed=0, out_dir=".", epochs=300, verbose=True, n
     for it in range(iters):
         t0 = time.perf_counter()
         if acq == "random":
-            fitter = fit_only(x, fid, epochs, seed + it, model_kwargs=model_kwargs)
+            fitter = fit_only(x, fid, epochs, seed + it, model_kwargs=model_kwargs, previous=previous,
+                              warm_epochs=warm_epochs)
+            previous = fitter if warm_start else None
             cand, fidelity = chooser.get_nextpoint_coupled(iteration=it)
         else:
-            fitter, _, cand, fidelity = run(seed=seed + it, data=(x, fid), epochs=epochs, verbose=False,
-                                            model_kwargs=model_kwargs, **kw)
+            fitter, jes, cand, fidelity = run(seed=seed + it, data=(x, fid), epochs=epochs, verbose=False,
+                                              model_kwargs=model_kwargs, previous=previous, warm_epochs=warm_epochs, **kw)
+            previous = jes.blackbox_mfdgp_fitter_uncond if warm_start else None
         row = score(fitter, grid)
         with open(path, "a") as f:
             print("%lf %lf %lf %lf %lf %lf" % row, file=f)
@@ -120,6 +137,12 @@ if __name__ == "__main__":
     ap.add_argument("--num-inducing", type=int, default=None, help="inducing points per surrogate (default: every training row)")
     ap.add_argument("--inducing", choices=["first", "greedy"], default="first",
                     help="with --num-inducing: the first M training rows, or M rows by greedy conditional variance")
+    ap.add_argument("--warm-start", action="store_true",
+                    help="start every iteration after the first from the previous iteration's fit (warm_start='posterior')")
+    ap.add_argument("--warm-epochs", type=int, default=None,
+                    help="with --warm-start: phase-2 epochs of a warm refit (default: --epochs)")
     a = ap.parse_args()
+    if a.warm_epochs is not None and not a.warm_start:
+        ap.error("--warm-epochs needs --warm-start")
     loop_hv(iters=a.iters, acq=a.acq, seed=a.seed, out_dir=a.out, epochs=a.epochs, num_inducing=a.num_inducing,
-            inducing=a.inducing)
+            inducing=a.inducing, warm_start=a.warm_start, warm_epochs=a.warm_epochs)

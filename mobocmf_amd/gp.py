@@ -188,21 +188,28 @@ def pack_hypers_many(modules_kinds):
     return F.softplus_pack_segments([[getattr(m, n) for m, n in src] for src in srcs])
 
 
-def gram_cpu_init(covar_module, kind, X):
-    """k(X, X) on the host, ONLY for the one-time initial S of the top layer (mfdgp_hidden_layer.py:131-132)."""
-    h = pack_hypers(covar_module, kind).detach().double()
-    X = X.double()
+def gram_cpu(hyp, kind, X1, X2):
+    """k(X1, X2) in float64 on the host.  ``hyp``: the constrained hyper-parameters in the C-ABI order (``pack_hypers``): kind 0
+    [alpha, ls (d)], kind 1 [a1, af, nu, a2, lsf, ls1 (d), ls2 (d)]; kind 1 rows are [x, f].  Set-up algebra only (the initial S
+    of the top layer, the warm start's extension of q(u)): the hot path's Gram matrices come from the HIP library."""
+    h = torch.as_tensor(hyp).detach().double().cpu().reshape(-1)
+    X1, X2 = X1.double(), X2.double()
 
-    def rbf(a, ls):
-        a = a / ls
-        return torch.exp(-0.5 * ((a[:, None, :] - a[None, :, :]) ** 2).sum(-1))
+    def rbf(a, b, ls):
+        a, b = a / ls, b / ls
+        return torch.exp(-0.5 * ((a[:, None, :] - b[None, :, :]) ** 2).sum(-1))
 
     if kind == 0:
-        return h[0] * rbf(X, h[1:])
-    d = X.shape[1] - 1
-    x, f = X[:, :d], X[:, d:]
+        return h[0] * rbf(X1, X2, h[1:])
+    d = X1.shape[1] - 1
+    x1, f1, x2, f2 = X1[:, :d], X1[:, d:], X2[:, :d], X2[:, d:]
     a1, af, nu, a2, lsf = h[0], h[1], h[2], h[3], h[4]
-    return a1 * rbf(x, h[5:5 + d]) * (nu * (f @ f.T) + af * rbf(f, lsf.reshape(1))) + a2 * rbf(x, h[5 + d:])
+    return a1 * rbf(x1, x2, h[5:5 + d]) * (nu * (f1 @ f2.T) + af * rbf(f1, f2, lsf.reshape(1))) + a2 * rbf(x1, x2, h[5 + d:])
+
+
+def gram_cpu_init(covar_module, kind, X):
+    """k(X, X) on the host, ONLY for the one-time initial S of the top layer (mfdgp_hidden_layer.py:131-132)."""
+    return gram_cpu(pack_hypers(covar_module, kind), kind, X, X)
 
 
 # ------------------------------------------------------------------------------ distributions / likelihood

@@ -8,6 +8,8 @@ Extensions (documented in DESIGN.md; defaults reproduce the reference):
   * ``inducing_selection="greedy_variance"`` (with ``num_inducing``): the inducing inputs are chosen among the training rows by
     greedy conditional variance on the GPU (``functional.select_inducing``) instead of taking the first ``num_inducing`` rows.
   * more than two fidelities: Z~_l = [Z_x, m_{l-1}] for every l >= 1 (reference works for 2 only, F8).
+  * ``warm_start="posterior"`` (with ``previously_trained_model``): q(u) of every layer is carried over too, extended exactly
+    to the new inducing inputs (util/warm_start.py); the default ``"hypers"`` carries over what the reference does.
 """
 from enum import Enum
 
@@ -20,6 +22,7 @@ from torch import nn
 from .. import functional as F
 from .. import gp
 from ..layers.mfdgp_hidden_layer import MFDGPHiddenLayer
+from ..util import warm_start as ws
 from ..util.util import compute_dist, triu_indices
 
 
@@ -48,8 +51,17 @@ class MFDGP(nn.Module):
                  num_samples_for_acquisition=25, previously_trained_model=None, ini_inducing_using_layer_0=False,
                  use_only_highest_fidelity=False, init_params_to_prior_and_fix_them=False,
                  num_inducing=None, inducing_points=None, num_samples_for_training=1, median_mode="reference",
-                 inducing_selection="first", inducing_tol=0.0, inducing_device=None):
+                 inducing_selection="first", inducing_tol=0.0, inducing_device=None, warm_start="hypers"):
         super().__init__()
+        if warm_start not in ("hypers", "posterior"):
+            raise ValueError("warm_start must be 'hypers' or 'posterior', got %r" % (warm_start,))
+        if warm_start == "posterior":
+            if previously_trained_model is None:
+                raise ValueError("warm_start='posterior' needs previously_trained_model")
+            if use_only_highest_fidelity or previously_trained_model.use_only_highest_fidelity:
+                raise ValueError("warm_start='posterior' is not defined with use_only_highest_fidelity=True (the layers "
+                                 "have inducing inputs of their own)")
+        self.warm_start = warm_start
         if inducing_selection not in ("first", "greedy_variance"):
             raise ValueError("inducing_selection must be 'first' or 'greedy_variance', got %r" % (inducing_selection,))
         self.inducing_selection = inducing_selection
@@ -105,6 +117,47 @@ class MFDGP(nn.Module):
             likelihood.noise = 1e-2 * y_high_std if i == self.num_fidelities - 1 else 1e-6
             setattr(self, self.name_hidden_layer_likelihood + str(i), likelihood)
         self.variational_strategy = _DeepGPVariationalStrategy(self)
+        if warm_start == "posterior":
+            self._carry_over_posterior(previously_trained_model)
+
+    def _carry_over_posterior(self, prev):
+        """``warm_start="posterior"``: on top of what ``"hypers"`` carries over, every layer's q(u) of ``prev`` extended to
+        this model's inducing inputs (``util.warm_start.extend_qu``, layer by layer from 0 upward: the f column of layer l's
+        new inducing inputs is the extended mean of layer l - 1), its jitter, and each likelihood's noise clipped into this
+        model's interval (``util.warm_start.clip_noise``).  The layers' predictive distributions at every input and their KL
+        terms are those of ``prev``.  The carried-over values keep their precision: ``prev`` must be float64 (as in every driver)
+        and this model becomes float64 here, the kernel hyper-parameters included, which ``"hypers"`` rounds to this
+        constructor's float32."""
+        if prev.num_hidden_layers != self.num_hidden_layers:
+            raise ValueError("warm_start='posterior': the previous model has %d layers, the new one %d"
+                             % (prev.num_hidden_layers, self.num_hidden_layers))
+        if any(p.dtype != torch.float64 for p in prev.parameters()):
+            raise ValueError("warm_start='posterior' carries float64 values over bitwise: call .double() on the previous model")
+        Zx = self.hidden_layer_0.variational_strategy.Zx
+        Zx_old = prev.hidden_layer_0.variational_strategy.Zx
+        ws.check_inducing_rule(Zx_old, Zx, self.inducing_selection)
+        Zx, Zx_old = Zx.detach().double().cpu(), Zx_old.detach().double().cpu()
+        M = Zx_old.shape[0]
+        self.double()
+        f_old = f_new = None
+        with torch.no_grad():
+            for old, new in zip(prev._layers(), self._layers()):
+                new.covar_module.load_state_dict(old.covar_module.state_dict())      # again, now without the rounding
+                jitter = old.variational_strategy.jitter_val
+                new.variational_strategy.jitter_val = jitter
+                vd_old, vd = old.variational_strategy._variational_distribution, new.variational_strategy._variational_distribution
+                Z_old = Zx_old if new.kind == 0 else torch.cat((Zx_old, f_old[:, None]), 1)
+                Z_new = Zx[M:] if new.kind == 0 else torch.cat((Zx[M:], f_new[:, None]), 1)
+                m, L_S, _ = ws.extend_qu(gp.pack_hypers(old.covar_module, old.kind), new.kind, Z_old, Z_new,
+                                         vd_old.variational_mean, vd_old.chol_variational_covar, jitter)
+                vd.variational_mean.copy_(m)
+                vd.chol_variational_covar.copy_(L_S)
+                f_old, f_new = m[:M], m[M:]
+            for i in range(self.num_hidden_layers):
+                lik = getattr(self, self.name_hidden_layer_likelihood + str(i))
+                c = lik.raw_noise_constraint
+                lik.noise = ws.clip_noise(getattr(prev, prev.name_hidden_layer_likelihood + str(i)).noise.detach().double(),
+                                          c.lower_bound, c.upper_bound)
 
     # ------------------------------------------------------------------ init heuristics
     def clip_inducing_values(self, x_0, x_1, y_1):

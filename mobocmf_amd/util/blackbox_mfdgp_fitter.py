@@ -114,13 +114,14 @@ class MFDGPHandler:
 
     def __init__(self, x_train, y_train, fidelities_train, num_fidelities, batch_size, type_lengthscale,
                  previously_trained_model=None, init_params_to_prior_and_fix_them=False,
-                 use_only_highest_fidelity=False, device="cuda", **model_kwargs):
+                 use_only_highest_fidelity=False, device="cuda", warm_start="hypers", **model_kwargs):
         if model_kwargs.get("inducing_selection", "first") != "first":
             model_kwargs.setdefault("inducing_device", device)     # the selection runs where the model will live
         self.mfdgp = MFDGP(x_train, y_train, fidelities_train, num_fidelities=num_fidelities,
                            type_lengthscale=type_lengthscale, previously_trained_model=previously_trained_model,
                            use_only_highest_fidelity=use_only_highest_fidelity,
-                           init_params_to_prior_and_fix_them=init_params_to_prior_and_fix_them, **model_kwargs)
+                           init_params_to_prior_and_fix_them=init_params_to_prior_and_fix_them, warm_start=warm_start,
+                           **model_kwargs)
         self.mfdgp.double()  # float64 end to end, as the reference (:32)
         self.mfdgp.to(device)
         self.elbo = VariationalELBOMF(self.mfdgp, x_train.shape[-2], num_fidelities=num_fidelities)
@@ -193,9 +194,13 @@ class BlackBoxMFDGPFitter:
 
     def initialize_mfdgp(self, x_train, y_train, fidelities, blackbox_name, threshold_constraint=0.0,
                          is_constraint=False, previously_trained_model=None,
-                         init_params_to_prior_and_fix_them=False, use_only_highest_fidelity=False, global_index=None):
+                         init_params_to_prior_and_fix_them=False, use_only_highest_fidelity=False, global_index=None,
+                         warm_start="hypers"):
         """``global_index`` (sharded surrogates only): this black-box's position among ALL objectives -- the column of the
-        Pareto front it is conditioned on -- or among ALL constraints; default: its position on this rank."""
+        Pareto front it is conditioned on -- or among ALL constraints; default: its position on this rank.
+        ``warm_start`` (with ``previously_trained_model``): "hypers" carries over the kernel hyper-parameters and the fixed
+        samples, "posterior" every layer's q(u) and the noise as well (``MFDGP``, util/warm_start.py): a refit on appended
+        rows then starts from the previous optimum and needs no phase 1 (``num_epochs_1 = 0``)."""
         if self.x_train is None:
             self.x_train = x_train
         else:
@@ -206,7 +211,7 @@ class BlackBoxMFDGPFitter:
                                previously_trained_model=previously_trained_model,
                                init_params_to_prior_and_fix_them=init_params_to_prior_and_fix_them,
                                use_only_highest_fidelity=use_only_highest_fidelity, device=self.device,
-                               **self.model_kwargs)
+                               warm_start=warm_start, **self.model_kwargs)
         handler.global_index = global_index
         if is_constraint:
             self.cons_train = torch.cat((self.cons_train, y_train.cpu().double()), 1)
@@ -402,11 +407,16 @@ class BlackBoxMFDGPFitter:
         if self._natgrad() and not use_graphs:
             raise ValueError("variational_optimizer='natgrad' lives in the captured steps on the GPU: not with use_graphs=False "
                              "(the host loader) or CPU tensors")
+        # a fitter whose models all start from a previous posterior and that has no phase 1 builds nothing for it
+        warm = all(getattr(h.mfdgp, "warm_start", "hypers") == "posterior" for _, _, h in self._handlers())
+        skip_1 = use_graphs and warm and self.num_epochs_1 <= 0 and bool(self._handlers())
         if use_graphs and full_batch:
-            self._train_mfdgp_graphed(True, self.num_epochs_1, self.lr_1)
+            if not skip_1:
+                self._train_mfdgp_graphed(True, self.num_epochs_1, self.lr_1)
             self._train_mfdgp_graphed(False, self.num_epochs_2, self.lr_2)
         elif use_graphs:      # the one-launch steps (TinyELBOStep / CoopELBOStep) are full-batch kernels: not taken here
-            self._train_mfdgp_minibatch(True, self.num_epochs_1, self.lr_1)
+            if not skip_1:
+                self._train_mfdgp_minibatch(True, self.num_epochs_1, self.lr_1)
             self._train_mfdgp_minibatch(False, self.num_epochs_2, self.lr_2)
         else:
             self._train_mfdgp(self.update_model, fix_variational_hypers=True, num_epochs=self.num_epochs_1, lr=self.lr_1)
