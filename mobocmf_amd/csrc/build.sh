@@ -1,7 +1,7 @@
 #!/bin/bash
 # Builds libmobocmf_hip.so for gfx950 (cross-compiles without a GPU).
-# An object is reused only when the hash of everything that went into it -- compiler version, flags, its source, the shared headers
-# and the public header -- equals the stamp written next to it (file times say nothing after a checkout or a flag
+# An object is reused only when the hash of everything that went into it -- compiler version, flags, its source, every header
+# of this directory and the public header -- equals the stamp written next to it (file times say nothing after a checkout or a flag
 # change).  `build.sh -B` rebuilds everything.
 set -e
 cd "$(dirname "$0")"
@@ -13,7 +13,7 @@ ccver=$($HIPCC --version 2>/dev/null | sha256sum | cut -c1-16)
 objs=""
 pids=""
 for f in gemm_f64 chol gram elementwise rff rff_opt pareto inducing minibatch natgrad natgrad_small acq_search tiny_step coop_step api; do
-  want=$( (echo "$ccver $FLAGS"; cat $f.hip common.h inlaunch.h small_step_common.h tile16.h natgrad_schedule.h minibatch_perm.h rff_desc.h ../../include/mobocmf_hip.h) | sha256sum | cut -c1-32)
+  want=$( (echo "$ccver $FLAGS"; cat $f.hip *.h ../../include/mobocmf_hip.h) | sha256sum | cut -c1-32)
   have=$(cat $f.o.stamp 2>/dev/null || true)
   if [ $force = 1 ] || [ ! -f $f.o ] || [ "$want" != "$have" ]; then
     rm -f $f.o $f.o.stamp           # a failed compile must not leave a stale object for the link step
@@ -23,5 +23,6 @@ for f in gemm_f64 chol gram elementwise rff rff_opt pareto inducing minibatch na
   objs="$objs $f.o"
 done
 for p in $pids; do wait $p; done      # set -e: any failed compile aborts the build
-$HIPCC --offload-arch=gfx950 -shared -fPIC -o libmobocmf_hip.so $objs
+# --no-undefined: a definition that has drifted from its declaration in common.h fails here, not when the library is loaded
+$HIPCC --offload-arch=gfx950 -shared -fPIC -Wl,--no-undefined -o libmobocmf_hip.so $objs
 echo "built $(pwd)/libmobocmf_hip.so"

@@ -498,20 +498,6 @@ __device__ __forceinline__ void pc_mm64(const double* As, const double* Bs, v4f6
         acc[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, bf, acc[1], 0, 0, 0);
     }
 }
-// dst (global 64 x 64 block) += sgn * acc: all loads first, then the stores
-__device__ __forceinline__ void pc_add_global(double* blk, int64_t ld, const v4f64 (&acc)[2], double sgn, int wr, int wc, int lane) {
-    const int li = lane & 15, lk = lane >> 4;
-    pc_gw g = (pc_gw)blk;
-    double v[2][4];
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[t][r] = g[(int64_t)(wr * 32 + t * 16 + lk + 4 * r) * ld + wc * 16 + li];
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) g[(int64_t)(wr * 32 + t * 16 + lk + 4 * r) * ld + wc * 16 + li] = __builtin_fma(sgn, acc[t][r], v[t][r]);
-}
 // tile (a, b <= a) number u of a packed lower triangle, u < 10
 __device__ __forceinline__ void pc_tile_of(int u, int& a, int& b) {
     a = (u >= 1) + (u >= 3) + (u >= 6);
@@ -969,20 +955,6 @@ __global__ __launch_bounds__(PC_T) void potrf_coop_kernel(double* A, int64_t ld,
     }
 }
 
-// zero the strict upper triangle
-__global__ void tril_inplace_kernel(double* A, int64_t ld, int n) {
-    int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= (int64_t)n * n) return;
-    int i = (int)(idx / n), j = (int)(idx % n);
-    if (j > i) A[(int64_t)i * ld + j] = 0.0;
-}
-
-int launch_tril_inplace(double* A, int64_t ld, int n, hipStream_t s) {
-    int64_t n2 = (int64_t)n * n;
-    hipLaunchKernelGGL(tril_inplace_kernel, dim3((unsigned)((n2 + 255) / 256)), dim3(256), 0, s, A, ld, n);
-    return hipGetLastError() == hipSuccess ? MOBOCMF_OK : MOBOCMF_HIP_ERROR;
-}
-
 // strict upper triangle <- 0, diagonal 64x64 blocks <- the factors kept in Ld; z0 / z1 (n x n each, may be null) <- 0: the
 // buffers the triangular inverse and U = L^-1 L_S fill only on and below the block diagonal (no separate zero launches)
 // Diagonal blocks >= nreal lie entirely in the identity padding of K_mm (no panel touched them): their Ld / Dinv blocks are
@@ -1099,11 +1071,6 @@ int launch_potrf_z(double* A, int64_t ld, int Mp, int M, double* Dinv, double* L
     hipLaunchKernelGGL(finish_l_kernel, dim3((unsigned)((n2 + 255) / 256), 1, nz), dim3(256), 0, s, A, ld, Mp, Ld, Dinv, nreal,
                        zs, zero0, zero1, one_launch ? (const unsigned long long*)sync : nullptr, iz, linv);
     return hipGetLastError() == hipSuccess ? MOBOCMF_OK : MOBOCMF_HIP_ERROR;
-}
-
-int launch_potrf(double* A, int64_t ld, int Mp, int M, double* Dinv, double* Ld, int32_t* info, hipStream_t s) {
-    int32_t* one[1] = {info};
-    return launch_potrf_z(A, ld, Mp, M, Dinv, Ld, one, 1, 0, nullptr, nullptr, nullptr, nullptr, s);
 }
 
 // ---------------------------------------------------------------------------------- triangular inverse

@@ -107,29 +107,13 @@ struct GemmArgs {
 };
 
 int launch_gemm(const GemmArgs& g, bool B_T, int splitk, hipStream_t s);
-// out[j] (+)= sum_p part[p*stride + j] (+ sum_p part2[p*stride2 + j]); several such reductions in ONE launch when every
-// partial count is small (small problems: each separate launch is ~4.5 us of pure latency)
-struct SumTask {
-    const double* part; int64_t P, stride;
-    const double* part2; int64_t P2, stride2;      // optional second source (part2 == nullptr: none)
-    double* out; int64_t len; int accumulate;
-    const double* extra;                           // optional single row added to the result (nullptr: none)
-};
-int launch_sum_partials_multi(const SumTask* tasks, int n, hipStream_t s);
 int gemm_nt_slabs(const GemmArgs& g, int splitk);   // k-slices (slabs) an A B^T launch will really write
 bool gemm_nt_is_small(const GemmArgs& g);           // the product runs on the small-operand kernel (GemmArgs.sym_full applies)
 int gemm_rowdot_parts(const GemmArgs& g);   // number of column slices EPI_DA writes to rowdot_part
 int gemm_colstat_rows(const GemmArgs& g);   // number of partial rows EPI_COLSTATS writes to colsq_part / coldot_part
 int launch_gemm_auto(const GemmArgs& g, bool B_T, double* ws, int64_t ws_elems, hipStream_t s);
 int launch_gemm_auto_pair(const GemmArgs& a, const GemmArgs& b, double* ws, int64_t ws_elems, hipStream_t s);
-// out[i][j] = scale * sum_z slabs[z][i][j]  (lower_only: zero above the diagonal), Mr x Mr
-int launch_reduce_slabs(const double* slabs, int64_t slab_stride, int nslab, double* out, int64_t ld, int Mr,
-                        double scale, int lower_only, int accumulate, hipStream_t s);
 
-// zero-fill by a kernel (32-bit words); used instead of hipMemsetAsync so that a captured step contains only
-// kernel nodes (a replayed memset node was observed to leave 0xFE bytes in a 4-byte word on ROCm 7.2)
-int launch_zero32(void* ptr, int64_t nwords, hipStream_t s);
-int launch_zero32_z(void* ptr, int64_t nwords, int nz, int64_t zs_bytes, hipStream_t s);   // nz regions, zs_bytes apart
 #define MAX_ZL 4   // layers whose chains one batched call may carry
 
 // ------------------------------------------------------------------ Gram (gram.hip)
@@ -159,6 +143,74 @@ struct GramArgs {
     double* dx_part;      // [gridDim.y][nbase*d]   (want_dx)
     const int32_t* colact; // per 128 columns of G (GemmArgs.colact): inactive blocks of G were never written and count as zero
 };
+int launch_gram_fwd(const GramArgs& g, hipStream_t s);
+int launch_gram_bwd(const GramArgs& g, bool want_dx, hipStream_t s);
+void gram_grid(const GramArgs& g, dim3* grid);
+// out[j] (+)= sum_p part[p*stride + j] (+ sum_p part2[p*stride2 + j]); several such reductions in ONE launch when every
+// partial count is small (small problems: each separate launch is ~4.5 us of pure latency)
+struct SumTask {
+    const double* part; int64_t P, stride;
+    const double* part2; int64_t P2, stride2;      // optional second source (part2 == nullptr: none)
+    double* out; int64_t len; int accumulate;
+    const double* extra;                           // optional single row added to the result (nullptr: none)
+};
+int launch_sum_partials_multi(const SumTask* tasks, int n, hipStream_t s);
+
+// ------------------------------------------------------------------ Cholesky and triangular inverse (chol.hip)
+int launch_trtri(const double* L, int64_t ld, int Mp, const double* Dinv, double* Linv, double* T, double* ws,
+                 int64_t ws_elems, hipStream_t s);
+// layer-batched forms (blockIdx.z = layer, workspace pointers + z*zs doubles, user tensors as tables)
+int launch_potrf_z(double* A, int64_t ld, int Mp, int M, double* Dinv, double* Ld, int32_t* const* info, int nz, int64_t zs,
+                   double* zero0, double* zero1, void* sync, int* inverse_done, hipStream_t s);
+int launch_trtri_z(const double* L, int64_t ld, int Mp, const double* Dinv, double* Linv, double* T, double* ws,
+                   int64_t ws_elems, int nz, int64_t zs, hipStream_t s);
+
+// ------------------------------------------------------------------ elementwise and glue launchers (elementwise.hip)
+// zero-fill by a kernel (32-bit words); used instead of hipMemsetAsync so that a captured step contains only
+// kernel nodes (a replayed memset node was observed to leave 0xFE bytes in a 4-byte word on ROCm 7.2)
+int launch_zero32(void* ptr, int64_t nwords, hipStream_t s);
+int launch_pad_vec(const double* src, int64_t n, double* dst, int64_t np, hipStream_t s);
+int launch_gemv_rows(const double* Mat, int64_t ld, const double* vec, double* out, int rows, int64_t cols, double scale,
+                     int accumulate, hipStream_t s);
+int launch_moments_finish(const double* qpart, const double* mupart, const double* rpart, int nrb, int64_t Np, int64_t N,
+                          const double* knn, int branch, double min_var, double* q, double* r, double* varraw,
+                          double* mean, double* var, int32_t* zero_word, hipStream_t s);
+int launch_moments_bwd_prep(const double* g_mean, const double* g_var, const double* knn, const double* q,
+                            const double* varraw, int branch, double min_var, int64_t N, int64_t Np, double* gmu,
+                            double* gv, double* gv2, double* cgv, int32_t* nclamped, int zeroed, int32_t* blkact, hipStream_t s);
+int launch_reduce_slabs_sym(const double* slabs, int64_t slab_stride, int nslab, int nslab_diag, double* out, int Mp, const int32_t* flag,
+                            const double* fallback, hipStream_t s);
+int launch_reduce_slabs_sym2(const double* slabs, const double* slabs2, int64_t slab_stride, int nslab, int nslab_diag,
+                             double* out, double* out2, int Mp, const int32_t* flag, hipStream_t s);
+int launch_copy_block(const double* src, int64_t lds, double* dst, int64_t ldd, int64_t rows, int64_t cols, hipStream_t s);
+int launch_mf_combine(const double* Ks, const double* Kn, int64_t ld, const double* s1, const double* s2, const int32_t* l1,
+                      const int32_t* l2, const double* ntab, int64_t n1, int64_t n2, double diag, double* out, int64_t ldo,
+                      int64_t rows_p, int64_t cols_p, hipStream_t s);
+int launch_copy_pad_identity(const double* src, int64_t lds, int n, double* dst, int np, hipStream_t s);
+int launch_exact_gp_mll(const double* L, int64_t ld, const double* a, int n, double* mll, hipStream_t s);
+int launch_exact_gp_finish(const double* qpart, const double* mupart, int nparts, int64_t ntp, int64_t nt, const double* kss,
+                           double* mean, double* var, hipStream_t s);
+int launch_mirror_lower(const double* src, int64_t lds, double* dst, int64_t ldd, int64_t row0, int64_t rows, int64_t cols,
+                        int64_t n_real, hipStream_t s);
+// layer-batched forms (blockIdx.z = layer, workspace pointers + z*zs doubles, user tensors as tables)
+int launch_chain_outputs_z(const double* X, const double* LSp, const double* LinvT, const double* da_tot, int M, int Mp,
+                           const double* const* gkl, double* const* gLS, double* const* gm, int nz, int64_t zs, hipStream_t s);
+int launch_transpose_z(const double* in, int64_t ldi, double* out, int64_t ldo, int64_t rows, int64_t cols, int nz,
+                       int64_t zs, hipStream_t s);
+int launch_gemv_rows_z(const double* Mat, int64_t ld, const double* vec, double* out, int rows, int64_t cols, double scale,
+                       int accumulate, int nz, int64_t zs, hipStream_t s);
+int launch_transpose_pad_z(const double* in, double* out, int Mp, const double* const* LS, const double* const* m, int M,
+                           double* LSp, double* mp, int nz, int64_t zs, hipStream_t s);
+int launch_transpose_gemv_z(const double* in, double* out, int Mp, const double* Mat, const double* vec, double* vout, int nz,
+                            int64_t zs, hipStream_t s);
+int launch_kl_z(const double* L, const double* LSp, const double* U, const double* a, int M, int Mp, double* const* kl,
+                double* part, int nz, int64_t zs, hipStream_t s);
+int launch_dutot_y_z(const double* G1, const double* G2, const double* Hc, const double* U, const double* da, const double* a,
+                     const double* const* gkl, int Mp, double* dU, double* da_tot, double* Y, int nz, int64_t zs, hipStream_t s);
+int launch_dl_from_t2_z(const double* T2, const double* L, const double* const* gkl, int M, int Mp, double* dL, int nz,
+                        int64_t zs, hipStream_t s);
+int launch_phi_z(const double* T3, int Mp, double* P, int nz, int64_t zs, hipStream_t s);
+int launch_symmetrize_z(const double* S, int Mp, double* G, int nz, int64_t zs, hipStream_t s);
 
 // ------------------------------------------------------------------ hyper-parameter packing
 // kind 0: [alpha, ls[0..d)]                                   (1 + d doubles)

@@ -151,19 +151,6 @@ __device__ __forceinline__ void store_x(double* X, int t, int lane, v4d acc) {  
 #pragma unroll
     for (int r = 0; r < 4; ++r) X[(t * 16 + 4 * r + lk) * XLD + lj] = acc[r];
 }
-// row tiles of a column-block product dealt to the CNW wavefronts in pairs (t, nt-1-t): a triangular T gives every pair the same
-// number of k tiles
-__device__ __forceinline__ int pair_tile(int idx, int nt) { return (idx & 1) ? nt - 1 - (idx >> 1) : (idx >> 1); }
-
-// the row tiles a wavefront takes in a column-block product with nt row tiles (at most 2 for nt <= 8)
-__device__ __forceinline__ int wave_tiles(int wave, int nt, int (&t)[2]) {
-    if (nt <= CNW) { t[0] = wave; return wave < nt ? 1 : 0; }
-    const int p = wave;
-    if (p >= (nt + 1) / 2) return 0;
-    t[0] = p;
-    t[1] = nt - 1 - p;
-    return t[1] != p ? 2 : 1;
-}
 __device__ __forceinline__ void tile_of_slow(int t, int& ti, int& tj) {      // index in the packed lower triangle -> (ti, tj <= ti)
     ti = 0;
     while ((ti + 1) * (ti + 2) / 2 <= t) ++ti;

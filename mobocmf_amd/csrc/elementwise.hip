@@ -58,29 +58,8 @@ int launch_zero32(void* ptr, int64_t nwords, hipStream_t s) {
 // (g_kl, info, ...) travel as small pointer tables.
 #define GRIDZ(n, nz) dim3((unsigned)(((n) + 255) / 256), 1, (unsigned)(nz)), dim3(256)
 struct ScalZ { const double* p[MAX_ZL]; };
-__global__ void zero32_z_kernel(uint32_t* p, int64_t n, int64_t zs_words) {
-    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) p[blockIdx.z * zs_words + i] = 0u;
-}
-int launch_zero32_z(void* ptr, int64_t nwords, int nz, int64_t zs_bytes, hipStream_t s) {
-    if (nwords <= 0) return MOBOCMF_OK;
-    hipLaunchKernelGGL(zero32_z_kernel, GRIDZ(nwords, nz), 0, s, (uint32_t*)ptr, nwords, zs_bytes / 4);
-    return CHECK_LAUNCH();
-}
 
 // ------------------------------------------------------------------ M x M helpers
-// dst (Mp x Mp) = tril(src (M x M, ld lds)) zero padded
-__global__ void pad_tril_kernel(const double* src, int64_t lds, int M, double* dst, int Mp) {
-    int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= (int64_t)Mp * Mp) return;
-    int i = (int)(idx / Mp), j = (int)(idx % Mp);
-    dst[idx] = (i < M && j <= i) ? src[(int64_t)i * lds + j] : 0.0;
-}
-int launch_pad_tril(const double* src, int64_t lds, int M, double* dst, int Mp, hipStream_t s) {
-    hipLaunchKernelGGL(pad_tril_kernel, GRID1((int64_t)Mp * Mp), 0, s, src, lds, M, dst, Mp);
-    return CHECK_LAUNCH();
-}
-
 __global__ void pad_vec_kernel(const double* src, int64_t n, double* dst, int64_t np) {
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < np) dst[i] = (src && i < n) ? src[i] : 0.0;
@@ -90,23 +69,8 @@ int launch_pad_vec(const double* src, int64_t n, double* dst, int64_t np, hipStr
     return CHECK_LAUNCH();
 }
 
-// the same for every layer of a chain batch in ONE launch: LSp + z*zs = tril(L_S[z]) padded, mp + z*zs = m[z] padded
+// the user tensors of every layer of a chain batch (transpose_pad_z: LSp + z*zs = tril(L_S[z]) padded, mp + z*zs = m[z] padded)
 struct PadZ { const double* LS[MAX_ZL]; const double* m[MAX_ZL]; };
-__global__ void pad_params_z_kernel(PadZ t, int M, double* LSp, double* mp, int Mp, int64_t zs) {
-    int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= (int64_t)Mp * Mp) return;
-    const int z = blockIdx.z;
-    int i = (int)(idx / Mp), j = (int)(idx % Mp);
-    LSp[z * zs + idx] = (i < M && j <= i) ? t.LS[z][(int64_t)i * M + j] : 0.0;
-    if (idx < Mp) mp[z * zs + idx] = idx < M ? t.m[z][idx] : 0.0;
-}
-int launch_pad_params_z(const double* const* LS, const double* const* m, int M, double* LSp, double* mp, int Mp, int nz,
-                        int64_t zs, hipStream_t s) {
-    PadZ t = {};
-    for (int z = 0; z < nz; ++z) { t.LS[z] = LS[z]; t.m[z] = m[z]; }
-    hipLaunchKernelGGL(pad_params_z_kernel, GRIDZ((int64_t)Mp * Mp, nz), 0, s, t, M, LSp, mp, Mp, zs);
-    return CHECK_LAUNCH();
-}
 
 // out[c][r] = in[r][c]   (rows x cols -> cols x rows), 32x32 LDS tiles
 __global__ void transpose_kernel(const double* in, int64_t ldi, double* out, int64_t ldo, int64_t rows, int64_t cols,
@@ -183,9 +147,6 @@ int launch_transpose_gemv_z(const double* in, double* out, int Mp, const double*
     hipLaunchKernelGGL(transpose_gemv_z_kernel, dim3((unsigned)(Mp / 32), (unsigned)(Mp / 32), (unsigned)nz), dim3(32, 8), 0, s, in,
                        out, Mp, zs, Mat, vec, vout);
     return CHECK_LAUNCH();
-}
-int launch_transpose(const double* in, int64_t ldi, double* out, int64_t ldo, int64_t rows, int64_t cols, hipStream_t s) {
-    return launch_transpose_z(in, ldi, out, ldo, rows, cols, 1, 0, s);
 }
 
 // out[i] = sum_j Mat[i][j] * vec[j]   (one wavefront per row), optional accumulate
@@ -284,11 +245,6 @@ int launch_kl_z(const double* L, const double* LSp, const double* U, const doubl
     for (int z = 0; z < nz; ++z) kz.p[z] = kl[z];      // kl[z] is a user tensor
     hipLaunchKernelGGL(kl_final_kernel, dim3(nz), dim3(256), 0, s, (const double*)part, nb, M, kz, zs);
     return CHECK_LAUNCH();
-}
-int launch_kl(const double* L, const double* LSp, const double* U, const double* a, int M, int Mp, double* kl,
-              double* part, hipStream_t s) {
-    double* one[1] = {kl};
-    return launch_kl_z(L, LSp, U, a, M, Mp, one, part, 1, 0, s);
 }
 
 // ------------------------------------------------------------------ predictive moments
@@ -473,30 +429,6 @@ int launch_dutot_y_z(const double* G1, const double* G2, const double* Hc, const
 
 
 // ------------------------------------------------------------------ Cholesky-chain backward glue (Mp x Mp)
-// dU_tot = dU + gkl*U ;  da_tot = da + gkl*a        (in place on dU, da)
-__global__ void add_kl_terms_kernel(double* dU, const double* U, double* da, const double* a, const double* gkl, int Mp) {
-    int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const double g = gkl ? gkl[0] : 0.0;
-    if (idx < (int64_t)Mp * Mp) dU[idx] += g * U[idx];
-    if (idx < Mp) da[idx] += g * a[idx];
-}
-int launch_add_kl_terms(double* dU, const double* U, double* da, const double* a, const double* gkl, int Mp, hipStream_t s) {
-    hipLaunchKernelGGL(add_kl_terms_kernel, GRID1((int64_t)Mp * Mp), 0, s, dU, U, da, a, gkl, Mp);
-    return CHECK_LAUNCH();
-}
-
-// X[i][j] += da[i] * m[j]   (rank-1, lower part is what matters)
-__global__ void rank1_add_kernel(double* X, const double* u, const double* v, int Mp) {
-    int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= (int64_t)Mp * Mp) return;
-    int i = (int)(idx / Mp), j = (int)(idx % Mp);
-    X[idx] += u[i] * v[j];
-}
-int launch_rank1_add(double* X, const double* u, const double* v, int Mp, hipStream_t s) {
-    hipLaunchKernelGGL(rank1_add_kernel, GRID1((int64_t)Mp * Mp), 0, s, X, u, v, Mp);
-    return CHECK_LAUNCH();
-}
-
 // dL = -tril(T2) + gkl * diag(1/L_ii)  (rows/cols < M only; zero elsewhere)
 __global__ void dl_from_t2_kernel(const double* T2, const double* L, ScalZ gklz, int M, int Mp, double* dL, int64_t zs) {
     int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -518,10 +450,6 @@ int launch_dl_from_t2_z(const double* T2, const double* L, const double* const* 
     hipLaunchKernelGGL(dl_from_t2_kernel, GRIDZ((int64_t)Mp * Mp, nz), 0, s, T2, L, t, M, Mp, dL, zs);
     return CHECK_LAUNCH();
 }
-int launch_dl_from_t2(const double* T2, const double* L, const double* gkl, int M, int Mp, double* dL, hipStream_t s) {
-    const double* one[1] = {gkl};
-    return launch_dl_from_t2_z(T2, L, one, M, Mp, dL, 1, 0, s);
-}
 
 // P = Phi(T3): lower triangle with halved diagonal
 __global__ void phi_kernel(const double* T3, int Mp, double* P, int64_t zs) {
@@ -535,7 +463,6 @@ int launch_phi_z(const double* T3, int Mp, double* P, int nz, int64_t zs, hipStr
     hipLaunchKernelGGL(phi_kernel, GRIDZ((int64_t)Mp * Mp, nz), 0, s, T3, Mp, P, zs);
     return CHECK_LAUNCH();
 }
-int launch_phi(const double* T3, int Mp, double* P, hipStream_t s) { return launch_phi_z(T3, Mp, P, 1, 0, s); }
 
 // G = (S + S^T)/2
 __global__ void symmetrize_kernel(const double* S, int Mp, double* G, int64_t zs) {
@@ -547,24 +474,6 @@ __global__ void symmetrize_kernel(const double* S, int Mp, double* G, int64_t zs
 }
 int launch_symmetrize_z(const double* S, int Mp, double* G, int nz, int64_t zs, hipStream_t s) {
     hipLaunchKernelGGL(symmetrize_kernel, GRIDZ((int64_t)Mp * Mp, nz), 0, s, S, Mp, G, zs);
-    return CHECK_LAUNCH();
-}
-int launch_symmetrize(const double* S, int Mp, double* G, hipStream_t s) { return launch_symmetrize_z(S, Mp, G, 1, 0, s); }
-
-// g_LS (M x M, ld M) = tril(X (Mp x Mp)) - gkl * diag(1/LS_ii)
-__global__ void gls_out_kernel(const double* X, const double* LSp, const double* gkl, int M, int Mp, double* gLS) {
-    int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= (int64_t)M * M) return;
-    int i = (int)(idx / M), j = (int)(idx % M);
-    double v = 0.0;
-    if (j <= i) {
-        v = X[(int64_t)i * Mp + j];
-        if (i == j && gkl) v -= gkl[0] / LSp[(int64_t)i * Mp + i];
-    }
-    gLS[idx] = v;
-}
-int launch_gls_out(const double* X, const double* LSp, const double* gkl, int M, int Mp, double* gLS, hipStream_t s) {
-    hipLaunchKernelGGL(gls_out_kernel, GRID1((int64_t)M * M), 0, s, X, LSp, gkl, M, Mp, gLS);
     return CHECK_LAUNCH();
 }
 

@@ -3,14 +3,11 @@
 //   C[Mr x Nc] (+)= alpha * A[Mr x Kd] * B        B_T=0: B is [Kd x Nc] (n contiguous)
 //                                                 B_T=1: B is [Nc x Kd] (k contiguous)  -> A * B^T
 //
-// Matrix instruction: v_mfma_f64_16x16x4_f64 (GEMM_MI == 16, the default since round 4).  Measured on MI355X with the
-// instruction issued on VGPR tuples (tools/mfma_peak.hip, profiles/r04_mfma_peak.txt): 77.1 TFLOP/s, against 73.3 for
-// v_mfma_f64_4x4x4_4b_f64 and 67-71 for v_fma_f64.  (Rounds 1-3 ran the 4x4x4 form -- -DGEMM_MI=4 still builds it -- because the
-// builtin's accumulator copies made the 16x16x4 microbenchmark read 36 TFLOP/s: an artefact)  Lane map of
-// the 16x16x4 form: lane (li = l & 15, lk = l >> 4) feeds A[row li][k = 4 lk + kq] to MFMA kq of a K step and holds the result
-// rows 4 r + lk, column li.  The 4x4x4 form uses its four independent blocks as four column groups of one 4 x 16 output strip:
-// lane (kk = l>>4, b = (l>>2)&3, i = l&3) holds A[row i][k] -- the same 4 rows in every block, an LDS broadcast read -- and
-// B[k][col 4b+j]; result lane (i = l>>4, col = l&15) (layout verified with one-hot operands, tools/probe_mfma444.hip).
+// Matrix instruction: v_mfma_f64_16x16x4_f64.  Measured on MI355X with the instruction issued on VGPR tuples
+// (tools/mfma_peak.hip, profiles/r04_mfma_peak.txt): 77.1 TFLOP/s, against 73.3 for v_mfma_f64_4x4x4_4b_f64 and 67-71 for
+// v_fma_f64.  Lane map: lane (li = l & 15, lk = l >> 4) feeds A[row li][k = 4 lk + kq] to MFMA kq of a K step and holds the
+// result rows 4 r + lk, column li.  (Rounds 1-3 ran a v_mfma_f64_4x4x4_4b_f64 main loop; its A/B against this one is
+// profiles/r04_mfma16_vs_mfma4_ab.txt, its lane map tools/probe_mfma444.hip, its code the git history.)
 //
 // Workgroup = 256 threads = 4 wavefronts (2 x 2), tile 128 x 128, K step 16.  Each wavefront owns 64 x 64 =
 // 64 accumulator registers (128 VGPRs).  Tiles are staged global -> LDS by global_load_lds_dwordx4 (LDS-DMA,
@@ -18,7 +15,7 @@
 // LDS-DMA writes 64 lanes x 16 B contiguously, so the LDS images are unpadded; bank conflicts of the fragment
 // reads are removed by an XOR swizzle of the 16-byte chunk applied on the SOURCE address of the DMA and on
 // the fragment read (same involution on both sides):
-//   A / B_T image [128 rows][16 k]   : chunk ^= ((row >> 1) & 1) << 2
+//   A / B_T image [128 rows][16 k]   : chunk ^= IMG_SWZ(row), derived below
 //   B image       [16 k][128 cols]   : none -- every lane owns ADJACENT column pairs (columns 2*li, 2*li+1 and 32 + 2*li,
 //                                      33 + 2*li of its wavefront's 64), so a B fragment is one ds_read_b128 per k and
 //                                      column pair, and the lane groups the LDS services a b128 read in ({0-3,12-15,
@@ -39,26 +36,15 @@ typedef double v2f64 __attribute__((ext_vector_type(2)));
 #define KL_MAX 1024   // active K blocks one k-slice of an A B^T product can hold (GemmArgs.kact; launch_gemm checks)
 #define TILE_ELEMS (BM * BK)   // 2048 doubles = 16 KiB per operand tile
 
-// Matrix instruction of gemm_f64_kernel's main loop.  16: v_mfma_f64_16x16x4_f64 (round 4; 77 TFLOP/s sustained, one fragment
-// value feeds 2048 flops).  4: v_mfma_f64_4x4x4_4b_f64 (rounds 1-3; 73 TFLOP/s, 512 flops per fragment value) -- kept for
-// A/B builds (EXTRA_HIPCC_FLAGS=-DGEMM_MI=4).  Accumulator lane map is the SAME for both: acc[mt][nt][r] of lane (li, lk) is
-// row mt*32 + wr*16 + 4r + lk, so every epilogue serves either.  What differs is the operand side:
-//   4x4x4:   lane (kk = l>>4, i = l&3) feeds A[4r + i][k = kk] to MFMA r (four MFMAs cover 16 rows), 16 ds_read_b128 of A per kpair
-//   16x16x4: lane (li, lk) feeds A[li][k = lk] -- one MFMA covers the 16 rows x 16 columns x 4 k; with MFMA kq of a K step
-//            taking k = 4*lk + kq a lane's four A values are 32 contiguous bytes of its image row: two ds_read_b128 per
-//            16-row group and K step (16 b128 per K step and wavefront where the 4x4x4 form issues 40, 64 MFMAs instead of 256).
+// gemm_f64_kernel's main loop: one v_mfma_f64_16x16x4_f64 covers 16 rows x 16 columns x 4 k (one fragment value feeds 2048
+// flops).  Accumulator lane map: acc[mt][nt][r] of lane (li, lk) is row mt*32 + wr*16 + 4r + lk.  Operand side: lane (li, lk)
+// feeds A[li][k = lk]; with MFMA kq of a K step taking k = 4*lk + kq a lane's four A values are 32 contiguous bytes of its
+// image row: two ds_read_b128 per 16-row group and K step (16 b128 and 64 MFMAs per K step and wavefront).
 // Image swizzle (XOR on the 16-byte chunk index of a [rows][16 k] image row, applied on the DMA source and on the read):
 // the four 16-lane groups a ds_read_b128 is serviced in ({0-3,12-15,20-27}, ...) must hit 16 different 16-byte slots of the
-// 256-byte bank row.  16x16x4: a group holds 8 rows x chunk c and 8 other rows x chunk c^2; slot = (row&1)*8 + chunk, so the
+// 256-byte bank row.  A group holds 8 rows x chunk c and 8 other rows x chunk c^2; slot = (row&1)*8 + chunk, so the
 // four rows of one parity need four different XOR values that keep bit 1 clear: s = bit1(row) | bit3(row) << 2.
-#ifndef GEMM_MI
-#define GEMM_MI 16
-#endif
-#if GEMM_MI == 16
 #define IMG_SWZ(row) ((((row) >> 1) & 1) | ((((row) >> 3) & 1) << 2))
-#else
-#define IMG_SWZ(row) ((((row) >> 1) & 1) << 2)
-#endif
 
 
 // Cross-lane sums without the LDS crossbar (ds_bpermute round trips): DPP moves inside a 16-lane row, permlane swaps across
@@ -307,21 +293,13 @@ __global__ __launch_bounds__(256, RM == 64 ? 3 : 2) void gemm_f64_kernel(GemmArg
 
     // ---- fragment read offsets (doubles).  k pairs (2*kp', 2*kp'+1) are adjacent: one ds_read_b128 per pair.
     // kpair p (0,1) covers ks = 2p, 2p+1, i.e. k = 4*lk + 2p + {0,1}: logical 16-B chunk 2*lk + p.
-#if GEMM_MI == 16
-    // 16x16x4: lane (li, lk) feeds row li of a 16-row group with k = 4*lk + kq (kq = 0..3: MFMA number kq of the K step takes
+    // Lane (li, lk) feeds row li of a 16-row group with k = 4*lk + kq (kq = 0..3: MFMA number kq of the K step takes
     // lane group lk's k = 4*lk + kq on both operands), i.e. logical 16-byte chunks 2*lk and 2*lk + 1 of its row.
     const int swA = IMG_SWZ(li);
-#else
-    const int swA = ((lane >> 1) & 1) << 2;
-#endif
     const int colP0 = ((2 * lk + 0) ^ swA) << 1, colP1 = ((2 * lk + 1) ^ swA) << 1;
     // the two row-wavefronts own INTERLEAVED 16-row groups (group 2*mt + wr): inside a triangular diagonal block both
     // then skip a similar share of structurally-zero groups (critical path 20/32 of a dense block instead of 26/32)
-#if GEMM_MI == 16
     const int a_base = (wr * 16 + li) * BK;                         // + mt*32*BK + colP
-#else
-    const int a_base = (wr * 16 + (lane & 3)) * BK;                 // + (mt*32 + 4r)*BK + colP
-#endif
     // A B^T: the two column-wavefronts own INTERLEAVED 16-column groups (group 2*nt + wc), like the row-wavefronts their row
     // groups: in a diagonal tile of a symmetric product the 16 x 16 blocks strictly above the diagonal (column group > row
     // group) then spread evenly over the four wavefronts
@@ -434,15 +412,11 @@ __global__ __launch_bounds__(256, RM == 64 ? 3 : 2) void gemm_f64_kernel(GemmArg
     STAMP(1 + 4 * part);      // first stage landed
     v4f64 w_nxt = (v4f64){1.0, 1.0, 1.0, 1.0};
     if (B_T && g.bscale && nk > 0) w_nxt = *(const v4f64*)(g.bscale + KOFF(0) + 4 * lk);
-    // Software pipeline of one K step over 8 groups g = (kpair p, row tile mt): the A fragments of group g+1
-    // (4 x ds_read_b128) and, at a kpair boundary, the B fragments of the next kpair are read while the 32 MFMAs of
-    // group g issue.  sched_barrier(0) pins the group boundaries so the register allocator sees two fragment sets, not
-    // eight.  (Literal indices through macros: lambdas / late-unrolled loops left the fragment arrays in scratch.)
-#if GEMM_MI == 16
-    // ---- 16x16x4 main loop.  All fragments of a K step are read up front (B: 8 ds_read_b128, A: 2 per 16-row group), the
+    // ---- main loop.  All fragments of a K step are read up front (B: 8 ds_read_b128, A: 2 per 16-row group), the
     // next stage's DMA is issued behind the first of them, then the MFMAs go row group by row group -- a wavefront issues one
     // 64-cycle MFMA after the other, so the reads of the later groups return under the first group's MFMAs and the
-    // co-resident wavefronts' bursts; no software pipeline of fragment sets is needed (the 4x4x4 form's eight groups).
+    // co-resident wavefronts' bursts; no software pipeline of fragment sets is needed.  (Literal indices through macros:
+    // lambdas / late-unrolled loops left the fragment arrays in scratch.)
     v2f64 fa[MT][2];             // A: [row group][chunk]: k = 4*lk + 2*chunk + {0, 1}
     double fb[4][4];             // B: [kq][nt]: k = 4*lk + kq
 #define LOAD_A16(MT_)                                                                                       \
@@ -478,44 +452,6 @@ __global__ __launch_bounds__(256, RM == 64 ? 3 : 2) void gemm_f64_kernel(GemmArg
 #define MMA_ALL(MT_) MMA16(MT_, 4)
 #define MMA_IF(MT_)                                                                                         \
     if (act & (1 << (MT_))) { MMA16(MT_, 4) }
-#endif
-#if GEMM_MI != 16
-    v2f64 a0[4], a1[4];          // A fragment sets (even / odd group)
-    double b0[2][4], b1[2][4];   // B fragment sets (kpair 0 / 1): [ks&1][nt]
-#define LOAD_A(dst, P, MT)                                                                                  \
-    _Pragma("unroll") for (int r = 0; r < 4; ++r)                                                          \
-        dst[r] = *(const v2f64*)(As + a_base + ((MT) * 32 + 4 * r) * BK + ((P) ? colP1 : colP0));
-#define LOAD_B(dst, P)                                                                                      \
-    if (B_T) {                                                                                              \
-        _Pragma("unroll") for (int t = 0; t < 4; ++t) {                                                    \
-            v2f64 v = *(const v2f64*)(Bs + bt_base + t * 32 * BK + ((P) ? colP1 : colP0));                  \
-            dst[0][t] = v[0];                                                                               \
-            dst[1][t] = v[1];                                                                               \
-        }                                                                                                   \
-        if (g.bscale) {                                                                                     \
-            _Pragma("unroll") for (int t = 0; t < 4; ++t) {                                                \
-                dst[0][t] *= w4[2 * (P)];                                                                   \
-                dst[1][t] *= w4[2 * (P) + 1];                                                               \
-            }                                                                                               \
-        }                                                                                                   \
-    } else {                                                                                                \
-        _Pragma("unroll") for (int e = 0; e < 2; ++e)                                                      \
-            _Pragma("unroll") for (int h = 0; h < 2; ++h) {                                                \
-                const v2f64 v = *(const v2f64*)(Bs + bn_base + (2 * (P) + e) * BN + h * 32);                \
-                dst[e][2 * h] = v[0];                                                                       \
-                dst[e][2 * h + 1] = v[1];                                                                   \
-            }                                                                                               \
-    }
-#define MMA_DO(asrc, bsrc, MT)                                                                              \
-    _Pragma("unroll") for (int e = 0; e < 2; ++e)                                                          \
-        _Pragma("unroll") for (int r = 0; r < 4; ++r)                                                      \
-            _Pragma("unroll") for (int j = 0; j < 4; ++j)                                                  \
-                acc[MT][j][r] = __builtin_amdgcn_mfma_f64_4x4x4f64(asrc[r][e], bsrc[e][j], acc[MT][j][r], 0, 0, 0);
-#define MMA_ALL(asrc, bsrc, MT) MMA_DO(asrc, bsrc, MT) __builtin_amdgcn_sched_barrier(0);
-#define MMA_IF(asrc, bsrc, MT)                                                                              \
-    if (act & (1 << (MT))) { MMA_DO(asrc, bsrc, MT) }                                                       \
-    __builtin_amdgcn_sched_barrier(0);
-#endif
 // The LDS-DMA of the NEXT stage is issued behind the step's first fragment reads (it writes the other buffer): in front
 // of them its address arithmetic and eight issues sat on the critical path between the barrier and the first MFMA.
 #define STAGE_NEXT                                                                                          \
@@ -526,7 +462,6 @@ __global__ __launch_bounds__(256, RM == 64 ? 3 : 2) void gemm_f64_kernel(GemmArg
             stage(Ag, knext, buf ^ 1);                                                                      \
         }                                                                                                   \
         STEP_STAMP(1);
-#if GEMM_MI == 16
 #define KSTEP_STD(MMA)                                                                                      \
         LOAD_B16                                                                                            \
         LOAD_A16(0)                                                                                         \
@@ -546,7 +481,7 @@ __global__ __launch_bounds__(256, RM == 64 ? 3 : 2) void gemm_f64_kernel(GemmArg
         /* the MFMAs stay IN FRONT of the step's closing wait + barrier: they only touch registers, so without this fence   \
            hipcc hoists "s_waitcnt vmcnt(0); s_barrier" to right behind the first MFMA -- the wavefront then waits for the   \
            next stage's DMA (a full L2 / HBM round trip) before it has issued anything that could hide it (first build of   \
-           this loop: 5-10 % slower than the 4x4x4 form at every shape) */                                                 \
+           this loop: 5-10 % slower at every shape) */                                                                     \
         __builtin_amdgcn_sched_barrier(0);
 // Diagonal tile of a symmetric A B^T product (sym_out): with row group 2*mt + wr and column group 2*nt + wc a 16 x 16
 // block lies on or below the diagonal iff 2*nt + wc <= 2*mt + wr, i.e. nt <= mt for three of the wavefronts (KSTEP_LE:
@@ -567,60 +502,6 @@ __global__ __launch_bounds__(256, RM == 64 ? 3 : 2) void gemm_f64_kernel(GemmArg
         __builtin_amdgcn_sched_barrier(0);                                                                  \
         MMA16(1, 1) MMA16(2, 2) MMA16(3, 3)                                                                 \
         __builtin_amdgcn_sched_barrier(0);
-#else
-// The standard K step: all four row groups, MMA = MMA_ALL or the skipping MMA_IF.
-#define KSTEP_STD(MMA)                                                                                      \
-        LOAD_B(b0, 0)                                                                                       \
-        LOAD_A(a0, 0, 0)                                                                                    \
-        STAGE_NEXT                                                                                          \
-        if constexpr (MT == 4) {                                                                            \
-            LOAD_A(a1, 0, 1) MMA(a0, b0, 0)                                                                 \
-            LOAD_A(a0, 0, 2) MMA(a1, b0, 1)                                                                 \
-            LOAD_A(a1, 0, 3) MMA(a0, b0, 2)                                                                 \
-            LOAD_A(a0, 1, 0) LOAD_B(b1, 1) MMA(a1, b0, 3)                                                   \
-            LOAD_A(a1, 1, 1) MMA(a0, b1, 0)                                                                 \
-            LOAD_A(a0, 1, 2) MMA(a1, b1, 1)                                                                 \
-            LOAD_A(a1, 1, 3) MMA(a0, b1, 2)                                                                 \
-            MMA(a1, b1, 3)                                                                                  \
-        } else {      /* 64-row tiles: four groups of 32 MFMAs */                                           \
-            LOAD_A(a1, 0, MT - 1) MMA(a0, b0, 0)                                                            \
-            LOAD_A(a0, 1, 0) LOAD_B(b1, 1) MMA(a1, b0, MT - 1)                                              \
-            LOAD_A(a1, 1, MT - 1) MMA(a0, b1, 0)                                                            \
-            MMA(a1, b1, MT - 1)                                                                             \
-        }
-// Diagonal tile of a symmetric A B^T product (sym_out): with row group 2*mt + wr and column group 2*nt + wc a 16 x 16
-// block lies on or below the diagonal iff 2*nt + wc <= 2*mt + wr, i.e. nt <= mt for three of the wavefronts (KSTEP_LE:
-// 10 of 16 blocks) and nt < mt for (wr, wc) = (0, 1) (KSTEP_LT: 6 of 16); the slab reduction mirrors the rest.
-// GRPJ = the first JN column groups of row group MT, compile-time counts, no branch inside the K step.
-#define GRPJ(asrc, bsrc, MT, JN)                                                                            \
-    _Pragma("unroll") for (int e = 0; e < 2; ++e)                                                          \
-        _Pragma("unroll") for (int r = 0; r < 4; ++r)                                                      \
-            _Pragma("unroll") for (int j = 0; j < (JN); ++j)                                               \
-                acc[MT][j][r] = __builtin_amdgcn_mfma_f64_4x4x4f64(asrc[r][e], bsrc[e][j], acc[MT][j][r], 0, 0, 0); \
-    __builtin_amdgcn_sched_barrier(0);
-#define KSTEP_LE                                                                                            \
-        LOAD_B(b0, 0)                                                                                       \
-        LOAD_A(a0, 0, 0)                                                                                    \
-        STAGE_NEXT                                                                                          \
-        LOAD_A(a1, 0, 1) GRPJ(a0, b0, 0, 1)                                                                 \
-        LOAD_A(a0, 0, 2) GRPJ(a1, b0, 1, 2)                                                                 \
-        LOAD_A(a1, 0, 3) GRPJ(a0, b0, 2, 3)                                                                 \
-        LOAD_A(a0, 1, 0) LOAD_B(b1, 1) GRPJ(a1, b0, 3, 4)                                                   \
-        LOAD_A(a1, 1, 1) GRPJ(a0, b1, 0, 1)                                                                 \
-        LOAD_A(a0, 1, 2) GRPJ(a1, b1, 1, 2)                                                                 \
-        LOAD_A(a1, 1, 3) GRPJ(a0, b1, 2, 3)                                                                 \
-        GRPJ(a1, b1, 3, 4)
-#define KSTEP_LT                                                                                            \
-        LOAD_B(b0, 0)                                                                                       \
-        LOAD_A(a0, 0, 1)                                                                                    \
-        STAGE_NEXT                                                                                          \
-        LOAD_A(a1, 0, 2) GRPJ(a0, b0, 1, 1)                                                                 \
-        LOAD_A(a0, 0, 3) GRPJ(a1, b0, 2, 2)                                                                 \
-        LOAD_A(a1, 1, 1) LOAD_B(b1, 1) GRPJ(a0, b0, 3, 3)                                                   \
-        LOAD_A(a0, 1, 2) GRPJ(a1, b1, 1, 1)                                                                 \
-        LOAD_A(a1, 1, 3) GRPJ(a0, b1, 2, 2)                                                                 \
-        GRPJ(a1, b1, 3, 3)
-#endif
 // K steps [KT0, KT1) of the pipeline with the K-step body BODY.  COND = 1: inside a triangular diagonal block, 16-row
 // groups that are structurally zero for the step are skipped (bit mt of `act`, used by MMA_IF).
 #define STAGE_LOOP(KT0, KT1, COND, BODY)                                                                    \
@@ -687,12 +568,8 @@ __global__ __launch_bounds__(256, RM == 64 ? 3 : 2) void gemm_f64_kernel(GemmArg
 #undef STAGE_NEXT
 #undef KSTEP_LE
 #undef KSTEP_LT
-#undef GRPJ
 #undef MMA_IF
 #undef MMA_ALL
-#undef MMA_DO
-#undef LOAD_A
-#undef LOAD_B
 #undef LOAD_A16
 #undef LOAD_B16
 #undef MMA16
@@ -943,20 +820,7 @@ int launch_gemm(const GemmArgs& g0, bool B_T, int splitk, hipStream_t s) {
     // instantiation spills loop-invariant LDS addresses and reloads them -- a scratch round trip -- in every K step
     // (dense 512 x 65536 x 512: 0.62 ms against 0.53 ms through this instantiation)
     const bool tri = (g.tri & (TRI_LOWER_A | TRI_UPPER_A)) != 0 || g.epi == EPI_STORE;
-#ifdef GEMM_LDS_PAD64
-    // experiment (tools/build_variant.sh): dynamic LDS on the 64-row launches caps the workgroups a CU takes (48 KB static:
-    // three fit in 160 KB; + 32 KB -> two, + 64 KB -> one), to see how the dispatcher spreads a grid smaller than the slots
-    const size_t dyn64 = GEMM_LDS_PAD64;
-#define LAUNCH(BT, TR, EP, RM_)                                                                                         \
-    do {                                                                                                                \
-        const size_t dyn = (RM_) == 64 ? dyn64 : 0;                                                                     \
-        if (dyn) (void)hipFuncSetAttribute((const void*)gemm_f64_kernel<BT, TR, EP, RM_>,                               \
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);                       \
-        hipLaunchKernelGGL((gemm_f64_kernel<BT, TR, EP, RM_>), grid, dim3(256), dyn, s, g, nrb, ncb, splitk, pair);      \
-    } while (0)
-#else
 #define LAUNCH(BT, TR, EP, RM_) hipLaunchKernelGGL((gemm_f64_kernel<BT, TR, EP, RM_>), grid, dim3(256), 0, s, g, nrb, ncb, splitk, pair)
-#endif
     if (B_T) {
         if (g.epi != EPI_STORE) return MOBOCMF_BAD_ARG;
         LAUNCH(true, false, EPI_STORE, 128);
@@ -1006,14 +870,6 @@ __global__ void reduce_slabs_kernel(const double* slabs, int64_t slab_stride, in
     if (tril && j > i) v = 0.0;
     if (accumulate) v += out[(int64_t)i * ld + j];
     out[(int64_t)i * ld + j] = v;
-}
-
-int launch_reduce_slabs(const double* slabs, int64_t slab_stride, int nslab, double* out, int64_t ld, int Mr,
-                        double scale, int lower_only, int accumulate, hipStream_t s) {
-    int64_t n = (int64_t)Mr * Mr;
-    hipLaunchKernelGGL(reduce_slabs_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, slabs, slab_stride,
-                       nslab, out, ld, Mr, (int64_t)Mr, scale, lower_only, lower_only, accumulate, (int64_t)0, (int64_t)0);
-    return hipGetLastError() == hipSuccess ? MOBOCMF_OK : MOBOCMF_HIP_ERROR;
 }
 
 // Hand-over to the tiled MFMA kernels (largest dimension), from tools/size_sweep.py + the C3 bench: the 16x16-block

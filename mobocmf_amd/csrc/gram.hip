@@ -387,43 +387,6 @@ __global__ __launch_bounds__(GT) void gram_bwd_kernel(GramArgs g) {
     if (KIND == 1 && tid < gm) g.dzf_part[(int64_t)blockIdx.x * g.Mp + m0 + tid] = dzf_s[tid];
 }
 
-// out[j] (+)= scale * sum_p part[p*stride + j]
-__global__ void sum_partials_kernel(const double* part, int64_t P, int64_t stride, double* out, int64_t len,
-                                    double scale, int accumulate) {
-    int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= len) return;
-    double v = 0.0;
-    for (int64_t p = 0; p < P; ++p) v += part[p * stride + j];
-    v *= scale;
-    out[j] = accumulate ? out[j] + v : v;
-}
-
-// many partials, few outputs: one block per output j, threads stride over the partials
-__global__ void sum_partials_wide_kernel(const double* part, int64_t P, int64_t stride, double* out, int64_t len,
-                                         double scale, int accumulate) {
-    __shared__ double sh[4];
-    const int64_t j = blockIdx.x;
-    double v = 0.0;
-    for (int64_t p = threadIdx.x; p < P; p += 256) v += part[p * stride + j];
-    v += __shfl_xor(v, 1); v += __shfl_xor(v, 2); v += __shfl_xor(v, 4);
-    v += __shfl_xor(v, 8); v += __shfl_xor(v, 16); v += __shfl_xor(v, 32);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        v = (sh[0] + sh[1] + sh[2] + sh[3]) * scale;
-        out[j] = accumulate ? out[j] + v : v;
-    }
-}
-
-// out[b] = sum_{s<div} in[b*div + s]
-__global__ void group_sum_kernel(const double* in, double* out, int64_t nout, int div, int accumulate) {
-    int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= nout) return;
-    double v = 0.0;
-    for (int s = 0; s < div; ++s) v += in[j * div + s];
-    out[j] = accumulate ? out[j] + v : v;
-}
-
 #define SUM_MULTI_MAX 8
 // Several reductions in ONE launch: consecutive block ranges belong to consecutive tasks; a task with many partials per
 // output and few outputs is reduced "wide" (one block per output, threads stride over the partials), the others one
@@ -482,9 +445,6 @@ __global__ void sum_partials_multi_kernel(SumTasksArg T) {
     t.out[j] = t.accumulate ? t.out[j] + v : v;
 }
 
-int launch_sum_partials(const double* part, int64_t P, int64_t stride, double* out, int64_t len, double scale,
-                        int accumulate, hipStream_t s);
-
 int launch_sum_partials_multi(const SumTask* tasks, int n, hipStream_t s) {
     if (n > SUM_MULTI_MAX) {
         for (int i = 0; i < n; i += SUM_MULTI_MAX) {
@@ -510,19 +470,6 @@ int launch_sum_partials_multi(const SumTask* tasks, int n, hipStream_t s) {
     if (m == 0) return MOBOCMF_OK;
     if (nb > 0x7fffffff) return MOBOCMF_BAD_ARG;
     hipLaunchKernelGGL(sum_partials_multi_kernel, dim3((unsigned)nb), dim3(256), 0, s, T);
-    return hipGetLastError() == hipSuccess ? MOBOCMF_OK : MOBOCMF_HIP_ERROR;
-}
-
-int launch_sum_partials(const double* part, int64_t P, int64_t stride, double* out, int64_t len, double scale,
-                        int accumulate, hipStream_t s) {
-    if (len <= 0) return MOBOCMF_OK;
-    if (P >= 64 && len <= 4096) {
-        hipLaunchKernelGGL(sum_partials_wide_kernel, dim3((unsigned)len), dim3(256), 0, s, part, P, stride, out, len,
-                           scale, accumulate);
-        return hipGetLastError() == hipSuccess ? MOBOCMF_OK : MOBOCMF_HIP_ERROR;
-    }
-    hipLaunchKernelGGL(sum_partials_kernel, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, s, part, P, stride, out,
-                       len, scale, accumulate);
     return hipGetLastError() == hipSuccess ? MOBOCMF_OK : MOBOCMF_HIP_ERROR;
 }
 

@@ -79,13 +79,6 @@ __device__ __forceinline__ void il_publish_store(unsigned long long* w, unsigned
         __hip_atomic_store(w, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 }
-__device__ __forceinline__ void il_publish_add(unsigned long long* w) {
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        __threadfence();
-        atomicAdd(w, 1ull);
-    }
-}
 
 // ---------------------------------------------------------------------------------------------------- host side
 struct IlGuard {

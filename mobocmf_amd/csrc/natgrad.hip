@@ -12,12 +12,6 @@
 #include "common.h"
 #include "natgrad_schedule.h"
 
-int launch_potrf_z(double* A, int64_t ld, int Mp, int M, double* Dinv, double* Ld, int32_t* const* info, int nz, int64_t zs,
-                   double* zero0, double* zero1, void* sync, int* inverse_done, hipStream_t s);
-int launch_trtri_z(const double* L, int64_t ld, int Mp, const double* Dinv, double* Linv, double* T, double* ws,
-                   int64_t ws_elems, int nz, int64_t zs, hipStream_t s);
-int launch_phi_z(const double* T3, int Mp, double* P, int nz, int64_t zs, hipStream_t s);
-
 #define TRY(x)               \
     do {                     \
         int _rc = (x);       \
