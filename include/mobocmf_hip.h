@@ -905,6 +905,50 @@ int mobocmf_ascent_adam_step(double* x, const double* gx, int32_t n_models, int3
 int mobocmf_select_topk(const double* vals, int32_t n, int32_t k, const double* x, int32_t d, double* out_vals,
                         int64_t* out_idx, double* out_x, mobocmf_stream_t stream);
 
+/* ---- Predictive moments of fitted surrogates LARGER than the one-launch steps take (MOBOCMF_COOP_MAX_M < M <=
+ * MOBOCMF_FROZEN_MAX_M) against their FROZEN chains, and the gradient w.r.t. the test points (csrc/frozen_predict.hip): the two
+ * model evaluations of a device acquisition search at those sizes.  n models at the same kind of T test points; the parameters
+ * are constants, so every layer's M x M chain exists already: chain[l] is the layer's CHAIN state, the first
+ * mobocmf_layer_chain_state_bytes of the `saved` buffer a MOBOCMF_PHASE_CHAIN forward with branch = 1 filled, read only.
+ * The algebra is the layer's eval branch (no clamp, floor 1e-10), column by column:
+ *   layer 0 at x_t:               k = k(Z, x_t), A = L^-1 k, C = U^T A, mean = a^T A, var = max(k_nn - |A|^2 + |C|^2, 1e-10)
+ *   layer l >= 1 at column t S + s: f = mean_{l-1} + sqrt(var_{l-1}) samples[l][s] (layer 0's column t serves the S replicas),
+ *                                 then the same with k = k([Z_x, zf_l], [x_t, f])
+ * mode MOBOCMF_STEP_FORWARD: top_mean / top_var (T S; T for L = 1) <- the top layer's moments WITHOUT likelihood noise.
+ * mode MOBOCMF_STEP_INPUT_GRADIENTS: the same, and grad (T x d) <- d / d x of <seed_gmean, top mean> + <seed_gvar, top var>
+ *   (a column at the variance floor passes no variance gradient), summed over the layers and the S columns of a base row in a
+ *   fixed order.  The launch forms its panels itself: it does not depend on an earlier FORWARD launch.
+ * One launch on `stream`; a workgroup owns (model, a block of base rows) and nothing is shared between workgroups: no in-launch
+ * wait, no atomics, no status word; two calls on the same inputs are bitwise equal; capturable (the FIRST call per device and
+ * mode sets a function attribute and belongs outside a capture).  The kernel reads the descriptors from DEVICE memory
+ * (dev_models); host_models is the same array in host memory, for validation and launch geometry.
+ * Limits: 1 <= L <= MOBOCMF_TINY_MAX_LAYERS layers of kind 0, 1, 1 with one M; 1 <= M <= MOBOCMF_FROZEN_MAX_M (two [M][16]
+ * panels in LDS); d <= MOBOCMF_TINY_MAX_D; L = 1: S = 1, else 2 <= S <= MOBOCMF_MAX_XDIV; T S <= MOBOCMF_ACQ_MAX_COLUMNS;
+ * n_models <= 256.  MOBOCMF_BAD_ARG otherwise, for a NULL pointer among those the mode reads, or for another mode.
+ * mobocmf_frozen_predict_work_bytes: the bytes of `work` a launch of `mode` needs -- 0 for both modes of this version (the
+ * panels never leave LDS: a group built for values only, or for 5000 columns, holds no M x T S storage); work may then be NULL. */
+#define MOBOCMF_FROZEN_MAX_M 512
+typedef struct mobocmf_frozen_predict_model {
+    int32_t L, M, d, S;
+    int32_t T;                                   /* test points */
+    int32_t kind[MOBOCMF_TINY_MAX_LAYERS];       /* 0, 1, 1 */
+    const void* chain[MOBOCMF_TINY_MAX_LAYERS];  /* the layer's CHAIN state (mobocmf_layer_chain_state_bytes) */
+    const double* Zx[MOBOCMF_TINY_MAX_LAYERS];   /* M x d (the layers share one Z_x; the pointers may be equal) */
+    const double* zf[MOBOCMF_TINY_MAX_LAYERS];   /* M (layers >= 1) */
+    const double* hyp[MOBOCMF_TINY_MAX_LAYERS];  /* packed constrained hyper-parameters (the layer entry points' order) */
+    const double* samples[MOBOCMF_TINY_MAX_LAYERS]; /* S (layers >= 1): the layer's fixed draws */
+    const double* x;                             /* T x d, shared by the models of a group */
+    double* top_mean;                            /* T S */
+    double* top_var;
+    const double* seed_gmean;                    /* T S (MOBOCMF_STEP_INPUT_GRADIENTS) */
+    const double* seed_gvar;
+    double* grad;                                /* T x d (MOBOCMF_STEP_INPUT_GRADIENTS) */
+    void* work;                                  /* mobocmf_frozen_predict_work_bytes (NULL when that is 0) */
+} mobocmf_frozen_predict_model;
+int mobocmf_frozen_predict_work_bytes(const mobocmf_frozen_predict_model* model, int32_t mode, size_t* bytes);
+int mobocmf_frozen_predict(const mobocmf_frozen_predict_model* host_models, const mobocmf_frozen_predict_model* dev_models,
+                           int32_t n_models, int32_t mode, mobocmf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

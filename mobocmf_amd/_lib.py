@@ -40,6 +40,7 @@ class LayerDesc(ctypes.Structure):
 
 TINY_MAX_LAYERS, TINY_MAX_M, TINY_MAX_D = 3, 32, 8      # MOBOCMF_TINY_MAX_* of include/mobocmf_hip.h
 COOP_MAX_M = 128                                         # MOBOCMF_COOP_MAX_M
+FROZEN_MAX_M = 512                                       # MOBOCMF_FROZEN_MAX_M
 # MOBOCMF_STEP_*: do_update of mobocmf_tiny_elbo_step / mobocmf_coop_elbo_step
 STEP_GRADIENTS, STEP_UPDATE, STEP_FORWARD, STEP_INPUT_GRADIENTS, STEP_COUPLED = range(5)
 STEP_CHAIN_VALID = 16                                    # MOBOCMF_STEP_CHAIN_VALID
@@ -72,6 +73,18 @@ class TinyCoupling(ctypes.Structure):
                 ("log_eps", ctypes.c_double), ("log_1m_eps", ctypes.c_double), ("losses", ctypes.c_void_p),
                 ("barrier", ctypes.c_void_p), ("status", ctypes.c_void_p), ("n_models", ctypes.c_int32),
                 ("reserved", ctypes.c_int32)]
+
+
+class FrozenPredictModel(ctypes.Structure):
+    """mobocmf_frozen_predict_model: one surrogate of mobocmf_frozen_predict (the kernel reads the array from DEVICE memory)."""
+    _L = TINY_MAX_LAYERS
+    _fields_ = [("L", ctypes.c_int32), ("M", ctypes.c_int32), ("d", ctypes.c_int32), ("S", ctypes.c_int32),
+                ("T", ctypes.c_int32), ("kind", ctypes.c_int32 * _L),
+                ("chain", ctypes.c_void_p * _L), ("Zx", ctypes.c_void_p * _L), ("zf", ctypes.c_void_p * _L),
+                ("hyp", ctypes.c_void_p * _L), ("samples", ctypes.c_void_p * _L),
+                ("x", ctypes.c_void_p), ("top_mean", ctypes.c_void_p), ("top_var", ctypes.c_void_p),
+                ("seed_gmean", ctypes.c_void_p), ("seed_gvar", ctypes.c_void_p), ("grad", ctypes.c_void_p),
+                ("work", ctypes.c_void_p)]
 
 
 class NatgradSmallLayer(ctypes.Structure):
@@ -203,8 +216,11 @@ SYMBOLS = {
     "mobocmf_jes_group_forward": [_P, _P, _I32, _I32, _I32, _P, _I32, _P, _I32, _P, _I32, _P, _P, _P],
     "mobocmf_ascent_adam_step": [_P, _P, _I32, _I32, _I32, _P, _P, _P, _P, _D, _D, _D, _D, _P, _P],
     "mobocmf_select_topk": [_P, _I32, _I32, _P, _I32, _P, _P, _P, _P],
+    "mobocmf_frozen_predict_work_bytes": [ctypes.POINTER(FrozenPredictModel), _I32, ctypes.POINTER(_SZ)],
+    "mobocmf_frozen_predict": [_P, _P, _I32, _I32, _P],
 }
 ACQ_MAX_PAIRS, TOPK_MAX_K, TOPK_MAX_N = 32, 64, 4096      # MOBOCMF_ACQ_MAX_PAIRS / MOBOCMF_TOPK_MAX_K / MOBOCMF_TOPK_MAX_N
+ACQ_MAX_COLUMNS = 1 << 24                                 # MOBOCMF_ACQ_MAX_COLUMNS
 NATGRAD_MAX_M, NATGRAD_MAX_LAYERS = 1024, 4      # MOBOCMF_NATGRAD_MAX_M, layers per mobocmf_natgrad_step call
 NATGRAD_SMALL_MAX_M = 128                        # MOBOCMF_NATGRAD_SMALL_MAX_M
 MAX_D, MAX_XDIV = 32, 48        # MOBOCMF_MAX_D / MOBOCMF_MAX_XDIV of include/mobocmf_hip.h

@@ -8,10 +8,10 @@ N3) is replaced by ``optimize_acqf_multistart``: the same recipe -- ``raw_sample
 iteration is a single pair of model evaluations.  With surrogates sharded over ranks the coupled acquisition is the
 all-gather + sum of mobocmf_amd.parallel.coupled_acquisition.
 
-``JESMOC_MFDGP(search="device")``: wherever the black-boxes of a fidelity fit a one-launch predict group the whole search --
-scoring of the raw candidates, choice of the restarts, the ascent, the best iterate, the final pick -- runs on the GPU
-(util/acq_search.py DeviceAcqSearch, csrc/acq_search.hip), one graph replay per iterate, and the host reads the device once per
-``get_nextpoint_coupled`` call.
+``JESMOC_MFDGP(search="device")``: wherever the black-boxes of a fidelity fit a one-launch predict group (M <= 128) or the
+frozen-chain predict group (128 < M <= 512, util/panel_predict.py) the whole search -- scoring of the raw candidates, choice of
+the restarts, the ascent, the best iterate, the final pick -- runs on the GPU (util/acq_search.py DeviceAcqSearch,
+csrc/acq_search.hip), one graph replay per iterate, and the host reads the device once per ``get_nextpoint_coupled`` call.
 """
 import contextlib
 
@@ -172,6 +172,7 @@ class JESMOC_MFDGP:
     def __getstate__(self):
         state = self.__dict__.copy()
         state.pop("_tiny_groups", None)      # device descriptors: rebuilt on first use
+        state.pop("_panel_groups", None)
         state.pop("_device_searches", None)  # ... and the captured graphs over them
         return state
 
@@ -191,6 +192,20 @@ class JESMOC_MFDGP:
                 from ..util import coop_step as CS
                 ok = on_gpu and all(CS.fits_predict(m, fidelity, T, d) for m in models)
                 cache[key] = CS.CoopPredictGroup(models, fidelity, T, d) if ok else None
+        return cache[key]
+
+    def _panel_group(self, jess, fidelity, T, d, want_gradients):
+        """PanelPredictGroup (128 < M <= 512, util/panel_predict.py) over (uncond, cond) of every black-box of ``fidelity`` for T
+        test points when all of them fit, else None.  A cache of the DEVICE engine alone: ``coupled_acq`` never looks here, so
+        the host engine evaluates these sizes through the layer path as ever."""
+        cache = self.__dict__.setdefault("_panel_groups", {})
+        key = (fidelity, T, d, bool(want_gradients))
+        if key not in cache:
+            from ..util import panel_predict as PP
+            models = [m for jes in jess for m in (jes.mfdgp_uncond, jes.mfdgp_cond)]
+            ok = bool(models) and all(p.is_cuda for p in models[0].parameters()) and \
+                all(PP.fits_predict(m, fidelity, T, d) for m in models)
+            cache[key] = PP.PanelPredictGroup(models, fidelity, T, d, want_gradients=want_gradients) if ok else None
         return cache[key]
 
     def coupled_acq(self, X, fidelity):
@@ -227,7 +242,8 @@ class JESMOC_MFDGP:
         finally:
             self._search_running = False
             failed = None      # every group is thawed, also after one of them reported an abandoned wait
-            for grp in self.__dict__.get("_tiny_groups", {}).values():
+            groups = list(self.__dict__.get("_tiny_groups", {}).values()) + list(self.__dict__.get("_panel_groups", {}).values())
+            for grp in groups:
                 if grp is not None and hasattr(grp, "thaw"):
                     try:
                         grp.thaw()
@@ -239,18 +255,24 @@ class JESMOC_MFDGP:
     def _device_search(self, fidelity):
         """(DeviceAcqSearch, raw-candidate group) of ``fidelity`` when its search can stay on the GPU -- the condition under
         which ``coupled_acq`` evaluates through a one-launch group, and a group fits T = num_restarts and the raw candidates,
-        whole or in up to ``MAX_RAW_CHUNKS`` equal chunks (200 candidates x 25 samples are beyond the kernels' 4096 columns) --
-        else None: M > 128, sharded surrogates, CPU tensors keep the host loop."""
+        whole or in up to ``MAX_RAW_CHUNKS`` equal chunks (200 candidates x 25 samples are beyond the kernels' 4096 columns); or,
+        where no one-launch group fits, frozen-chain groups do (128 < M <= 512: the raw candidates whole, no column limit
+        there) -- else None: M > 512, S = 1, sharded surrogates, CPU tensors keep the host loop."""
         jess = list(self.objectives[fidelity].values()) + list(self.constraints[fidelity].values())
         bounds = self.standard_bounds
         if not (self.use_tiny_step and jess and bounds is not None and bounds.is_cuda and parallel.world()[1] == 1):
             return None
         d = bounds.shape[1]
-        grp = self._tiny_group(jess, fidelity, self.num_restarts, d)
-        if grp is None or self.num_restarts > self.raw_samples:
+        if self.num_restarts > self.raw_samples:
             return None
-        chunks = [c for c in range(1, self.MAX_RAW_CHUNKS + 1) if self.raw_samples % c == 0]
-        raw = next((g for g in (self._tiny_group(jess, fidelity, self.raw_samples // c, d) for c in chunks) if g is not None), None)
+        grp = self._tiny_group(jess, fidelity, self.num_restarts, d)
+        if grp is None:
+            grp = self._panel_group(jess, fidelity, self.num_restarts, d, True)
+            raw = None if grp is None else self._panel_group(jess, fidelity, self.raw_samples, d, False)
+        else:
+            chunks = [c for c in range(1, self.MAX_RAW_CHUNKS + 1) if self.raw_samples % c == 0]
+            raw = next((g for g in (self._tiny_group(jess, fidelity, self.raw_samples // c, d) for c in chunks) if g is not None),
+                       None)
         if raw is None:
             return None
         cache = self.__dict__.setdefault("_device_searches", {})

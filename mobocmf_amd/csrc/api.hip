@@ -1183,4 +1183,48 @@ int mobocmf_check_info(const int32_t* info, int32_t* pivot, mobocmf_stream_t str
     return h == 0 ? MOBOCMF_OK : MOBOCMF_NOT_PD;
 }
 
+// ---- frozen-chain predict (frozen_predict.hip)
+static bool frozen_model_sizes_ok(const mobocmf_frozen_predict_model* m) {
+    if (!m || m->L < 1 || m->L > MOBOCMF_TINY_MAX_LAYERS || m->M < 1 || m->M > MOBOCMF_FROZEN_MAX_M || m->d < 1 ||
+        m->d > MOBOCMF_TINY_MAX_D || m->T < 1)
+        return false;
+    if (m->L == 1 ? m->S != 1 : (m->S < 2 || m->S > MOBOCMF_MAX_XDIV)) return false;
+    return (int64_t)m->T * m->S <= MOBOCMF_ACQ_MAX_COLUMNS;
+}
+
+int mobocmf_frozen_predict_work_bytes(const mobocmf_frozen_predict_model* model, int32_t mode, size_t* bytes) {
+    if (!bytes || !frozen_model_sizes_ok(model) || (mode != MOBOCMF_STEP_FORWARD && mode != MOBOCMF_STEP_INPUT_GRADIENTS))
+        return MOBOCMF_BAD_ARG;
+    *bytes = 0;      // both modes form their panels in LDS
+    return MOBOCMF_OK;
+}
+
+int mobocmf_frozen_predict(const mobocmf_frozen_predict_model* host_models, const mobocmf_frozen_predict_model* dev_models,
+                           int32_t n_models, int32_t mode, mobocmf_stream_t stream) {
+    if (!host_models || !dev_models || n_models < 1 || n_models > 256) return MOBOCMF_BAD_ARG;
+    if (mode != MOBOCMF_STEP_FORWARD && mode != MOBOCMF_STEP_INPUT_GRADIENTS) return MOBOCMF_BAD_ARG;
+    for (int i = 0; i < n_models; ++i) {
+        const mobocmf_frozen_predict_model& m = host_models[i];
+        if (!frozen_model_sizes_ok(&m) || !m.x || !m.top_mean || !m.top_var) return MOBOCMF_BAD_ARG;
+        if (mode == MOBOCMF_STEP_INPUT_GRADIENTS && (!m.grad || !m.seed_gmean || !m.seed_gvar)) return MOBOCMF_BAD_ARG;
+        for (int l = 0; l < m.L; ++l) {
+            if (m.kind[l] != (l ? 1 : 0) || !m.chain[l] || !m.Zx[l] || !m.hyp[l] || (l && (!m.zf[l] || !m.samples[l])))
+                return MOBOCMF_BAD_ARG;
+            // the kernel indexes the CHAIN state by the FCS_* order (common.h): this library's own carving must agree
+            Dims D = {};
+            D.M = m.M;
+            D.Mp = (int)round_up(m.M, TILE);
+            const int64_t mm = (int64_t)D.Mp * D.Mp;
+            Bump b((void*)m.chain[l], ~(size_t)0 >> 1);
+            ChainWs c;
+            carve_chain_state(b, D, c);
+            const double* cs = (const double*)m.chain[l];
+            if (c.Linv != cs + FCS_LINV * mm || c.LinvT != cs + FCS_LINVT * mm || c.U != cs + FCS_U * mm ||
+                c.UT != cs + FCS_UT * mm || c.a != cs + FCS_A * mm)
+                return MOBOCMF_BAD_ARG;
+        }
+    }
+    return launch_frozen_predict(host_models, dev_models, n_models, mode == MOBOCMF_STEP_INPUT_GRADIENTS, (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -212,6 +212,13 @@ int launch_dl_from_t2_z(const double* T2, const double* L, const double* const* 
 int launch_phi_z(const double* T3, int Mp, double* P, int nz, int64_t zs, hipStream_t s);
 int launch_symmetrize_z(const double* S, int Mp, double* G, int nz, int64_t zs, hipStream_t s);
 
+// ------------------------------------------------------------------ frozen-chain predict (frozen_predict.hip)
+// The kernel indexes a layer's CHAIN state as Mp x Mp matrices in this order, then the Mp-vectors a and m; api.hip checks its
+// own carving of the state against these before a launch.
+enum { FCS_L = 0, FCS_LINV = 1, FCS_LINVT = 2, FCS_U = 3, FCS_UT = 4, FCS_LS = 5, FCS_A = 6 };
+int launch_frozen_predict(const mobocmf_frozen_predict_model* host_models, const mobocmf_frozen_predict_model* dev_models,
+                          int n_models, bool input_gradients, hipStream_t s);
+
 // ------------------------------------------------------------------ hyper-parameter packing
 // kind 0: [alpha, ls[0..d)]                                   (1 + d doubles)
 // kind 1: [a1, af, nu, a2, lsf, ls1[0..d), ls2[0..d)]         (5 + 2d doubles)

@@ -1,0 +1,361 @@
+// Predictive moments of fitted surrogates with 128 < M <= 512 inducing points against their FROZEN chains, and the gradient
+// w.r.t. the test points: mobocmf_frozen_predict (include/mobocmf_hip.h), the model evaluation of an acquisition search
+// (JESMOC_MFDGP(search="device"), util/panel_predict.py) where the one-launch steps (tiny_step.hip, coop_step.hip) stop.
+//
+// A search evaluates n models at the same T test points, T S columns per model -- 125 at the search's own sizes: one tile of
+// the layer path's grid-filling products -- against parameters that stay constant, so L^-1, L^-T, U, U^T and a of every layer
+// exist already (the layer's CHAIN state, mobocmf_layer_chain_state_bytes).  Every column of every layer depends on its own
+// base row only:
+//
+//   a WORKGROUP owns (model, a block of base rows), runs ALL layers for those rows and their S replicas, 16 columns at a time,
+//   and sums its rows' d/dx in a fixed order.
+//
+// Nothing is shared between workgroups: no in-launch barrier, no counters, no atomics, no wait -- hence nothing to abandon and no
+// status word.  Per block of 16 columns the layer's eval branch runs column by column,
+//
+//   K = k(Z~, [x, f])   A = L^-1 K   C = U^T A   mean = a^T A   var = max(k_nn - |A|^2 + |C|^2, 1e-10)
+//   dA = 2 U (C gv) + a g_mean - 2 A gv   dK = L^-T dA   then the Gram backward w.r.t. x and f,
+//
+// the four triangular products on v_mfma_f64_16x16x4_f64 with the M x M operand streamed from global memory (L2: every workgroup
+// of a model reads the same 2 MB at M = 512) and the [M][16] panels in LDS -- two of them, 64 KB each at M = 512, which is what
+// bounds M: K -> A -> C reuse them in turn (C over K), and so do dA (over A, element by element) and dK (over C).
+// MOBOCMF_STEP_INPUT_GRADIENTS forms the panels again instead of reading saved ones: the top layer's blocks run forward and
+// backward back to back on the panels they have in LDS, the layers below are re-formed (their S-fold fewer columns at layer 0),
+// and no M x T S storage exists in either mode.
+#include <atomic>
+
+#include "small_step_common.h"
+#include "tile16.h"
+
+namespace {
+
+constexpr int FT = 512;                      // threads per workgroup: two wavefronts per SIMD (the products wait for L2)
+constexpr int FNW = FT / 64;
+constexpr int FXLD = 16;                     // a panel row: the 32 lanes of a ds_read_b64 group read 256 contiguous bytes
+constexpr int FCOLS = MOBOCMF_MAX_XDIV;      // columns of a layer a workgroup holds, at most (S > 16: one base row)
+constexpr int FXFW = DBT + 2;                // a staged column: x (zero padded), f, valid flag
+constexpr int FRED = DBT + 1;
+
+typedef const __attribute__((address_space(1))) double* gcd;
+#define GC(p) ((gcd)(p))
+
+// base rows per workgroup: one 16-column block per layer where S allows it
+__host__ __device__ inline int frozen_rows_per_wg(int L, int S) { return L == 1 ? 16 : (S >= 16 ? 1 : 16 / S); }
+
+// One 16 x 16 tile of T X for a panel X [k][FXLD] in LDS and T given k-major in global memory (Tk[k * ld + row] = T[row][k]),
+// k tiles kt0 .. kt1-1; the fragments of four k tiles are requested together (coop_step.hip tile_tx).
+__device__ __forceinline__ v4d tile_tx(const double* Tk_, int ld, const double* X, int t, int kt0, int kt1, int lane) {
+    v4d acc = {0.0, 0.0, 0.0, 0.0};
+    const int li = lane & 15, lk = lane >> 4;
+    gcd tp = GC(Tk_) + (int64_t)lk * ld + t * 16 + li;
+    const double* xp = X + lk * FXLD + li;
+    for (int kb = kt0; kb < kt1; kb += 4) {
+        double a[4][4];
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk) {
+            const int kt = kb + kk < kt1 ? kb + kk : kt1 - 1;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) a[kk][q] = tp[(int64_t)(kt * 16 + 4 * q) * ld];
+        }
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk) {
+            if (kb + kk < kt1) {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) acc = mfma(a[kk][q], xp[((kb + kk) * 16 + 4 * q) * FXLD], acc);
+            }
+        }
+    }
+    return acc;
+}
+__device__ __forceinline__ double xor_add(double v, int mask) { return v + __shfl_xor(v, mask); }
+// the i-th output tile of wavefront w: w, 2 FNW - 1 - w, 2 FNW + w, ... -- a lower and an upper triangular operand (k tiles
+// 0..t and t..nt-1) both give every wavefront the same number of k tiles
+__device__ __forceinline__ int tile_of_wave(int i, int w) { return (i & 1) ? i * FNW + FNW - 1 - w : i * FNW + w; }
+
+template <bool INGRAD>
+__global__ __launch_bounds__(FT) void frozen_predict_kernel(const mobocmf_frozen_predict_model* models) {
+    extern __shared__ __attribute__((aligned(16))) double fp_lds[];
+    __shared__ double hy[TLM * HS], il[TLM * 2 * DBT], epsv[TLM * FCOLS];
+    __shared__ double xr[16 * DBT], gxacc[16 * DBT], xf[16 * FXFW], gcol[32], dxblk[16 * FRED];
+    __shared__ double vmean[TLM * FCOLS], vvar[TLM * FCOLS];      // per column of every layer: the moments ...
+    __shared__ double vgm[TLM * FCOLS], vge[TLM * FCOLS];         // ... and what the layer above sent back: sum g_f, sum g_f eps
+    __shared__ double red[FNW * 16 * FRED];
+
+    const mobocmf_frozen_predict_model& md = models[blockIdx.y];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 15, lk = lane >> 4;
+    const int L = md.L, M = md.M, d = md.d, S = L > 1 ? md.S : 1, T = md.T;
+    const int Mp = (M + TILE - 1) / TILE * TILE, nt = (M + 15) / 16, Mr = nt * 16;
+    const int RB = frozen_rows_per_wg(L, S);
+    const int r0 = blockIdx.x * RB;
+    if (r0 >= T) return;      // (a launch's grid is sized for its largest model)
+    const int nb = T - r0 < RB ? T - r0 : RB;
+    double* X0 = fp_lds;
+    double* X1 = X0 + Mr * FXLD;
+    double* av = X1 + Mr * FXLD;
+
+    // ---- constants of the launch: packed hyper-parameters, inverse lengthscales, the layers' fixed samples, the base rows
+    for (int e = tid; e < TLM * HS; e += FT) {
+        const int l = e / HS, t = e % HS;
+        hy[e] = (l < L && t < (l ? 5 + 2 * d : 1 + d)) ? GC(md.hyp[l])[t] : 0.0;
+    }
+    for (int e = tid; e < TLM * FCOLS; e += FT) {
+        const int l = e / FCOLS, s = e % FCOLS;
+        epsv[e] = (l >= 1 && l < L && s < S) ? GC(md.samples[l])[s] : 0.0;
+        vgm[e] = 0.0;
+        vge[e] = 0.0;
+    }
+    for (int e = tid; e < 16 * DBT; e += FT) {
+        const int r = e / DBT, k = e % DBT;
+        xr[e] = (r < nb && k < d) ? GC(md.x)[(int64_t)(r0 + r) * d + k] : 0.0;
+        gxacc[e] = 0.0;
+    }
+    __syncthreads();
+    for (int e = tid; e < TLM * 2 * DBT; e += FT) {
+        const int l = e / (2 * DBT), kk = e % (2 * DBT), k2 = kk % DBT;
+        double v = 0.0;
+        if (l < L && k2 < d) {
+            if (l == 0) v = kk < DBT ? 1.0 / hy[l * HS + 1 + k2] : 0.0;
+            else v = 1.0 / hy[l * HS + 5 + (kk < DBT ? 0 : d) + k2];
+        }
+        il[e] = v;
+    }
+    __syncthreads();
+
+    // ---- one block of 16 columns of layer l: forward, and (bwd) backward on the panels it has just formed
+    auto block = [&](int l, int cb, bool bwd) {
+        const int kind = l > 0, div = l ? S : 1, nc = nb * div, c0 = cb * 16;
+        const double* hyl = hy + l * HS;
+        const double* ill = il + l * 2 * DBT;
+        const int64_t mm = (int64_t)Mp * Mp;
+        const double* cs = (const double*)md.chain[l];      // [L | L^-1 | L^-T | U | U^T | L_S | a | m], Mp x Mp each, then Mp
+        const double *Linv = cs + FCS_LINV * mm, *LinvT = cs + FCS_LINVT * mm, *U = cs + FCS_U * mm, *UT = cs + FCS_UT * mm;
+        gcd ag = GC(cs + FCS_A * mm), zx = GC(md.Zx[l]), zf = GC(md.zf[l]);
+        // the block's columns: base row, f = mean + sqrt(var) eps of the layer below (layer 0's column serves the S replicas)
+        if (tid < 16) {
+            const int c = c0 + tid, valid = c < nc, b = valid ? c / div : 0;
+            double f = 0.0;
+            if (valid && l > 0) {
+                const int pc = (l - 1) * FCOLS + (l == 1 ? b : c);
+                f = vmean[pc] + sqrt(vvar[pc]) * epsv[l * FCOLS + c % S];
+            }
+#pragma unroll
+            for (int k = 0; k < DBT; ++k) xf[tid * FXFW + k] = valid ? xr[b * DBT + k] : 0.0;
+            xf[tid * FXFW + DBT] = f;
+            xf[tid * FXFW + DBT + 1] = valid ? 1.0 : 0.0;
+        }
+        for (int e = tid; e < Mr; e += FT) av[e] = e < M ? ag[e] : 0.0;
+        __syncthreads();
+        // K
+#pragma unroll 1
+        for (int e = tid; e < Mr * 16; e += FT) {
+            const int m = e >> 4, j = e & 15;
+            double v = 0.0;
+            if (m < M && xf[j * FXFW + DBT + 1] != 0.0) {
+                double zb[ZW];
+#pragma unroll
+                for (int k = 0; k < DBT; ++k) zb[k] = k < d ? zx[(int64_t)m * d + k] : 0.0;
+                zb[DBT] = kind ? zf[m] : 0.0;
+                KV o;
+                kern_eval(kind, d, xf + j * FXFW, xf[j * FXFW + DBT], zb, hyl, ill, o);
+                v = o.k;
+            }
+            X0[m * FXLD + j] = v;
+        }
+        __syncthreads();
+        // A = L^-1 K
+        for (int i = 0; i * FNW < nt; ++i) {
+            const int t = tile_of_wave(i, wave);
+            if (t < nt) {
+                const v4d acc = tile_tx(LinvT, Mp, X0, t, 0, t + 1, lane);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) X1[(t * 16 + 4 * r + lk) * FXLD + li] = acc[r];
+            }
+        }
+        __syncthreads();
+        // C = U^T A (over K)
+        for (int i = 0; i * FNW < nt; ++i) {
+            const int t = tile_of_wave(i, wave);
+            if (t < nt) {
+                const v4d acc = tile_tx(U, Mp, X1, t, t, nt, lane);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) X0[(t * 16 + 4 * r + lk) * FXLD + li] = acc[r];
+            }
+        }
+        __syncthreads();
+        // moments: a thread keeps one column and every 32nd row; summed through the wavefront, then over the wavefronts in order
+        {
+            const int part = tid >> 4;
+            double q = 0.0, mu = 0.0, r = 0.0;
+            for (int m = part; m < Mr; m += FT / 16) {
+                const double a = X1[m * FXLD + li], c = X0[m * FXLD + li];
+                q += a * a;
+                mu += av[m] * a;
+                r += c * c;
+            }
+            q = xor_add(xor_add(q, 16), 32);
+            mu = xor_add(xor_add(mu, 16), 32);
+            r = xor_add(xor_add(r, 16), 32);
+            if (lane < 16) {
+                red[(wave * 16 + lane) * 3 + 0] = q;
+                red[(wave * 16 + lane) * 3 + 1] = mu;
+                red[(wave * 16 + lane) * 3 + 2] = r;
+            }
+        }
+        __syncthreads();
+        if (tid < 16) {
+            const int c = c0 + tid;
+            double gm = 0.0, gvc = 0.0;
+            if (c < nc) {
+                double q = 0.0, mu = 0.0, r = 0.0;
+#pragma unroll
+                for (int p = 0; p < FNW; ++p) {
+                    q += red[(p * 16 + tid) * 3 + 0];
+                    mu += red[(p * 16 + tid) * 3 + 1];
+                    r += red[(p * 16 + tid) * 3 + 2];
+                }
+                const double fn = xf[tid * FXFW + DBT];
+                const double knn = kind ? hyl[0] * (hyl[2] * fn * fn + hyl[1]) + hyl[3] : hyl[0];
+                const double vr = (knn - q) + r, var = vr < MINV ? MINV : vr;
+                vmean[l * FCOLS + c] = mu;
+                vvar[l * FCOLS + c] = var;
+                const int64_t gc = (int64_t)r0 * div + c;
+                if (l == L - 1) { md.top_mean[gc] = mu; md.top_var[gc] = var; }
+                if (INGRAD && bwd) {
+                    double gv;
+                    if (l == L - 1) { gm = GC(md.seed_gmean)[gc]; gv = GC(md.seed_gvar)[gc]; }
+                    else { gm = vgm[l * FCOLS + c]; gv = vge[l * FCOLS + c] * 0.5 / sqrt(var); }
+                    gvc = vr > MINV ? gv : 0.0;      // clamp_min passes gradient only above the floor
+                }
+            }
+            gcol[tid] = gm;
+            gcol[16 + tid] = gvc;
+        }
+        __syncthreads();
+        if (!INGRAD || !bwd) return;
+        // dA = 2 U (C gv) + a g_mean - 2 A gv (over A: an element of dA needs the same element of A only)
+        for (int i = 0; i * FNW < nt; ++i) {
+            const int t = tile_of_wave(i, wave);
+            if (t < nt) {
+                const v4d acc = tile_tx(UT, Mp, X0, t, 0, t + 1, lane);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int row = t * 16 + 4 * r + lk;
+                    X1[row * FXLD + li] = 2.0 * gcol[16 + li] * acc[r] + av[row] * gcol[li] - 2.0 * X1[row * FXLD + li] * gcol[16 + li];
+                }
+            }
+        }
+        __syncthreads();
+        // dK = L^-T dA (over C)
+        for (int i = 0; i * FNW < nt; ++i) {
+            const int t = tile_of_wave(i, wave);
+            if (t < nt) {
+                const v4d acc = tile_tx(Linv, Mp, X1, t, t, nt, lane);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) X0[(t * 16 + 4 * r + lk) * FXLD + li] = acc[r];
+            }
+        }
+        __syncthreads();
+        // Gram backward w.r.t. the columns' inputs: a thread keeps one column (FT is a multiple of 16) and sums over its inducing rows
+        {
+            double dxa[DBT], dfs = 0.0;
+#pragma unroll
+            for (int t = 0; t < DBT; ++t) dxa[t] = 0.0;
+#pragma unroll 1
+            for (int e = tid; e < Mr * 16; e += FT) {
+                const int m = e >> 4;
+                if (m < M && xf[li * FXFW + DBT + 1] != 0.0) {
+                    double zb[ZW];
+#pragma unroll
+                    for (int k = 0; k < DBT; ++k) zb[k] = k < d ? zx[(int64_t)m * d + k] : 0.0;
+                    zb[DBT] = kind ? zf[m] : 0.0;
+                    kern_back_in(kind, d, xf + li * FXFW, xf[li * FXFW + DBT], zb, hyl, ill, X0[m * FXLD + li], dxa, dfs);
+                }
+            }
+#pragma unroll
+            for (int t = 0; t <= DBT; ++t) {
+                const double v = xor_add(xor_add(t < DBT ? dxa[t < DBT ? t : 0] : dfs, 16), 32);
+                if (lane < 16) red[(wave * 16 + lane) * FRED + t] = v;
+            }
+        }
+        __syncthreads();
+        if (tid < 16 * FRED) {
+            const int j = tid / FRED, t = tid % FRED, c = c0 + j;
+            double sum = 0.0;
+#pragma unroll
+            for (int p = 0; p < FNW; ++p) sum += red[(p * 16 + j) * FRED + t];
+            if (t == DBT && kind) sum += gcol[16 + j] * hyl[0] * 2.0 * hyl[2] * xf[j * FXFW + DBT];      // d k_nn / d f
+            dxblk[tid] = c < nc ? sum : 0.0;
+        }
+        __syncthreads();
+        // the block's share of its base rows' d/dx, and of the gradients of the layer below, column by column in order
+        if (tid < 16 * DBT) {
+            const int r = tid / DBT, t = tid % DBT;
+            if (r < nb) {
+                double sum = gxacc[tid];
+                for (int j = 0; j < 16; ++j)
+                    if (c0 + j < nc && (c0 + j) / div == r) sum += dxblk[j * FRED + t];
+                gxacc[tid] = sum;
+            }
+        } else if (l > 0 && tid >= 256 && tid < 256 + FCOLS) {
+            const int pc = tid - 256, npc = l == 1 ? nb : nc;
+            if (pc < npc) {
+                double gm = vgm[(l - 1) * FCOLS + pc], ge = vge[(l - 1) * FCOLS + pc];
+                for (int j = 0; j < 16; ++j) {
+                    const int c = c0 + j;
+                    if (c < nc && (l == 1 ? c / S : c) == pc) {
+                        const double g = dxblk[j * FRED + DBT];
+                        gm += g;
+                        ge += g * epsv[l * FCOLS + c % S];
+                    }
+                }
+                vgm[(l - 1) * FCOLS + pc] = gm;
+                vge[(l - 1) * FCOLS + pc] = ge;
+            }
+        }
+        __syncthreads();
+    };
+
+    auto blocks_of = [&](int l) { return (nb * (l ? S : 1) + 15) / 16; };
+    for (int l = 0; l < L; ++l)
+        for (int cb = 0; cb < blocks_of(l); ++cb) block(l, cb, l == L - 1);
+    if constexpr (INGRAD) {
+        for (int l = L - 2; l >= 0; --l)
+            for (int cb = 0; cb < blocks_of(l); ++cb) block(l, cb, true);
+        if (tid < nb * d) md.grad[(int64_t)r0 * d + tid] = gxacc[(tid / d) * DBT + tid % d];
+    }
+}
+
+inline size_t frozen_lds_bytes(int M) { return (size_t)(2 * FXLD + 1) * ((M + 15) / 16 * 16) * sizeof(double); }
+
+template <bool INGRAD>
+int launch_kernel(const mobocmf_frozen_predict_model* dev_models, dim3 grid, size_t shm, hipStream_t s) {
+    // the dynamic-LDS attribute is per device: one bit per device ordinal (gemm_f64.hip launch_small_panel)
+    static std::atomic<uint64_t> configured{0};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return MOBOCMF_HIP_ERROR;
+    if (!(configured.load(std::memory_order_acquire) & (1ull << dev))) {
+        if (hipFuncSetAttribute((const void*)frozen_predict_kernel<INGRAD>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)frozen_lds_bytes(MOBOCMF_FROZEN_MAX_M)) != hipSuccess)
+            return MOBOCMF_HIP_ERROR;
+        configured.fetch_or(1ull << dev, std::memory_order_release);
+    }
+    hipLaunchKernelGGL(frozen_predict_kernel<INGRAD>, grid, dim3(FT), shm, s, dev_models);
+    return hipGetLastError() == hipSuccess ? MOBOCMF_OK : MOBOCMF_HIP_ERROR;
+}
+
+}  // namespace
+
+// Descriptors validated by the caller (api.hip, which also vouches for the chain-state layout the kernel indexes).
+int launch_frozen_predict(const mobocmf_frozen_predict_model* host_models, const mobocmf_frozen_predict_model* dev_models,
+                          int n_models, bool input_gradients, hipStream_t s) {
+    int mmax = 0, gx = 1;
+    for (int i = 0; i < n_models; ++i) {
+        const mobocmf_frozen_predict_model& m = host_models[i];
+        const int rb = frozen_rows_per_wg(m.L, m.L > 1 ? m.S : 1);
+        if (m.M > mmax) mmax = m.M;
+        if ((m.T + rb - 1) / rb > gx) gx = (m.T + rb - 1) / rb;
+    }
+    const dim3 grid((unsigned)gx, (unsigned)n_models);
+    const size_t shm = frozen_lds_bytes(mmax);
+    return input_gradients ? launch_kernel<true>(dev_models, grid, shm, s) : launch_kernel<false>(dev_models, grid, shm, s);
+}

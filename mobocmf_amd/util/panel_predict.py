@@ -1,0 +1,166 @@
+"""Predictive moments of fitted surrogates with 128 < M <= 512 inducing points, and their gradient w.r.t. the test points, against
+FROZEN chains: mobocmf_frozen_predict (csrc/frozen_predict.hip).
+
+The one-launch predict groups stop at M = 128 (util/tiny_step.py TinyPredictGroup, util/coop_step.py CoopPredictGroup); beyond,
+an acquisition search evaluated every iterate through the layer entry points -- five launches per layer forward, as many again
+backward, for T S = 125 columns.  ``PanelPredictGroup`` has the surface of those groups that ``DeviceAcqSearch``
+(util/acq_search.py) and ``JESMOC_MFDGP`` drive: one launch for the moments of ALL models of a fidelity (MOBOCMF_STEP_FORWARD), one
+more for d / dX (MOBOCMF_STEP_INPUT_GRADIENTS).  The M x M chain of every layer is the layer's own (``layer.freeze_chain()``: the
+jitter ladder, the host check and NotPSDError all happen there, before any launch of a search).
+"""
+import contextlib
+import ctypes
+
+import torch
+
+from .. import _lib
+from . import tiny_step as TS
+
+MIN_M = _lib.COOP_MAX_M + 1      # up to COOP_MAX_M the cooperative one-launch group is the engine
+MAX_M = _lib.FROZEN_MAX_M
+
+
+def why_not(model, fidelity, T, d, on_gpu=True):
+    """None when ``model``'s predictive moments at T test points up to layer ``fidelity`` fit mobocmf_frozen_predict, else the
+    reason as a sentence."""
+    try:
+        layers = model._layers()[:fidelity + 1]
+        M = layers[0].variational_strategy._inducing_points.shape[0]
+        S = model.num_samples_for_acquisition
+    except (AttributeError, IndexError):
+        return "not an MFDGP with layer %d" % fidelity
+    if len(layers) != fidelity + 1:
+        return "the model has no layer %d" % fidelity
+    if not MIN_M <= M <= MAX_M:
+        return "M = %d inducing points (this kernel takes %d .. %d)" % (M, MIN_M, MAX_M)
+    if not 1 <= d <= _lib.TINY_MAX_D:
+        return "d = %d input columns (at most %d)" % (d, _lib.TINY_MAX_D)
+    if fidelity > 0 and not 2 <= S <= _lib.MAX_XDIV:
+        return "S = %d samples for acquisition (2 .. %d)" % (S, _lib.MAX_XDIV)
+    if T < 1 or T * (S if fidelity > 0 else 1) > _lib.ACQ_MAX_COLUMNS:
+        return "T S = %d columns (1 .. %d)" % (T * S, _lib.ACQ_MAX_COLUMNS)
+    if any(layer.samples.numel() != S for layer in layers[1:]):
+        return "a layer whose fixed samples are not the model's num_samples_for_acquisition"
+    if not TS.structure_fits(model, fidelity + 1, d, MAX_M, training=False, on_gpu=on_gpu):
+        return "the structure (tiny_step.structure_fits: <= 3 layers of the expected kinds sharing one Z_x and one jitter, " \
+               "softplus / Interval constraints, float64 contiguous parameters%s)" % (" on the GPU" if on_gpu else "")
+    return None
+
+
+def fits_predict(model, fidelity, T, d, on_gpu=True):
+    """The gate of ``PanelPredictGroup``, next to tiny_step.fits_predict and coop_step.fits_predict."""
+    return why_not(model, fidelity, T, d, on_gpu=on_gpu) is None
+
+
+def describe(rec, chains, samples, S, T, d, x, top_mean, top_var, seed_gmean=None, seed_gvar=None, grad=None):
+    """Fills one mobocmf_frozen_predict_model ``rec`` from the layers' FrozenChain objects (``chains``: their state bytes, Zx, zf
+    and packed hyper-parameters) and fixed ``samples`` (per layer; None for layer 0); the other arguments are tensors (or
+    None).  Returns the tensors the record points at."""
+    L = len(chains)
+    rec.L, rec.M, rec.d, rec.S, rec.T = L, chains[0].M, d, (S if L > 1 else 1), T
+    keep = []
+    for l, fc in enumerate(chains):
+        if fc.kind != (1 if l else 0) or fc.M != rec.M or fc.d != d:
+            raise _lib.MobocmfError("frozen predict: layer %d is not a kind-%d layer of M = %d, d = %d" % (l, 1 if l else 0, rec.M, d))
+        rec.kind[l] = fc.kind
+        rec.chain[l], rec.Zx[l], rec.hyp[l] = fc.state.data_ptr(), fc.Zx.data_ptr(), fc.hyp.data_ptr()
+        rec.zf[l] = fc.zf.data_ptr() if l else None
+        rec.samples[l] = samples[l].data_ptr() if l else None
+        keep += [fc.state, fc.Zx, fc.hyp] + ([fc.zf, samples[l]] if l else [])
+    for l in range(L, _lib.TINY_MAX_LAYERS):
+        rec.kind[l], rec.chain[l], rec.Zx[l], rec.zf[l], rec.hyp[l], rec.samples[l] = 0, None, None, None, None, None
+    ptr = lambda t: None if t is None else t.data_ptr()
+    rec.x, rec.top_mean, rec.top_var = ptr(x), ptr(top_mean), ptr(top_var)
+    rec.seed_gmean, rec.seed_gvar, rec.grad, rec.work = ptr(seed_gmean), ptr(seed_gvar), ptr(grad), None
+    return keep
+
+
+class PanelPredictGroup(TS.TinyPredictGroup):
+    """Predictive moments of SEVERAL fitted models with 128 < M <= 512 at the same T test points in ONE launch, their gradient
+    w.r.t. the test points in one more: the attributes and methods of ``TinyPredictGroup`` that a search uses (``models``,
+    ``device``, ``stream``, ``T``, ``d``, ``S``, ``x``, ``moments`` (n, 2, T S), ``seeds``, ``gx`` (n, T, d), ``_launch``,
+    ``moments_at``, ``noise``, ``acquisition_moments``, ``info_words``), ``freeze()`` / ``thaw()`` as ``CoopPredictGroup``.
+    ``want_gradients=False``: a group for values only (the raw candidates of a search) has no seeds and no gx.
+
+    Inside ``freeze()`` ... ``thaw()`` the parameters are constants and the layers' chains are formed once, by ``freeze()``
+    (shared with ``MFDGP.frozen_chains()`` where that context is active); a launch outside forms them first."""
+    _frozen = False
+
+    def __init__(self, models, fidelity, T, d, stream=None, want_gradients=True):
+        _lib.require_device()
+        self.models = list(models)
+        self.device = next(self.models[0].parameters()).device
+        self.stream = stream
+        self.fidelity, self.T, self.d = fidelity, int(T), int(d)
+        n, L = len(self.models), fidelity + 1
+        self.S = self.models[0].num_samples_for_acquisition if L > 1 else 1
+        for i, model in enumerate(self.models):
+            reason = why_not(model, fidelity, self.T, self.d)
+            if reason is None and L > 1 and model.num_samples_for_acquisition != self.S:
+                reason = "S differs from the first model's"
+            if reason is not None:
+                raise _lib.MobocmfError("PanelPredictGroup: model %d does not fit: %s" % (i, reason))
+        ncol = self.T * self.S
+        z = lambda *shape: torch.zeros(*shape, dtype=torch.float64, device=self.device)
+        self.x, self.moments = z(self.T, self.d), z(n, 2, ncol)
+        self.want_gradients = bool(want_gradients)
+        self.seeds, self.gx = (z(n, 2, ncol), z(n, self.T, self.d)) if want_gradients else (None, None)
+        self._samples = [[None] + [layer.samples.detach().reshape(-1).to(self.device, torch.float64).contiguous()
+                                   for layer in m._layers()[1:L]] for m in self.models]
+        self.host = (_lib.FrozenPredictModel * n)()
+        self._dev_table = torch.zeros(ctypes.sizeof(self.host), dtype=torch.uint8, device=self.device)
+        self._chains, self.info_words = None, []
+
+    # ------------------------------------------------------------------ the chains
+    def _form_chains(self):
+        """Every layer's chain through ``layer.freeze_chain()`` in eval mode (a model inside ``frozen_chains()`` hands out the
+        ones it has), the descriptors pointed at them, the table uploaded.  Synchronising (the layers' host check)."""
+        L = self.fidelity + 1
+        self._chains, self._keep = [], []
+        for i, model in enumerate(self.models):
+            model.eval()
+            try:
+                if model._frozen is not None:
+                    chains = model._frozen_chains(L)
+                else:
+                    chains = [layer.freeze_chain() for layer in model._layers()[:L]]
+            finally:
+                model.train()
+            self._chains.append(chains)
+            sd = (None, None) if self.seeds is None else (self.seeds[i, 0], self.seeds[i, 1])
+            self._keep += describe(self.host[i], chains, self._samples[i], self.S, self.T, self.d, self.x, self.moments[i, 0],
+                                   self.moments[i, 1], sd[0], sd[1], None if self.gx is None else self.gx[i])
+        self.info_words = [fc.info for chains in self._chains for fc in chains]
+        self._dev_table.copy_(torch.frombuffer(bytearray(bytes(self.host)), dtype=torch.uint8))
+        if self.stream is not None:      # (formed and uploaded on the current stream: the launches on self.stream come after)
+            self.stream.wait_stream(torch.cuda.current_stream(self.device))
+
+    def freeze(self):
+        """The parameters are constants until ``thaw()``: the chains are formed here, once, before any launch of the search."""
+        if not self._frozen:
+            self._form_chains()
+            self._frozen = True
+
+    def thaw(self):
+        """Drops the chains: the parameters may change afterwards.  (``info_words`` keep the verdicts of the last chains.)"""
+        self._frozen = False
+        self._chains = None
+
+    @contextlib.contextmanager
+    def frozen(self):
+        self.freeze()
+        try:
+            yield self
+        finally:
+            self.thaw()
+
+    # ------------------------------------------------------------------ the launches
+    def _launch(self, mode):
+        if mode == _lib.STEP_INPUT_GRADIENTS and not self.want_gradients:
+            raise _lib.MobocmfError("PanelPredictGroup: built with want_gradients=False")
+        if not self._frozen:
+            self._form_chains()      # (kept until the next ones replace them: the launch below reads them)
+        stream = self.stream if self.stream is not None else torch.cuda.current_stream(self.device)
+        _lib.check(_lib.require_device().mobocmf_frozen_predict(
+            ctypes.cast(self.host, ctypes.c_void_p), ctypes.c_void_p(self._dev_table.data_ptr()), len(self.models), int(mode),
+            ctypes.c_void_p(stream.cuda_stream)), "mobocmf_frozen_predict")

@@ -1,17 +1,21 @@
 #!/usr/bin/env python3
 """The acquisition search of one BO iteration, host engine against device engine (JESMOC_MFDGP(search=...)), at the sizes of
 tools/bo_iteration_mid.py -- N = M = 64 (44 low + 20 high fidelity), two objectives + one constraint, 2 fidelities, 5 restarts of
-200 raw candidates, 200 iterations: the cooperative kernel -- and at N = M = 20 (14 + 6: the one-workgroup kernel).
+200 raw candidates, 200 iterations: the cooperative kernel -- at N = M = 20 (14 + 6: the one-workgroup kernel), and above the
+one-launch kernels at N = M = 160 (112 + 48) and 512 (358 + 154): the frozen-chain predict kernel (util/panel_predict.py).
 
 Both engines are warmed up once (group construction, graph capture: reported as one-off cost), then whole
 ``get_nextpoint_coupled`` calls are timed with a host clock around a final synchronise, the engines alternating in the same
 process, from equal generator states; the median of ``--repeats`` calls is reported, with the time per replayed iterate (the
 captured graph replayed back to back), the same with several iterates per graph (``--unroll``), the chosen fidelity and the
-distance between the two engines' candidates.  One JSON line per size.
+distance between the two engines' candidates; ``spread_s`` is the largest minus the smallest of the repeats.  One JSON line per
+size.
 
-usage: python tools/acq_search_bench.py [--epochs 300] [--cond-iters 200] [--iters 200] [--repeats 5] [--unroll 1,4,8] [--sizes 64,20]
+usage: python tools/acq_search_bench.py [--epochs 300] [--cond-iters 200] [--iters 200] [--repeats 5] [--unroll 1,4,8]
+                                        [--sizes 64,20 | 160,512]
 """
 import argparse
+import contextlib
 import json
 import os
 import statistics
@@ -24,7 +28,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "examples"))
 import bo_iteration_toy2d as B  # noqa: E402
 
-SPLIT = {64: (44, 20), 20: (14, 6)}
+SPLIT = {64: (44, 20), 20: (14, 6), 160: (112, 48), 512: (358, 154)}
 
 
 def timed(acq, engine, iters, seed=0):
@@ -40,17 +44,19 @@ def timed(acq, engine, iters, seed=0):
 def replay_us(acq, per, n=200):
     """Microseconds per iterate of the captured graph of ``per`` iterates replayed back to back, per fidelity.  Only a graph
     that a search has captured is replayed: captured here, with the group thawed, it would lack STEP_CHAIN_VALID and stay
-    cached for the searches that follow."""
+    cached for the searches that follow.  A frozen-chain group reads chains that only exist between freeze() and thaw(): it is
+    frozen for the replays."""
     out = {}
     for f, eng in sorted(acq._device_searches.items()):
         assert per in eng._graphs, "replay_us: run a search with iters_per_graph = %d first" % per
         graph = eng._graphs[per]
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(n // per):
-            graph.replay()
-        torch.cuda.synchronize()
-        out[f] = round(1e6 * (time.perf_counter() - t0) / (n // per * per), 2)
+        with eng.group.frozen() if hasattr(eng.group, "frozen") else contextlib.nullcontext():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(n // per):
+                graph.replay()
+            torch.cuda.synchronize()
+            out[f] = round(1e6 * (time.perf_counter() - t0) / (n // per * per), 2)
     return out
 
 
@@ -79,6 +85,7 @@ def main():
         for e in times:
             res[e]["median_s"] = round(statistics.median(times[e]), 4)
             res[e]["min_s"] = round(min(times[e]), 4)
+            res[e]["spread_s"] = round(max(times[e]) - min(times[e]), 4)
         res["candidate_distance"] = float((torch.tensor(res["host"]["candidate"]) - torch.tensor(res["device"]["candidate"])).norm())
         res["unroll"] = {}
         for per in unroll:
