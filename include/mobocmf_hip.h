@@ -943,11 +943,28 @@ typedef struct mobocmf_frozen_predict_model {
     const double* seed_gmean;                    /* T S (MOBOCMF_STEP_INPUT_GRADIENTS) */
     const double* seed_gvar;
     double* grad;                                /* T x d (MOBOCMF_STEP_INPUT_GRADIENTS) */
-    void* work;                                  /* mobocmf_frozen_predict_work_bytes (NULL when that is 0) */
+    void* work;                                  /* mobocmf_frozen_predict[_split]_work_bytes (NULL when that is 0) */
 } mobocmf_frozen_predict_model;
 int mobocmf_frozen_predict_work_bytes(const mobocmf_frozen_predict_model* model, int32_t mode, size_t* bytes);
 int mobocmf_frozen_predict(const mobocmf_frozen_predict_model* host_models, const mobocmf_frozen_predict_model* dev_models,
                            int32_t n_models, int32_t mode, mobocmf_stream_t stream);
+
+/* ---- The same for surrogates up to MOBOCMF_FROZEN_SPLIT_MAX_M inducing points: the same descriptors, modes, algebra and results
+ * layout, on panels of 8 columns (two [M][8] panels and a: 136 KB of LDS at M = 1024) with the S replicas of a base row SPLIT over
+ * workgroups.  L >= 2: a workgroup owns (model, base row t, part p) -- the replicas s in [8 p, 8 p + 8), ceil(S / 8) parts -- and
+ * runs the whole chain for them (layer 0's column of row t is formed by every part); L = 1: a workgroup owns 8 base rows.
+ * mode MOBOCMF_STEP_INPUT_GRADIENTS, L >= 2: every part writes its partial d / d x of its base row to `work` ([part][T][d]
+ * doubles), and a second small kernel of the same call sums the parts in ascending order into grad; every slot it reads was
+ * written by the first kernel of the same call.  L = 1 writes grad directly (no second kernel).  Nothing is shared between the
+ * workgroups of a launch: no in-launch wait, no atomics, no status word; two calls on the same inputs are bitwise equal;
+ * capturable (the FIRST call per device and mode sets a function attribute and belongs outside a capture).
+ * mobocmf_frozen_predict_split_work_bytes: ceil(S / 8) T d 8 for MOBOCMF_STEP_INPUT_GRADIENTS with L >= 2, else 0.
+ * Limits: those of mobocmf_frozen_predict with 1 <= M <= MOBOCMF_FROZEN_SPLIT_MAX_M; `work` non-NULL where its bytes are
+ * non-zero.  MOBOCMF_BAD_ARG otherwise.  mobocmf_frozen_predict and its limit are unchanged by this entry point. */
+#define MOBOCMF_FROZEN_SPLIT_MAX_M 1024
+int mobocmf_frozen_predict_split_work_bytes(const mobocmf_frozen_predict_model* model, int32_t mode, size_t* bytes);
+int mobocmf_frozen_predict_split(const mobocmf_frozen_predict_model* host_models, const mobocmf_frozen_predict_model* dev_models,
+                                 int32_t n_models, int32_t mode, mobocmf_stream_t stream);
 
 #ifdef __cplusplus
 }

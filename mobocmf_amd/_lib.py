@@ -41,6 +41,7 @@ class LayerDesc(ctypes.Structure):
 TINY_MAX_LAYERS, TINY_MAX_M, TINY_MAX_D = 3, 32, 8      # MOBOCMF_TINY_MAX_* of include/mobocmf_hip.h
 COOP_MAX_M = 128                                         # MOBOCMF_COOP_MAX_M
 FROZEN_MAX_M = 512                                       # MOBOCMF_FROZEN_MAX_M
+FROZEN_SPLIT_MAX_M = 1024                                # MOBOCMF_FROZEN_SPLIT_MAX_M
 # MOBOCMF_STEP_*: do_update of mobocmf_tiny_elbo_step / mobocmf_coop_elbo_step
 STEP_GRADIENTS, STEP_UPDATE, STEP_FORWARD, STEP_INPUT_GRADIENTS, STEP_COUPLED = range(5)
 STEP_CHAIN_VALID = 16                                    # MOBOCMF_STEP_CHAIN_VALID
@@ -76,7 +77,7 @@ class TinyCoupling(ctypes.Structure):
 
 
 class FrozenPredictModel(ctypes.Structure):
-    """mobocmf_frozen_predict_model: one surrogate of mobocmf_frozen_predict (the kernel reads the array from DEVICE memory)."""
+    """mobocmf_frozen_predict_model: one surrogate of mobocmf_frozen_predict[_split] (the kernel reads the array from DEVICE memory)."""
     _L = TINY_MAX_LAYERS
     _fields_ = [("L", ctypes.c_int32), ("M", ctypes.c_int32), ("d", ctypes.c_int32), ("S", ctypes.c_int32),
                 ("T", ctypes.c_int32), ("kind", ctypes.c_int32 * _L),
@@ -218,6 +219,8 @@ SYMBOLS = {
     "mobocmf_select_topk": [_P, _I32, _I32, _P, _I32, _P, _P, _P, _P],
     "mobocmf_frozen_predict_work_bytes": [ctypes.POINTER(FrozenPredictModel), _I32, ctypes.POINTER(_SZ)],
     "mobocmf_frozen_predict": [_P, _P, _I32, _I32, _P],
+    "mobocmf_frozen_predict_split_work_bytes": [ctypes.POINTER(FrozenPredictModel), _I32, ctypes.POINTER(_SZ)],
+    "mobocmf_frozen_predict_split": [_P, _P, _I32, _I32, _P],
 }
 ACQ_MAX_PAIRS, TOPK_MAX_K, TOPK_MAX_N = 32, 64, 4096      # MOBOCMF_ACQ_MAX_PAIRS / MOBOCMF_TOPK_MAX_K / MOBOCMF_TOPK_MAX_N
 ACQ_MAX_COLUMNS = 1 << 24                                 # MOBOCMF_ACQ_MAX_COLUMNS

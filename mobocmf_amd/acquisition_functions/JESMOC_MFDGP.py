@@ -9,7 +9,7 @@ iteration is a single pair of model evaluations.  With surrogates sharded over r
 all-gather + sum of mobocmf_amd.parallel.coupled_acquisition.
 
 ``JESMOC_MFDGP(search="device")``: wherever the black-boxes of a fidelity fit a one-launch predict group (M <= 128) or the
-frozen-chain predict group (128 < M <= 512, util/panel_predict.py) the whole search -- scoring of the raw candidates, choice of
+frozen-chain predict groups (128 < M <= 1024, util/panel_predict.py) the whole search -- scoring of the raw candidates, choice of
 the restarts, the ascent, the best iterate, the final pick -- runs on the GPU (util/acq_search.py DeviceAcqSearch,
 csrc/acq_search.hip), one graph replay per iterate, and the host reads the device once per ``get_nextpoint_coupled`` call.
 """
@@ -196,16 +196,20 @@ class JESMOC_MFDGP:
 
     def _panel_group(self, jess, fidelity, T, d, want_gradients):
         """PanelPredictGroup (128 < M <= 512, util/panel_predict.py) over (uncond, cond) of every black-box of ``fidelity`` for T
-        test points when all of them fit, else None.  A cache of the DEVICE engine alone: ``coupled_acq`` never looks here, so
+        test points when all of them fit; else SplitPredictGroup (M <= 1024: 8-column panels, replicas split over workgroups)
+        when all of them fit that; else None.  A cache of the DEVICE engine alone: ``coupled_acq`` never looks here, so
         the host engine evaluates these sizes through the layer path as ever."""
         cache = self.__dict__.setdefault("_panel_groups", {})
         key = (fidelity, T, d, bool(want_gradients))
         if key not in cache:
             from ..util import panel_predict as PP
             models = [m for jes in jess for m in (jes.mfdgp_uncond, jes.mfdgp_cond)]
-            ok = bool(models) and all(p.is_cuda for p in models[0].parameters()) and \
-                all(PP.fits_predict(m, fidelity, T, d) for m in models)
-            cache[key] = PP.PanelPredictGroup(models, fidelity, T, d, want_gradients=want_gradients) if ok else None
+            on_gpu = bool(models) and all(p.is_cuda for p in models[0].parameters())
+            cache[key] = None
+            for fits, group in ((PP.fits_predict, PP.PanelPredictGroup), (PP.fits_predict_split, PP.SplitPredictGroup)):
+                if on_gpu and all(fits(m, fidelity, T, d) for m in models):
+                    cache[key] = group(models, fidelity, T, d, want_gradients=want_gradients)
+                    break
         return cache[key]
 
     def coupled_acq(self, X, fidelity):
@@ -256,8 +260,8 @@ class JESMOC_MFDGP:
         """(DeviceAcqSearch, raw-candidate group) of ``fidelity`` when its search can stay on the GPU -- the condition under
         which ``coupled_acq`` evaluates through a one-launch group, and a group fits T = num_restarts and the raw candidates,
         whole or in up to ``MAX_RAW_CHUNKS`` equal chunks (200 candidates x 25 samples are beyond the kernels' 4096 columns); or,
-        where no one-launch group fits, frozen-chain groups do (128 < M <= 512: the raw candidates whole, no column limit
-        there) -- else None: M > 512, S = 1, sharded surrogates, CPU tensors keep the host loop."""
+        where no one-launch group fits, frozen-chain groups do (128 < M <= 1024: the raw candidates whole, no column limit
+        there) -- else None: M > 1024, S = 1, sharded surrogates, CPU tensors keep the host loop."""
         jess = list(self.objectives[fidelity].values()) + list(self.constraints[fidelity].values())
         bounds = self.standard_bounds
         if not (self.use_tiny_step and jess and bounds is not None and bounds.is_cuda and parallel.world()[1] == 1):

@@ -1184,8 +1184,8 @@ int mobocmf_check_info(const int32_t* info, int32_t* pivot, mobocmf_stream_t str
 }
 
 // ---- frozen-chain predict (frozen_predict.hip)
-static bool frozen_model_sizes_ok(const mobocmf_frozen_predict_model* m) {
-    if (!m || m->L < 1 || m->L > MOBOCMF_TINY_MAX_LAYERS || m->M < 1 || m->M > MOBOCMF_FROZEN_MAX_M || m->d < 1 ||
+static bool frozen_model_sizes_ok(const mobocmf_frozen_predict_model* m, int max_m = MOBOCMF_FROZEN_MAX_M) {
+    if (!m || m->L < 1 || m->L > MOBOCMF_TINY_MAX_LAYERS || m->M < 1 || m->M > max_m || m->d < 1 ||
         m->d > MOBOCMF_TINY_MAX_D || m->T < 1)
         return false;
     if (m->L == 1 ? m->S != 1 : (m->S < 2 || m->S > MOBOCMF_MAX_XDIV)) return false;
@@ -1199,14 +1199,32 @@ int mobocmf_frozen_predict_work_bytes(const mobocmf_frozen_predict_model* model,
     return MOBOCMF_OK;
 }
 
-int mobocmf_frozen_predict(const mobocmf_frozen_predict_model* host_models, const mobocmf_frozen_predict_model* dev_models,
-                           int32_t n_models, int32_t mode, mobocmf_stream_t stream) {
+// the bytes of `work` of the split form: the parts' partial d/dx, [part][T][d]
+static size_t frozen_split_work_bytes(const mobocmf_frozen_predict_model& m, int32_t mode) {
+    if (mode != MOBOCMF_STEP_INPUT_GRADIENTS || m.L < 2) return 0;
+    return (size_t)((m.S + 7) / 8) * m.T * m.d * sizeof(double);
+}
+
+int mobocmf_frozen_predict_split_work_bytes(const mobocmf_frozen_predict_model* model, int32_t mode, size_t* bytes) {
+    if (!bytes || !frozen_model_sizes_ok(model, MOBOCMF_FROZEN_SPLIT_MAX_M) ||
+        (mode != MOBOCMF_STEP_FORWARD && mode != MOBOCMF_STEP_INPUT_GRADIENTS))
+        return MOBOCMF_BAD_ARG;
+    *bytes = frozen_split_work_bytes(*model, mode);
+    return MOBOCMF_OK;
+}
+
+// the validation both entry points share, before any HIP call
+static int frozen_predict_args_ok(const mobocmf_frozen_predict_model* host_models, const mobocmf_frozen_predict_model* dev_models,
+                                  int32_t n_models, int32_t mode, bool split) {
     if (!host_models || !dev_models || n_models < 1 || n_models > 256) return MOBOCMF_BAD_ARG;
     if (mode != MOBOCMF_STEP_FORWARD && mode != MOBOCMF_STEP_INPUT_GRADIENTS) return MOBOCMF_BAD_ARG;
     for (int i = 0; i < n_models; ++i) {
         const mobocmf_frozen_predict_model& m = host_models[i];
-        if (!frozen_model_sizes_ok(&m) || !m.x || !m.top_mean || !m.top_var) return MOBOCMF_BAD_ARG;
+        if (!frozen_model_sizes_ok(&m, split ? MOBOCMF_FROZEN_SPLIT_MAX_M : MOBOCMF_FROZEN_MAX_M) || !m.x || !m.top_mean ||
+            !m.top_var)
+            return MOBOCMF_BAD_ARG;
         if (mode == MOBOCMF_STEP_INPUT_GRADIENTS && (!m.grad || !m.seed_gmean || !m.seed_gvar)) return MOBOCMF_BAD_ARG;
+        if (split && frozen_split_work_bytes(m, mode) != 0 && !m.work) return MOBOCMF_BAD_ARG;
         for (int l = 0; l < m.L; ++l) {
             if (m.kind[l] != (l ? 1 : 0) || !m.chain[l] || !m.Zx[l] || !m.hyp[l] || (l && (!m.zf[l] || !m.samples[l])))
                 return MOBOCMF_BAD_ARG;
@@ -1224,7 +1242,21 @@ int mobocmf_frozen_predict(const mobocmf_frozen_predict_model* host_models, cons
                 return MOBOCMF_BAD_ARG;
         }
     }
+    return MOBOCMF_OK;
+}
+
+int mobocmf_frozen_predict(const mobocmf_frozen_predict_model* host_models, const mobocmf_frozen_predict_model* dev_models,
+                           int32_t n_models, int32_t mode, mobocmf_stream_t stream) {
+    const int rc = frozen_predict_args_ok(host_models, dev_models, n_models, mode, false);
+    if (rc != MOBOCMF_OK) return rc;
     return launch_frozen_predict(host_models, dev_models, n_models, mode == MOBOCMF_STEP_INPUT_GRADIENTS, (hipStream_t)stream);
+}
+
+int mobocmf_frozen_predict_split(const mobocmf_frozen_predict_model* host_models, const mobocmf_frozen_predict_model* dev_models,
+                                 int32_t n_models, int32_t mode, mobocmf_stream_t stream) {
+    const int rc = frozen_predict_args_ok(host_models, dev_models, n_models, mode, true);
+    if (rc != MOBOCMF_OK) return rc;
+    return launch_frozen_predict_split(host_models, dev_models, n_models, mode == MOBOCMF_STEP_INPUT_GRADIENTS, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -218,6 +218,8 @@ int launch_symmetrize_z(const double* S, int Mp, double* G, int nz, int64_t zs, 
 enum { FCS_L = 0, FCS_LINV = 1, FCS_LINVT = 2, FCS_U = 3, FCS_UT = 4, FCS_LS = 5, FCS_A = 6 };
 int launch_frozen_predict(const mobocmf_frozen_predict_model* host_models, const mobocmf_frozen_predict_model* dev_models,
                           int n_models, bool input_gradients, hipStream_t s);
+int launch_frozen_predict_split(const mobocmf_frozen_predict_model* host_models, const mobocmf_frozen_predict_model* dev_models,
+                                int n_models, bool input_gradients, hipStream_t s);
 
 // ------------------------------------------------------------------ hyper-parameter packing
 // kind 0: [alpha, ls[0..d)]                                   (1 + d doubles)

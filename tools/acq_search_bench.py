@@ -2,7 +2,9 @@
 """The acquisition search of one BO iteration, host engine against device engine (JESMOC_MFDGP(search=...)), at the sizes of
 tools/bo_iteration_mid.py -- N = M = 64 (44 low + 20 high fidelity), two objectives + one constraint, 2 fidelities, 5 restarts of
 200 raw candidates, 200 iterations: the cooperative kernel -- at N = M = 20 (14 + 6: the one-workgroup kernel), and above the
-one-launch kernels at N = M = 160 (112 + 48) and 512 (358 + 154): the frozen-chain predict kernel (util/panel_predict.py).
+one-launch kernels at N = M = 160 (112 + 48) and 512 (358 + 154): the frozen-chain predict kernel (util/panel_predict.py), and at
+640 (448 + 192) and 1024 (717 + 307): its split form.  ``--force-split`` routes 128 < M <= 512 to the split form too (a measurement
+only: the library's routing is untouched).
 
 Both engines are warmed up once (group construction, graph capture: reported as one-off cost), then whole
 ``get_nextpoint_coupled`` calls are timed with a host clock around a final synchronise, the engines alternating in the same
@@ -12,7 +14,7 @@ distance between the two engines' candidates; ``spread_s`` is the largest minus 
 size.
 
 usage: python tools/acq_search_bench.py [--epochs 300] [--cond-iters 200] [--iters 200] [--repeats 5] [--unroll 1,4,8]
-                                        [--sizes 64,20 | 160,512]
+                                        [--sizes 64,20 | 160,512 | 640,1024] [--force-split]
 """
 import argparse
 import contextlib
@@ -28,7 +30,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "examples"))
 import bo_iteration_toy2d as B  # noqa: E402
 
-SPLIT = {64: (44, 20), 20: (14, 6), 160: (112, 48), 512: (358, 154)}
+SPLIT = {64: (44, 20), 20: (14, 6), 160: (112, 48), 512: (358, 154), 640: (448, 192), 1024: (717, 307)}
 
 
 def timed(acq, engine, iters, seed=0):
@@ -68,14 +70,19 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--unroll", default="1,4,8")
     ap.add_argument("--sizes", default="64,20")
+    ap.add_argument("--force-split", action="store_true")
     a = ap.parse_args()
+    if a.force_split:
+        from mobocmf_amd.util import panel_predict
+        panel_predict.fits_predict = lambda *args, **kw: False
     unroll = [int(u) for u in a.unroll.split(",")]
     for size in [int(s) for s in a.sizes.split(",")]:
         n_low, n_high = SPLIT[size]
         _, acq, _, _ = B.run(epochs=a.epochs, cond_iters=a.cond_iters, acq_iters=1, n_low=n_low, n_high=n_high, verbose=False)
         first = {e: timed(acq, e, a.iters)[0] for e in ("host", "device")}      # warm-up: groups, descriptors, graph capture
         res = {"size": size, "iters": a.iters, "repeats": a.repeats, "first_call_s": {k: round(v, 4) for k, v in first.items()},
-               "engines": dict(acq.last_search_engine)}
+               "engines": dict(acq.last_search_engine),
+               "groups": sorted({type(g).__name__ for g in acq.__dict__.get("_panel_groups", {}).values() if g is not None})}
         times = {"host": [], "device": []}
         for _ in range(a.repeats):
             for e in ("host", "device"):
