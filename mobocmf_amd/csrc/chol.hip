@@ -682,7 +682,7 @@ __global__ __launch_bounds__(PC_T) void potrf_coop_kernel(double* A, int64_t ld,
                         for (int q = 0; q < 4; ++q) d2 = mfma(Aii[tel(li, 4 * q + lk)], acc[q], d2);      // the accumulator IS the B fragment
                         double* X = Lip + tix(s, c);
 #pragma unroll
-                        for (int r = 0; r < 4; ++r) X[tel(4 * r + lk, li)] = -d2[r];
+                        for (int r = 0; r < 4; ++r) X[tel(4 * r + lk, li)] = 0.0 - d2[r];      // (0 - x, not -x: a zero in a padding row stays +0)
                     }
                     try_fetch(false);
                 }
@@ -705,7 +705,7 @@ __global__ __launch_bounds__(PC_T) void potrf_coop_kernel(double* A, int64_t ld,
                     for (int q = 0; q < 4; ++q) d2 = mfma(Aii[tel(li, 4 * q + lk)], acc[q], d2);
                     double* X = Lip + tix(3, c);
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) X[tel(4 * r + lk, li)] = -d2[r];
+                    for (int r = 0; r < 4; ++r) X[tel(4 * r + lk, li)] = 0.0 - d2[r];      // (0 - x, not -x: a zero in a padding row stays +0)
                 }
                 try_fetch(true);
             }
@@ -936,7 +936,7 @@ __global__ __launch_bounds__(PC_T) void potrf_coop_kernel(double* A, int64_t ld,
                 for (int t = 0; t < 2; ++t)
 #pragma unroll
                     for (int r = 0; r < 4; ++r)
-                        ((pc_gw)Xc)[(int64_t)(wr * 32 + t * 16 + lk + 4 * r) * ldi + wc * 16 + li] = -acc[t][r];
+                        ((pc_gw)Xc)[(int64_t)(wr * 32 + t * 16 + lk + 4 * r) * ldi + wc * 16 + li] = 0.0 - acc[t][r];
                 __syncthreads();
             }
         }
@@ -1129,12 +1129,14 @@ __global__ __launch_bounds__(256) void trtri_level0_kernel(const double* L, int6
         for (int j = 0; j < 2; ++j)
 #pragma unroll
             for (int r = 0; r < 4; ++r)
-                Linv[(o + 64 + wr * 32 + i * 16 + lk + 4 * r) * ldi + o + wc * 32 + j * 16 + li] = -acc[i][j][r];
+                Linv[(o + 64 + wr * 32 + i * 16 + lk + 4 * r) * ldi + o + wc * 32 + j * 16 + li] = 0.0 - acc[i][j][r];      // (+0 in the padding rows)
 }
 
 // Linv (Mp x Mp, pre-zeroed above the block diagonal by the caller) = L^-1.  T = scratch Mp x Mp.
 // Power-of-two block counts: recursive doubling, [[A,0],[B,C]]^-1 = [[A^-1,0],[-C^-1 B A^-1, C^-1]], every level
 // is two (batched) MFMA GEMMs; otherwise block row by block row.
+// The sign rides on the FIRST product of a pair (T = -B A^-1, then C^-1 T): the same numbers, but a padding row of the result
+// -- an identity row of C^-1 times zeros -- comes out as +0, where a negated second product left -0 below the identity.
 int launch_trtri_z(const double* L, int64_t ld, int Mp, const double* Dinv, double* Linv, double* T, double* ws,
                    int64_t ws_elems, int nz, int64_t zs, hipStream_t s) {
     // nz layers: every operand of layer z is the layer-0 pointer + z*zs (doubles)
@@ -1150,12 +1152,12 @@ int launch_trtri_z(const double* L, int64_t ld, int Mp, const double* Dinv, doub
             g.A = L + (int64_t)sz * ld;  g.lda = ld;              // L21
             g.B = Linv;                  g.ldb = Mp;              // Linv11 (lower)
             g.C = T + (int64_t)sz * Mp;  g.ldc = Mp;
-            g.Mr = sz; g.Nc = sz; g.Kd = sz; g.tri = TRI_LOWER_B; g.alpha = 1.0;
+            g.Mr = sz; g.Nc = sz; g.Kd = sz; g.tri = TRI_LOWER_B; g.alpha = -1.0;      // T = -L21 Linv11: see above
             GemmArgs h = {};
             h.A = Linv + (int64_t)sz * Mp + sz; h.lda = Mp;       // Linv22 (lower)
             h.B = T + (int64_t)sz * Mp;         h.ldb = Mp;
             h.C = Linv + (int64_t)sz * Mp;      h.ldc = Mp;
-            h.Mr = sz; h.Nc = sz; h.Kd = sz; h.tri = TRI_LOWER_A; h.alpha = -1.0;
+            h.Mr = sz; h.Nc = sz; h.Kd = sz; h.tri = TRI_LOWER_A; h.alpha = 1.0;
             layered(g);
             layered(h);
             int rc;
@@ -1176,7 +1178,7 @@ int launch_trtri_z(const double* L, int64_t ld, int Mp, const double* Dinv, doub
         return hipGetLastError() == hipSuccess ? MOBOCMF_OK : MOBOCMF_HIP_ERROR;
     }
     for (int i = 1; i < nb; ++i) {
-        // T[128 x i*128] = L[i, 0:i] * Linv[0:i, 0:i]       (B lower triangular)
+        // T[128 x i*128] = -L[i, 0:i] * Linv[0:i, 0:i]       (B lower triangular)
         GemmArgs g = {};
         g.A = L + (int64_t)i * TILE * ld;
         g.lda = ld;
@@ -1188,11 +1190,11 @@ int launch_trtri_z(const double* L, int64_t ld, int Mp, const double* Dinv, doub
         g.Nc = (int64_t)i * TILE;
         g.Kd = (int64_t)i * TILE;
         g.tri = TRI_LOWER_B;
-        g.alpha = 1.0;
+        g.alpha = -1.0;
         layered(g);
         int rc = launch_gemm_auto(g, false, ws, ws_elems, s);
         if (rc) return rc;
-        // Linv[i, 0:i] = -Linv[i,i] * T
+        // Linv[i, 0:i] = Linv[i,i] * T
         GemmArgs h = {};
         h.A = Linv + (int64_t)i * TILE * Mp + (int64_t)i * TILE;
         h.lda = Mp;
@@ -1203,7 +1205,7 @@ int launch_trtri_z(const double* L, int64_t ld, int Mp, const double* Dinv, doub
         h.Mr = TILE;
         h.Nc = (int64_t)i * TILE;
         h.Kd = TILE;
-        h.alpha = -1.0;
+        h.alpha = 1.0;
         layered(h);
         rc = zl ? launch_gemm_auto(h, false, ws, ws_elems, s) : launch_gemm(h, false, 1, s);
         if (rc) return rc;

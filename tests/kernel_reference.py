@@ -332,6 +332,249 @@ def elbo_hp(layers, y, fid, kls, scale, g_elbo, g_skl):
     return out
 
 
+# ------------------------------------------------------------- factorisation chain: cases, references, a-priori bounds
+# (chol.hip: three factorisation forms selected by mobocmf_tuning.potrf_cols, two routes of launch_trtri_z and the one-launch
+# form's own inverse; elementwise.hip: gemv_rows, exact_gp_mll_kernel; the column statistics of mobocmf_exact_gp_predict.)
+FACTOR_FAMILIES = ("rbf", "rbf_scaled", "signed")
+POTRF_FORMS = (0, 1, 4)                  # potrf_cols: one launch | one column per hand-over | four columns per hand-over
+FACTOR_ORDERS = (1, 15, 16, 17, 63, 64, 65, 80, 127, 128, 129, 191, 192, 193, 257, 320, 384, 385)
+FACTOR_ORDER_COOP_CAPS = 640             # potrf_cols = 0, family rbf only: both workgroup caps of potrf_coop_workgroups bind
+PREDICT_N = (80, 200, 320)
+PREDICT_NT = (1, 127, 129, 300)
+_RBF = {2: 0.6, 3: 0.9}                  # lengthscale per input dimension (n >= 63; 2.5 below): cond(K) within 1e6 .. 1e9
+
+
+def _rbf_points(n, seed):
+    """(training points, lengthscale) of the rbf families at order n."""
+    d = 2 + (n + seed) % 2
+    return np.random.default_rng(7919 * n + seed).random((n, d)), (2.5 if n < 63 else _RBF[d])
+
+
+def factor_families(n):
+    """The families run at order n: all three below 320; from 320 on the host's longdouble products dominate a test, so
+    every order keeps ``rbf`` (the workload) and the other two alternate (rbf_scaled at 320 and 385, signed at 384)."""
+    if n < 320:
+        return FACTOR_FAMILIES
+    if n == FACTOR_ORDER_COOP_CAPS:
+        return ("rbf",)
+    return ("rbf", "signed") if n == 384 else ("rbf", "rbf_scaled")
+
+
+def one_launch_runs(n, cols):
+    """launch_potrf_z takes potrf_coop_kernel for potrf_cols = 0 and 3 <= nreal <= 16 real 64-blocks (129 <= n <= 1024)."""
+    return cols == 0 and 3 <= (n + 63) // 64 <= 16
+
+
+_factor_cache = {}
+
+
+def factor_case(family, n, seed=0):
+    """(K [n x n], y [n]) as float64 numpy, read-only and cached.
+    rbf         exp(-|x - x'|^2 / 2 l^2) + 1e-6 I on uniform points in [0, 1]^d, d = 2 (n + seed even) or 3, l = 0.6 / 0.9
+                (2.5 below n = 63, where few points need a longer lengthscale to be as dependent): the workload's
+                conditioning, cond(K) 1e6 .. 1e9 from n = 15 on (n = 1 has cond 1: the largest eigenvalue, <= n, cannot
+                reach 1e6 against a jitter of 1e-6); test_factor_cases_have_the_stated_conditioning.
+    rbf_scaled  D K_rbf D and D y with D = tile_scales(n, 64, .): powers of two in 2^+-[80, 100], constant on 64-blocks,
+                neighbours >= 2^160 apart.  Every rounding commutes with them and every bound below is invariant, so a quiet
+                64-block cannot hide behind a loud one.  chol.hip documents no dependence on magnitude (pivots are tested by
+                !(a > 0) alone), entries stay within 2^+-200 and every intermediate -- squares of factor entries, products of
+                L and L^-1 blocks -- within 2^+-400: the full exponent range of tile_scales is kept.
+    signed      W W^T + n I, W = exact_ints((n, n)): exactly representable, cond < 100, off-diagonals of mixed sign (an RBF
+                matrix has none).  y integer."""
+    key = (family, n, seed)
+    if key not in _factor_cache:
+        if family == "signed":
+            W = exact_ints((n, n), 31 * n + seed).astype(np.float64)
+            K = W @ W.T + n * np.eye(n)
+            y = exact_ints(n, 31 * n + seed + 1).astype(np.float64)
+        else:
+            assert family in ("rbf", "rbf_scaled"), family
+            x, ls = _rbf_points(n, seed)
+            d2 = ((x[:, None, :] - x[None, :, :]) ** 2).sum(-1)
+            K = np.exp(-0.5 * d2 / ls ** 2) + 1e-6 * np.eye(n)
+            y = np.random.default_rng(7919 * n + seed + 1).standard_normal(n)
+            if family == "rbf_scaled":
+                D = tile_scales(n, 64, 17 * n + seed)
+                K, y = D[:, None] * K * D[None, :], D * y
+        K.setflags(write=False)
+        y.setflags(write=False)
+        _factor_cache[key] = (K, y)
+    return _factor_cache[key]
+
+
+def cross_kernel(family, n, nt, seed=0):
+    """(Kts [n x nt], kss [nt]) for the predict tests: the family's kernel between the training points of factor_case and
+    nt fresh uniform points (rbf; kss = 1 + 1e-6), or signed integers (signed; kss integer >= 0)."""
+    if family == "signed":
+        return exact_ints((n, nt), 5 * n + nt + seed).astype(np.float64), np.abs(exact_ints(nt, n + 7 * nt + seed)).astype(np.float64)
+    assert family == "rbf"
+    x, ls = _rbf_points(n, seed)                                        # the training points of factor_case
+    xt = np.random.default_rng(104729 * n + nt + seed).random((nt, x.shape[1]))
+    d2 = ((x[:, None, :] - xt[None, :, :]) ** 2).sum(-1)
+    return np.exp(-0.5 * d2 / ls ** 2), np.full(nt, 1.0 + 1e-6)
+
+
+def tri_inverse_hp(L):
+    """Inverse of the lower triangle of L by forward substitution, row by row, in extended precision (longdouble; mpmath at
+    50 digits where longdouble is no wider than float64).  numpy.linalg.inv -- a general LU -- misses the componentwise
+    bounds below by factors of 1e3 .. 1e13 and is no reference."""
+    n = L.shape[0]
+    if HAVE_LONGDOUBLE:
+        Lq = np.tril(ld(L))
+        X = np.zeros((n, n), np.longdouble)
+        for i in range(n):
+            row = -(Lq[i, :i] @ X[:i, :i]) if i else np.zeros(0, np.longdouble)
+            X[i, :i] = row / Lq[i, i]
+            X[i, i] = 1 / Lq[i, i]
+        return X
+    import mpmath
+    mpmath.mp.dps = 50
+    Lm = [[mpmath.mpf(float(v)) for v in r] for r in np.asarray(L, np.float64)]
+    X = [[mpmath.mpf(0)] * n for _ in range(n)]
+    for i in range(n):
+        for j in range(i + 1):
+            s = (mpmath.mpf(1) if i == j else mpmath.mpf(0)) - sum((Lm[i][k] * X[k][j] for k in range(j, i)), mpmath.mpf(0))
+            X[i][j] = s / Lm[i][i]
+    return np.array([[float(v) for v in r] for r in X], dtype=np.float64).astype(np.longdouble)
+
+
+# Constants of the bounds.  u = 2^-53; every bound is first order in u (k u <= 1.2e-13 at k = 1024: the second-order terms are
+# below 1e-12 of the bound).  None is fitted to device output; the CPU proof (test_kernel_reference_cpu.py) holds float64
+# restatements of the same algorithms to HALF of each.
+#
+# CHOL_CR.  Entry (i, j), i >= j, k = j + 1 terms: the code forms s_ij = a_ij - sum_{t<j} l_it l_jt, r_j = rsqrt_nr(s_jj) =
+# (1 + d_r) / sqrt(s_jj), and l_ij = fl(s_ij r_j), l_jj = fl(s_jj r_j) (no divide, no sqrt: potrf_panel2/4_kernel,
+# chol64_pad_rows, chol_inv_tile16).  Hence l_ij l_jj = s_ij (1 + d_r)^2 (1 + d)(1 + d'): the k - 1 subtractions of the sum
+# and the two multiplies give the classical k + 1 (Higham, Accuracy and Stability, Thm 10.3 / Lemma 8.4, which has a divide
+# and a sqrt in their place), the reciprocal root adds 2 |d_r|.  rsqrt_nr is documented (chol.hip) as ~1 ulp, and 1 ulp is at
+# most 2 u relative: + 4.  The updates do not run one term at a time: a 64-column step subtracts a 64-term partial sum formed
+# on the matrix cores (syrk64_update_kernel, pc_tasks), the four-column panel subtracts a 4-term one; either costs the first
+# term of a group one rounding more than a term-by-term chain: + 1.  That is k + 6; C_r = 8 leaves 2 u for the "~" (a
+# reciprocal root 1.5 ulp off).  (Read the other way -- "~1 ulp" doubled to 4 u, entering twice -- it is 8 as well.)
+CHOL_CR = 8
+# TRINV_CX.  |Xh - X| <= (n + C_x) u |X||L||X| is the forward-error bound of inversion by substitution (Higham, Ch. 14:
+# |X - Xh| <= c_n u |L^-1||L||L^-1| for the unblocked methods).  The code runs substitution only inside a 64-block (with the
+# reciprocal root r_i in place of a divide: x_i = fl(s r_i), (1 + d_r)(1 + d), + 3 at |d_r| <= 2 u; + 1 for l_ii = fl(s_ii r_i)
+# being the diagonal it inverts) and the block recursion X21 = -X22 (L21 X11) above it.  One level of it on halves of order m:
+#   Xh21 - X21 = -(Xh22 - X22) L21 X11 - X22 L21 (Xh11 - X11) - X22 E_T + E_2,  |E_T| <= m u |L21||X11|, |E_2| <= m u |X22||L21 X11|
+# so with c(m) for the halves, c(2m) = c(m) + 2m IF the inherited terms |X22||L22||X22| |L21||X11| and |X22||L21| |X11||L11||X11|
+# are measured by |X22||L22||X21| + |X22||L21||X11| + |X21||L11||X11| = (|X||L||X|)_21.  Componentwise that replaces
+# |X22||L21||X11| by |X21| = |X22 L21 X11|: exact where the product does not cancel, and where it cancels the block recursion
+# is known to satisfy only the weaker bound with one more factor |L||X| (Higham, section 14.2.2, on block methods).  The
+# recursion then gives c(n) = n + c(64) - 64, also for the block-row route (products of order 128 i and 128 per block row)
+# and the right-looking one-launch inverse (one 64-term product per step), so C_x = c(64) - 64 = 4, doubled for the level-0
+# kernel's two 64-term products on top of the two 64-blocks: C_x = 8.  The issue fixes this form; the CPU proof measures how
+# far inside it the float64 restatement of the recursion stays on every case the GPU tests use.
+TRINV_CX = 8
+# MLL_CLOG.  exact_gp_mll_kernel sums t_i = -a_i^2 / 2 - log(l_ii) over a thread chain and a block tree (<= n roundings),
+# then subtracts fl(n / 2 * log 2 pi).  Per term: a_i^2 / 2 one rounding (the halving is exact), log at most 1 ulp = 2 u (HIP
+# programming guide, "HIP math API", double-precision functions: log, maximum error 1 ULP), the subtraction 1; the constant's
+# own rounding, its product with n / 2 and the last subtraction 3: C_log = 1 + 2 + 1 + 3 = 7, taken as 8.
+MLL_CLOG = 8
+
+
+def _ratio(err, R):
+    """worst err / (u R) over the entries given (R = 0: any error is infinite)."""
+    if err.size == 0:
+        return 0.0
+    pos = R > 0
+    return float(np.max(np.where(pos, err / np.where(pos, ld(U) * R, 1), np.where(err > 0, np.inf, 0))))
+
+
+def chol_bound_units(Lh, Xh=None):
+    """The allowed |Lh Lh^T - K| in units of u as (B, R), R = |Lh||Lh^T| (float64; n x n, the lower triangle counts).
+    Xh None -- the substitution forms (potrf_cols 1 and 4, every form at n <= 128): B = (min(i, j) + 1 + C_r) R.
+    Xh given -- the one-launch form, Xh its inverse, whose diagonal 64-blocks (16-tiles) ARE the explicit inverses the
+    kernel multiplies with.  potrf_coop_kernel forms EVERY block below the diagonal block J as a product with the computed
+    inverse: the look-ahead block in the panel workgroup (D), all others in the trailing workgroups (do_row), and inside the
+    diagonal block the 16-tiles below a pivot tile likewise (L_is = A_is L_ss^-T).  For such a block, m = 64 (16):
+        Lh_iJ = S_iJ Xh^T + E_1,                       |E_1| <= m u |S_iJ||Xh^T|      (an m-term product)
+        Lh_iJ Lh_JJ^T - S_iJ = S_iJ (Lh_JJ Xh - I)^T + E_1 Lh_JJ^T
+        |Lh_JJ Xh - I| = |Lh_JJ (Xh - X)| <= (m + C_x) u |Lh_JJ||X||Lh_JJ||X|        (the inverse's forward error)
+    and |S_iJ| <= |Lh_iJ||Lh_JJ^T| to first order, so with G = |Xh_JJ^T||Lh_JJ^T| the block's residual carries, on top of the
+    substitution bound (which covers S_iJ's own sum), u |Lh_iJ| |Lh_JJ^T| (m G + (m + C_x) G G).  A substitution-form panel has
+    no such term: that is why the classical bound does not hold for this form (ratio 1.2 .. 7.7 on RBF matrices)."""
+    Lh = np.tril(np.asarray(Lh, np.float64))
+    n = Lh.shape[0]
+    aL = np.abs(Lh)
+    R = aL @ aL.T
+    i = np.arange(n)
+    B = (np.minimum(i[:, None], i[None, :]) + 1 + CHOL_CR) * R
+    if Xh is not None:
+        aX = np.abs(np.asarray(Xh, np.float64))
+        for m in (64, 16):
+            for j0 in range(0, n, m):
+                j1 = min(j0 + m, n)
+                r1 = n if m == 64 else min((j0 // 64 + 1) * 64, n)      # 16-tiles: the rows of the same 64-block only
+                if j1 >= r1:
+                    continue
+                LJt = aL[j0:j1, j0:j1].T
+                G = aX[j0:j1, j0:j1].T @ LJt
+                B[j1:r1, j0:j1] += aL[j1:r1, j0:j1] @ (LJt @ (m * G + (m + TRINV_CX) * (G @ G)))
+    return B, R
+
+
+def chol_check(Lh, K, Xh=None):
+    """(ok, worst |Lh Lh^T - K| / (u R), worst fraction of the bound) over the lower triangle; residual in extended precision."""
+    Lh = np.tril(np.asarray(Lh, np.float64))
+    n = Lh.shape[0]
+    err = np.abs(matmul_hp(Lh, Lh.T) - ld(K))
+    B, R = chol_bound_units(Lh, Xh)
+    low = tri_mask(n, True)
+    return bool(np.all(err[low] <= ld(U) * B[low])), _ratio(err[low], R[low]), _ratio(err[low], B[low])
+
+
+def trinv_check(Xh, Lh, X=None):
+    """Forward error of the inverse against X = tri_inverse_hp(Lh) -- the inverse of the factor GIVEN, so the factorisation's
+    error is not counted again: |Xh - X| <= (n + C_x) u |X||Lh||X| on the lower triangle.  (ok, worst ratio in u R)."""
+    Lh = np.tril(np.asarray(Lh, np.float64))
+    n = Lh.shape[0]
+    X = tri_inverse_hp(Lh) if X is None else X
+    aX = np.abs(np.asarray(X, np.float64))
+    R = aX @ np.abs(Lh) @ aX
+    err = np.abs(ld(Xh) - X)
+    low = tri_mask(n, True)
+    return bool(np.all(err[low] <= (n + TRINV_CX) * ld(U) * R[low])), _ratio(err[low], R[low])
+
+
+def solve_check(ah, Xh, y):
+    """a = L^-1 y as gemv_rows forms it (a row's i + 1 non-zero terms: a lane chain and a butterfly, zeros add exactly):
+    |ah - Xh y| <= (n + 2) u |Xh||y|, against extended precision on the inverse GIVEN."""
+    n = len(y)
+    ref = matmul_hp(np.tril(Xh), np.asarray(y)[:, None])[:, 0]
+    R = np.abs(np.tril(Xh)) @ np.abs(y)
+    err = np.abs(ld(ah) - ref)
+    return bool(np.all(err <= (n + 2) * ld(U) * R)), _ratio(err, R)
+
+
+def mll_check(mll, Lh, ah):
+    """mll against -1/2 sum a^2 - sum log l_ii - n/2 log 2 pi in extended precision on the factor and the a GIVEN; tolerance
+    (n + C_log) u (1/2 sum a^2 + sum |log l_ii| + n/2 log 2 pi)."""
+    n = len(ah)
+    a, lg = ld(ah), np.log(ld(np.diag(Lh)))
+    half = ld(0.5)
+    ref = -half * (a * a).sum() - lg.sum() - half * n * LOG_2PI
+    R = half * (a * a).sum() + np.abs(lg).sum() + half * n * LOG_2PI
+    err = np.abs(ld(mll) - ref)
+    return bool(err <= (n + MLL_CLOG) * ld(U) * R), float(err / (ld(U) * R))
+
+
+def predict_check(mean, var, Xh, ah, Kts, kss):
+    """With A = Xh Kts exactly (the device: an n-term triangular product, then an n-term column sum in partial rows):
+    |mean_j - sum_i A_ij a_i| <= (2n + 4) u (|a|^T |Xh||Kts|)_j,  |var_j - (kss_j - sum_i A_ij^2)| <= (2n + 4) u (|kss_j| +
+    sum_i (|Xh||Kts|)_ij^2).  Returns (ok_mean, ratio_mean, ok_var, ratio_var), ratios in u R."""
+    n = len(ah)
+    Xl = np.tril(np.asarray(Xh, np.float64))
+    A = matmul_hp(Xl, Kts)
+    mref = (A * ld(ah)[:, None]).sum(0)
+    vref = ld(kss) - (A * A).sum(0)
+    G = np.abs(Xl) @ np.abs(Kts)
+    Rm, Rv = np.abs(ah) @ G, np.abs(kss) + (G * G).sum(0)
+    em, ev = np.abs(ld(mean) - mref), np.abs(ld(var) - vref)
+    c = (2 * n + 4) * ld(U)
+    return bool(np.all(em <= c * Rm)), _ratio(em, Rm), bool(np.all(ev <= c * Rv)), _ratio(ev, Rv)
+
+
 # ------------------------------------------------------------------------------------------------ direct C-ABI callers
 def lib():
     from mobocmf_amd import _lib
@@ -481,3 +724,90 @@ def elbo_backward(layers, y, fid, scale, g_elbo, g_skl):
                                      scratch.numel() * 8, _stream())
     _lib.check(rc, "mobocmf_elbo_backward")
     return gm, gv, gr, gkl
+
+
+# ---- exact GP (mobocmf_exact_gp_factor / _predict) and mobocmf_mf_kernel_combine
+def factors(st, n):
+    """(L, L^-1, npad) as padded views of an exact-GP state (anything with a byte tensor ``state``): L at 0, L^-1 at the next
+    256-byte boundary behind npad^2 doubles (api.hip carve_exact_state)."""
+    npad = (n + 127) // 128 * 128
+    buf = st.state.view(torch.float64)
+    L = buf[:npad * npad].view(npad, npad)
+    off = (npad * npad * 8 + 255) // 256 * 256 // 8
+    Li = buf[off:off + npad * npad].view(npad, npad)
+    return L, Li, npad
+
+
+class ExactGP:
+    """What exact_gp leaves behind: state / scratch (byte tensors, NaN before the call), views L, Li (npad x npad), a (npad),
+    mll (0-d), info (int), the Strided K."""
+
+
+def _exact_bytes(n, nt):
+    from mobocmf_amd import _lib
+    sb, cb = ctypes.c_size_t(), ctypes.c_size_t()
+    _lib.check(lib().mobocmf_exact_gp_workspace_bytes(n, nt, ctypes.byref(sb), ctypes.byref(cb)), "mobocmf_exact_gp_workspace_bytes")
+    assert sb.value % 8 == 0 and cb.value % 8 == 0
+    return sb.value, cb.value
+
+
+def _nan_bytes(nbytes):
+    return torch.full((nbytes // 8,), NAN, dtype=torch.float64, device="cuda").view(torch.uint8)
+
+
+def exact_gp(K, ldk, y, tune, state=None):
+    """mobocmf_exact_gp_factor through the C ABI: K (n x n numpy) inside a NaN-filled store of leading dimension ``ldk``,
+    sizes from mobocmf_exact_gp_workspace_bytes, state and scratch NaN before the call (``state``: reuse that one, poisoned
+    again), ``ldk`` and the explicit ``tune`` passed unchanged.  Returns an ExactGP."""
+    from mobocmf_amd import _lib
+    n = K.shape[0]
+    sb, cb = _exact_bytes(n, 1)
+    g = ExactGP()
+    g.n, g.K = n, Strided(n, n, pad=ldk - n, fill=np.array(K))
+    g.state = _nan_bytes(sb) if state is None else state
+    g.state.view(torch.float64).fill_(NAN)
+    g.scratch = _nan_bytes(cb)
+    g.mll = torch.full((), NAN, dtype=torch.float64, device="cuda")
+    info = torch.full((), -77, dtype=torch.int32, device="cuda")
+    yd = torch.as_tensor(np.array(y), dtype=torch.float64).cuda()
+    rc = lib().mobocmf_exact_gp_factor(n, g.K.ptr, ldk, _p(yd), _p(g.mll), _p(info), _p(g.state), sb, _p(g.scratch), cb,
+                                       ctypes.byref(tune), _stream())
+    _lib.check(rc, "mobocmf_exact_gp_factor")
+    torch.cuda.synchronize()
+    g.info = int(info)
+    g.L, g.Li, g.npad = factors(g, n)
+    off = (g.npad * g.npad * 8 + 255) // 256 * 256 // 8
+    g.a = g.state.view(torch.float64)[2 * off:2 * off + g.npad]
+    return g
+
+
+def exact_gp_predict_direct(g, Kts, ld, kss, tune, guard=8):
+    """mobocmf_exact_gp_predict on the state of ``g``: Kts (n x nt numpy) with leading dimension ``ld`` (slack NaN), scratch
+    of the reported size NaN before the call, mean / var inside stores with ``guard`` sentinels behind them.  Returns
+    (mean, var, untouched): float64 numpy and whether every sentinel and all slack of Kts is as it was."""
+    from mobocmf_amd import _lib
+    n, nt = Kts.shape
+    sb, cb = _exact_bytes(n, nt)
+    assert sb == g.state.numel()
+    Kd = Strided(n, nt, pad=ld - nt, fill=Kts)
+    scratch = _nan_bytes(cb)
+    kd = torch.as_tensor(np.ascontiguousarray(kss), dtype=torch.float64).cuda()
+    SENT = -12345.0
+    mean = torch.full((nt + guard,), SENT, dtype=torch.float64, device="cuda")
+    var = torch.full((nt + guard,), SENT, dtype=torch.float64, device="cuda")
+    rc = lib().mobocmf_exact_gp_predict(n, nt, Kd.ptr, ld, _p(kd), _p(mean), _p(var), _p(g.state), sb, _p(scratch), cb,
+                                        ctypes.byref(tune), _stream())
+    _lib.check(rc, "mobocmf_exact_gp_predict")
+    torch.cuda.synchronize()
+    untouched = bool((mean[nt:] == SENT).all()) and bool((var[nt:] == SENT).all()) and Kd.slack_untouched()
+    return mean[:nt].cpu().numpy(), var[:nt].cpu().numpy(), untouched
+
+
+def mf_combine(Ks, Kn, s1, s2, l1, l2, ntab, diag, out, n1, n2, rows_p, cols_p):
+    """mobocmf_mf_kernel_combine on Strided Ks / Kn (one leading dimension) and a Strided ``out`` of rows_p x cols_p; s1 / s2
+    may be None (NULL)."""
+    from mobocmf_amd import _lib
+    assert Ks.ld == Kn.ld and out.rows >= rows_p and out.width == cols_p
+    rc = lib().mobocmf_mf_kernel_combine(n1, n2, Ks.ptr, Kn.ptr, Ks.ld, _p(s1), _p(s2), _p(l1), _p(l2), _p(ntab), float(diag),
+                                         out.ptr, out.ld, rows_p, cols_p, _stream())
+    _lib.check(rc, "mobocmf_mf_kernel_combine")

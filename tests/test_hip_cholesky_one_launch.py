@@ -5,6 +5,8 @@ Reference behaviour: gpytorch psd_safe_cholesky(K_mm) inside the variational str
 import pytest
 import torch
 
+from tests.kernel_reference import factors as _factors
+
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda")
 
@@ -16,15 +18,6 @@ def _gram(n, d, ls, jitter, seed):
     d2 = ((x[:, None, :] - x[None, :, :]) ** 2).sum(-1)
     K = torch.exp(-0.5 * d2 / ls ** 2) + jitter * torch.eye(n, dtype=torch.float64, device=DEV)
     return K, torch.randn(n, dtype=torch.float64, device=DEV, generator=g)
-
-
-def _factors(st, n):
-    npad = (n + 127) // 128 * 128
-    buf = st.state.view(torch.float64)
-    L = buf[:npad * npad].view(npad, npad)
-    off = (npad * npad * 8 + 255) // 256 * 256 // 8
-    Li = buf[off:off + npad * npad].view(npad, npad)
-    return L, Li, npad
 
 
 @pytest.mark.parametrize("n,d,ls", [(129, 3, 0.7), (192, 4, 1.0), (200, 2, 0.6), (320, 5, 1.2), (512, 8, 1.4), (700, 2, 0.5),

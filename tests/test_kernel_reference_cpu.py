@@ -7,6 +7,10 @@
   longdouble reference, and compared with the constant recorded in kernel_reference.py.
 * The longdouble ELBO reference against a plain float64 restatement.
 * The product dispatch refuses, on the host, the sizes no kernel takes.
+* The factorisation chain: float64 restatements of every algorithm of chol.hip (substitution-form Cholesky with the
+  reciprocal-root multiply, the one-launch form's explicit-inverse panels, the three inverses) stay within HALF of the
+  a-priori bounds of kernel_reference.py on every case the GPU tests run; the explicit-inverse panels exceed the classical
+  bound (why that form has its own); tri_inverse_hp against mpmath; and slightly wrong references trip each checker.
 """
 import numpy as np
 import pytest
@@ -199,3 +203,279 @@ def test_gemm_declined_shapes_are_refused_on_the_host(shape, trans_b, tune_kw):
     rc = _lib.load().mobocmf_gemm_f64(0, trans_b, Mr, Nc, Kd, p, Kd, p, Kd if trans_b else Nc, p, Nc, ctypes.c_double(1.0), 0,
                                       ctypes.byref(tune), None)
     assert rc == R.BAD_ARG
+
+
+# ------------------------------------------------------------------------------------------------ factorisation chain
+# float64 restatements of the algorithms of chol.hip, run through the checkers the GPU tests use.  Each must stay at or below
+# HALF of its bound on every (family, n) the GPU tests run: where one did not, the case would change, never the constant.
+def _chol_recip(K, drop=None):
+    """Unblocked right-looking Cholesky with the reciprocal-root multiply (l_ij = s_ij r_j, l_jj = s_jj r_j, r_j = 1 / sqrt(s_jj):
+    two roundings, inside the 2 u allowed for rsqrt_nr).  drop = (i0, i1, j): the update of rows i0:i1 by column j is left out."""
+    S = np.array(K, np.float64)
+    n = S.shape[0]
+    for j in range(n):
+        r = 1.0 / np.sqrt(S[j, j])
+        S[j:, j] *= r
+        l = S[j + 1:, j].copy()
+        if drop is not None and drop[2] == j:
+            l[max(drop[0] - j - 1, 0):max(drop[1] - j - 1, 0)] = 0.0
+            S[j + 1:, j + 1:] -= np.outer(l, S[j + 1:, j])
+        else:
+            S[j + 1:, j + 1:] -= np.outer(l, l)
+    return np.tril(S)
+
+
+def _inv_recip(L):
+    """Inverse of a small lower triangle by substitution with a reciprocal diagonal, row i from the rows above."""
+    m = L.shape[0]
+    X = np.zeros((m, m))
+    for i in range(m):
+        r = 1.0 / L[i, i]
+        X[i, :i] = -(L[i, :i] @ X[:i, :i]) * r
+        X[i, i] = r
+    return X
+
+
+def _block_explicit(A, m):
+    """One diagonal block by panels of width m formed as PRODUCTS with the explicit inverse of the pivot block (m = 16 inside
+    a 64-block: potrf_coop_kernel part (A); the pivot tile itself by _chol_recip / _inv_recip as chol_inv_tile16 does), and the
+    block's inverse assembled as X_sc = -X_ss sum_t L_st X_tc.  Returns (L, X)."""
+    S = np.array(A, np.float64)
+    n = S.shape[0]
+    X = np.zeros((n, n))
+    for s0 in range(0, n, m):
+        s1 = min(s0 + m, n)
+        Lss = _chol_recip(S[s0:s1, s0:s1])
+        Xss = _inv_recip(Lss)
+        S[s0:s1, s0:s1] = Lss
+        S[s1:, s0:s1] = S[s1:, s0:s1] @ Xss.T
+        S[s1:, s1:] -= S[s1:, s0:s1] @ S[s1:, s0:s1].T
+        X[s0:s1, s0:s1] = Xss
+        if s0:
+            X[s0:s1, :s0] = -(Xss @ (S[s0:s1, :s0] @ X[:s0, :s0]))
+    return np.tril(S), X
+
+
+def _chol_explicit(K):
+    """Blocked Cholesky as the one-launch form runs it: 64-column steps, the diagonal block by _block_explicit(16), EVERY
+    block below it as a product with the block's computed inverse, the trailing update as one product per step.  Returns
+    (L, X) with X holding the explicit inverses on its diagonal 64-blocks (zero elsewhere)."""
+    S = np.array(K, np.float64)
+    n = S.shape[0]
+    X = np.zeros((n, n))
+    for j0 in range(0, n, 64):
+        j1 = min(j0 + 64, n)
+        LJ, XJ = _block_explicit(S[j0:j1, j0:j1], 16)
+        S[j0:j1, j0:j1] = LJ
+        X[j0:j1, j0:j1] = XJ
+        S[j1:, j0:j1] = S[j1:, j0:j1] @ XJ.T
+        S[j1:, j1:] -= S[j1:, j0:j1] @ S[j1:, j0:j1].T
+    return np.tril(S), X
+
+
+def _trtri(L, route):
+    """launch_trtri_z restated: 64-block inverses by substitution, level 0 [[D0, 0], [-D1 (L10 D0), D1]] per 128-block, then
+    recursive doubling X21 = -X22 (L21 X11) ('doubling': power-of-two block counts) or block row by block row ('rows').
+    The matrix is padded to a multiple of 128 with the identity, as the device pads it."""
+    n = L.shape[0]
+    Mp = (n + 127) // 128 * 128
+    Lp = np.eye(Mp)
+    Lp[:n, :n] = np.tril(L)
+    X = np.zeros((Mp, Mp))
+    for o in range(0, Mp, 128):
+        D0, D1 = _inv_recip(Lp[o:o + 64, o:o + 64]), _inv_recip(Lp[o + 64:o + 128, o + 64:o + 128])
+        X[o:o + 64, o:o + 64], X[o + 64:o + 128, o + 64:o + 128] = D0, D1
+        X[o + 64:o + 128, o:o + 64] = -(D1 @ (Lp[o + 64:o + 128, o:o + 64] @ D0))
+    nb = Mp // 128
+    if route == "doubling":
+        assert nb & (nb - 1) == 0
+        sz = 128
+        while sz < Mp:
+            for o in range(0, Mp, 2 * sz):
+                T = Lp[o + sz:o + 2 * sz, o:o + sz] @ X[o:o + sz, o:o + sz]
+                X[o + sz:o + 2 * sz, o:o + sz] = -(X[o + sz:o + 2 * sz, o + sz:o + 2 * sz] @ T)
+            sz *= 2
+    else:
+        for i in range(1, nb):
+            o = 128 * i
+            T = Lp[o:o + 128, :o] @ X[:o, :o]
+            X[o:o + 128, :o] = -(X[o:o + 128, o:o + 128] @ T)
+    return X[:n, :n]
+
+
+def _trtri_right_looking(L, Xd):
+    """The one-launch form's own inverse (potrf_coop_kernel, the inverse workgroups) restated: right-looking in 64-blocks,
+    S_ic = sum_{t < i} L_it X_tc accumulated in X's own storage as the block rows complete, X_jc = -X_jj S_jc, X_jj = the
+    explicit inverse of the diagonal block (the diagonal 64-blocks of ``Xd``)."""
+    n = L.shape[0]
+    X = np.zeros((n, n))
+    for j0 in range(0, n, 64):
+        j1 = min(j0 + 64, n)
+        Xjj = Xd[j0:j1, j0:j1]
+        X[j0:j1, :j0] = 0.0 - Xjj @ X[j0:j1, :j0]
+        X[j0:j1, j0:j1] = Xjj
+        X[j1:, :j1] += L[j1:, j0:j1] @ X[j0:j1, :j1]
+    return X
+
+
+def _cases():
+    return [(f, n) for n in R.FACTOR_ORDERS + (R.FACTOR_ORDER_COOP_CAPS,) for f in R.factor_families(n)]
+
+
+def test_factor_cases_have_the_stated_conditioning():
+    for f, n in _cases():
+        K, y = R.factor_case(f, n)
+        assert K.shape == (n, n) and y.shape == (n,) and np.array_equal(K, K.T) and np.isfinite(K).all()
+        if f == "rbf" and n >= 15:
+            w = np.linalg.eigvalsh(K)
+            assert 1e6 <= w[-1] / w[0] <= 1e9, (n, w[-1] / w[0])
+            assert K.min() > 0
+        if f == "signed":
+            w = np.linalg.eigvalsh(K)
+            assert w[-1] / w[0] < 100 and np.array_equal(K, np.round(K)) and (n < 3 or K.min() < 0 < K.max())
+            assert np.abs(K).max() < 2 ** 20
+        if f == "rbf_scaled":
+            K0, y0 = R.factor_case("rbf", n)
+            D = R.tile_scales(n, 64, 17 * n)
+            assert np.array_equal(K, D[:, None] * K0 * D[None, :]) and np.array_equal(y, D * y0)       # (exact scalings)
+            assert np.array_equal(K / D[:, None] / D[None, :], K0)
+            assert 2.0 ** -201 < np.abs(K[K != 0]).min() and np.abs(K).max() < 2.0 ** 201
+
+
+def test_tri_inverse_hp_matches_an_mpmath_inverse():
+    import mpmath
+    n = 40
+    L = np.linalg.cholesky(R.factor_case("rbf", 40)[0])
+    X = R.tri_inverse_hp(L)
+    mpmath.mp.dps = 50
+    Xm = mpmath.inverse(mpmath.matrix(L.tolist()))
+    aX = np.abs(np.asarray(X, np.float64))
+    Rb = aX @ np.abs(L) @ aX
+    for i in range(n):
+        for j in range(n):
+            ref = Xm[i, j]
+            if j > i:
+                assert X[i, j] == 0 and abs(ref) < mpmath.mpf(10) ** -30
+                continue
+            # the reference's own error, n 2^-64 |X||L||X| when longdouble carries it; compared at 50 digits
+            err = abs(mpmath.mpf(float(X[i, j])) + mpmath.mpf(float(X[i, j] - np.longdouble(float(X[i, j])))) - ref)
+            assert err <= (n + 2) * 2.0 ** -64 * Rb[i, j] * (1 if R.HAVE_LONGDOUBLE else 2 ** 11), (i, j)
+
+
+_worst = {}
+
+
+@pytest.mark.parametrize("family,n", _cases(), ids=lambda v: str(v))
+def test_factor_restatements_stay_within_half_of_each_bound(family, n):
+    """Worst fractions of the bound over all cases (printed per case; this machine, numpy float64 against longdouble):
+    substitution-form Cholesky 0.39 of (k + 8) u |L||L^T| (rbf, n = 192, at k = 1; 2.2 .. 3.9 u R on the rbf families, up to
+    16.5 u R at k in the hundreds on ``signed``), explicit-inverse Cholesky 0.39 of its own bound (41 .. 1053 u R on the rbf
+    families from n = 63 on: far outside the classical bound; 3 .. 5.4 u R on ``signed``, where it keeps the classical one too),
+    inverse by recursive doubling / block rows / the one-launch form's right-looking sweep 0.2 .. 4.63 in units of
+    u |X||L||X| (4.63 at n = 640) against n + 8, at most 0.035 of the bound, a = L^-1 y at most 2.1 of n + 2, mll at most 2.8 of n + 8 (both worst where n + . is >= 130).  The
+    two routes of the inverse agree to the printed digits: their products differ in shape, not in the terms they sum."""
+    K, y = R.factor_case(family, n)
+    L = _chol_recip(K)
+    ok, ru, frac = R.chol_check(L, K)
+    assert ok and frac <= 0.5, (ru, frac)
+    _worst["sub"] = max(_worst.get("sub", 0), frac)
+    Le, Xe = _chol_explicit(K)
+    ok, rue, frace = R.chol_check(Le, K, Xe)
+    assert ok and frace <= 0.5, (rue, frace)
+    _worst["exp"] = max(_worst.get("exp", 0), frace)
+    Xhp = R.tri_inverse_hp(L)
+    nb = (n + 127) // 128
+    routes = ("doubling", "rows") if nb & (nb - 1) == 0 else ("rows",)
+    ri = {}
+    for route in routes:
+        X = _trtri(L, route)
+        ok, ri[route] = R.trinv_check(X, L, Xhp)
+        assert ok and ri[route] <= 0.5 * (n + R.TRINV_CX), (route, ri[route])
+        _worst["inv"] = max(_worst.get("inv", 0), ri[route])
+        _worst["invfrac"] = max(_worst.get("invfrac", 0), ri[route] / (n + R.TRINV_CX))
+    if R.one_launch_runs(n, 0):
+        ok, ri["one launch"] = R.trinv_check(_trtri_right_looking(Le, Xe), Le)
+        assert ok and ri["one launch"] <= 0.5 * (n + R.TRINV_CX), ri
+        _worst["inv"] = max(_worst["inv"], ri["one launch"])
+    a = X @ y
+    ok, ra = R.solve_check(a, X, y)
+    assert ok and ra <= 0.5 * (n + 2), ra
+    mll = float(-0.5 * (a * a).sum() - np.log(np.diag(L)).sum() - 0.5 * n * np.log(2 * np.pi))
+    ok, rm = R.mll_check(mll, L, a)
+    assert ok and rm <= 0.5 * (n + R.MLL_CLOG), rm
+    print("n=%d %s: chol %.2f uR (%.3f of bound), explicit %.2f uR (%.3f of its bound), inverse %s uR, a %.2f, mll %.2f; worst so far %s"
+          % (n, family, ru, frac, rue, frace, {k: round(v, 2) for k, v in ri.items()}, ra, rm,
+             {k: round(v, 3) for k, v in _worst.items()}))
+
+
+@pytest.mark.parametrize("family", ("rbf", "signed"))
+@pytest.mark.parametrize("n", R.PREDICT_N)
+def test_predict_restatement_stays_within_half_of_its_bound(family, n):
+    K, y = R.factor_case(family, n)
+    L = _chol_recip(K)
+    X = _trtri(L, "rows")
+    a = X @ y
+    for nt in R.PREDICT_NT:
+        Kts, kss = R.cross_kernel(family, n, nt)
+        A = X @ Kts
+        okm, rm, okv, rv = R.predict_check(a @ A, kss - (A * A).sum(0), X, a, Kts, kss)
+        assert okm and okv and max(rm, rv) <= 0.5 * (2 * n + 4), (nt, rm, rv)
+
+
+def test_explicit_inverse_panels_exceed_the_classical_bound():
+    """Why the one-launch form carries a bound of its own: the restatement of its panels -- products with the computed
+    inverse of the diagonal block -- misses the classical (k + 8) u |L||L^T| on the workload's own conditioning, while the
+    substitution form on the same matrix keeps it and the explicit form keeps ITS bound."""
+    K, _ = R.factor_case("rbf", 257)
+    Le, Xe = _chol_explicit(K)
+    ok, ru, frac = R.chol_check(Le, K)
+    print("explicit-inverse panels against the classical bound: %.1f u R, %.2f of the bound" % (ru, frac))
+    assert not ok and frac > 1.0
+    assert R.chol_check(Le, K, Xe)[0] and R.chol_check(_chol_recip(K), K)[0]
+
+
+# ---- the bounds bite: a reference that is deliberately, slightly wrong trips the assertion
+@pytest.mark.parametrize("family", R.FACTOR_FAMILIES)
+def test_mutation_one_sign_in_a_tile_of_the_factor(family):
+    K, _ = R.factor_case(family, 129)
+    L = _chol_recip(K)
+    assert R.chol_check(L, K)[0]
+    for (i, j) in ((40, 5), (128, 70), (127, 127)):
+        Lm = L.copy()
+        Lm[i, j] = -Lm[i, j]
+        assert not R.chol_check(Lm, K)[0], (i, j)
+    Le, Xe = _chol_explicit(K)
+    Le[100, 66] = -Le[100, 66]
+    assert not R.chol_check(Le, K, Xe)[0]
+
+
+@pytest.mark.parametrize("family", R.FACTOR_FAMILIES)
+def test_mutation_one_dropped_trailing_update(family):
+    """Column 63's update of the last 64-block's rows alone is left out (one of 128 terms of those entries)."""
+    K, _ = R.factor_case(family, 193)
+    assert R.chol_check(_chol_recip(K), K)[0]
+    with np.errstate(invalid="ignore"):
+        Lm = _chol_recip(K, drop=(128, 192, 63))
+    # (at the rbf families' conditioning the missing term makes a later pivot negative; ``signed`` stays finite, so there it
+    # is the bound that notices)
+    assert family != "signed" or np.isfinite(Lm).all()
+    assert not R.chol_check(Lm, K)[0]
+
+
+@pytest.mark.parametrize("family", R.FACTOR_FAMILIES)
+def test_mutation_one_row_of_the_inverse_off_by_1e12(family):
+    K, y = R.factor_case(family, 129)
+    L = _chol_recip(K)
+    X = _trtri(L, "rows")
+    Xhp = R.tri_inverse_hp(L)
+    assert R.trinv_check(X, L, Xhp)[0]
+    for row in (0, 70, 128):
+        Xm = X.copy()
+        Xm[row] *= 1 + 1e-12
+        assert not R.trinv_check(Xm, L, Xhp)[0], row
+    a = X @ y
+    am = a.copy()
+    am[77] *= 1 + 1e-9
+    assert R.solve_check(a, X, y)[0] and not R.solve_check(am, X, y)[0]
+    mll = float(-0.5 * (a * a).sum() - np.log(np.diag(L)).sum() - 0.5 * 129 * np.log(2 * np.pi))
+    assert R.mll_check(mll, L, a)[0] and not R.mll_check(mll * (1 + 1e-11), L, a)[0]
