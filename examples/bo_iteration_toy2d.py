@@ -5,10 +5,11 @@ step on the MI355X path -- the flow of examples/example_acquisition_mfdgp_toy_2d
   fit the unconditioned MFDGPs  ->  sample a Pareto solution (RFF posterior samples + MOOP)  ->  fit the conditioned
   MFDGPs (theta / omega factors)  ->  maximise the cost-weighted JES acquisition per fidelity  ->  next (x, fidelity).
 
-    python examples/bo_iteration_toy2d.py [--epochs 300] [--seed 0] [--iters K [--warm-epochs E]]
+    python examples/bo_iteration_toy2d.py [--epochs 300] [--seed 0] [--iters K [--warm-epochs E]] [--pareto-samples K]
 
 With ``--warm-epochs E`` every iteration after the first starts from the previous iteration's unconditioned fit
 (``warm_start="posterior"``: hyper-parameters, q(u) and noise carried over) and trains E epochs of phase 2 only.
+With ``--pareto-samples K`` the acquisition is the average of JES over K sampled Pareto sets, each with its own conditioned fit.
 """
 import argparse
 import faulthandler
@@ -37,8 +38,11 @@ def blackboxes():
 
 
 def run(epochs=300, cond_iters=200, acq_iters=50, n_low=14, n_high=6, grid=100, seed=0, device="cuda", verbose=True,
-        data=None, model_kwargs=None, acq_search="host", previous=None, warm_epochs=None):
-    """``previous`` with ``warm_epochs``: a fitter holding the UNCONDITIONED fits of the same black-boxes on ``data`` without its
+        data=None, model_kwargs=None, acq_search="host", previous=None, warm_epochs=None, pareto_samples=1, pareto_seed=None):
+    """``pareto_samples`` = K > 1: JES averaged over K sampled Pareto sets (sample 0 is the one drawn here; ``pareto_seed``: the
+    seeded procedure for the others).
+
+    ``previous`` with ``warm_epochs``: a fitter holding the UNCONDITIONED fits of the same black-boxes on ``data`` without its
     last rows -- the acquisition's ``blackbox_mfdgp_fitter_uncond`` of the last iteration (the fitter this function returns has
     been trained conditioned since).  Every black-box is then initialised from its predecessor with ``warm_start="posterior"``,
     there is no phase 1 and phase 2 runs ``warm_epochs`` epochs."""
@@ -68,7 +72,8 @@ def run(epochs=300, cond_iters=200, acq_iters=50, n_low=14, n_high=6, grid=100, 
     fitter.sample_and_store_pareto_solution()
     t.append(time.perf_counter())
     fitter.num_epochs_2 = cond_iters
-    acq = JESMOC_MFDGP(model=fitter, num_fidelities=2, search=acq_search,
+    acq = JESMOC_MFDGP(model=fitter, num_fidelities=2, search=acq_search, num_pareto_samples=pareto_samples,
+                       pareto_seed=pareto_seed,
                        standard_bounds=torch.tensor([[0.0, 0.0], [1.0, 1.0]], dtype=torch.float64, device=device))
     torch.cuda.synchronize(); t.append(time.perf_counter())
     for f in range(2):
@@ -77,7 +82,8 @@ def run(epochs=300, cond_iters=200, acq_iters=50, n_low=14, n_high=6, grid=100, 
     cand, fidelity = acq.get_nextpoint_coupled(iteration=0, verbose=verbose, maxiter=acq_iters)
     torch.cuda.synchronize(); t.append(time.perf_counter())
     if verbose:
-        print("pareto set %s, front %s" % (tuple(fitter.pareto_set.shape), tuple(fitter.pareto_front.shape)))
+        print("pareto set %s, front %s" % (tuple(fitter.pareto_set.shape), tuple(fitter.pareto_front.shape)) +
+              ("" if pareto_samples == 1 else "  (sample 0 of %d)" % pareto_samples))
         print("seconds: fit %.2f | pareto sample %.2f | conditioned fit %.2f | acquisition search %.2f" %
               tuple(b - a for a, b in zip(t[:-1], t[1:])))
         print("next point", cand.cpu().numpy(), "at fidelity", fidelity)
@@ -114,10 +120,12 @@ if __name__ == "__main__":
     ap.add_argument("--iters", type=int, default=1, help="number of BO iterations (1 = a single, verbose iteration)")
     ap.add_argument("--warm-epochs", type=int, default=None,
                     help="with --iters > 1: warm-start every iteration after the first and train this many phase-2 epochs")
+    ap.add_argument("--pareto-samples", type=int, default=1,
+                    help="average the JES acquisition over this many sampled Pareto sets (one conditioned fit each)")
     a = ap.parse_args()
     if a.warm_epochs is not None and a.iters < 2:
         ap.error("--warm-epochs needs --iters > 1: the first iteration has no predecessor to start from")
     if a.iters > 1:
-        loop(iters=a.iters, seed=a.seed, epochs=a.epochs, warm_epochs=a.warm_epochs)
+        loop(iters=a.iters, seed=a.seed, epochs=a.epochs, warm_epochs=a.warm_epochs, pareto_samples=a.pareto_samples)
     else:
-        run(epochs=a.epochs, seed=a.seed)
+        run(epochs=a.epochs, seed=a.seed, pareto_samples=a.pareto_samples)

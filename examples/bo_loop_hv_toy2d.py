@@ -17,8 +17,11 @@ training rows by greedy conditional variance (``inducing_selection="greedy_varia
 (``warm_start="posterior"``) and trains ``--warm-epochs`` epochs of phase 2 only (default: ``--epochs``).  The new inducing
 inputs must extend the old ones, which all training rows and the first M rows do and a greedy re-selection in general does not.
 
+``--pareto-samples K`` averages the JES acquisition over K sampled Pareto sets (JESMOC_MFDGP(num_pareto_samples=K)).
+
     python examples/bo_loop_hv_toy2d.py [--iters 5] [--acq jes|random] [--epochs 300] [--seed 0] [--out .]
                                         [--num-inducing M] [--inducing first|greedy] [--warm-start [--warm-epochs E]]
+                                        [--pareto-samples K]
 """
 import argparse
 import faulthandler
@@ -82,10 +85,10 @@ def score(fitter, grid):
 
 
 def loop_hv(iters=5, acq="jes", seed=0, out_dir=".", epochs=300, verbose=True, num_inducing=None, inducing="first",
-            warm_start=False, warm_epochs=None, **kw):
+            warm_start=False, warm_epochs=None, pareto_samples=1, **kw):
     """``iters`` BO iterations, each one scored and appended to ``out_dir``/hypervolumes.txt; returns the rows.
     ``warm_start``: every iteration after the first starts from the last one's unconditioned fit, ``warm_epochs`` epochs of
-    phase 2 (default: ``epochs``)."""
+    phase 2 (default: ``epochs``).  ``pareto_samples``: JES averaged over this many sampled Pareto sets."""
     warm_epochs = (epochs if warm_epochs is None else warm_epochs) if warm_start else None
     previous = None
     model_kwargs = {}
@@ -113,7 +116,8 @@ def loop_hv(iters=5, acq="jes", seed=0, out_dir=".", epochs=300, verbose=True, n
             cand, fidelity = chooser.get_nextpoint_coupled(iteration=it)
         else:
             fitter, jes, cand, fidelity = run(seed=seed + it, data=(x, fid), epochs=epochs, verbose=False,
-                                              model_kwargs=model_kwargs, previous=previous, warm_epochs=warm_epochs, **kw)
+                                              model_kwargs=model_kwargs, previous=previous, warm_epochs=warm_epochs,
+                                              pareto_samples=pareto_samples, **kw)
             previous = jes.blackbox_mfdgp_fitter_uncond if warm_start else None
         row = score(fitter, grid)
         with open(path, "a") as f:
@@ -141,8 +145,10 @@ if __name__ == "__main__":
                     help="start every iteration after the first from the previous iteration's fit (warm_start='posterior')")
     ap.add_argument("--warm-epochs", type=int, default=None,
                     help="with --warm-start: phase-2 epochs of a warm refit (default: --epochs)")
+    ap.add_argument("--pareto-samples", type=int, default=1,
+                    help="average the JES acquisition over this many sampled Pareto sets (one conditioned fit each)")
     a = ap.parse_args()
     if a.warm_epochs is not None and not a.warm_start:
         ap.error("--warm-epochs needs --warm-start")
     loop_hv(iters=a.iters, acq=a.acq, seed=a.seed, out_dir=a.out, epochs=a.epochs, num_inducing=a.num_inducing,
-            inducing=a.inducing, warm_start=a.warm_start, warm_epochs=a.warm_epochs)
+            inducing=a.inducing, warm_start=a.warm_start, warm_epochs=a.warm_epochs, pareto_samples=a.pareto_samples)

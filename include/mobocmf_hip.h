@@ -861,7 +861,8 @@ int mobocmf_natgrad_small_step(const mobocmf_natgrad_small_layer* host_layers, c
 
 /* ---- The acquisition search on the device (csrc/acq_search.hip): the glue between the two one-launch model evaluations of an
  * iterate (mobocmf_tiny_elbo_step / mobocmf_coop_elbo_step, MOBOCMF_STEP_FORWARD then MOBOCMF_STEP_INPUT_GRADIENTS, over a predict
- * group whose models 2p / 2p + 1 are the unconditioned / conditioned surrogate of black-box p) and the selection of restarts and
+ * group whose models 2p / 2p + 1 are the unconditioned / conditioned surrogate of black-box p -- or, with K sampled Pareto sets,
+ * whose models p (1 + K) .. p (1 + K) + K are the unconditioned and the K conditioned ones) and the selection of restarts and
  * winner -- the loop of optimize_acqf at mobocmf/acquisition_functions/JESMOC_MFDGP.py:137-184 with no host in it.  Each entry
  * point is ONE launch on `stream`, has no atomics and a fixed summation order (two calls on the same inputs are bitwise equal),
  * allocates nothing, reads nothing on the host and keeps no state: capturable.  A bad argument is refused with MOBOCMF_BAD_ARG
@@ -887,6 +888,25 @@ int mobocmf_natgrad_small_step(const mobocmf_natgrad_small_layer* host_layers, c
 int mobocmf_jes_group_forward(const double* moments, const double* noise, int32_t n_pairs, int32_t T, int32_t S,
                               double* acq, int32_t want_seeds, double* seeds, int32_t track, const double* x, int32_t d,
                               double* best_v, double* best_x, mobocmf_stream_t stream);
+
+/* JES averaged over K sampled Pareto sets (a Monte Carlo estimate of the information gain: the unconditioned surrogate of a
+ * black-box is evaluated ONCE, against K surrogates conditioned on K different sampled Pareto sets).
+ *   moments  (n_boxes (1 + K), 2, T S), noise (n_boxes (1 + K)): as above; model p (1 + K) is the unconditioned surrogate of
+ *            black-box p, model p (1 + K) + 1 + k the one conditioned on sample k = 0 .. K - 1.  v and mbar per model as above.
+ *   diff_pk = log v_u,p - log v_c,pk
+ *   acq[t]  = sum_p (1 / K) sum_k 0.5 max(diff_pk, 0): the k-sum in the order of k, the product with 1 / K rounded, then the sum
+ *             over p in the order of p.  A NaN stays a NaN.
+ * want_seeds = 1: seeds (the layout of moments) = d (sum_t acq[t]) / d (raw mean, raw variance):
+ *   d a / d v_c,pk = -0.5 / (K v_c,pk) where diff_pk >= 0, else 0;  d a / d v_u,p = #{k: diff_pk >= 0} 0.5 / (K v_u,p);
+ *   d v / d var_s and d v / d mu_s as above.
+ * track = 1: as above.
+ * With K = 1 the results (acq, seeds, best_v, best_x) are bitwise those of mobocmf_jes_group_forward with n_pairs = n_boxes.
+ * One launch of T workgroups of one wavefront: a lane per model, the sums by one lane in a fixed order, no atomics.
+ * MOBOCMF_BAD_ARG: as for mobocmf_jes_group_forward, with n_boxes < 1, K < 1 or n_boxes (1 + K) > 2 MOBOCMF_ACQ_MAX_PAIRS in
+ * place of its bound on n_pairs. */
+int mobocmf_jes_mc_group_forward(const double* moments, const double* noise, int32_t n_boxes, int32_t K, int32_t T, int32_t S,
+                                 double* acq, int32_t want_seeds, double* seeds, int32_t track, const double* x, int32_t d,
+                                 double* best_v, double* best_x, mobocmf_stream_t stream);
 
 /* One projected Adam ASCENT step on the iterate x (T x d): g[t][j] = -sum_i gx[i][t][j] over the n_models slices of the group's
  * input gradients gx (n_models, T, d) in the order of i, then the update of mobocmf_adam_multi (the same expressions in the same

@@ -22,31 +22,45 @@ from .. import parallel
 
 
 class _JES_MFDGP:
+    """JES of one black-box at one fidelity.  ``mfdgp_cond``: the conditioned model, or a list of K models conditioned on K
+    sampled Pareto sets: the value is then the mean of the K single-sample values (the Monte Carlo estimate of the information
+    gain), the unconditioned model evaluated once.  ``mfdgp_conds`` is the list, ``mfdgp_cond`` its first."""
 
     def __init__(self, fidelity, mfdgp_uncond, mfdgp_cond, model=None):
         assert model is None
         self.fidelity = fidelity
         self.mfdgp_uncond = mfdgp_uncond
-        self.mfdgp_cond = mfdgp_cond
+        self.mfdgp_conds = list(mfdgp_cond) if isinstance(mfdgp_cond, (list, tuple)) else [mfdgp_cond]
+        if not self.mfdgp_conds:
+            raise ValueError("_JES_MFDGP: at least one conditioned model")
+        self.mfdgp_cond = self.mfdgp_conds[0]
 
     def forward(self, X):
-        """Evaluate JES at X (T, d) or (T, 1, d).  Both models are switched to ``.eval()`` (full predictive branch,
-        no clamp) exactly as the reference does (:42-50)."""
+        """Evaluate JES at X (T, d) or (T, 1, d).  The models are switched to ``.eval()`` (full predictive branch,
+        no clamp) exactly as the reference does (:42-50).  K > 1: (1/K) sum_k 0.5 clamp(log v_u - log v_c,k, 0), summed in the
+        order of k."""
         self.mfdgp_uncond.eval()
         _, v_u = self.mfdgp_uncond.predict_for_acquisition(X, self.fidelity)
         self.mfdgp_uncond.train()
-        self.mfdgp_cond.eval()
-        _, v_c = self.mfdgp_cond.predict_for_acquisition(X, self.fidelity)
-        self.mfdgp_cond.train()
-        return F.jes(v_u, v_c)
+        total = None
+        for cond in self.mfdgp_conds:
+            cond.eval()
+            _, v_c = cond.predict_for_acquisition(X, self.fidelity)
+            cond.train()
+            term = F.jes(v_u, v_c)
+            total = term if total is None else total + term
+        K = len(self.mfdgp_conds)
+        return total if K == 1 else (1.0 / K) * total
 
     __call__ = forward
 
     @contextlib.contextmanager
     def frozen(self):
-        """Both models' parameters are constants while the acquisition is optimised: their M x M chains are computed
+        """All models' parameters are constants while the acquisition is optimised: their M x M chains are computed
         once (MFDGP.frozen_chains) instead of at each of the ~400 evaluations."""
-        with self.mfdgp_uncond.frozen_chains(), self.mfdgp_cond.frozen_chains():
+        with contextlib.ExitStack() as stack:
+            for m in [self.mfdgp_uncond] + self.mfdgp_conds:
+                stack.enter_context(m.frozen_chains())
             yield self
 
 
@@ -119,25 +133,34 @@ class JESMOC_MFDGP:
     MAX_RAW_CHUNKS = 8        # the device engine scores the raw candidates in at most this many forward launches
 
     def __init__(self, model, num_fidelities=1, model_cond=None, standard_bounds=None, eval_highest_fidelity=False,
-                 search="host"):
+                 search="host", num_pareto_samples=1, pareto_seed=None):
+        """``num_pareto_samples`` = K: the acquisition is the average of JES over K sampled Pareto sets, each with its own
+        conditioned fit (BlackBoxMFDGPFitter.conditioned_copies; ``pareto_seed``: the seeded sampling procedure, sample k from a
+        seed derived from (pareto_seed, k), sample 0 from pareto_seed itself).  ``model_cond``: a conditioned fitter, or a
+        list / tuple of K of them (``num_pareto_samples`` is then their number).  K = 1 is the reference's estimator."""
         if search not in ("host", "device"):
             raise ValueError("search must be 'host' or 'device' (got %r)" % (search,))
+        conds = None if model_cond is None else (list(model_cond) if isinstance(model_cond, (list, tuple)) else [model_cond])
+        K = int(num_pareto_samples) if conds is None else len(conds)
+        if K < 1:
+            raise ValueError("num_pareto_samples must be >= 1 (got %r)" % (num_pareto_samples,))
+        if K > 1 and not parallel._no_group():
+            raise ValueError("num_pareto_samples = %d: several Pareto samples are limited to one process (surrogates sharded "
+                             "over a process group take num_pareto_samples = 1)" % K)
+        self.num_pareto_samples = K
         self.search = search
         self.last_search_engine = {}      # fidelity -> "host" / "device": the engine its last search ran on
         self.standard_bounds = standard_bounds
         self.eval_highest_fidelity = eval_highest_fidelity
         self.blackbox_mfdgp_fitter_uncond = model.copy_uncond()
-        if model_cond is None:
-            # reference (:64-66): sample a Pareto solution (RFF posterior samples + MOOP) unless one was provided
-            if getattr(model, "pareto_set", None) is None:
-                model.sample_and_store_pareto_solution()
-            self.pareto_set, self.pareto_front = model.pareto_set, model.pareto_front
+        if conds is None:
+            # reference (:64-66): sample a Pareto solution (RFF posterior samples + MOOP) unless one was provided; K > 1: K of them
+            conds = model.conditioned_copies(K, seed=pareto_seed)
             self.samples_objs, self.samples_cons = getattr(model, "samples_objs", None), getattr(model, "samples_cons", None)
-            model.train_conditioned_mfdgps()
-            self.blackbox_mfdgp_fitter_cond = model
-        else:
-            self.pareto_set, self.pareto_front = model_cond.pareto_set, model_cond.pareto_front
-            self.blackbox_mfdgp_fitter_cond = model_cond
+        self.blackbox_mfdgp_fitters_cond = conds
+        self.pareto_sets, self.pareto_fronts = [c.pareto_set for c in conds], [c.pareto_front for c in conds]
+        self.pareto_set, self.pareto_front = self.pareto_sets[0], self.pareto_fronts[0]      # (sample 0, as ever)
+        self.blackbox_mfdgp_fitter_cond = conds[0]
         self.num_fidelities = num_fidelities
         self.objectives, self.constraints, self.costs_blackboxes = {}, {}, {}
         for n_f in range(num_fidelities):
@@ -156,8 +179,9 @@ class JESMOC_MFDGP:
             self.costs_blackboxes[fidelity][blackbox_name] = cost_evaluation
             return None
         mfdgp_uncond = self.blackbox_mfdgp_fitter_uncond.get_model(blackbox_name, is_constraint=is_constraint)
-        mfdgp_cond = self.blackbox_mfdgp_fitter_cond.get_model(blackbox_name, is_constraint=is_constraint)
-        jes_mfdgp = _JES_MFDGP(fidelity, mfdgp_uncond, mfdgp_cond)
+        fitters_cond = self.__dict__.get("blackbox_mfdgp_fitters_cond") or [self.blackbox_mfdgp_fitter_cond]
+        mfdgp_conds = [c.get_model(blackbox_name, is_constraint=is_constraint) for c in fitters_cond]
+        jes_mfdgp = _JES_MFDGP(fidelity, mfdgp_uncond, mfdgp_conds if len(mfdgp_conds) > 1 else mfdgp_conds[0])
         (self.constraints if is_constraint else self.objectives)[fidelity][blackbox_name] = jes_mfdgp
         self.costs_blackboxes[fidelity]["total"] += cost_evaluation
         self.costs_blackboxes[fidelity][blackbox_name] = cost_evaluation
@@ -176,26 +200,54 @@ class JESMOC_MFDGP:
         state.pop("_device_searches", None)  # ... and the captured graphs over them
         return state
 
+    @staticmethod
+    def _group_models(jess):
+        """The model list of a predict group: per black-box its unconditioned surrogate, then the K conditioned ones."""
+        return [m for jes in jess for m in [jes.mfdgp_uncond] + jes.mfdgp_conds]
+
+    def _group_value(self, v):
+        """The coupled acquisition from a group's v (n_boxes (1 + K), T): sum_p (1/K) sum_k 0.5 clamp(log v_u,p - log v_c,pk, 0),
+        the k-sum in the order of k (the expression of mobocmf_jes_mc_group_forward)."""
+        K = self.__dict__.get("num_pareto_samples", 1)
+        if K == 1:
+            return (0.5 * torch.clamp(torch.log(v[0::2]) - torch.log(v[1::2]), min=0.0)).sum(0)
+        lu = torch.log(v[0::1 + K])
+        box = None
+        for k in range(1, K + 1):
+            term = 0.5 * torch.clamp(lu - torch.log(v[k::1 + K]), min=0.0)
+            box = term if box is None else box + term
+        return ((1.0 / K) * box).sum(0)
+
+    def _make_group(self, make):
+        """``make()``; with several Pareto samples a group that its constructor refuses (MobocmfError) is no group: None."""
+        if self.__dict__.get("num_pareto_samples", 1) == 1:
+            return make()
+        from .._lib import MobocmfError
+        try:
+            return make()
+        except MobocmfError:
+            return None
+
     def _tiny_group(self, jess, fidelity, T, d):
-        """TinyPredictGroup (M <= 32) or CoopPredictGroup (M <= 128) over (uncond, cond) of every black-box of ``fidelity`` for T
+        """TinyPredictGroup (M <= 32) or CoopPredictGroup (M <= 128) over (uncond, cond_1 .. cond_K) of every black-box of ``fidelity`` for T
         test points -- when all of them fit a one-launch kernel (util/tiny_step.py, util/coop_step.py) -- else None.  Built once
         per (fidelity, T)."""
         cache = self.__dict__.setdefault("_tiny_groups", {})
         key = (fidelity, T, d)
         if key not in cache:
             from ..util import tiny_step as TS
-            models = [m for jes in jess for m in (jes.mfdgp_uncond, jes.mfdgp_cond)]
+            models = self._group_models(jess)
             on_gpu = bool(models) and all(p.is_cuda for p in models[0].parameters())
             if on_gpu and all(TS.fits_predict(m, fidelity, T, d) for m in models):
-                cache[key] = TS.TinyPredictGroup(models, fidelity, T, d)
+                cache[key] = self._make_group(lambda: TS.TinyPredictGroup(models, fidelity, T, d))
             else:      # mid-size surrogates (M <= 128): the cooperative launch, several workgroups per model
                 from ..util import coop_step as CS
                 ok = on_gpu and all(CS.fits_predict(m, fidelity, T, d) for m in models)
-                cache[key] = CS.CoopPredictGroup(models, fidelity, T, d) if ok else None
+                cache[key] = self._make_group(lambda: CS.CoopPredictGroup(models, fidelity, T, d)) if ok else None
         return cache[key]
 
     def _panel_group(self, jess, fidelity, T, d, want_gradients):
-        """PanelPredictGroup (128 < M <= 512, util/panel_predict.py) over (uncond, cond) of every black-box of ``fidelity`` for T
+        """PanelPredictGroup (128 < M <= 512, util/panel_predict.py) over (uncond, cond_1 .. cond_K) of every black-box of ``fidelity`` for T
         test points when all of them fit; else SplitPredictGroup (M <= 1024: 8-column panels, replicas split over workgroups)
         when all of them fit that; else None.  A cache of the DEVICE engine alone: ``coupled_acq`` never looks here, so
         the host engine evaluates these sizes through the layer path as ever."""
@@ -203,12 +255,12 @@ class JESMOC_MFDGP:
         key = (fidelity, T, d, bool(want_gradients))
         if key not in cache:
             from ..util import panel_predict as PP
-            models = [m for jes in jess for m in (jes.mfdgp_uncond, jes.mfdgp_cond)]
+            models = self._group_models(jess)
             on_gpu = bool(models) and all(p.is_cuda for p in models[0].parameters())
             cache[key] = None
             for fits, group in ((PP.fits_predict, PP.PanelPredictGroup), (PP.fits_predict_split, PP.SplitPredictGroup)):
                 if on_gpu and all(fits(m, fidelity, T, d) for m in models):
-                    cache[key] = group(models, fidelity, T, d, want_gradients=want_gradients)
+                    cache[key] = self._make_group(lambda: group(models, fidelity, T, d, want_gradients=want_gradients))
                     break
         return cache[key]
 
@@ -216,7 +268,8 @@ class JESMOC_MFDGP:
         """Sum over all black-boxes (:125-135).  Sharded surrogates: each rank adds its own, one all-gather sums.
         Small surrogates (the reference's own sizes): the predictive moments of ALL models -- unconditioned and conditioned,
         every black-box -- come from one launch, their gradient w.r.t. X from one more (TinyPredictGroup); the JES value
-        0.5 clamp(log v_uncond - log v_cond, 0) (:38-52) is then a handful of element-wise operations over all of them."""
+        0.5 clamp(log v_uncond - log v_cond, 0) (:38-52) is then a handful of element-wise operations over all of them.
+        With K > 1 sampled Pareto sets the value of a black-box is the mean over its K conditioned surrogates (_group_value)."""
         X = X.double()
         jess = list(self.objectives[fidelity].values()) + list(self.constraints[fidelity].values())
         if self.use_tiny_step and jess and X.is_cuda and parallel.world()[1] == 1:
@@ -226,7 +279,7 @@ class JESMOC_MFDGP:
                 if self.__dict__.get("_search_running") and hasattr(grp, "freeze"):
                     grp.freeze()      # (constant parameters for the whole search: the chains are formed by its first launch only)
                 _, v = grp.acquisition_moments(X2)
-                return (0.5 * torch.clamp(torch.log(v[0::2]) - torch.log(v[1::2]), min=0.0)).sum(0)
+                return self._group_value(v)
         local = [obj(X) for obj in self.objectives[fidelity].values()] + \
                 [con(X) for con in self.constraints[fidelity].values()]
         if not local:
@@ -261,11 +314,17 @@ class JESMOC_MFDGP:
         which ``coupled_acq`` evaluates through a one-launch group, and a group fits T = num_restarts and the raw candidates,
         whole or in up to ``MAX_RAW_CHUNKS`` equal chunks (200 candidates x 25 samples are beyond the kernels' 4096 columns); or,
         where no one-launch group fits, frozen-chain groups do (128 < M <= 1024: the raw candidates whole, no column limit
-        there) -- else None: M > 1024, S = 1, sharded surrogates, CPU tensors keep the host loop."""
+        there) -- else None: M > 1024, S = 1, sharded surrogates, CPU tensors keep the host loop.  With K > 1 Pareto samples a
+        group holds 1 + K models per black-box: more than 2 MOBOCMF_ACQ_MAX_PAIRS models keep the host loop too."""
         jess = list(self.objectives[fidelity].values()) + list(self.constraints[fidelity].values())
         bounds = self.standard_bounds
         if not (self.use_tiny_step and jess and bounds is not None and bounds.is_cuda and parallel.world()[1] == 1):
             return None
+        K = self.__dict__.get("num_pareto_samples", 1)
+        if K > 1:
+            from .. import _lib
+            if len(jess) * (1 + K) > 2 * _lib.ACQ_MAX_PAIRS:
+                return None
         d = bounds.shape[1]
         if self.num_restarts > self.raw_samples:
             return None
@@ -282,7 +341,7 @@ class JESMOC_MFDGP:
         cache = self.__dict__.setdefault("_device_searches", {})
         if fidelity not in cache or cache[fidelity].group is not grp:
             from ..util.acq_search import DeviceAcqSearch
-            cache[fidelity] = DeviceAcqSearch(grp, bounds, self.num_restarts, self.search_lr)
+            cache[fidelity] = DeviceAcqSearch(grp, bounds, self.num_restarts, self.search_lr, num_pareto_samples=K)
         return cache[fidelity], raw
 
     def _optimize(self, fidelity, **kw):

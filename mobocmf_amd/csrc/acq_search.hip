@@ -3,7 +3,7 @@
 // gradient w.r.t. those moments and the best-iterate tracking, the projected Adam ascent step on the iterate -- and the
 // selection of the k best of n values (the restarts among the raw candidates, the winner among the restarts).
 //
-// All three are latency-bound glue on a few hundred to a few thousand doubles: each is ONE launch, has no atomics and sums in a
+// All of them are latency-bound glue on a few hundred to a few thousand doubles: each is ONE launch, has no atomics and sums in a
 // fixed order (two calls on the same inputs are bitwise equal), reads nothing on the host and keeps no state: capturable.
 #include "common.h"
 
@@ -68,6 +68,73 @@ jes_group_kernel(const double* __restrict__ moments, const double* __restrict__ 
         best_v[t] = a;
         for (int j = 0; j < d; ++j) best_x[(int64_t)t * d + j] = x[(int64_t)t * d + j];
     }
+}
+
+// JES averaged over K sampled Pareto sets: black-box p owns the 1 + K consecutive models p (1 + K) (unconditioned) and
+// p (1 + K) + 1 + k (conditioned on sample k).  ONE wavefront per test point (the replayed iterate has T = 5: one thread per test
+// point would leave five lanes looping over every model and sample): lane m forms v and mbar of model m and parks log v in
+// LDS; the lane of a conditioned model forms its term and whether the clamp passes; lane 0 sums the terms in (p, k) order while
+// every lane writes its own model's seeds.  No atomics, static LDS only.  At K = 1 every expression reduces to that of
+// jes_group_kernel with the same operands in the same order: the same bits.
+__global__ void __launch_bounds__(AS_WAVE)
+jes_mc_group_kernel(const double* __restrict__ moments, const double* __restrict__ noise, int n_boxes, int K, int T, int S,
+                    double* __restrict__ acq, double* __restrict__ seeds, const double* __restrict__ x, int d,
+                    double* __restrict__ best_v, double* __restrict__ best_x) {
+    __shared__ double s_lv[AS_WAVE], s_term[AS_WAVE];
+    __shared__ int s_pass[AS_WAVE], s_win;
+    const int t = blockIdx.x, m = threadIdx.x;      // (the grid is T workgroups: every thread reaches every barrier)
+    const int stride = 1 + K, n_models = n_boxes * stride;
+    const int64_t ncol = (int64_t)T * S, c0 = (int64_t)t * S;
+    const bool mine = m < n_models;
+    const int p = m / stride, k1 = m % stride;      // k1 = 0: the unconditioned model of box p; else sample k1 - 1
+    const double* mu = moments + (int64_t)m * 2 * ncol;
+    double v = 0.0, bar = 0.0;
+    if (mine) {
+        v = as_model_v(mu, mu + ncol, noise[m], c0, S, &bar);
+        s_lv[m] = log(v);
+    }
+    __syncthreads();
+    if (mine && k1 > 0) {
+        const double diff = s_lv[p * stride] - s_lv[m];
+        s_term[m] = 0.5 * (diff < 0.0 ? 0.0 : diff);      // (a NaN stays a NaN, as torch.clamp)
+        s_pass[m] = diff >= 0.0;                           // torch.clamp's backward (a NaN passes nothing)
+    }
+    __syncthreads();
+    if (m == 0) {
+#pragma clang fp contract(off)      // (1/K) * (the box's sum) is rounded before it is added, as the restatement has it
+        const double inv_k = 1.0 / K;
+        double a = 0.0;
+        for (int q = 0; q < n_boxes; ++q) {
+            double box = s_term[q * stride + 1];
+            for (int k = 2; k <= K; ++k) box += s_term[q * stride + k];
+            a += inv_k * box;
+        }
+        acq[t] = a;
+        int win = 0;
+        if (best_v && a > best_v[t]) {      // strict; a NaN never wins
+            best_v[t] = a;
+            win = 1;
+        }
+        s_win = win;
+    }
+    if (seeds && mine) {
+        double g;
+        if (k1 > 0) {
+            g = s_pass[m] ? -0.5 / (K * v) : 0.0;
+        } else {
+            int cnt = 0;
+            for (int k = 1; k <= K; ++k) cnt += s_pass[m + k];
+            g = cnt > 0 ? cnt * (0.5 / (K * v)) : 0.0;
+        }
+        const double inv_s = 1.0 / S;
+        double* sm = seeds + (int64_t)m * 2 * ncol;
+        for (int s = 0; s < S; ++s) {
+            sm[c0 + s] = g * (2.0 * (mu[c0 + s] - bar) / S);
+            sm[ncol + c0 + s] = g * inv_s;
+        }
+    }
+    __syncthreads();
+    if (s_win && m < d) best_x[(int64_t)t * d + m] = x[(int64_t)t * d + m];
 }
 
 // One workgroup.  Every thread reads the step count, the workgroup meets, thread 0 advances it: no trailing launch.
@@ -162,6 +229,21 @@ int mobocmf_jes_group_forward(const double* moments, const double* noise, int32_
     hipLaunchKernelGGL(jes_group_kernel, dim3((unsigned)((T + AS_JES_BLOCK - 1) / AS_JES_BLOCK)), dim3(AS_JES_BLOCK), 0,
                        (hipStream_t)stream, moments, noise, n_pairs, T, S, acq, want_seeds ? seeds : (double*)nullptr, x,
                        track ? d : 0, track ? best_v : (double*)nullptr, best_x);
+    return CHECK_LAUNCH();
+}
+
+int mobocmf_jes_mc_group_forward(const double* moments, const double* noise, int32_t n_boxes, int32_t K, int32_t T, int32_t S,
+                                 double* acq, int32_t want_seeds, double* seeds, int32_t track, const double* x, int32_t d,
+                                 double* best_v, double* best_x, mobocmf_stream_t stream) {
+    if (!moments || !noise || !acq || n_boxes < 1 || K < 1 || T < 1 || S < 1) return MOBOCMF_BAD_ARG;
+    if ((int64_t)n_boxes * (1 + (int64_t)K) > 2 * MOBOCMF_ACQ_MAX_PAIRS) return MOBOCMF_BAD_ARG;      // one lane per model
+    if ((int64_t)T * S > MOBOCMF_ACQ_MAX_COLUMNS) return MOBOCMF_BAD_ARG;
+    if (want_seeds < 0 || want_seeds > 1 || track < 0 || track > 1 || (want_seeds && !seeds)) return MOBOCMF_BAD_ARG;
+    if (track && (!x || !best_v || !best_x || d < 1 || d > MOBOCMF_MAX_D)) return MOBOCMF_BAD_ARG;
+    static_assert(2 * MOBOCMF_ACQ_MAX_PAIRS <= AS_WAVE && MOBOCMF_MAX_D <= AS_WAVE, "one lane per model, one per coordinate");
+    hipLaunchKernelGGL(jes_mc_group_kernel, dim3((unsigned)T), dim3(AS_WAVE), 0, (hipStream_t)stream, moments, noise, n_boxes, K,
+                       T, S, acq, want_seeds ? seeds : (double*)nullptr, x, track ? d : 0,
+                       track ? best_v : (double*)nullptr, best_x);
     return CHECK_LAUNCH();
 }
 

@@ -1486,6 +1486,23 @@ def jes_group_forward(moments, noise, T, S, acq, seeds=None, x=None, best_v=None
     return acq
 
 
+def jes_mc_group_forward(moments, noise, K, T, S, acq, seeds=None, x=None, best_v=None, best_x=None, stream=None):
+    """mobocmf_jes_mc_group_forward: JES averaged over ``K`` sampled Pareto sets.  ``moments`` (n_boxes (1 + K), 2, T S) and
+    ``noise`` (n_boxes (1 + K),): per black-box its unconditioned surrogate, then the K conditioned ones; ``acq`` (T,) =
+    sum_p (1/K) sum_k 0.5 max(log v_u,p - log v_c,pk, 0).  ``seeds``, ``x``, ``best_v``, ``best_x`` as in ``jes_group_forward``;
+    with K = 1 the same bits as that.  One launch, only enqueues (on ``stream``, default the current one): capturable."""
+    lib = _lib.require_device()
+    K = int(K)
+    if K >= 1 and moments.shape[0] % (1 + K):      # (K < 1 is the library's to refuse)
+        raise _lib.MobocmfError("jes_mc_group_forward: 1 + K models per black-box (got K = %d, %d models)" % (K, moments.shape[0]))
+    track = best_v is not None
+    _lib.check(lib.mobocmf_jes_mc_group_forward(_ptr(moments), _ptr(noise), moments.shape[0] // max(1 + K, 1), K, int(T), int(S),
+                                                _ptr(acq), int(seeds is not None), _ptr(seeds), int(track), _ptr(x),
+                                                x.shape[-1] if track else 0, _ptr(best_v), _ptr(best_x), _on(stream)),
+               "mobocmf_jes_mc_group_forward")
+    return acq
+
+
 def ascent_adam_step(x, gx, lo, hi, exp_avg, exp_avg_sq, steps_done, lr, betas=(0.9, 0.999), eps=1e-8, stream=None):
     """mobocmf_ascent_adam_step: one projected Adam ascent step on the iterate ``x`` (T, d), in place, along
     -gx.sum(0) of the group's input gradients ``gx`` (n_models, T, d) -- FusedAdam's update, then the clamp to [lo, hi] (d,);

@@ -6,7 +6,8 @@ it issues a dozen element-wise framework kernels, three copies and an optimiser 
 time than device time.  ``DeviceAcqSearch`` keeps the same search on the GPU (csrc/acq_search.hip): one iterate is FOUR launches
 in stream order --
 
-    group STEP_FORWARD  ->  mobocmf_jes_group_forward (value, seeds, best iterate)  ->  group STEP_INPUT_GRADIENTS  ->
+    group STEP_FORWARD  ->  mobocmf_jes_group_forward (value, seeds, best iterate; mobocmf_jes_mc_group_forward when the
+    acquisition averages over several sampled Pareto sets)  ->  group STEP_INPUT_GRADIENTS  ->
     mobocmf_ascent_adam_step (the iterate IS the group's x buffer)
 
 -- captured once as a HIP graph (a single chain, no parallel branches) and replayed; nothing is read on the host until the
@@ -22,6 +23,8 @@ class DeviceAcqSearch:
     """Projected-Adam multi-start ascent of the coupled JES acquisition over ``group`` -- a TinyPredictGroup / CoopPredictGroup
     for T = ``num_restarts`` test points whose models 2p / 2p + 1 are the unconditioned / conditioned surrogate of black-box p
     (JESMOC_MFDGP._tiny_group) -- inside the box ``bounds`` (2, d).  ``lr`` is scaled by mean(hi - lo) as the host loop does.
+    ``num_pareto_samples`` = K > 1: black-box p owns the models p (1 + K) (unconditioned) and p (1 + K) + 1 + k (conditioned on
+    sampled Pareto set k), and the JES launch is mobocmf_jes_mc_group_forward, their average; the iterate stays four launches.
 
     ``run(x0, maxiter)`` -> device tensors (candidate (1, d), value ()), WITHOUT synchronising: X_0 ... X_maxiter are each
     scored once, the best iterate of every restart is kept, the best of those is returned.  The first iterate of a search runs
@@ -34,12 +37,16 @@ class DeviceAcqSearch:
     use_graph = True          # False: the same launches issued eagerly (tests, A/B)
     iters_per_graph = 1       # iterates unrolled into one graph (DESIGN.md 5.6 on what tools/acq_search_bench.py reports)
 
-    def __init__(self, group, bounds, num_restarts, lr, betas=(0.9, 0.999), eps=1e-8):
+    def __init__(self, group, bounds, num_restarts, lr, betas=(0.9, 0.999), eps=1e-8, num_pareto_samples=1):
         _lib.require_device()
-        if group.T != int(num_restarts) or len(group.models) % 2:
-            raise _lib.MobocmfError("DeviceAcqSearch: a group of (uncond, cond) pairs built for T = num_restarts test points")
-        if not 1 <= len(group.models) // 2 <= _lib.ACQ_MAX_PAIRS:
-            raise _lib.MobocmfError("DeviceAcqSearch: 1..%d black-boxes per group" % _lib.ACQ_MAX_PAIRS)
+        K = self.K = int(num_pareto_samples)
+        if K < 1:
+            raise ValueError("DeviceAcqSearch: num_pareto_samples >= 1 (got %d)" % K)
+        if group.T != int(num_restarts) or len(group.models) % (1 + K):
+            raise _lib.MobocmfError("DeviceAcqSearch: a group of (uncond, cond_1 .. cond_K) per black-box built for T = "
+                                    "num_restarts test points")
+        if not 1 + K <= len(group.models) <= 2 * _lib.ACQ_MAX_PAIRS:
+            raise _lib.MobocmfError("DeviceAcqSearch: 1 + K..%d models per group" % (2 * _lib.ACQ_MAX_PAIRS))
         dev, T, d = group.device, group.T, group.d
         self.group, self.T, self.d = group, T, d
         self.lo = bounds[0].detach().to(dev, torch.float64).contiguous()
@@ -56,12 +63,18 @@ class DeviceAcqSearch:
         self._capture_stream = group.stream
 
     # ------------------------------------------------------------------ the launches
+    def _jes(self, moments, noise, T, S, acq, **kw):
+        """One Pareto sample: the pair kernel, as ever; K > 1: the kernel that averages over the K conditioned models."""
+        if self.K == 1:
+            return F.jes_group_forward(moments, noise, T, S, acq, **kw)
+        return F.jes_mc_group_forward(moments, noise, self.K, T, S, acq, **kw)
+
     def _score(self, seeds):
         """The forward launch and the JES kernel on the group's current x: acq, the best iterate so far, optionally the seeds."""
         g = self.group
         g._launch(_lib.STEP_FORWARD)
-        F.jes_group_forward(g.moments, self.noise, self.T, g.S, self.acq, seeds=g.seeds if seeds else None, x=g.x,
-                            best_v=self.best_v, best_x=self.best_x, stream=g.stream)
+        self._jes(g.moments, self.noise, self.T, g.S, self.acq, seeds=g.seeds if seeds else None, x=g.x,
+                  best_v=self.best_v, best_x=self.best_x, stream=g.stream)
 
     def _iterate(self):
         """One iterate: four launches (on the group's stream; None: the current one)."""
@@ -111,7 +124,7 @@ class DeviceAcqSearch:
         for c in range(n // Tc):
             raw_group.x.copy_(xraw[c * Tc:(c + 1) * Tc])
             raw_group._launch(_lib.STEP_FORWARD)
-            F.jes_group_forward(raw_group.moments, noise, Tc, raw_group.S, vals[c * Tc:(c + 1) * Tc], stream=raw_group.stream)
+            self._jes(raw_group.moments, noise, Tc, raw_group.S, vals[c * Tc:(c + 1) * Tc], stream=raw_group.stream)
         F.select_topk(vals, self.T, top_v, top_i, x=xraw, out_x=self.group.x, stream=self.group.stream)
         return vals, top_v, top_i
 

@@ -482,6 +482,36 @@ class BlackBoxMFDGPFitter:
                 sys.stdout.flush()
                 attempt += 1
 
+    @staticmethod
+    def _pareto_sample_seed(seed, k):
+        """The seed of Pareto sample k of ``conditioned_copies``: ``seed`` itself for k = 0 (one sample is the plain seeded
+        call), else a 62-bit function of (seed, k) alone, in the style of ``_blackbox_generator``."""
+        if seed is None or k == 0:
+            return seed
+        import hashlib
+        key = hashlib.sha256(("%d:PARETO_SAMPLE:%d" % (int(seed), int(k))).encode()).digest()
+        return int.from_bytes(key[:8], "big") >> 2
+
+    def conditioned_copies(self, K, seed=None, **sample_kw):
+        """K fitters conditioned on K sampled Pareto sets (JESMOC_MFDGP(num_pareto_samples=K)): ``[self, copy_1 ...
+        copy_{K-1}]``.  The copies are ``copy_uncond()`` of this fitter taken BEFORE it is conditioned; then, one after the other
+        (never concurrently: the one-launch conditioned steps wait inside the launch and assume an otherwise idle device), every
+        fitter samples its Pareto solution and trains its conditioned surrogates.  This fitter keeps a solution it already holds.
+        ``seed=None``: the unseeded procedure on the process generators, in order; else sample k is the seeded procedure with
+        ``_pareto_sample_seed(seed, k)``.  ``sample_kw`` pass to ``sample_and_store_pareto_solution``."""
+        K = int(K)
+        if K < 1:
+            raise ValueError("conditioned_copies: K >= 1 (got %d)" % K)
+        if K > 1 and not parallel._no_group():
+            raise ValueError("conditioned_copies: several Pareto samples (K = %d) are limited to one process; surrogates "
+                             "sharded over a process group take K = 1" % K)
+        fitters = [self] + [self.copy_uncond() for _ in range(K - 1)]
+        for k, fitter in enumerate(fitters):
+            if k > 0 or getattr(fitter, "pareto_set", None) is None:
+                fitter.sample_and_store_pareto_solution(seed=self._pareto_sample_seed(seed, k), **sample_kw)
+            fitter.train_conditioned_mfdgps()
+        return fitters
+
     # status words of one try of the seeded procedure (rank 0's decides; ERROR anywhere makes every rank raise)
     _FEASIBLE, _INFEASIBLE, _ERROR = 0, 1, 2
 
