@@ -872,7 +872,8 @@ int mobocmf_natgrad_small_step(const mobocmf_natgrad_small_layer* host_layers, c
 #define MOBOCMF_TOPK_MAX_K 64
 #define MOBOCMF_TOPK_MAX_N 4096
 
-/* JES of every test point from the group's raw top-layer moments (JESMOC_MFDGP.py:38-52 over mfdgp.py:237-262).
+/* JES of every test point from the group's raw top-layer moments (JESMOC_MFDGP.py:38-52 over mfdgp.py:237-262): this IS
+ * mobocmf_jes_mc_group_forward (below) with n_boxes = n_pairs and K = 1 -- the same launch, the same bits.
  *   moments  (2 n_pairs, 2, T S): per model its means then its variances WITHOUT noise, column t S + s
  *   noise    (2 n_pairs): the models' likelihood noise tau
  *   per model and test point, mbar = (1/S) sum_s mu_s:  v = (1/S) sum_s (var_s + tau + mu_s^2) - mbar^2   (S = 1: var + tau)
@@ -900,7 +901,8 @@ int mobocmf_jes_group_forward(const double* moments, const double* noise, int32_
  *   d a / d v_c,pk = -0.5 / (K v_c,pk) where diff_pk >= 0, else 0;  d a / d v_u,p = #{k: diff_pk >= 0} 0.5 / (K v_u,p);
  *   d v / d var_s and d v / d mu_s as above.
  * track = 1: as above.
- * With K = 1 the results (acq, seeds, best_v, best_x) are bitwise those of mobocmf_jes_group_forward with n_pairs = n_boxes.
+ * With K = 1 every expression is that of mobocmf_jes_group_forward with n_pairs = n_boxes (1.0 * the single term is exact),
+ * which is this entry point at K = 1.
  * One launch of T workgroups of one wavefront: a lane per model, the sums by one lane in a fixed order, no atomics.
  * MOBOCMF_BAD_ARG: as for mobocmf_jes_group_forward, with n_boxes < 1, K < 1 or n_boxes (1 + K) > 2 MOBOCMF_ACQ_MAX_PAIRS in
  * place of its bound on n_pairs. */

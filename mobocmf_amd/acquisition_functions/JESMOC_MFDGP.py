@@ -129,6 +129,9 @@ def _read_once(vals, words=None):
 class JESMOC_MFDGP:
 
     search = "host"           # "device": the search itself on the GPU wherever a one-launch predict group fits (_optimize)
+    num_pareto_samples = 1    # (class defaults: what an object made with __new__ has)
+    _search_running = False   # inside _frozen_groups(): coupled_acq freezes the group it evaluates through
+    blackbox_mfdgp_fitters_cond = None
     num_restarts, raw_samples, search_lr = 5, 200, 0.02      # the recipe of both engines
     MAX_RAW_CHUNKS = 8        # the device engine scores the raw candidates in at most this many forward launches
 
@@ -179,7 +182,7 @@ class JESMOC_MFDGP:
             self.costs_blackboxes[fidelity][blackbox_name] = cost_evaluation
             return None
         mfdgp_uncond = self.blackbox_mfdgp_fitter_uncond.get_model(blackbox_name, is_constraint=is_constraint)
-        fitters_cond = self.__dict__.get("blackbox_mfdgp_fitters_cond") or [self.blackbox_mfdgp_fitter_cond]
+        fitters_cond = self.blackbox_mfdgp_fitters_cond or [self.blackbox_mfdgp_fitter_cond]
         mfdgp_conds = [c.get_model(blackbox_name, is_constraint=is_constraint) for c in fitters_cond]
         jes_mfdgp = _JES_MFDGP(fidelity, mfdgp_uncond, mfdgp_conds if len(mfdgp_conds) > 1 else mfdgp_conds[0])
         (self.constraints if is_constraint else self.objectives)[fidelity][blackbox_name] = jes_mfdgp
@@ -207,10 +210,8 @@ class JESMOC_MFDGP:
 
     def _group_value(self, v):
         """The coupled acquisition from a group's v (n_boxes (1 + K), T): sum_p (1/K) sum_k 0.5 clamp(log v_u,p - log v_c,pk, 0),
-        the k-sum in the order of k (the expression of mobocmf_jes_mc_group_forward)."""
-        K = self.__dict__.get("num_pareto_samples", 1)
-        if K == 1:
-            return (0.5 * torch.clamp(torch.log(v[0::2]) - torch.log(v[1::2]), min=0.0)).sum(0)
+        the k-sum in the order of k (the expression of mobocmf_jes_mc_group_forward).  K = 1: 1.0 * the single term is exact."""
+        K = self.num_pareto_samples
         lu = torch.log(v[0::1 + K])
         box = None
         for k in range(1, K + 1):
@@ -218,50 +219,47 @@ class JESMOC_MFDGP:
             box = term if box is None else box + term
         return ((1.0 / K) * box).sum(0)
 
-    def _make_group(self, make):
-        """``make()``; with several Pareto samples a group that its constructor refuses (MobocmfError) is no group: None."""
-        if self.__dict__.get("num_pareto_samples", 1) == 1:
-            return make()
+    def _first_group(self, classes, jess, fidelity, T, d, speed_rule=(), **kw):
+        """A predict group (util/predict_group.py) over (uncond, cond_1 .. cond_K) of every black-box in ``jess`` for T test
+        points, of the first of ``classes`` whose ``why_not`` is None for every model (for a class in ``speed_rule``: with its
+        speed rule on); None where none fits or the models are not on the GPU.  ``kw``: further constructor arguments.  With
+        several Pareto samples a group that its constructor refuses (MobocmfError) is no group either; with one it raises."""
         from .._lib import MobocmfError
-        try:
-            return make()
-        except MobocmfError:
+        models = self._group_models(jess)
+        if not (models and all(p.is_cuda for p in models[0].parameters())):
             return None
+        for cls in classes:
+            gate = dict(speed_rule=True) if cls in speed_rule else {}
+            if all(cls.why_not(m, fidelity, T, d, **gate) is None for m in models):
+                try:
+                    return cls(models, fidelity, T, d, **kw)
+                except MobocmfError:
+                    if self.num_pareto_samples == 1:
+                        raise
+                    return None
+        return None
 
     def _tiny_group(self, jess, fidelity, T, d):
-        """TinyPredictGroup (M <= 32) or CoopPredictGroup (M <= 128) over (uncond, cond_1 .. cond_K) of every black-box of ``fidelity`` for T
-        test points -- when all of them fit a one-launch kernel (util/tiny_step.py, util/coop_step.py) -- else None.  Built once
-        per (fidelity, T)."""
+        """TinyPredictGroup (M <= 32, where one workgroup beats the layer path) or CoopPredictGroup (M <= 128: the cooperative
+        launch, several workgroups per model) when all models fit a one-launch kernel (util/tiny_step.py, util/coop_step.py) --
+        else None.  Built once per (fidelity, T, d)."""
         cache = self.__dict__.setdefault("_tiny_groups", {})
         key = (fidelity, T, d)
         if key not in cache:
-            from ..util import tiny_step as TS
-            models = self._group_models(jess)
-            on_gpu = bool(models) and all(p.is_cuda for p in models[0].parameters())
-            if on_gpu and all(TS.fits_predict(m, fidelity, T, d) for m in models):
-                cache[key] = self._make_group(lambda: TS.TinyPredictGroup(models, fidelity, T, d))
-            else:      # mid-size surrogates (M <= 128): the cooperative launch, several workgroups per model
-                from ..util import coop_step as CS
-                ok = on_gpu and all(CS.fits_predict(m, fidelity, T, d) for m in models)
-                cache[key] = self._make_group(lambda: CS.CoopPredictGroup(models, fidelity, T, d)) if ok else None
+            from ..util.coop_step import CoopPredictGroup
+            from ..util.tiny_step import TinyPredictGroup
+            cache[key] = self._first_group((TinyPredictGroup, CoopPredictGroup), jess, fidelity, T, d, speed_rule=(TinyPredictGroup,))
         return cache[key]
 
     def _panel_group(self, jess, fidelity, T, d, want_gradients):
-        """PanelPredictGroup (128 < M <= 512, util/panel_predict.py) over (uncond, cond_1 .. cond_K) of every black-box of ``fidelity`` for T
-        test points when all of them fit; else SplitPredictGroup (M <= 1024: 8-column panels, replicas split over workgroups)
-        when all of them fit that; else None.  A cache of the DEVICE engine alone: ``coupled_acq`` never looks here, so
-        the host engine evaluates these sizes through the layer path as ever."""
+        """PanelPredictGroup (128 < M <= 512, util/panel_predict.py) when all models fit; else SplitPredictGroup (M <= 1024:
+        8-column panels, replicas split over workgroups) when all of them fit that; else None.  A cache of the DEVICE engine
+        alone: ``coupled_acq`` never looks here, so the host engine evaluates these sizes through the layer path as ever."""
         cache = self.__dict__.setdefault("_panel_groups", {})
         key = (fidelity, T, d, bool(want_gradients))
         if key not in cache:
-            from ..util import panel_predict as PP
-            models = self._group_models(jess)
-            on_gpu = bool(models) and all(p.is_cuda for p in models[0].parameters())
-            cache[key] = None
-            for fits, group in ((PP.fits_predict, PP.PanelPredictGroup), (PP.fits_predict_split, PP.SplitPredictGroup)):
-                if on_gpu and all(fits(m, fidelity, T, d) for m in models):
-                    cache[key] = self._make_group(lambda: group(models, fidelity, T, d, want_gradients=want_gradients))
-                    break
+            from ..util.panel_predict import PanelPredictGroup, SplitPredictGroup
+            cache[key] = self._first_group((PanelPredictGroup, SplitPredictGroup), jess, fidelity, T, d, want_gradients=want_gradients)
         return cache[key]
 
     def coupled_acq(self, X, fidelity):
@@ -276,7 +274,7 @@ class JESMOC_MFDGP:
             X2 = X[:, 0, :] if X.dim() > 2 else X
             grp = self._tiny_group(jess, fidelity, X2.shape[0], X2.shape[1])
             if grp is not None:
-                if self.__dict__.get("_search_running") and hasattr(grp, "freeze"):
+                if self._search_running:
                     grp.freeze()      # (constant parameters for the whole search: the chains are formed by its first launch only)
                 _, v = grp.acquisition_moments(X2)
                 return self._group_value(v)
@@ -301,7 +299,7 @@ class JESMOC_MFDGP:
             failed = None      # every group is thawed, also after one of them reported an abandoned wait
             groups = list(self.__dict__.get("_tiny_groups", {}).values()) + list(self.__dict__.get("_panel_groups", {}).values())
             for grp in groups:
-                if grp is not None and hasattr(grp, "thaw"):
+                if grp is not None:
                     try:
                         grp.thaw()
                     except F.InLaunchWaitAbandoned as e:
@@ -320,7 +318,7 @@ class JESMOC_MFDGP:
         bounds = self.standard_bounds
         if not (self.use_tiny_step and jess and bounds is not None and bounds.is_cuda and parallel.world()[1] == 1):
             return None
-        K = self.__dict__.get("num_pareto_samples", 1)
+        K = self.num_pareto_samples
         if K > 1:
             from .. import _lib
             if len(jess) * (1 + K) > 2 * _lib.ACQ_MAX_PAIRS:

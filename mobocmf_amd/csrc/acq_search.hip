@@ -9,7 +9,6 @@
 
 #define CHECK_LAUNCH() (hipGetLastError() == hipSuccess ? MOBOCMF_OK : MOBOCMF_HIP_ERROR)
 #define AS_BLOCK 256
-#define AS_JES_BLOCK 64        // test points per workgroup of the JES kernel (T = 200 raw candidates: four workgroups)
 #define AS_WAVE 64
 
 namespace {
@@ -33,49 +32,12 @@ __device__ __forceinline__ double as_model_v(const double* __restrict__ mean, co
     return s2 / S - sm * sm;
 }
 
-__global__ void __launch_bounds__(AS_JES_BLOCK)
-jes_group_kernel(const double* __restrict__ moments, const double* __restrict__ noise, int n_pairs, int T, int S,
-                 double* __restrict__ acq, double* __restrict__ seeds, const double* __restrict__ x, int d,
-                 double* __restrict__ best_v, double* __restrict__ best_x) {
-    const int t = blockIdx.x * AS_JES_BLOCK + threadIdx.x;
-    if (t >= T) return;
-    const int64_t ncol = (int64_t)T * S, c0 = (int64_t)t * S;
-    const double inv_s = 1.0 / S;
-    double a = 0.0;
-    for (int p = 0; p < n_pairs; ++p) {
-        const double* mu_u = moments + (int64_t)(2 * p) * 2 * ncol;      // model 2p: (mean | variance), ncol each
-        const double* mu_c = mu_u + 2 * ncol;                            // model 2p + 1
-        double bar_u, bar_c;
-        const double vu = as_model_v(mu_u, mu_u + ncol, noise[2 * p], c0, S, &bar_u);
-        const double vc = as_model_v(mu_c, mu_c + ncol, noise[2 * p + 1], c0, S, &bar_c);
-        const double diff = log(vu) - log(vc);
-        a += 0.5 * (diff < 0.0 ? 0.0 : diff);      // (a NaN stays a NaN, as torch.clamp)
-        if (seeds) {
-            // torch.clamp's backward: the gradient passes where diff >= 0 (a NaN passes nothing)
-            const double gu = diff >= 0.0 ? 0.5 / vu : 0.0, gc = diff >= 0.0 ? -0.5 / vc : 0.0;
-            double* su = seeds + (int64_t)(2 * p) * 2 * ncol;
-            double* sc = su + 2 * ncol;
-            for (int s = 0; s < S; ++s) {
-                su[c0 + s] = gu * (2.0 * (mu_u[c0 + s] - bar_u) / S);
-                su[ncol + c0 + s] = gu * inv_s;
-                sc[c0 + s] = gc * (2.0 * (mu_c[c0 + s] - bar_c) / S);
-                sc[ncol + c0 + s] = gc * inv_s;
-            }
-        }
-    }
-    acq[t] = a;
-    if (best_v && a > best_v[t]) {      // strict; a NaN never wins
-        best_v[t] = a;
-        for (int j = 0; j < d; ++j) best_x[(int64_t)t * d + j] = x[(int64_t)t * d + j];
-    }
-}
-
 // JES averaged over K sampled Pareto sets: black-box p owns the 1 + K consecutive models p (1 + K) (unconditioned) and
 // p (1 + K) + 1 + k (conditioned on sample k).  ONE wavefront per test point (the replayed iterate has T = 5: one thread per test
 // point would leave five lanes looping over every model and sample): lane m forms v and mbar of model m and parks log v in
 // LDS; the lane of a conditioned model forms its term and whether the clamp passes; lane 0 sums the terms in (p, k) order while
-// every lane writes its own model's seeds.  No atomics, static LDS only.  At K = 1 every expression reduces to that of
-// jes_group_kernel with the same operands in the same order: the same bits.
+// every lane writes its own model's seeds.  No atomics, static LDS only.  At K = 1 (mobocmf_jes_group_forward) 1.0 * the single
+// term and 0.5 / (1 * v) are exact: the pair expression 0.5 max(log v_u - log v_c, 0) of the public header, bit for bit.
 __global__ void __launch_bounds__(AS_WAVE)
 jes_mc_group_kernel(const double* __restrict__ moments, const double* __restrict__ noise, int n_boxes, int K, int T, int S,
                     double* __restrict__ acq, double* __restrict__ seeds, const double* __restrict__ x, int d,
@@ -219,19 +181,6 @@ select_topk_kernel(const double* __restrict__ vals, int n, int k, const double* 
 
 extern "C" {
 
-int mobocmf_jes_group_forward(const double* moments, const double* noise, int32_t n_pairs, int32_t T, int32_t S,
-                              double* acq, int32_t want_seeds, double* seeds, int32_t track, const double* x, int32_t d,
-                              double* best_v, double* best_x, mobocmf_stream_t stream) {
-    if (!moments || !noise || !acq || n_pairs < 1 || n_pairs > MOBOCMF_ACQ_MAX_PAIRS || T < 1 || S < 1) return MOBOCMF_BAD_ARG;
-    if ((int64_t)T * S > MOBOCMF_ACQ_MAX_COLUMNS) return MOBOCMF_BAD_ARG;
-    if (want_seeds < 0 || want_seeds > 1 || track < 0 || track > 1 || (want_seeds && !seeds)) return MOBOCMF_BAD_ARG;
-    if (track && (!x || !best_v || !best_x || d < 1 || d > MOBOCMF_MAX_D)) return MOBOCMF_BAD_ARG;
-    hipLaunchKernelGGL(jes_group_kernel, dim3((unsigned)((T + AS_JES_BLOCK - 1) / AS_JES_BLOCK)), dim3(AS_JES_BLOCK), 0,
-                       (hipStream_t)stream, moments, noise, n_pairs, T, S, acq, want_seeds ? seeds : (double*)nullptr, x,
-                       track ? d : 0, track ? best_v : (double*)nullptr, best_x);
-    return CHECK_LAUNCH();
-}
-
 int mobocmf_jes_mc_group_forward(const double* moments, const double* noise, int32_t n_boxes, int32_t K, int32_t T, int32_t S,
                                  double* acq, int32_t want_seeds, double* seeds, int32_t track, const double* x, int32_t d,
                                  double* best_v, double* best_x, mobocmf_stream_t stream) {
@@ -245,6 +194,15 @@ int mobocmf_jes_mc_group_forward(const double* moments, const double* noise, int
                        T, S, acq, want_seeds ? seeds : (double*)nullptr, x, track ? d : 0,
                        track ? best_v : (double*)nullptr, best_x);
     return CHECK_LAUNCH();
+}
+
+// The pair form (model 2p unconditioned, 2p + 1 conditioned): K = 1 of the above, whose checks are then this entry point's own
+// (n_pairs in 1 .. MOBOCMF_ACQ_MAX_PAIRS is n_boxes (1 + K) in 2 .. 2 MOBOCMF_ACQ_MAX_PAIRS).
+int mobocmf_jes_group_forward(const double* moments, const double* noise, int32_t n_pairs, int32_t T, int32_t S,
+                              double* acq, int32_t want_seeds, double* seeds, int32_t track, const double* x, int32_t d,
+                              double* best_v, double* best_x, mobocmf_stream_t stream) {
+    return mobocmf_jes_mc_group_forward(moments, noise, n_pairs, 1, T, S, acq, want_seeds, seeds, track, x, d, best_v, best_x,
+                                        stream);
 }
 
 int mobocmf_ascent_adam_step(double* x, const double* gx, int32_t n_models, int32_t T, int32_t d, const double* lo,

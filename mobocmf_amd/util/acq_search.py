@@ -6,9 +6,8 @@ it issues a dozen element-wise framework kernels, three copies and an optimiser 
 time than device time.  ``DeviceAcqSearch`` keeps the same search on the GPU (csrc/acq_search.hip): one iterate is FOUR launches
 in stream order --
 
-    group STEP_FORWARD  ->  mobocmf_jes_group_forward (value, seeds, best iterate; mobocmf_jes_mc_group_forward when the
-    acquisition averages over several sampled Pareto sets)  ->  group STEP_INPUT_GRADIENTS  ->
-    mobocmf_ascent_adam_step (the iterate IS the group's x buffer)
+    group STEP_FORWARD  ->  mobocmf_jes_mc_group_forward (value, seeds, best iterate; K sampled Pareto sets, K = 1 being
+    mobocmf_jes_group_forward)  ->  group STEP_INPUT_GRADIENTS  ->  mobocmf_ascent_adam_step (the iterate IS the group's x buffer)
 
 -- captured once as a HIP graph (a single chain, no parallel branches) and replayed; nothing is read on the host until the
 caller fetches the winner.
@@ -20,17 +19,17 @@ from .. import functional as F
 
 
 class DeviceAcqSearch:
-    """Projected-Adam multi-start ascent of the coupled JES acquisition over ``group`` -- a TinyPredictGroup / CoopPredictGroup
-    for T = ``num_restarts`` test points whose models 2p / 2p + 1 are the unconditioned / conditioned surrogate of black-box p
-    (JESMOC_MFDGP._tiny_group) -- inside the box ``bounds`` (2, d).  ``lr`` is scaled by mean(hi - lo) as the host loop does.
-    ``num_pareto_samples`` = K > 1: black-box p owns the models p (1 + K) (unconditioned) and p (1 + K) + 1 + k (conditioned on
-    sampled Pareto set k), and the JES launch is mobocmf_jes_mc_group_forward, their average; the iterate stays four launches.
+    """Projected-Adam multi-start ascent of the coupled JES acquisition over ``group`` -- a PredictGroup (util/predict_group.py)
+    for T = ``num_restarts`` test points (JESMOC_MFDGP._tiny_group / _panel_group) -- inside the box ``bounds`` (2, d).  ``lr`` is
+    scaled by mean(hi - lo) as the host loop does.  ``num_pareto_samples`` = K: black-box p owns the models p (1 + K)
+    (unconditioned) and p (1 + K) + 1 + k (conditioned on sampled Pareto set k); the JES launch, mobocmf_jes_mc_group_forward,
+    averages over the K (K = 1: models 2p / 2p + 1, the reference's estimator).
 
     ``run(x0, maxiter)`` -> device tensors (candidate (1, d), value ()), WITHOUT synchronising: X_0 ... X_maxiter are each
     scored once, the best iterate of every restart is kept, the best of those is returned.  The first iterate of a search runs
     eagerly (a frozen CoopPredictGroup forms its chains there, so the replayed launches carry STEP_CHAIN_VALID); the others are
-    replays of the captured iterate(s).  A cooperative group is frozen by ``run``, and a cooperative raw-candidate group by
-    ``start_from_raw`` (``self.raw_group``); neither is thawed here, because ``thaw()`` reads the status word and that read
+    replays of the captured iterate(s).  The group is frozen by ``run``, and the raw-candidate group by ``start_from_raw``
+    (``self.raw_group``); neither is thawed here, because a cooperative group's ``thaw()`` reads the status word and that read
     synchronises.  The caller thaws BOTH once it has fetched the result (``group.thaw()`` reports an abandoned in-launch
     wait; JESMOC_MFDGP does it for every group it built): a group left frozen keeps chains of parameters that may since have
     changed.  ``info_words()`` are the models' Cholesky verdicts."""
@@ -63,18 +62,12 @@ class DeviceAcqSearch:
         self._capture_stream = group.stream
 
     # ------------------------------------------------------------------ the launches
-    def _jes(self, moments, noise, T, S, acq, **kw):
-        """One Pareto sample: the pair kernel, as ever; K > 1: the kernel that averages over the K conditioned models."""
-        if self.K == 1:
-            return F.jes_group_forward(moments, noise, T, S, acq, **kw)
-        return F.jes_mc_group_forward(moments, noise, self.K, T, S, acq, **kw)
-
     def _score(self, seeds):
         """The forward launch and the JES kernel on the group's current x: acq, the best iterate so far, optionally the seeds."""
         g = self.group
         g._launch(_lib.STEP_FORWARD)
-        self._jes(g.moments, self.noise, self.T, g.S, self.acq, seeds=g.seeds if seeds else None, x=g.x,
-                  best_v=self.best_v, best_x=self.best_x, stream=g.stream)
+        F.jes_mc_group_forward(g.moments, self.noise, self.K, self.T, g.S, self.acq, seeds=g.seeds if seeds else None, x=g.x,
+                               best_v=self.best_v, best_x=self.best_x, stream=g.stream)
 
     def _iterate(self):
         """One iterate: four launches (on the group's stream; None: the current one)."""
@@ -118,13 +111,13 @@ class DeviceAcqSearch:
                                   torch.zeros(n, self.d, dtype=torch.float64, device=dev))
         vals, top_v, top_i, noise, xraw = self._raw[(n, Tc)]
         self.raw_group, self.raw_values = raw_group, vals
-        if hasattr(raw_group, "freeze"):
-            raw_group.freeze()
+        raw_group.freeze()
         xraw.copy_(Xraw.detach().reshape(n, self.d))
         for c in range(n // Tc):
             raw_group.x.copy_(xraw[c * Tc:(c + 1) * Tc])
             raw_group._launch(_lib.STEP_FORWARD)
-            self._jes(raw_group.moments, noise, Tc, raw_group.S, vals[c * Tc:(c + 1) * Tc], stream=raw_group.stream)
+            F.jes_mc_group_forward(raw_group.moments, noise, self.K, Tc, raw_group.S, vals[c * Tc:(c + 1) * Tc],
+                                   stream=raw_group.stream)
         F.select_topk(vals, self.T, top_v, top_i, x=xraw, out_x=self.group.x, stream=self.group.stream)
         return vals, top_v, top_i
 
@@ -139,8 +132,7 @@ class DeviceAcqSearch:
             self.exp_avg.zero_()
             self.exp_avg_sq.zero_()
             self.steps_done.zero_()
-            if hasattr(g, "freeze"):
-                g.freeze()
+            g.freeze()
             left = maxiter
             if left > 0:
                 self._iterate()

@@ -56,7 +56,8 @@ class CoopPredictGroup(TS.TinyPredictGroup):
     """``TinyPredictGroup`` for mid-size models (32 < M <= 128): predictive moments of several fitted models at the same T test
     points in ONE cooperative launch (STEP_FORWARD), their gradient w.r.t. the test points in one more (STEP_INPUT_GRADIENTS) --
     the acquisition search of the reference's later BO iterations (JESMOC_MFDGP.py:137-184 against M = N = 33 ... 75
-    surrogates).  A give-up of an in-launch wait is reported by ``thaw()``, at the end of the search."""
+    surrogates).  A give-up of an in-launch wait is reported by ``thaw()``, at the end of the search.  (``why_not``: inherited,
+    with this class's ``kernel``: ``fits_predict`` above.)"""
     kernel = COOP
     _frozen = False            # inside freeze() ... thaw(): the models' parameters do not change between launches
     _chain_ready = False       # ... and a launch since freeze() has left their chains (L^-1, U, a) in the workspaces

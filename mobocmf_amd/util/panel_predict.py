@@ -12,13 +12,13 @@ jitter ladder, the host check and NotPSDError all happen there, before any launc
 and the S replicas of a test point split over workgroups, whose partial gradients meet in the group's ``work`` buffer
 (DESIGN.md 5.6.2).  ``JESMOC_MFDGP`` uses it where ``PanelPredictGroup`` stops (M > 512).
 """
-import contextlib
 import ctypes
 
 import torch
 
 from .. import _lib
 from . import tiny_step as TS
+from .predict_group import PredictGroup
 
 MIN_M = _lib.COOP_MAX_M + 1      # up to COOP_MAX_M the cooperative one-launch group is the engine
 MAX_M = _lib.FROZEN_MAX_M
@@ -90,17 +90,19 @@ def describe(rec, chains, samples, S, T, d, x, top_mean, top_var, seed_gmean=Non
     return keep
 
 
-class PanelPredictGroup(TS.TinyPredictGroup):
+class PanelPredictGroup(PredictGroup):
     """Predictive moments of SEVERAL fitted models with 128 < M <= 512 at the same T test points in ONE launch, their gradient
-    w.r.t. the test points in one more: the attributes and methods of ``TinyPredictGroup`` that a search uses (``models``,
-    ``device``, ``stream``, ``T``, ``d``, ``S``, ``x``, ``moments`` (n, 2, T S), ``seeds``, ``gx`` (n, T, d), ``_launch``,
-    ``moments_at``, ``noise``, ``acquisition_moments``, ``info_words``), ``freeze()`` / ``thaw()`` as ``CoopPredictGroup``.
+    w.r.t. the test points in one more: a ``PredictGroup`` (util/predict_group.py) as ``TinyPredictGroup`` is one.
     ``want_gradients=False``: a group for values only (the raw candidates of a search) has no seeds and no gx.
 
     Inside ``freeze()`` ... ``thaw()`` the parameters are constants and the layers' chains are formed once, by ``freeze()``
     (shared with ``MFDGP.frozen_chains()`` where that context is active); a launch outside forms them first."""
     _frozen = False
-    _why_not, _entry = staticmethod(why_not), "mobocmf_frozen_predict"
+    _entry = "mobocmf_frozen_predict"
+
+    @classmethod
+    def why_not(cls, model, fidelity, T, d, on_gpu=True):
+        return why_not(model, fidelity, T, d, on_gpu=on_gpu)
 
     def __init__(self, models, fidelity, T, d, stream=None, want_gradients=True):
         _lib.require_device()
@@ -111,7 +113,7 @@ class PanelPredictGroup(TS.TinyPredictGroup):
         n, L = len(self.models), fidelity + 1
         self.S = self.models[0].num_samples_for_acquisition if L > 1 else 1
         for i, model in enumerate(self.models):
-            reason = self._why_not(model, fidelity, self.T, self.d)
+            reason = self.why_not(model, fidelity, self.T, self.d)
             if reason is None and L > 1 and model.num_samples_for_acquisition != self.S:
                 reason = "S differs from the first model's"
             if reason is not None:
@@ -168,14 +170,6 @@ class PanelPredictGroup(TS.TinyPredictGroup):
         self._frozen = False
         self._chains = None
 
-    @contextlib.contextmanager
-    def frozen(self):
-        self.freeze()
-        try:
-            yield self
-        finally:
-            self.thaw()
-
     # ------------------------------------------------------------------ the launches
     def _launch(self, mode):
         if mode == _lib.STEP_INPUT_GRADIENTS and not self.want_gradients:
@@ -192,7 +186,11 @@ class SplitPredictGroup(PanelPredictGroup):
     """``PanelPredictGroup`` for 128 < M <= 1024 on mobocmf_frozen_predict_split: the same surface, freeze / thaw and chain
     sharing.  The parts of a test point's replicas leave their partial d / dX in ``work`` (n, ceil(S / 8) T d doubles, allocated
     once per group; None for fidelity 0 and for a group without gradients), summed by the same call."""
-    _why_not, _entry = staticmethod(why_not_split), "mobocmf_frozen_predict_split"
+    _entry = "mobocmf_frozen_predict_split"
+
+    @classmethod
+    def why_not(cls, model, fidelity, T, d, on_gpu=True):
+        return why_not_split(model, fidelity, T, d, on_gpu=on_gpu)
 
     def _allocate_work(self):
         if not self.want_gradients or self.fidelity == 0:

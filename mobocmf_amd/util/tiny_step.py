@@ -14,6 +14,7 @@ import torch
 from .. import _lib
 from .. import functional as F
 from .. import gp
+from .predict_group import PredictGroup
 
 LAYER_PATH_US = 240.0   # what a step of a small surrogate costs through the layer entry points (HIP-graph replay, MI355X)
 
@@ -116,12 +117,12 @@ def structure_fits(model, L, d, max_m, training, on_gpu=True):
         return False
 
 
-def fits_predict(model, fidelity, T, d, speed_rule=True, kernel=TINY):
+def fits_predict(model, fidelity, T, d, speed_rule=True, kernel=TINY, on_gpu=True):
     """True when ``model``'s predictive moments at T test points up to layer ``fidelity`` fit the one-launch kernel
     (``structure_fits``; the training flags do not matter), every layer has the model's number of fixed samples and the
     columns are within the kernel's limit -- and, with ``speed_rule``, few enough for one workgroup to beat the layer path."""
     try:
-        if not structure_fits(model, fidelity + 1, d, kernel.max_m, training=False):
+        if not structure_fits(model, fidelity + 1, d, kernel.max_m, training=False, on_gpu=on_gpu):
             return False
         layers = model._layers()[:fidelity + 1]
         S = model.num_samples_for_acquisition
@@ -748,33 +749,22 @@ class TinyConditionedStep(TinyELBOStep):
                 self.xrng.copy_(xr)
 
 
-class _TinyMomentsFn(torch.autograd.Function):
-    """(n_models, 2, columns) top-layer moments of a TinyPredictGroup at X; backward: d / d X through every model, one launch."""
-
-    @staticmethod
-    def forward(ctx, group, X):
-        ctx.group = group
-        ctx.save_for_backward(X.detach())
-        group.x.copy_(X.detach().reshape(group.T, group.d))
-        group._launch(_lib.STEP_FORWARD)
-        return group.moments.clone()
-
-    @staticmethod
-    def backward(ctx, g):
-        group = ctx.group
-        (X,) = ctx.saved_tensors
-        group.x.copy_(X.reshape(group.T, group.d))      # (another evaluation may have used the group since the forward)
-        group.seeds.copy_(g)
-        group._launch(_lib.STEP_INPUT_GRADIENTS)
-        return None, group.gx.sum(0).reshape(X.shape)
-
-
-class TinyPredictGroup(_OneLaunchGroup):
+class TinyPredictGroup(_OneLaunchGroup, PredictGroup):
     """Predictive moments of SEVERAL fitted small models at the same T test points (eval branch, the layers' fixed
     ``samples``: MFDGP.predict_for_acquisition, mfdgp.py:237-262) in ONE launch -- mobocmf_tiny_elbo_step in its forward-only
     mode -- and their gradient w.r.t. the test points in one more (STEP_INPUT_GRADIENTS): what an acquisition search evaluates
     hundreds of times against constant parameters (JESMOC_MFDGP.py:137-184).  ``moments_at(X)`` -> (n_models, 2, T * S) (T for
-    fidelity 0): mean and variance of the top layer's columns, WITHOUT the likelihood noise; differentiable w.r.t. X."""
+    fidelity 0): mean and variance of the top layer's columns, WITHOUT the likelihood noise; differentiable w.r.t. X.  The
+    kernel recomputes every chain in every launch: ``freeze()`` / ``thaw()`` have nothing to do (util/predict_group.py)."""
+
+    @classmethod
+    def why_not(cls, model, fidelity, T, d, on_gpu=True, speed_rule=False):
+        """``fits_predict`` with this class's ``kernel`` (``speed_rule``: see there), as None or a sentence."""
+        if fits_predict(model, fidelity, T, d, speed_rule=speed_rule, kernel=cls.kernel, on_gpu=on_gpu):
+            return None
+        return "%s takes <= %d layers sharing M <= %d inducing inputs, d <= %d, T S <= %d columns%s, float64 parameters%s" % (
+            cls.kernel.entry, _lib.TINY_MAX_LAYERS, cls.kernel.max_m, _lib.TINY_MAX_D, cls.kernel.max_predict_columns,
+            " (fewer under the speed rule)" * speed_rule, " on the GPU" * on_gpu)
 
     def __init__(self, models, fidelity, T, d, stream=None):
         _lib.require_device()
@@ -794,9 +784,11 @@ class TinyPredictGroup(_OneLaunchGroup):
         self._keep += [zrow, nofid]
         self.info_words = []      # per model the int32 words its launches leave their Cholesky verdicts in (0: fine)
         for i, model in enumerate(models):
-            if not fits_predict(model, fidelity, self.T, d, speed_rule=False, kernel=self.kernel) or \
-                    (L > 1 and model.num_samples_for_acquisition != self.S):
-                raise _lib.MobocmfError("%s: model %d does not fit the one-launch kernel" % (type(self).__name__, i))
+            reason = self.why_not(model, fidelity, self.T, d)
+            if reason is None and L > 1 and model.num_samples_for_acquisition != self.S:
+                reason = "S differs from the first model's"
+            if reason is not None:
+                raise _lib.MobocmfError("%s: model %d does not fit: %s" % (type(self).__name__, i, reason))
             Tm = self.host[i]
             desc = Descriptor.for_prediction(Tm, model, fidelity, self.T, d)
             Tm.x, Tm.y, Tm.fid = self.x.data_ptr(), zrow.data_ptr(), nofid.data_ptr()
@@ -812,33 +804,3 @@ class TinyPredictGroup(_OneLaunchGroup):
             Tm.seed_gmean, Tm.seed_gvar, Tm.seed_scale = self.seeds[i, 0].data_ptr(), self.seeds[i, 1].data_ptr(), 1.0
             Tm.grad = self.gx[i].data_ptr()
         self._upload()
-
-    def moments_at(self, X):
-        X = X.reshape(self.T, self.d)
-        if X.requires_grad and torch.is_grad_enabled():
-            return _TinyMomentsFn.apply(self, X)
-        self.x.copy_(X.detach())
-        self._launch(_lib.STEP_FORWARD)
-        return self.moments.clone()
-
-    def noise(self, refresh=False):
-        """(n_models,) likelihood noise of the top layer (constrained values).  The parameters are constants while a group is
-        in use (an acquisition search against fitted models), so the values are formed once; ``refresh=True`` re-reads them."""
-        if refresh or self.__dict__.get("_noise") is None:
-            with torch.no_grad():
-                self._noise = torch.stack([getattr(m, m.name_hidden_layer_likelihood + str(self.fidelity)).noise.reshape(())
-                                           for m in self.models])
-        return self._noise
-
-    def acquisition_moments(self, X):
-        """(mus, vars), each (n_models, T): MFDGP.predict_for_acquisition of every model (noise added, moments over the S
-        fixed samples, mfdgp.py:237-262)."""
-        mom = self.moments_at(X)
-        mean, var = mom[:, 0], mom[:, 1] + self.noise()[:, None]
-        if self.fidelity == 0:
-            return mean, var
-        n = mean.shape[0]
-        mu = mean.reshape(n, self.T, self.S)
-        mus = mu.mean(2)
-        second = (var.reshape(n, self.T, self.S) + mu * mu).mean(2)
-        return mus, second - mus * mus

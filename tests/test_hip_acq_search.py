@@ -226,8 +226,7 @@ def test_engine_parity_at_short_horizon(M, seed, fidelity):
 
     def freeze(on):
         for grp in groups.values():
-            if hasattr(grp, "freeze"):
-                grp.freeze() if on else grp.thaw()
+            grp.freeze() if on else grp.thaw()
 
     freeze(True)
     cand_h, val_h = optimize_acqf_multistart(acq_fn, bounds, num_restarts=5, raw_samples=200, maxiter=10, generator=gen())

@@ -1,7 +1,7 @@
 """JES averaged over K sampled Pareto sets on the device (mobocmf_jes_mc_group_forward in csrc/acq_search.hip,
 DeviceAcqSearch(num_pareto_samples=K), JESMOC_MFDGP(num_pareto_samples=K)): the kernel against its float64 restatement
-(tests/jes_mc_reference.py) and, at K = 1, bit for bit against mobocmf_jes_group_forward; the search engine against the host
-loop over the same predict groups; the estimator through the public surface on the toy 2-D problem."""
+(tests/jes_mc_reference.py) and, at K = 1, bit for bit against what the retired pair kernel computed (tests/golden); the search
+engine against the host loop over the same predict groups; the estimator through the public surface on the toy 2-D problem."""
 import os
 import sys
 
@@ -77,20 +77,32 @@ def test_jes_mc_group_forward_matches_the_reference(n_boxes, K, T, S):
     assert all(s == want for s in seen), seen
 
 
-# ------------------------------------------------------------------ 2. K = 1: the existing entry point, bit for bit
-@pytest.mark.parametrize("n_pairs,T,S", [(3, 5, 4), (2, 67, 1)])
-def test_one_sample_is_bitwise_the_pair_kernel(n_pairs, T, S):
+# ------------------------------------------------------------------ 2. K = 1: what the retired pair kernel computed, bit for bit
+_GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "jes_pair_kernel_bits.npz")
+_golden = {}
+
+
+def _recorded(key):
+    if not _golden:
+        _golden.update(np.load(_GOLDEN))
+    return torch.from_numpy(_golden[key].copy()).view(torch.float64)
+
+
+@pytest.mark.parametrize("n_pairs,T,S", [(3, 5, 4), (2, 67, 1), (32, 3, 2)])
+def test_one_sample_reproduces_the_recorded_pair_kernel(n_pairs, T, S):
+    """tests/golden/jes_pair_kernel_bits.npz (tools/record_jes_pair_golden.py): inputs and outputs of three consecutive calls of
+    the one-thread-per-test-point kernel that mobocmf_jes_group_forward launched before it became the K = 1 case of
+    mobocmf_jes_mc_group_forward, recorded on an MI355X.  Both entry points reproduce acq, seeds, best_v and best_x after
+    every call; (32, 3, 2): 64 models, every lane of the wavefront busy."""
     from mobocmf_amd import functional as F
     d = 3
-    g = torch.Generator().manual_seed(T)
     z = lambda *s: torch.zeros(*s, dtype=torch.float64, device=DEV)
     best = {name: (torch.full((T,), float("-inf"), dtype=torch.float64, device=DEV), z(T, d)) for name in ("pair", "mc")}
     moved = []
-    for call in range(3):      # the second and third calls replace some tracked rows and keep others
-        mom, noise = R.mc_inputs(n_pairs, 1, T, S, seed=30 + call, flip=call)
-        x = torch.rand(T, d, dtype=torch.float64, generator=g).to(DEV)
-        md, nd = mom.to(DEV), noise.to(DEV)
-        out = {}
+    for call in range(3):      # (inputs: jes_mc_reference.mc_inputs(n_pairs, 1, T, S, seed=30 + call, flip=call), as recorded)
+        rec = lambda name: _recorded("%d_%d_%d/%d/%s" % (n_pairs, T, S, call, name))
+        md, nd, x = rec("moments").to(DEV), rec("noise").to(DEV), rec("x").to(DEV)
+        want = [rec(name) for name in ("acq", "seeds", "best_v", "best_x")]
         for name in ("pair", "mc"):
             acq, seeds = z(T), torch.full_like(md, float("nan"))
             before = best[name][0].clone()
@@ -98,12 +110,11 @@ def test_one_sample_is_bitwise_the_pair_kernel(n_pairs, T, S):
                 F.jes_group_forward(md, nd, T, S, acq, seeds=seeds, x=x, best_v=best[name][0], best_x=best[name][1])
             else:
                 F.jes_mc_group_forward(md, nd, 1, T, S, acq, seeds=seeds, x=x, best_v=best[name][0], best_x=best[name][1])
-            out[name] = (acq, seeds, best[name][0].clone(), best[name][1].clone())
+            for got, w in zip((acq, seeds, best[name][0], best[name][1]), want):
+                assert torch.equal(_bits(got), _bits(w)), (name, call)
             moved.append(int((acq > before).sum()))
-        for a, b in zip(out["pair"], out["mc"]):
-            assert torch.equal(_bits(a), _bits(b)), call
-        assert bool((out["pair"][1][0::2, 1] == 0.0).any()) and bool((out["pair"][1][0::2, 1] > 0.0).any())
-    assert moved[0] == T and (T == 5 or 0 < moved[-1] < T)
+        assert bool((want[1][0::2, 1] == 0.0).any()) and bool((want[1][0::2, 1] > 0.0).any())
+    assert moved[0] == T and (T <= 5 or 0 < moved[-1] < T)
 
 
 # ------------------------------------------------------------------ 3. tracking, bad arguments
@@ -244,8 +255,7 @@ def test_engine_parity_at_short_horizon_with_two_samples(M, seed, fidelity):
 
     def freeze(on):
         for grp in groups.values():
-            if hasattr(grp, "freeze"):
-                grp.freeze() if on else grp.thaw()
+            grp.freeze() if on else grp.thaw()
 
     freeze(True)
     cand_h, val_h = optimize_acqf_multistart(acq_fn, bounds, num_restarts=5, raw_samples=200, maxiter=10, generator=gen())

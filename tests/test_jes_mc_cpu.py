@@ -70,6 +70,30 @@ def test_identical_conditioned_models_give_the_one_sample_value(K):
         assert float((K * su[:, k] - s1[:, 1]).abs().max()) <= 4 * 2.0 ** -53 * float(s1[:, 1].abs().max())
 
 
+def test_group_value_at_one_sample_is_the_pair_expression_bitwise():
+    """JESMOC_MFDGP._group_value has one expression for every K; at K = 1 -- also on an object made with __new__, which has the
+    class default -- it is the pair expression bit for bit, value and gradient (1.0 * the single term is exact, and so is the
+    product of the incoming gradient with 1.0).  200 random cases: 2 .. 10 models, T in 1 .. 40, v over twenty decades."""
+    from mobocmf_amd.acquisition_functions.JESMOC_MFDGP import JESMOC_MFDGP
+    acq = JESMOC_MFDGP.__new__(JESMOC_MFDGP)
+    assert acq.num_pareto_samples == 1 and "num_pareto_samples" not in acq.__dict__
+    g = torch.Generator().manual_seed(5)
+    clamped = set()
+    for case in range(200):
+        n = 2 * int(torch.randint(1, 6, (1,), generator=g))
+        T = int(torch.randint(1, 41, (1,), generator=g))
+        v = 10.0 ** (20.0 * torch.rand(n, T, dtype=torch.float64, generator=g) - 10.0)
+        w = torch.randn(T, dtype=torch.float64, generator=g)      # (a gradient other than ones flows in)
+        va, vb = v.clone().requires_grad_(True), v.clone().requires_grad_(True)
+        got = acq._group_value(va)
+        want = (0.5 * torch.clamp(torch.log(vb[0::2]) - torch.log(vb[1::2]), min=0.0)).sum(0)
+        (got * w).sum().backward()
+        (want * w).sum().backward()
+        assert got.shape == (T,) and torch.equal(_bits(got), _bits(want)) and torch.equal(_bits(va.grad), _bits(vb.grad)), case
+        clamped |= set((va.grad == 0.0).reshape(-1).tolist())
+    assert clamped == {True, False}      # both sides of the clamp
+
+
 class _Stub:
     """A model whose predict_for_acquisition returns a fixed variance; counts its evaluations and mode switches."""
 

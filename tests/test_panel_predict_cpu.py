@@ -102,6 +102,28 @@ def test_fits_predict_limits_and_reasons():
     assert PP.MIN_M == _lib.COOP_MAX_M + 1 and PP.MAX_M == _lib.FROZEN_MAX_M == 512
 
 
+def test_every_group_class_gates_with_its_own_why_not():
+    """The classmethod every predict group has (util/predict_group.py) is the module-level gate of its kernel: None or a
+    sentence, the one-workgroup class with its speed rule only where asked."""
+    from mobocmf_amd.util import coop_step as CS
+    from mobocmf_amd.util import tiny_step as TS
+    from mobocmf_amd.util.predict_group import PredictGroup
+    classes = (TS.TinyPredictGroup, CS.CoopPredictGroup, PP.PanelPredictGroup, PP.SplitPredictGroup)
+    assert all(issubclass(c, PredictGroup) for c in classes) and not issubclass(PP.PanelPredictGroup, TS.TinyPredictGroup)
+    takes = {16: (True, True, False, False), 32: (True, True, False, False), 33: (False, True, False, False),
+             128: (False, True, False, False), 129: (False, False, True, True), 513: (False, False, False, True)}
+    for M, want in takes.items():
+        model = _cpu_model(M, 2, 3)
+        got = [c.why_not(model, 1, 5, 2, on_gpu=False) for c in classes]
+        assert tuple(g is None for g in got) == want and all(g is None or isinstance(g, str) for g in got), (M, got)
+        host = [c.why_not(model, 1, 5, 2) for c in classes]      # (parameters on the host: no class takes it)
+        assert all(isinstance(h, str) for h in host) and all("on the GPU" in h for h, g in zip(host, got) if g is None)
+    assert PP.PanelPredictGroup.why_not(_cpu_model(513, 2, 3), 1, 5, 2, on_gpu=False) == PP.why_not(_cpu_model(513, 2, 3), 1, 5, 2, on_gpu=False)
+    wide = _cpu_model(32, 2, 25)      # 100 x 25 columns: within the kernel's limit, beyond what one workgroup is quick at
+    assert TS.TinyPredictGroup.why_not(wide, 1, 100, 2, on_gpu=False) is None
+    assert "speed rule" in TS.TinyPredictGroup.why_not(wide, 1, 100, 2, on_gpu=False, speed_rule=True)
+
+
 def _fake_chain(kind, M, d):
     """A FrozenChain of host tensors with the library's own state size (nothing is computed)."""
     lib = _lib.load()

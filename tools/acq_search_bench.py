@@ -17,7 +17,6 @@ usage: python tools/acq_search_bench.py [--epochs 300] [--cond-iters 200] [--ite
                                         [--sizes 64,20 | 160,512 | 640,1024] [--force-split]
 """
 import argparse
-import contextlib
 import json
 import os
 import statistics
@@ -52,7 +51,7 @@ def replay_us(acq, per, n=200):
     for f, eng in sorted(acq._device_searches.items()):
         assert per in eng._graphs, "replay_us: run a search with iters_per_graph = %d first" % per
         graph = eng._graphs[per]
-        with eng.group.frozen() if hasattr(eng.group, "frozen") else contextlib.nullcontext():
+        with eng.group.frozen():
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             for _ in range(n // per):
@@ -74,7 +73,7 @@ def main():
     a = ap.parse_args()
     if a.force_split:
         from mobocmf_amd.util import panel_predict
-        panel_predict.fits_predict = lambda *args, **kw: False
+        panel_predict.PanelPredictGroup.why_not = classmethod(lambda cls, *args, **kw: "switched off by --force-split")
     unroll = [int(u) for u in a.unroll.split(",")]
     for size in [int(s) for s in a.sizes.split(",")]:
         n_low, n_high = SPLIT[size]
