@@ -910,6 +910,34 @@ int mobocmf_jes_mc_group_forward(const double* moments, const double* noise, int
                                  double* acq, int32_t want_seeds, double* seeds, int32_t track, const double* x, int32_t d,
                                  double* best_v, double* best_x, mobocmf_stream_t stream);
 
+/* JES per black-box, for decoupled evaluations (which black-box is evaluated next): moments, noise, the model layout (p (1 + K)
+ * unconditioned, p (1 + K) + 1 + k conditioned), v, mbar and diff_pk exactly as for mobocmf_jes_mc_group_forward.
+ *   term_p[t] = (1 / K) sum_k 0.5 max(diff_pk, 0): the k-sum in the order of k, the product with 1 / K rounded -- the summand of
+ *               black-box p in mobocmf_jes_mc_group_forward's acq[t].  A NaN stays a NaN.
+ * box_of_point == NULL (all boxes: the raw candidates are scored once for every black-box):
+ *   acq[p acq_ld + t] = term_p[t] for p = 0 .. n_boxes - 1, acq_ld >= T the distance between two boxes' rows (a chunk of
+ *   candidates writes its slice of an (n_boxes, n) array with acq_ld = n).  want_seeds and track must be 0.
+ * box_of_point != NULL (T device words: the box each test point is searched for -- the replayed iterate), b = box_of_point[t]:
+ *   acq[t] = term_b[t]; acq_ld is ignored.
+ *   want_seeds = 1: the seeds (the layout of moments) of the 1 + K models of box b at the columns of t are d term_b[t] / d (raw
+ *     mean, raw variance), the expressions of mobocmf_jes_mc_group_forward for those models (a model's seeds there depend on
+ *     its own box only); the seeds of EVERY OTHER model at those columns are written as 0.0 in both arrays (never left stale:
+ *     the MOBOCMF_STEP_INPUT_GRADIENTS launch that follows reads all of them).
+ *   track = 1: as for mobocmf_jes_group_forward, on acq[t] = term_b[t].
+ *   b outside [0, n_boxes) (the host cannot see the words): acq[t] = NaN, every seed at the columns of t 0.0, nothing tracked.
+ * What ties it to mobocmf_jes_mc_group_forward on the same inputs, bit for bit:
+ *   P1  sum_p acq[p acq_ld + t] of the all-box mode, accumulated in the order of p from 0.0, is that entry point's acq[t];
+ *   P2  the selected-box acq[t] is the all-box acq[b acq_ld + t]; the seeds of box b's models are that entry point's seeds of
+ *       those models; every other seed is 0.0;
+ *   P3  n_boxes = 1 with all-zero words is that entry point in acq, seeds, best_v and best_x.
+ * One launch of T workgroups of one wavefront: a lane per model, the lane of the unconditioned model of box p sums that box's K
+ * terms in order; static LDS, no atomics, no wait on another workgroup.
+ * MOBOCMF_BAD_ARG: as for mobocmf_jes_mc_group_forward; with box_of_point NULL also acq_ld < T, want_seeds != 0 or track != 0. */
+int mobocmf_jes_mc_box_forward(const double* moments, const double* noise, int32_t n_boxes, int32_t K, int32_t T, int32_t S,
+                               const int32_t* box_of_point, double* acq, int32_t acq_ld, int32_t want_seeds, double* seeds,
+                               int32_t track, const double* x, int32_t d, double* best_v, double* best_x,
+                               mobocmf_stream_t stream);
+
 /* One projected Adam ASCENT step on the iterate x (T x d): g[t][j] = -sum_i gx[i][t][j] over the n_models slices of the group's
  * input gradients gx (n_models, T, d) in the order of i, then the update of mobocmf_adam_multi (the same expressions in the same
  * order: with n_models = 1 the same bits) with the bias corrections of step steps_done[0] + 1, then x[t][j] clamped to

@@ -216,6 +216,7 @@ SYMBOLS = {
     "mobocmf_natgrad_small_step": [_P, _P, _I32, _D, _D, _I32, _P],
     "mobocmf_jes_group_forward": [_P, _P, _I32, _I32, _I32, _P, _I32, _P, _I32, _P, _I32, _P, _P, _P],
     "mobocmf_jes_mc_group_forward": [_P, _P, _I32, _I32, _I32, _I32, _P, _I32, _P, _I32, _P, _I32, _P, _P, _P],
+    "mobocmf_jes_mc_box_forward": [_P, _P, _I32, _I32, _I32, _I32, _P, _P, _I32, _I32, _P, _I32, _P, _I32, _P, _P, _P],
     "mobocmf_ascent_adam_step": [_P, _P, _I32, _I32, _I32, _P, _P, _P, _P, _D, _D, _D, _D, _P, _P],
     "mobocmf_select_topk": [_P, _I32, _I32, _P, _I32, _P, _P, _P, _P],
     "mobocmf_frozen_predict_work_bytes": [ctypes.POINTER(FrozenPredictModel), _I32, ctypes.POINTER(_SZ)],

@@ -12,6 +12,10 @@ all-gather + sum of mobocmf_amd.parallel.coupled_acquisition.
 frozen-chain predict groups (128 < M <= 1024, util/panel_predict.py) the whole search -- scoring of the raw candidates, choice of
 the restarts, the ascent, the best iterate, the final pick -- runs on the GPU (util/acq_search.py DeviceAcqSearch,
 csrc/acq_search.hip), one graph replay per iterate, and the host reads the device once per ``get_nextpoint_coupled`` call.
+
+``get_nextpoint_decoupled`` answers which black-box to evaluate next: every black-box's own JES term is maximised from one draw
+of raw candidates and weighed by that black-box's cost (the reference has ``decoupled_acq`` :118-123 and nothing that maximises
+it); with ``search="device"`` all black-boxes of a fidelity are searched at once (DecoupledDeviceAcqSearch).
 """
 import contextlib
 
@@ -65,13 +69,17 @@ class _JES_MFDGP:
 
 
 def optimize_acqf_multistart(acq_function, bounds, num_restarts=5, raw_samples=200, maxiter=200, lr=0.02,
-                             generator=None):
-    """Maximise ``acq_function`` over the box ``bounds`` (2, d).  Returns (candidate (1, d), value)."""
+                             generator=None, Xraw=None):
+    """Maximise ``acq_function`` over the box ``bounds`` (2, d).  Returns (candidate (1, d), value).  ``Xraw`` (n, d): the raw
+    candidates to start from, in place of the draw of ``raw_samples`` uniform ones (several searches from the same candidates)."""
     lo, hi = bounds[0], bounds[1]
     d = lo.numel()
     dev, dt = lo.device, lo.dtype
     with torch.no_grad():
-        Xraw = lo + (hi - lo) * torch.rand(raw_samples, d, dtype=dt, device=dev, generator=generator)
+        if Xraw is None:
+            Xraw = lo + (hi - lo) * torch.rand(raw_samples, d, dtype=dt, device=dev, generator=generator)
+        else:
+            Xraw, raw_samples = Xraw.detach().clone(), Xraw.shape[0]
         parallel.broadcast_(Xraw)     # sharded surrogates: every rank scores (and all-gathers values of) the same points
         vals = acq_function(Xraw)
         X = Xraw[torch.topk(vals, min(num_restarts, raw_samples)).indices].clone()
@@ -201,6 +209,7 @@ class JESMOC_MFDGP:
         state.pop("_tiny_groups", None)      # device descriptors: rebuilt on first use
         state.pop("_panel_groups", None)
         state.pop("_device_searches", None)  # ... and the captured graphs over them
+        state.pop("_decoupled_searches", None)
         return state
 
     @staticmethod
@@ -218,6 +227,18 @@ class JESMOC_MFDGP:
             term = 0.5 * torch.clamp(lu - torch.log(v[k::1 + K]), min=0.0)
             box = term if box is None else box + term
         return ((1.0 / K) * box).sum(0)
+
+    def _group_box_value(self, v, p):
+        """Black-box p's own term from a group's v (n_boxes (1 + K), T): (1/K) sum_k 0.5 clamp(log v_u,p - log v_c,pk, 0) -- the
+        summand of ``_group_value``, in its expression order (mobocmf_jes_mc_box_forward's term_p)."""
+        K = self.num_pareto_samples
+        u = p * (1 + K)
+        lu = torch.log(v[u])
+        box = None
+        for k in range(1, K + 1):
+            term = 0.5 * torch.clamp(lu - torch.log(v[u + k]), min=0.0)
+            box = term if box is None else box + term
+        return (1.0 / K) * box
 
     def _first_group(self, classes, jess, fidelity, T, d, speed_rule=(), **kw):
         """A predict group (util/predict_group.py) over (uncond, cond_1 .. cond_K) of every black-box in ``jess`` for T test
@@ -428,3 +449,118 @@ class JESMOC_MFDGP:
             print("Iter:", iteration, "Acquisition:", float(w * self.costs_blackboxes[fidelity]["total"]),
                   " Evaluating fidelity", fidelity, "at", cand[0].cpu().numpy())
         return cand[0, :], fidelity
+
+    # ------------------------------------------------------------------ decoupled evaluations: which black-box next
+    def _boxes(self, fidelity):
+        """[(name, is_constraint, jes)] of ``fidelity``: objectives, then constraints, in insertion order -- the order of the
+        models in a predict group (``_device_search``), so the position in this list is the box index p."""
+        return [(n, False, j) for n, j in self.objectives[fidelity].items()] + \
+               [(n, True, j) for n, j in self.constraints[fidelity].items()]
+
+    def _box_acq(self, X, fidelity, p, blackbox_name, is_constraint):
+        """Black-box p's own term at X: through the predict group ``coupled_acq`` would evaluate through, else ``decoupled_acq``."""
+        X = X.double()
+        jess = [j for _, _, j in self._boxes(fidelity)]
+        if self.use_tiny_step and jess and X.is_cuda and parallel.world()[1] == 1:
+            X2 = X[:, 0, :] if X.dim() > 2 else X
+            grp = self._tiny_group(jess, fidelity, X2.shape[0], X2.shape[1])
+            if grp is not None:
+                if self._search_running:
+                    grp.freeze()
+                _, v = grp.acquisition_moments(X2)
+                return self._group_box_value(v, p)
+        return self.decoupled_acq(X, fidelity, blackbox_name, is_constraint=is_constraint)
+
+    def _decoupled_device_search(self, fidelity):
+        """(DecoupledDeviceAcqSearch, raw-candidate group) under the routing of ``_device_search``, the search group built for
+        (black-boxes) x num_restarts test points; None: the host engine.  Cached apart from the coupled searches."""
+        from .. import _lib
+        jess = [j for _, _, j in self._boxes(fidelity)]
+        bounds = self.standard_bounds
+        if not (self.use_tiny_step and jess and bounds is not None and bounds.is_cuda and parallel.world()[1] == 1):
+            return None
+        K, B, R = self.num_pareto_samples, len(jess), self.num_restarts
+        if B * (1 + K) > 2 * _lib.ACQ_MAX_PAIRS or B * R > _lib.TOPK_MAX_N or R > self.raw_samples:
+            return None
+        d = bounds.shape[1]
+        grp = self._tiny_group(jess, fidelity, B * R, d)
+        if grp is None:
+            grp = self._panel_group(jess, fidelity, B * R, d, True)
+            raw = None if grp is None else self._panel_group(jess, fidelity, self.raw_samples, d, False)
+        else:
+            chunks = [c for c in range(1, self.MAX_RAW_CHUNKS + 1) if self.raw_samples % c == 0]
+            raw = next((g for g in (self._tiny_group(jess, fidelity, self.raw_samples // c, d) for c in chunks) if g is not None),
+                       None)
+        if raw is None:
+            return None
+        cache = self.__dict__.setdefault("_decoupled_searches", {})
+        if fidelity not in cache or cache[fidelity].group is not grp:
+            from ..util.acq_search import DecoupledDeviceAcqSearch
+            cache[fidelity] = DecoupledDeviceAcqSearch(grp, bounds, R, self.search_lr, num_pareto_samples=K)
+        return cache[fidelity], raw
+
+    def _optimize_decoupled(self, fidelity, maxiter=200, generator=None):
+        """[(candidate (1, d), value)] per black-box of ``fidelity`` in the order of ``_boxes``: every box's own term maximised
+        from ONE draw of raw candidates (the draw of ``_optimize``).  ``self.last_search_engine[fidelity]`` says where it ran."""
+        if self.search not in ("host", "device"):
+            raise ValueError("search must be 'host' or 'device' (got %r)" % (self.search,))
+        engines = self.__dict__.setdefault("last_search_engine", {})
+        boxes = self._boxes(fidelity)
+        lo, hi = self.standard_bounds[0], self.standard_bounds[1]
+        with contextlib.ExitStack() as stack:
+            for _, _, jes in boxes:
+                stack.enter_context(jes.frozen())
+            stack.enter_context(self._frozen_groups())
+            found = self._decoupled_device_search(fidelity) if self.search == "device" else None
+            with torch.no_grad():
+                Xraw = lo + (hi - lo) * torch.rand(self.raw_samples, lo.numel(), dtype=lo.dtype, device=lo.device,
+                                                   generator=generator)
+            if found is not None:
+                engine, raw = found
+                with torch.no_grad():
+                    engine.start_from_raw(raw, Xraw)
+                    engines[fidelity] = "device"
+                    cands, vals = engine.run(None, maxiter)
+                return [(cands[p:p + 1], vals[p]) for p in range(len(boxes))]
+            engines[fidelity] = "host"
+            return [optimize_acqf_multistart(lambda x, p=p, name=name, con=con: self._box_acq(x, fidelity, p, name, con),
+                                             self.standard_bounds, num_restarts=self.num_restarts, raw_samples=self.raw_samples,
+                                             maxiter=maxiter, lr=self.search_lr, Xraw=Xraw)
+                    for p, (name, con, _) in enumerate(boxes)]
+
+    def get_nextpoint_decoupled(self, iteration=None, verbose=False, maxiter=200, generator=None):
+        """Which black-box to evaluate next, where and at which fidelity: every registered (fidelity, black-box) has its own JES
+        term maximised (``search``: on the host, or all black-boxes of a fidelity at once on the GPU), the value is weighed by
+        1 / costs_blackboxes[fidelity][name], the largest wins, ties to the earlier (fidelity, black-box).  Returns
+        (x (d,), fidelity, blackbox_name, is_constraint); ``last_decoupled_values[(fidelity, name)]``: the unweighted values."""
+        from ..util.acq_search import raise_on_info
+        if not parallel._no_group():
+            raise ValueError("get_nextpoint_decoupled is limited to one process (surrogates sharded over a process group have "
+                             "get_nextpoint_coupled)")
+        fids = [self.num_fidelities - 1] if self.eval_highest_fidelity else list(range(self.num_fidelities))
+        found = []
+        for fidelity in fids:
+            boxes = self._boxes(fidelity)
+            if not boxes:
+                continue
+            res = self._optimize_decoupled(fidelity, maxiter=maxiter, generator=generator)
+            found += [(cand, val, fidelity, name, con) for (cand, val), (name, con, _) in zip(res, boxes)]
+        if not found:
+            raise ValueError("get_nextpoint_decoupled: no black-box registered (add_blackbox)")
+        vals = torch.stack([v.detach().reshape(()).double() for _, v, _, _, _ in found])
+        searches = self.__dict__.get("_decoupled_searches", {})
+        infos = [searches[f].info_words() for f in fids if self.last_search_engine.get(f) == "device" and f in searches]
+        host, words = _read_once(vals, torch.cat(infos) if infos else None)      # the one read of the device
+        if words is not None:
+            raise_on_info(words, "device acquisition search")
+        self.last_decoupled_values = {(f, name): float(host[k]) for k, (_, _, f, name, _) in enumerate(found)}
+        best = None
+        for k, (cand, _, fidelity, name, con) in enumerate(found):
+            w = float(host[k]) / self.costs_blackboxes[fidelity][name]
+            if best is None or best[0] < w:
+                best = (w, cand, fidelity, name, con)
+        w, cand, fidelity, name, con = best
+        if verbose:
+            print("Iter:", iteration, "Acquisition:", float(w * self.costs_blackboxes[fidelity][name]), " Evaluating",
+                  "constraint" if con else "objective", name, "at fidelity", fidelity, "at", cand[0].cpu().numpy())
+        return cand[0, :], fidelity, name, con

@@ -22,10 +22,24 @@ class Random_choice():
         self.coupled_costs_fidelities = torch.zeros(self.num_fidelities)
         self.total_cost_fidelities = 0.0
 
-    def add_blackbox(self, fidelity: int, blackbox_name: str, cost_evaluation: float = 1.0):
+    def add_blackbox(self, fidelity: int, blackbox_name: str, cost_evaluation: float = 1.0, is_constraint: bool = False):
         self.costs_blackboxes[fidelity][blackbox_name] = cost_evaluation
         self.coupled_costs_fidelities[fidelity] += cost_evaluation
         self.total_cost_fidelities += cost_evaluation
+        self.__dict__.setdefault("blackboxes", []).append((fidelity, blackbox_name, bool(is_constraint)))
+
+    def get_nextpoint_decoupled(self, iteration=None, verbose=False):
+        """The baseline of the decoupled setting: a uniformly chosen registered (fidelity, black-box) and a uniform point.
+        Returns (x (d,), fidelity, blackbox_name, is_constraint), as JESMOC_MFDGP.get_nextpoint_decoupled."""
+        boxes = self.__dict__.get("blackboxes", [])
+        if not boxes:
+            raise ValueError("get_nextpoint_decoupled: no black-box registered (add_blackbox)")
+        nextpoint = torch.rand(size=(self.input_size,))
+        fidelity, name, is_constraint = boxes[int(torch.randint(len(boxes), (1,)).item())]
+        if verbose:
+            print("Iter:", iteration, " Evaluating", "constraint" if is_constraint else "objective", name, "at fidelity",
+                  fidelity, "at", nextpoint.numpy())
+        return nextpoint, fidelity, name, is_constraint
 
     def decoupled_acq(self, X: Tensor, fidelity: int, blackbox_name) -> Tensor:
         return torch.rand(size=(X.shape[0],))

@@ -1503,6 +1503,38 @@ def jes_mc_group_forward(moments, noise, K, T, S, acq, seeds=None, x=None, best_
     return acq
 
 
+def jes_mc_box_forward(moments, noise, K, T, S, acq, box_of_point=None, seeds=None, x=None, best_v=None, best_x=None, stream=None):
+    """mobocmf_jes_mc_box_forward: JES per black-box, term_p = (1/K) sum_k 0.5 max(log v_u,p - log v_c,pk, 0), from ``moments``
+    (n_boxes (1 + K), 2, T S) and ``noise`` laid out as for ``jes_mc_group_forward``.  ``box_of_point`` None: ``acq``
+    (n_boxes, >= T) with unit column stride -- a column slice of a wider array will do -- gets term_p[t] in row p; no seeds, no
+    tracking.  ``box_of_point`` (T,) int32 on the device: ``acq`` (T,) = term_b[t] with b = box_of_point[t]; ``seeds`` given: the
+    coupled launch's seeds for the models of box b, 0.0 for every other model; ``best_v`` / ``best_x`` / ``x`` as in
+    ``jes_group_forward``.  One launch, only enqueues (on ``stream``, default the current one): capturable."""
+    lib = _lib.require_device()
+    K, T = int(K), int(T)
+    if K >= 1 and moments.shape[0] % (1 + K):      # (K < 1 is the library's to refuse)
+        raise _lib.MobocmfError("jes_mc_box_forward: 1 + K models per black-box (got K = %d, %d models)" % (K, moments.shape[0]))
+    n_boxes = moments.shape[0] // max(1 + K, 1)
+    ld = 0
+    if box_of_point is None:
+        if acq.dim() == 1:
+            acq = acq[None]
+        if acq.dim() != 2 or acq.shape[0] != n_boxes or acq.shape[1] < T or (acq.shape[1] > 1 and acq.stride(1) != 1):
+            raise _lib.MobocmfError("jes_mc_box_forward: acq (n_boxes, >= T) with unit column stride")
+        ld = acq.stride(0) if n_boxes > 1 else max(acq.stride(0), T)      # (the library refuses a row distance below T)
+    else:
+        if box_of_point.dtype != torch.int32 or box_of_point.numel() != T or not box_of_point.is_contiguous():
+            raise _lib.MobocmfError("jes_mc_box_forward: box_of_point (T,) int32, contiguous")
+        if acq.numel() < T:
+            raise _lib.MobocmfError("jes_mc_box_forward: acq (T,)")
+    track = best_v is not None
+    _lib.check(lib.mobocmf_jes_mc_box_forward(_ptr(moments), _ptr(noise), n_boxes, K, T, int(S), _ptr(box_of_point), _ptr(acq),
+                                              int(ld), int(seeds is not None), _ptr(seeds), int(track), _ptr(x),
+                                              x.shape[-1] if track else 0, _ptr(best_v), _ptr(best_x), _on(stream)),
+               "mobocmf_jes_mc_box_forward")
+    return acq
+
+
 def ascent_adam_step(x, gx, lo, hi, exp_avg, exp_avg_sq, steps_done, lr, betas=(0.9, 0.999), eps=1e-8, stream=None):
     """mobocmf_ascent_adam_step: one projected Adam ascent step on the iterate ``x`` (T, d), in place, along
     -gx.sum(0) of the group's input gradients ``gx`` (n_models, T, d) -- FusedAdam's update, then the clamp to [lo, hi] (d,);

@@ -11,6 +11,9 @@ in stream order --
 
 -- captured once as a HIP graph (a single chain, no parallel branches) and replayed; nothing is read on the host until the
 caller fetches the winner.
+
+``DecoupledDeviceAcqSearch`` runs the searches of all black-boxes of a fidelity at once, each for its own JES term
+(``JESMOC_MFDGP.get_nextpoint_decoupled``): the same chain with mobocmf_jes_mc_box_forward in the JES position.
 """
 import torch
 
@@ -148,14 +151,91 @@ class DeviceAcqSearch:
                 for _ in range(left):
                     self._iterate()
             self._score(seeds=False)      # X_maxiter
-            F.select_topk(self.best_v, 1, self.win_v, self.win_i, x=self.best_x, out_x=self.cand, stream=g.stream)
-            return self.cand.clone(), self.win_v[0].clone()
+            return self._winner()
+
+    def _winner(self):
+        """The best of the restarts' best iterates: (candidate (1, d), value ()), device tensors."""
+        F.select_topk(self.best_v, 1, self.win_v, self.win_i, x=self.best_x, out_x=self.cand, stream=self.group.stream)
+        return self.cand.clone(), self.win_v[0].clone()
 
     def info_words(self):
         """The Cholesky verdicts of the models of the search group and of the raw-candidate group last used (int32 words, 0:
         fine) as one device tensor; no synchronisation."""
         raw = self.__dict__.get("raw_group")
         return torch.cat([w.reshape(-1) for g in (self.group, raw) if g is not None for w in g.info_words])
+
+
+class DecoupledDeviceAcqSearch(DeviceAcqSearch):
+    """The searches of ALL black-boxes of a fidelity at once, each for its own JES term (decoupled evaluations:
+    JESMOC_MFDGP.get_nextpoint_decoupled).  ``group``: an ordinary predict group over the B (1 + K) models, built for
+    T = B R test points (R = ``num_restarts``); rows [p R, (p + 1) R) of its x are the restarts of black-box p.  An iterate is
+    the same chain of four launches with mobocmf_jes_mc_box_forward in selected-box mode in place of the coupled JES launch:
+    it seeds the models of a row's own box and writes ZERO seeds for every other model, so mobocmf_ascent_adam_step's sum of gx
+    over all models is the gradient of the row's own term.  Every model is therefore evaluated at all B R rows though only R
+    are its own.
+
+    ``start_from_raw`` scores the raw candidates ONCE for all boxes (the forward launches of the coupled search, then the all-box
+    mode into ``vals`` (B, n)) and picks each box's R best.  ``run`` -> (candidates (B, d), values (B,)), device tensors,
+    without synchronising."""
+
+    def __init__(self, group, bounds, num_restarts, lr, betas=(0.9, 0.999), eps=1e-8, num_pareto_samples=1):
+        K, R = int(num_pareto_samples), int(num_restarts)
+        if K < 1 or R < 1:
+            raise ValueError("DecoupledDeviceAcqSearch: num_pareto_samples >= 1 and num_restarts >= 1 (got %d, %d)" % (K, R))
+        n_models = len(group.models)
+        B = n_models // (1 + K)
+        if n_models % (1 + K) or B < 1 or group.T != B * R:
+            raise _lib.MobocmfError("DecoupledDeviceAcqSearch: a group of (uncond, cond_1 .. cond_K) per black-box built for T = "
+                                    "(black-boxes) x num_restarts test points")
+        if B * R > _lib.TOPK_MAX_N or B * (1 + K) > 2 * _lib.ACQ_MAX_PAIRS:
+            raise _lib.MobocmfError("DecoupledDeviceAcqSearch: at most %d rows and %d models" % (_lib.TOPK_MAX_N, 2 * _lib.ACQ_MAX_PAIRS))
+        super().__init__(group, bounds, B * R, lr, betas=betas, eps=eps, num_pareto_samples=K)
+        self.B, self.R = B, R
+        dev = group.device
+        self.box_of_point = torch.div(torch.arange(B * R, device=dev), R, rounding_mode="floor").to(torch.int32).contiguous()
+        self.win_v = torch.zeros(B, dtype=torch.float64, device=dev)
+        self.win_i = torch.zeros(B, dtype=torch.int64, device=dev)
+        self.cand = torch.zeros(B, self.d, dtype=torch.float64, device=dev)
+
+    def _score(self, seeds):
+        g = self.group
+        g._launch(_lib.STEP_FORWARD)
+        F.jes_mc_box_forward(g.moments, self.noise, self.K, self.T, g.S, self.acq, box_of_point=self.box_of_point,
+                             seeds=g.seeds if seeds else None, x=g.x, best_v=self.best_v, best_x=self.best_x, stream=g.stream)
+
+    def start_from_raw(self, raw_group, Xraw):
+        """As DeviceAcqSearch.start_from_raw -- the same raw group, chunks and forward launches -- with every chunk scored for all
+        boxes in one launch (row p of ``vals`` (B, n): box p's term at every candidate) and one selection per box writing its R
+        best rows into rows [p R, (p + 1) R) of the search group's x.  Returns (vals (B, n), the restarts' values (B, R), their
+        indices (B, R))."""
+        n, Tc, B, R = Xraw.shape[0], raw_group.T, self.B, self.R
+        if n % Tc or len(raw_group.models) != len(self.group.models) or not R <= n <= _lib.TOPK_MAX_N:
+            raise _lib.MobocmfError("DecoupledDeviceAcqSearch: the raw candidates in equal chunks of the raw group's T test points")
+        if (n, Tc) not in self._raw:
+            dev = self.group.device
+            self._raw[(n, Tc)] = (torch.zeros(B, n, dtype=torch.float64, device=dev), torch.zeros(B, R, dtype=torch.float64, device=dev),
+                                  torch.zeros(B, R, dtype=torch.int64, device=dev), raw_group.noise().detach().clone().contiguous(),
+                                  torch.zeros(n, self.d, dtype=torch.float64, device=dev))
+        vals, top_v, top_i, noise, xraw = self._raw[(n, Tc)]
+        self.raw_group, self.raw_values = raw_group, vals
+        raw_group.freeze()
+        xraw.copy_(Xraw.detach().reshape(n, self.d))
+        for c in range(n // Tc):
+            raw_group.x.copy_(xraw[c * Tc:(c + 1) * Tc])
+            raw_group._launch(_lib.STEP_FORWARD)
+            F.jes_mc_box_forward(raw_group.moments, noise, self.K, Tc, raw_group.S, vals[:, c * Tc:(c + 1) * Tc],
+                                 stream=raw_group.stream)
+        for p in range(B):
+            F.select_topk(vals[p], R, top_v[p], top_i[p], x=xraw, out_x=self.group.x[p * R:(p + 1) * R], stream=self.group.stream)
+        return vals, top_v, top_i
+
+    def _winner(self):
+        """Per box the best of its restarts' best iterates: (candidates (B, d), values (B,)), device tensors."""
+        R = self.R
+        for p in range(self.B):
+            F.select_topk(self.best_v[p * R:(p + 1) * R], 1, self.win_v[p:p + 1], self.win_i[p:p + 1],
+                          x=self.best_x[p * R:(p + 1) * R], out_x=self.cand[p:p + 1], stream=self.group.stream)
+        return self.cand.clone(), self.win_v.clone()
 
 
 def raise_on_info(words, what):

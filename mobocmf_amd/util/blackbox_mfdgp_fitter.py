@@ -201,7 +201,13 @@ class BlackBoxMFDGPFitter:
         ``warm_start`` (with ``previously_trained_model``): "hypers" carries over the kernel hyper-parameters and the fixed
         samples, "posterior" every layer's q(u) and the noise as well (``MFDGP``, util/warm_start.py): a refit on appended
         rows then starts from the previous optimum and needs no phase 1 (``num_epochs_1 = 0``)."""
-        if self.x_train is None:
+        if getattr(self, "decoupled_evals", False):
+            # every black-box has its own inputs: x_train is the union of the rows seen so far, in first-seen order without
+            # duplicates -- only MOOP's extra grid points and the input hash of the seeded exchange; the (unused) joint
+            # observation tables have no meaning
+            self._add_inputs(x_train)
+            self.objs_train = self.cons_train = None
+        elif self.x_train is None:
             self.x_train = x_train
         else:
             assert torch.equal(self.x_train, x_train), "The inputs for this new mfdgp do not match with inputs for " \
@@ -214,14 +220,27 @@ class BlackBoxMFDGPFitter:
                                warm_start=warm_start, **self.model_kwargs)
         handler.global_index = global_index
         if is_constraint:
-            self.cons_train = torch.cat((self.cons_train, y_train.cpu().double()), 1)
+            if self.cons_train is not None:
+                self.cons_train = torch.cat((self.cons_train, y_train.cpu().double()), 1)
             self.mfdgp_handlers_cons[blackbox_name] = handler
             self.thresholds_cons = torch.cat((self.thresholds_cons, torch.tensor([threshold_constraint]).double()), 0)
             self.num_con += 1
         else:
-            self.objs_train = torch.cat((self.objs_train, y_train.cpu().double()), 1)
+            if self.objs_train is not None:
+                self.objs_train = torch.cat((self.objs_train, y_train.cpu().double()), 1)
             self.mfdgp_handlers_objs[blackbox_name] = handler
             self.num_obj += 1
+
+    def _add_inputs(self, x_train):
+        """``decoupled_evals``: appends the rows of ``x_train`` that ``self.x_train`` does not hold yet, in their order."""
+        seen = set() if self.x_train is None else {tuple(r) for r in self.x_train.detach().cpu().double().tolist()}
+        keep = []
+        for i, r in enumerate(x_train.detach().cpu().double().tolist()):
+            if tuple(r) not in seen:
+                seen.add(tuple(r))
+                keep.append(i)
+        new = x_train[torch.tensor(keep, dtype=torch.int64, device=x_train.device)]
+        self.x_train = new if self.x_train is None else torch.cat([self.x_train, new.to(self.x_train)], 0)
 
     def _natgrad(self):
         return getattr(self, "variational_optimizer", "adam") == "natgrad"
