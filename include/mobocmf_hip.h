@@ -925,7 +925,8 @@ int mobocmf_jes_mc_group_forward(const double* moments, const double* noise, int
  *     the MOBOCMF_STEP_INPUT_GRADIENTS launch that follows reads all of them).
  *   track = 1: as for mobocmf_jes_group_forward, on acq[t] = term_b[t].
  *   b outside [0, n_boxes) (the host cannot see the words): acq[t] = NaN, every seed at the columns of t 0.0, nothing tracked.
- * What ties it to mobocmf_jes_mc_group_forward on the same inputs, bit for bit:
+ * What ties it to mobocmf_jes_mc_group_forward on the same inputs, bit for bit (the two entry points are modes of ONE launch:
+ * term_p and the seeds are formed by the same code in each, the modes differ in who sums and what is written):
  *   P1  sum_p acq[p acq_ld + t] of the all-box mode, accumulated in the order of p from 0.0, is that entry point's acq[t];
  *   P2  the selected-box acq[t] is the all-box acq[b acq_ld + t]; the seeds of box b's models are that entry point's seeds of
  *       those models; every other seed is 0.0;

@@ -217,28 +217,38 @@ class JESMOC_MFDGP:
         """The model list of a predict group: per black-box its unconditioned surrogate, then the K conditioned ones."""
         return [m for jes in jess for m in [jes.mfdgp_uncond] + jes.mfdgp_conds]
 
-    def _group_value(self, v):
-        """The coupled acquisition from a group's v (n_boxes (1 + K), T): sum_p (1/K) sum_k 0.5 clamp(log v_u,p - log v_c,pk, 0),
-        the k-sum in the order of k (the expression of mobocmf_jes_mc_group_forward).  K = 1: 1.0 * the single term is exact."""
+    def _box_values(self, v):
+        """Every black-box's own term from a group's v (n_boxes (1 + K), T): row p = (1/K) sum_k 0.5 clamp(log v_u,p - log v_c,pk, 0),
+        the k-sum in the order of k (mobocmf_jes_mc_box_forward's term_p).  K = 1: 1.0 * the single term is exact."""
         K = self.num_pareto_samples
         lu = torch.log(v[0::1 + K])
         box = None
         for k in range(1, K + 1):
             term = 0.5 * torch.clamp(lu - torch.log(v[k::1 + K]), min=0.0)
             box = term if box is None else box + term
-        return ((1.0 / K) * box).sum(0)
+        return (1.0 / K) * box
+
+    def _group_value(self, v):
+        """The coupled acquisition from a group's v: the sum of ``_box_values`` over the black-boxes (the expression of
+        mobocmf_jes_mc_group_forward)."""
+        return self._box_values(v).sum(0)
 
     def _group_box_value(self, v, p):
-        """Black-box p's own term from a group's v (n_boxes (1 + K), T): (1/K) sum_k 0.5 clamp(log v_u,p - log v_c,pk, 0) -- the
-        summand of ``_group_value``, in its expression order (mobocmf_jes_mc_box_forward's term_p)."""
-        K = self.num_pareto_samples
-        u = p * (1 + K)
-        lu = torch.log(v[u])
-        box = None
-        for k in range(1, K + 1):
-            term = 0.5 * torch.clamp(lu - torch.log(v[u + k]), min=0.0)
-            box = term if box is None else box + term
-        return (1.0 / K) * box
+        """Black-box p's own term from a group's v: the summand of ``_group_value``."""
+        return self._box_values(v)[p]
+
+    def _group_v(self, X, fidelity):
+        """v (n_boxes (1 + K), T) of every model of ``fidelity`` at X (float64) through the one-launch predict group, where the
+        acquisition is evaluated through one (small surrogates on the GPU, one process); else None: the layer path."""
+        jess = [j for _, _, j in self._boxes(fidelity)]
+        if self.use_tiny_step and jess and X.is_cuda and parallel.world()[1] == 1:
+            X2 = X[:, 0, :] if X.dim() > 2 else X
+            grp = self._tiny_group(jess, fidelity, X2.shape[0], X2.shape[1])
+            if grp is not None:
+                if self._search_running:
+                    grp.freeze()      # (constant parameters for the whole search: the chains are formed by its first launch only)
+                return grp.acquisition_moments(X2)[1]
+        return None
 
     def _first_group(self, classes, jess, fidelity, T, d, speed_rule=(), **kw):
         """A predict group (util/predict_group.py) over (uncond, cond_1 .. cond_K) of every black-box in ``jess`` for T test
@@ -290,15 +300,9 @@ class JESMOC_MFDGP:
         0.5 clamp(log v_uncond - log v_cond, 0) (:38-52) is then a handful of element-wise operations over all of them.
         With K > 1 sampled Pareto sets the value of a black-box is the mean over its K conditioned surrogates (_group_value)."""
         X = X.double()
-        jess = list(self.objectives[fidelity].values()) + list(self.constraints[fidelity].values())
-        if self.use_tiny_step and jess and X.is_cuda and parallel.world()[1] == 1:
-            X2 = X[:, 0, :] if X.dim() > 2 else X
-            grp = self._tiny_group(jess, fidelity, X2.shape[0], X2.shape[1])
-            if grp is not None:
-                if self._search_running:
-                    grp.freeze()      # (constant parameters for the whole search: the chains are formed by its first launch only)
-                _, v = grp.acquisition_moments(X2)
-                return self._group_value(v)
+        v = self._group_v(X, fidelity)
+        if v is not None:
+            return self._group_value(v)
         local = [obj(X) for obj in self.objectives[fidelity].values()] + \
                 [con(X) for con in self.constraints[fidelity].values()]
         if not local:
@@ -328,28 +332,30 @@ class JESMOC_MFDGP:
             if failed is not None:
                 raise failed
 
-    def _device_search(self, fidelity):
-        """(DeviceAcqSearch, raw-candidate group) of ``fidelity`` when its search can stay on the GPU -- the condition under
-        which ``coupled_acq`` evaluates through a one-launch group, and a group fits T = num_restarts and the raw candidates,
-        whole or in up to ``MAX_RAW_CHUNKS`` equal chunks (200 candidates x 25 samples are beyond the kernels' 4096 columns); or,
-        where no one-launch group fits, frozen-chain groups do (128 < M <= 1024: the raw candidates whole, no column limit
-        there) -- else None: M > 1024, S = 1, sharded surrogates, CPU tensors keep the host loop.  With K > 1 Pareto samples a
-        group holds 1 + K models per black-box: more than 2 MOBOCMF_ACQ_MAX_PAIRS models keep the host loop too."""
-        jess = list(self.objectives[fidelity].values()) + list(self.constraints[fidelity].values())
+    def _routed_search(self, fidelity, n_searches, engine_cls, cache_name):
+        """(engine, raw-candidate group) of ``fidelity`` when its ``n_searches`` searches of num_restarts rows each (None: the one
+        coupled search) can stay on the GPU -- the condition under which ``coupled_acq`` evaluates through a one-launch group, and a group fits
+        T = n_searches x num_restarts and the raw candidates, whole or in up to ``MAX_RAW_CHUNKS`` equal chunks (200 candidates
+        x 25 samples are beyond the kernels' 4096 columns); or, where no one-launch group fits, frozen-chain groups do
+        (128 < M <= 1024: the raw candidates whole, no column limit there) -- else None: M > 1024, S = 1, sharded surrogates,
+        CPU tensors keep the host loop.  A group holds 1 + K models per black-box: more than 2 MOBOCMF_ACQ_MAX_PAIRS models or
+        MOBOCMF_TOPK_MAX_N rows keep the host loop too (the coupled search at K = 1 leaves that to the group's constructor, as
+        ever).  ``engine_cls`` (util/acq_search.py) is built once per fidelity and group in the cache ``cache_name``."""
+        from .. import _lib
+        jess = [j for _, _, j in self._boxes(fidelity)]
         bounds = self.standard_bounds
         if not (self.use_tiny_step and jess and bounds is not None and bounds.is_cuda and parallel.world()[1] == 1):
             return None
-        K = self.num_pareto_samples
-        if K > 1:
-            from .. import _lib
-            if len(jess) * (1 + K) > 2 * _lib.ACQ_MAX_PAIRS:
-                return None
-        d = bounds.shape[1]
-        if self.num_restarts > self.raw_samples:
+        K, R = self.num_pareto_samples, self.num_restarts
+        rows = (n_searches or 1) * R
+        if (K > 1 or n_searches) and len(jess) * (1 + K) > 2 * _lib.ACQ_MAX_PAIRS:
             return None
-        grp = self._tiny_group(jess, fidelity, self.num_restarts, d)
+        if R > self.raw_samples or (n_searches and rows > _lib.TOPK_MAX_N):
+            return None
+        d = bounds.shape[1]
+        grp = self._tiny_group(jess, fidelity, rows, d)
         if grp is None:
-            grp = self._panel_group(jess, fidelity, self.num_restarts, d, True)
+            grp = self._panel_group(jess, fidelity, rows, d, True)
             raw = None if grp is None else self._panel_group(jess, fidelity, self.raw_samples, d, False)
         else:
             chunks = [c for c in range(1, self.MAX_RAW_CHUNKS + 1) if self.raw_samples % c == 0]
@@ -357,36 +363,52 @@ class JESMOC_MFDGP:
                        None)
         if raw is None:
             return None
-        cache = self.__dict__.setdefault("_device_searches", {})
+        cache = self.__dict__.setdefault(cache_name, {})
         if fidelity not in cache or cache[fidelity].group is not grp:
-            from ..util.acq_search import DeviceAcqSearch
-            cache[fidelity] = DeviceAcqSearch(grp, bounds, self.num_restarts, self.search_lr, num_pareto_samples=K)
+            cache[fidelity] = engine_cls(grp, bounds, R, self.search_lr, num_pareto_samples=K)
         return cache[fidelity], raw
 
-    def _optimize(self, fidelity, **kw):
-        """(candidate (1, d), value) of the search at ``fidelity``; ``self.last_search_engine[fidelity]`` says where it ran."""
+    def _device_search(self, fidelity):
+        """(DeviceAcqSearch, raw-candidate group) of the coupled search of ``fidelity``, or None: the host engine."""
+        from ..util.acq_search import DeviceAcqSearch
+        return self._routed_search(fidelity, None, DeviceAcqSearch, "_device_searches")
+
+    def _search(self, fidelity, maxiter, generator, decoupled):
+        """[(candidate (1, d), value)] of the searches at ``fidelity`` from ONE draw of raw candidates: the coupled search, or
+        (``decoupled``) every black-box's own term in the order of ``_boxes``.  ``self.last_search_engine[fidelity]`` says where
+        they ran."""
         if self.search not in ("host", "device"):
             raise ValueError("search must be 'host' or 'device' (got %r)" % (self.search,))
         engines = self.__dict__.setdefault("last_search_engine", {})
-        generator, maxiter = kw.get("generator"), kw.get("maxiter", 200)
+        boxes = self._boxes(fidelity)
         with contextlib.ExitStack() as stack:       # fitted models: freeze every surrogate's chain for the whole search
-            for jes in list(self.objectives[fidelity].values()) + list(self.constraints[fidelity].values()):
+            for _, _, jes in boxes:
                 stack.enter_context(jes.frozen())
             stack.enter_context(self._frozen_groups())      # (its exit thaws the groups: an abandoned in-launch wait raises there)
-            found = self._device_search(fidelity) if self.search == "device" else None
-            if found is not None:
-                engine, raw = found
-                lo, hi = self.standard_bounds[0], self.standard_bounds[1]
-                with torch.no_grad():      # the draw of the host engine: both engines see the same points
-                    Xraw = lo + (hi - lo) * torch.rand(self.raw_samples, lo.numel(), dtype=lo.dtype, device=lo.device,
-                                                       generator=generator)
+            route = self._decoupled_device_search if decoupled else self._device_search
+            found = route(fidelity) if self.search == "device" else None
+            lo, hi = self.standard_bounds[0], self.standard_bounds[1]
+            with torch.no_grad():      # the draw of optimize_acqf_multistart: both engines see the same points
+                Xraw = lo + (hi - lo) * torch.rand(self.raw_samples, lo.numel(), dtype=lo.dtype, device=lo.device,
+                                                   generator=generator)
+                if found is not None:
+                    engine, raw = found
                     engine.start_from_raw(raw, Xraw)
                     engines[fidelity] = "device"
-                    return engine.run(None, maxiter)
+                    cands, vals = engine.run(None, maxiter)
+                    return [(cands[p:p + 1], v) for p, v in enumerate(vals.reshape(-1))]
             engines[fidelity] = "host"
-            return optimize_acqf_multistart(lambda x: self.coupled_acq(x, fidelity=fidelity), self.standard_bounds,
-                                            num_restarts=self.num_restarts, raw_samples=self.raw_samples, maxiter=maxiter,
-                                            lr=self.search_lr, generator=generator)
+            if decoupled:
+                acqs = [lambda x, p=p, name=name, con=con: self._box_acq(x, fidelity, p, name, con)
+                        for p, (name, con, _) in enumerate(boxes)]
+            else:
+                acqs = [lambda x: self.coupled_acq(x, fidelity=fidelity)]
+            return [optimize_acqf_multistart(fn, self.standard_bounds, num_restarts=self.num_restarts, raw_samples=self.raw_samples,
+                                             maxiter=maxiter, lr=self.search_lr, Xraw=Xraw) for fn in acqs]
+
+    def _optimize(self, fidelity, **kw):
+        """(candidate (1, d), value) of the coupled search at ``fidelity``."""
+        return self._search(fidelity, kw.get("maxiter", 200), kw.get("generator"), False)[0]
 
     def _get_nextpoint_coupled_highest_fidelity(self, iteration=None, verbose=False, maxiter=200, generator=None):
         """Reference name (:137-149): search the highest fidelity only."""
@@ -404,25 +426,25 @@ class JESMOC_MFDGP:
         finally:
             self.eval_highest_fidelity = keep
 
-    def _pick_on_host(self, found):
-        """``found``: [(candidate, value, fidelity, cost)] with the winners still on the device.  ONE read fetches them all and the
-        info words of every model the device engine ran (``last_search_values``: fidelity -> value); the weighting and the choice
-        are the arithmetic of the loop in ``get_nextpoint_coupled`` on host doubles.  Returns (w, candidate, fidelity)."""
+    def _pick_on_host(self, found, cache_name):
+        """``found``: [(candidate, value, cost, key)], key = (fidelity, ...), with the winners still on the device.  ONE read
+        fetches them all and the info words of every model the device engines of ``cache_name`` ran; the weighting and the
+        choice are the arithmetic of the loop in ``get_nextpoint_coupled`` on host doubles (the largest value / cost, ties to
+        the earlier).  Returns ((w, candidate, key), {key: value})."""
         from ..util.acq_search import raise_on_info
         vals = torch.stack([v.detach().reshape(()).double() for _, v, _, _ in found])
-        searches = self.__dict__.get("_device_searches", {})
-        ran = [f for _, _, f, _ in found if self.last_search_engine.get(f) == "device"]
+        searches = self.__dict__.get(cache_name, {})
+        ran = [f for f in dict.fromkeys(key[0] for _, _, _, key in found) if self.last_search_engine.get(f) == "device"]
         infos = [searches[f].info_words() for f in ran]
         host, words = _read_once(vals, torch.cat(infos) if infos else None)
         if words is not None:
             raise_on_info(words, "device acquisition search")
         best = None
-        self.last_search_values = {fidelity: float(host[k]) for k, (_, _, fidelity, _) in enumerate(found)}
-        for k, (cand, _, fidelity, cost) in enumerate(found):
+        for k, (cand, _, cost, key) in enumerate(found):
             w = float(host[k]) / cost
             if best is None or best[0] < w:
-                best = (w, cand, fidelity)
-        return best
+                best = (w, cand, key)
+        return best, {key: float(host[k]) for k, (_, _, _, key) in enumerate(found)}
 
     def get_nextpoint_coupled(self, iteration=None, verbose=False, maxiter=200, generator=None):
         """Next point + fidelity by cost-weighted acquisition (:137-184).  ``generator``: the raw candidates' draw."""
@@ -432,14 +454,15 @@ class JESMOC_MFDGP:
             cand, val = self._optimize(fidelity, maxiter=maxiter, generator=generator)
             cost = self.costs_blackboxes[0 if self.eval_highest_fidelity else fidelity]["total"]
             if self.search == "device":      # the winners stay on the device until every fidelity is done
-                found.append((cand, val, fidelity, cost))
+                found.append((cand, val, cost, (fidelity,)))
                 continue
             w = val / cost
             if best is None or best[0] < w:
-                best = (w, cand, fidelity)
+                best = (w, cand, (fidelity,))
         if found:
-            best = self._pick_on_host(found)
-        w, cand, fidelity = best
+            best, values = self._pick_on_host(found, "_device_searches")
+            self.last_search_values = {f: v for (f,), v in values.items()}
+        w, cand, (fidelity,) = best
         if not parallel._no_group():     # sharded: every rank returns rank 0's choice (ties may break by an ulp)
             dec = torch.cat([cand.reshape(-1).detach().double(), torch.tensor([float(fidelity)], dtype=torch.float64,
                                                                              device=cand.device)])
@@ -460,80 +483,27 @@ class JESMOC_MFDGP:
     def _box_acq(self, X, fidelity, p, blackbox_name, is_constraint):
         """Black-box p's own term at X: through the predict group ``coupled_acq`` would evaluate through, else ``decoupled_acq``."""
         X = X.double()
-        jess = [j for _, _, j in self._boxes(fidelity)]
-        if self.use_tiny_step and jess and X.is_cuda and parallel.world()[1] == 1:
-            X2 = X[:, 0, :] if X.dim() > 2 else X
-            grp = self._tiny_group(jess, fidelity, X2.shape[0], X2.shape[1])
-            if grp is not None:
-                if self._search_running:
-                    grp.freeze()
-                _, v = grp.acquisition_moments(X2)
-                return self._group_box_value(v, p)
+        v = self._group_v(X, fidelity)
+        if v is not None:
+            return self._group_box_value(v, p)
         return self.decoupled_acq(X, fidelity, blackbox_name, is_constraint=is_constraint)
 
     def _decoupled_device_search(self, fidelity):
         """(DecoupledDeviceAcqSearch, raw-candidate group) under the routing of ``_device_search``, the search group built for
         (black-boxes) x num_restarts test points; None: the host engine.  Cached apart from the coupled searches."""
-        from .. import _lib
-        jess = [j for _, _, j in self._boxes(fidelity)]
-        bounds = self.standard_bounds
-        if not (self.use_tiny_step and jess and bounds is not None and bounds.is_cuda and parallel.world()[1] == 1):
-            return None
-        K, B, R = self.num_pareto_samples, len(jess), self.num_restarts
-        if B * (1 + K) > 2 * _lib.ACQ_MAX_PAIRS or B * R > _lib.TOPK_MAX_N or R > self.raw_samples:
-            return None
-        d = bounds.shape[1]
-        grp = self._tiny_group(jess, fidelity, B * R, d)
-        if grp is None:
-            grp = self._panel_group(jess, fidelity, B * R, d, True)
-            raw = None if grp is None else self._panel_group(jess, fidelity, self.raw_samples, d, False)
-        else:
-            chunks = [c for c in range(1, self.MAX_RAW_CHUNKS + 1) if self.raw_samples % c == 0]
-            raw = next((g for g in (self._tiny_group(jess, fidelity, self.raw_samples // c, d) for c in chunks) if g is not None),
-                       None)
-        if raw is None:
-            return None
-        cache = self.__dict__.setdefault("_decoupled_searches", {})
-        if fidelity not in cache or cache[fidelity].group is not grp:
-            from ..util.acq_search import DecoupledDeviceAcqSearch
-            cache[fidelity] = DecoupledDeviceAcqSearch(grp, bounds, R, self.search_lr, num_pareto_samples=K)
-        return cache[fidelity], raw
+        from ..util.acq_search import DecoupledDeviceAcqSearch
+        return self._routed_search(fidelity, len(self._boxes(fidelity)), DecoupledDeviceAcqSearch, "_decoupled_searches")
 
     def _optimize_decoupled(self, fidelity, maxiter=200, generator=None):
         """[(candidate (1, d), value)] per black-box of ``fidelity`` in the order of ``_boxes``: every box's own term maximised
-        from ONE draw of raw candidates (the draw of ``_optimize``).  ``self.last_search_engine[fidelity]`` says where it ran."""
-        if self.search not in ("host", "device"):
-            raise ValueError("search must be 'host' or 'device' (got %r)" % (self.search,))
-        engines = self.__dict__.setdefault("last_search_engine", {})
-        boxes = self._boxes(fidelity)
-        lo, hi = self.standard_bounds[0], self.standard_bounds[1]
-        with contextlib.ExitStack() as stack:
-            for _, _, jes in boxes:
-                stack.enter_context(jes.frozen())
-            stack.enter_context(self._frozen_groups())
-            found = self._decoupled_device_search(fidelity) if self.search == "device" else None
-            with torch.no_grad():
-                Xraw = lo + (hi - lo) * torch.rand(self.raw_samples, lo.numel(), dtype=lo.dtype, device=lo.device,
-                                                   generator=generator)
-            if found is not None:
-                engine, raw = found
-                with torch.no_grad():
-                    engine.start_from_raw(raw, Xraw)
-                    engines[fidelity] = "device"
-                    cands, vals = engine.run(None, maxiter)
-                return [(cands[p:p + 1], vals[p]) for p in range(len(boxes))]
-            engines[fidelity] = "host"
-            return [optimize_acqf_multistart(lambda x, p=p, name=name, con=con: self._box_acq(x, fidelity, p, name, con),
-                                             self.standard_bounds, num_restarts=self.num_restarts, raw_samples=self.raw_samples,
-                                             maxiter=maxiter, lr=self.search_lr, Xraw=Xraw)
-                    for p, (name, con, _) in enumerate(boxes)]
+        from ONE draw of raw candidates (the draw of ``_optimize``)."""
+        return self._search(fidelity, maxiter, generator, True)
 
     def get_nextpoint_decoupled(self, iteration=None, verbose=False, maxiter=200, generator=None):
         """Which black-box to evaluate next, where and at which fidelity: every registered (fidelity, black-box) has its own JES
         term maximised (``search``: on the host, or all black-boxes of a fidelity at once on the GPU), the value is weighed by
         1 / costs_blackboxes[fidelity][name], the largest wins, ties to the earlier (fidelity, black-box).  Returns
         (x (d,), fidelity, blackbox_name, is_constraint); ``last_decoupled_values[(fidelity, name)]``: the unweighted values."""
-        from ..util.acq_search import raise_on_info
         if not parallel._no_group():
             raise ValueError("get_nextpoint_decoupled is limited to one process (surrogates sharded over a process group have "
                              "get_nextpoint_coupled)")
@@ -544,22 +514,12 @@ class JESMOC_MFDGP:
             if not boxes:
                 continue
             res = self._optimize_decoupled(fidelity, maxiter=maxiter, generator=generator)
-            found += [(cand, val, fidelity, name, con) for (cand, val), (name, con, _) in zip(res, boxes)]
+            found += [(cand, val, self.costs_blackboxes[fidelity][name], (fidelity, name, con))
+                      for (cand, val), (name, con, _) in zip(res, boxes)]
         if not found:
             raise ValueError("get_nextpoint_decoupled: no black-box registered (add_blackbox)")
-        vals = torch.stack([v.detach().reshape(()).double() for _, v, _, _, _ in found])
-        searches = self.__dict__.get("_decoupled_searches", {})
-        infos = [searches[f].info_words() for f in fids if self.last_search_engine.get(f) == "device" and f in searches]
-        host, words = _read_once(vals, torch.cat(infos) if infos else None)      # the one read of the device
-        if words is not None:
-            raise_on_info(words, "device acquisition search")
-        self.last_decoupled_values = {(f, name): float(host[k]) for k, (_, _, f, name, _) in enumerate(found)}
-        best = None
-        for k, (cand, _, fidelity, name, con) in enumerate(found):
-            w = float(host[k]) / self.costs_blackboxes[fidelity][name]
-            if best is None or best[0] < w:
-                best = (w, cand, fidelity, name, con)
-        w, cand, fidelity, name, con = best
+        (w, cand, (fidelity, name, con)), values = self._pick_on_host(found, "_decoupled_searches")      # the one read of the device
+        self.last_decoupled_values = {(f, n): v for (f, n, _), v in values.items()}
         if verbose:
             print("Iter:", iteration, "Acquisition:", float(w * self.costs_blackboxes[fidelity][name]), " Evaluating",
                   "constraint" if con else "objective", name, "at fidelity", fidelity, "at", cand[0].cpu().numpy())

@@ -32,23 +32,46 @@ __device__ __forceinline__ double as_model_v(const double* __restrict__ mean, co
     return s2 / S - sm * sm;
 }
 
+enum { JES_COUPLED = 0, JES_ALL_BOXES = 1, JES_SELECTED_BOX = 2 };
+
+// Black-box p's term from the parked terms of its K conditioned models (u = p (1 + K): its unconditioned model): the k-sum in
+// the order of k, then the product with 1 / K, ROUNDED -- nothing is fused onto it, here or where the caller adds it.
+__device__ __forceinline__ double as_box_term(const double* s_term, int u, int K) {
+#pragma clang fp contract(off)
+    const double inv_k = 1.0 / K;
+    double box = s_term[u + 1];
+    for (int k = 2; k <= K; ++k) box += s_term[u + k];
+    return inv_k * box;
+}
+
 // JES averaged over K sampled Pareto sets: black-box p owns the 1 + K consecutive models p (1 + K) (unconditioned) and
 // p (1 + K) + 1 + k (conditioned on sample k).  ONE wavefront per test point (the replayed iterate has T = 5: one thread per test
 // point would leave five lanes looping over every model and sample): lane m forms v and mbar of model m and parks log v in
-// LDS; the lane of a conditioned model forms its term and whether the clamp passes; lane 0 sums the terms in (p, k) order while
-// every lane writes its own model's seeds.  No atomics, static LDS only.  At K = 1 (mobocmf_jes_group_forward) 1.0 * the single
-// term and 0.5 / (1 * v) are exact: the pair expression 0.5 max(log v_u - log v_c, 0) of the public header, bit for bit.
+// LDS; the lane of a conditioned model forms its term and whether the clamp passes.  Who sums and what is written is the MODE:
+//   JES_COUPLED (mobocmf_jes_mc_group_forward): lane 0 adds the box terms from 0.0 in the order of p into acq[t] and tracks; every
+//   lane writes its own model's seeds.  At K = 1 (mobocmf_jes_group_forward) 1.0 * the single term and 0.5 / (1 * v) are exact:
+//   the pair expression 0.5 max(log v_u - log v_c, 0) of the public header, bit for bit;
+//   JES_ALL_BOXES (mobocmf_jes_mc_box_forward, box_of_point NULL): the lane of the unconditioned model of box p writes
+//   acq[p acq_ld + t] = term_p[t]; no seeds, no tracking (the host refuses them);
+//   JES_SELECTED_BOX (the replayed decoupled iterate): b = box_of_point[t]; the lane of box b's unconditioned model writes acq[t]
+//   and tracks; the 1 + K models of box b get the coupled seeds (a model's seeds depend on its own box only), EVERY other
+//   model's seeds at the columns of t are written as 0.0 (the STEP_INPUT_GRADIENTS launch that follows reads them all);
+//   b outside [0, n_boxes): acq[t] = NaN, every seed 0.0, nothing tracked.
+// The box term is one expression (as_box_term) and the coupled sum adds it rounded: P1 - P3 of the public header hold by
+// construction.  No atomics, static LDS only, every thread reaches every barrier (the grid is T workgroups).
+template <int MODE>
 __global__ void __launch_bounds__(AS_WAVE)
-jes_mc_group_kernel(const double* __restrict__ moments, const double* __restrict__ noise, int n_boxes, int K, int T, int S,
-                    double* __restrict__ acq, double* __restrict__ seeds, const double* __restrict__ x, int d,
-                    double* __restrict__ best_v, double* __restrict__ best_x) {
+jes_kernel(const double* __restrict__ moments, const double* __restrict__ noise, int n_boxes, int K, int T, int S,
+           double* __restrict__ acq, double* __restrict__ seeds, const double* __restrict__ x, int d,
+           double* __restrict__ best_v, double* __restrict__ best_x, const int* __restrict__ box_of_point, int acq_ld) {
     __shared__ double s_lv[AS_WAVE], s_term[AS_WAVE];
     __shared__ int s_pass[AS_WAVE], s_win;
-    const int t = blockIdx.x, m = threadIdx.x;      // (the grid is T workgroups: every thread reaches every barrier)
+    const int t = blockIdx.x, m = threadIdx.x;
     const int stride = 1 + K, n_models = n_boxes * stride;
     const int64_t ncol = (int64_t)T * S, c0 = (int64_t)t * S;
     const bool mine = m < n_models;
     const int p = m / stride, k1 = m % stride;      // k1 = 0: the unconditioned model of box p; else sample k1 - 1
+    const int b = MODE == JES_SELECTED_BOX ? box_of_point[t] : -1;
     const double* mu = moments + (int64_t)m * 2 * ncol;
     double v = 0.0, bar = 0.0;
     if (mine) {
@@ -62,99 +85,34 @@ jes_mc_group_kernel(const double* __restrict__ moments, const double* __restrict
         s_pass[m] = diff >= 0.0;                           // torch.clamp's backward (a NaN passes nothing)
     }
     __syncthreads();
-    if (m == 0) {
+    if (MODE == JES_COUPLED ? m == 0 : mine && k1 == 0 && (MODE == JES_ALL_BOXES || p == b)) {
 #pragma clang fp contract(off)      // (1/K) * (the box's sum) is rounded before it is added, as the restatement has it
-        const double inv_k = 1.0 / K;
-        double a = 0.0;
-        for (int q = 0; q < n_boxes; ++q) {
-            double box = s_term[q * stride + 1];
-            for (int k = 2; k <= K; ++k) box += s_term[q * stride + k];
-            a += inv_k * box;
-        }
-        acq[t] = a;
-        int win = 0;
-        if (best_v && a > best_v[t]) {      // strict; a NaN never wins
-            best_v[t] = a;
-            win = 1;
-        }
-        s_win = win;
-    }
-    if (seeds && mine) {
-        double g;
-        if (k1 > 0) {
-            g = s_pass[m] ? -0.5 / (K * v) : 0.0;
+        double a;
+        if constexpr (MODE == JES_COUPLED) {
+            a = 0.0;
+            for (int q = 0; q < n_boxes; ++q) a += as_box_term(s_term, q * stride, K);
         } else {
-            int cnt = 0;
-            for (int k = 1; k <= K; ++k) cnt += s_pass[m + k];
-            g = cnt > 0 ? cnt * (0.5 / (K * v)) : 0.0;
+            a = as_box_term(s_term, m, K);
         }
-        const double inv_s = 1.0 / S;
-        double* sm = seeds + (int64_t)m * 2 * ncol;
-        for (int s = 0; s < S; ++s) {
-            sm[c0 + s] = g * (2.0 * (mu[c0 + s] - bar) / S);
-            sm[ncol + c0 + s] = g * inv_s;
-        }
-    }
-    __syncthreads();
-    if (s_win && m < d) best_x[(int64_t)t * d + m] = x[(int64_t)t * d + m];
-}
-
-// JES per black-box (the decoupled setting: which black-box is evaluated next).  The layout, v, mbar, diff and the expressions
-// of term and seeds are those of jes_mc_group_kernel; what differs is who sums and what is written.  The lane of the
-// UNCONDITIONED model of box p sums that box's K terms in the order of k and rounds the product with 1 / K:
-//   box_of_point == nullptr (all boxes): acq[p acq_ld + t] = term_p[t] for every p; no seeds, no tracking (the host refuses them);
-//   else (the replayed iterate): b = box_of_point[t]; the lane of box b writes acq[t] and tracks; the 1 + K models of box b get
-//   the coupled kernel's seeds (a model's seeds there depend on its own box only), EVERY other model's seeds at the columns of t
-//   are written as 0.0 (the STEP_INPUT_GRADIENTS launch that follows reads them all); b outside [0, n_boxes): acq[t] = NaN,
-//   every seed 0.0, nothing tracked.
-// One wavefront per test point, a lane per model, static LDS, no atomics.
-__global__ void __launch_bounds__(AS_WAVE)
-jes_mc_box_kernel(const double* __restrict__ moments, const double* __restrict__ noise, int n_boxes, int K, int T, int S,
-                  const int* __restrict__ box_of_point, double* __restrict__ acq, int acq_ld, double* __restrict__ seeds,
-                  const double* __restrict__ x, int d, double* __restrict__ best_v, double* __restrict__ best_x) {
-    __shared__ double s_lv[AS_WAVE], s_term[AS_WAVE];
-    __shared__ int s_pass[AS_WAVE], s_win;
-    const int t = blockIdx.x, m = threadIdx.x;      // (the grid is T workgroups: every thread reaches every barrier)
-    const int stride = 1 + K, n_models = n_boxes * stride;
-    const int64_t ncol = (int64_t)T * S, c0 = (int64_t)t * S;
-    const bool mine = m < n_models;
-    const int p = m / stride, k1 = m % stride;      // k1 = 0: the unconditioned model of box p; else sample k1 - 1
-    const bool all = box_of_point == nullptr;
-    const int b = all ? -1 : box_of_point[t];
-    const double* mu = moments + (int64_t)m * 2 * ncol;
-    double v = 0.0, bar = 0.0;
-    if (m == 0) s_win = 0;
-    if (mine) {
-        v = as_model_v(mu, mu + ncol, noise[m], c0, S, &bar);
-        s_lv[m] = log(v);
-    }
-    __syncthreads();
-    if (mine && k1 > 0) {
-        const double diff = s_lv[p * stride] - s_lv[m];
-        s_term[m] = 0.5 * (diff < 0.0 ? 0.0 : diff);      // (a NaN stays a NaN, as torch.clamp)
-        s_pass[m] = diff >= 0.0;                           // torch.clamp's backward (a NaN passes nothing)
-    }
-    __syncthreads();
-    if (mine && k1 == 0 && (all || p == b)) {
-#pragma clang fp contract(off)      // (1/K) * (the box's sum) is rounded: the coupled kernel's summand, bit for bit
-        const double inv_k = 1.0 / K;
-        double box = s_term[m + 1];
-        for (int k = 2; k <= K; ++k) box += s_term[m + k];
-        const double a = inv_k * box;
-        if (all) {
+        if constexpr (MODE == JES_ALL_BOXES) {
             acq[(int64_t)p * acq_ld + t] = a;
         } else {
             acq[t] = a;
+            int win = 0;
             if (best_v && a > best_v[t]) {      // strict; a NaN never wins
                 best_v[t] = a;
-                s_win = 1;
+                win = 1;
             }
+            s_win = win;      // (whoever writes acq[t] says whether it won: one lane per test point)
         }
     }
-    if (!all && m == 0 && (b < 0 || b >= n_boxes)) acq[t] = __builtin_nan("");      // (no lane above has p == b)
-    if (seeds && mine) {
+    if (MODE == JES_SELECTED_BOX && m == 0 && (b < 0 || b >= n_boxes)) {      // (no lane above has p == b)
+        acq[t] = __builtin_nan("");
+        s_win = 0;
+    }
+    if (MODE != JES_ALL_BOXES && seeds && mine) {
         double* sm = seeds + (int64_t)m * 2 * ncol;
-        if (p == b) {
+        if (MODE == JES_COUPLED || p == b) {
             double g;
             if (k1 > 0) {
                 g = s_pass[m] ? -0.5 / (K * v) : 0.0;
@@ -176,7 +134,7 @@ jes_mc_box_kernel(const double* __restrict__ moments, const double* __restrict__
         }
     }
     __syncthreads();
-    if (s_win && m < d) best_x[(int64_t)t * d + m] = x[(int64_t)t * d + m];
+    if (MODE != JES_ALL_BOXES && s_win && m < d) best_x[(int64_t)t * d + m] = x[(int64_t)t * d + m];
 }
 
 // One workgroup.  Every thread reads the step count, the workgroup meets, thread 0 advances it: no trailing launch.
@@ -257,6 +215,25 @@ select_topk_kernel(const double* __restrict__ vals, int n, int k, const double* 
     }
 }
 
+// The checks and the launch of the three JES entry points (the per-box one adds what the all-box mode refuses).
+int jes_launch(int mode, const double* moments, const double* noise, int32_t n_boxes, int32_t K, int32_t T, int32_t S,
+               const int32_t* box_of_point, double* acq, int32_t acq_ld, int32_t want_seeds, double* seeds, int32_t track,
+               const double* x, int32_t d, double* best_v, double* best_x, mobocmf_stream_t stream) {
+    if (!moments || !noise || !acq || n_boxes < 1 || K < 1 || T < 1 || S < 1) return MOBOCMF_BAD_ARG;
+    if ((int64_t)n_boxes * (1 + (int64_t)K) > 2 * MOBOCMF_ACQ_MAX_PAIRS) return MOBOCMF_BAD_ARG;      // one lane per model
+    if ((int64_t)T * S > MOBOCMF_ACQ_MAX_COLUMNS) return MOBOCMF_BAD_ARG;
+    if (want_seeds < 0 || want_seeds > 1 || track < 0 || track > 1 || (want_seeds && !seeds)) return MOBOCMF_BAD_ARG;
+    if (track && (!x || !best_v || !best_x || d < 1 || d > MOBOCMF_MAX_D)) return MOBOCMF_BAD_ARG;
+    if (mode == JES_ALL_BOXES && (acq_ld < T || want_seeds || track)) return MOBOCMF_BAD_ARG;
+    static_assert(2 * MOBOCMF_ACQ_MAX_PAIRS <= AS_WAVE && MOBOCMF_MAX_D <= AS_WAVE, "one lane per model, one per coordinate");
+    const auto kernel = mode == JES_COUPLED ? jes_kernel<JES_COUPLED>
+                                            : mode == JES_ALL_BOXES ? jes_kernel<JES_ALL_BOXES> : jes_kernel<JES_SELECTED_BOX>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)T), dim3(AS_WAVE), 0, (hipStream_t)stream, moments, noise, n_boxes, K, T, S,
+                       acq, want_seeds ? seeds : (double*)nullptr, x, track ? d : 0, track ? best_v : (double*)nullptr, best_x,
+                       (const int*)box_of_point, acq_ld);
+    return CHECK_LAUNCH();
+}
+
 }  // namespace
 
 extern "C" {
@@ -264,16 +241,8 @@ extern "C" {
 int mobocmf_jes_mc_group_forward(const double* moments, const double* noise, int32_t n_boxes, int32_t K, int32_t T, int32_t S,
                                  double* acq, int32_t want_seeds, double* seeds, int32_t track, const double* x, int32_t d,
                                  double* best_v, double* best_x, mobocmf_stream_t stream) {
-    if (!moments || !noise || !acq || n_boxes < 1 || K < 1 || T < 1 || S < 1) return MOBOCMF_BAD_ARG;
-    if ((int64_t)n_boxes * (1 + (int64_t)K) > 2 * MOBOCMF_ACQ_MAX_PAIRS) return MOBOCMF_BAD_ARG;      // one lane per model
-    if ((int64_t)T * S > MOBOCMF_ACQ_MAX_COLUMNS) return MOBOCMF_BAD_ARG;
-    if (want_seeds < 0 || want_seeds > 1 || track < 0 || track > 1 || (want_seeds && !seeds)) return MOBOCMF_BAD_ARG;
-    if (track && (!x || !best_v || !best_x || d < 1 || d > MOBOCMF_MAX_D)) return MOBOCMF_BAD_ARG;
-    static_assert(2 * MOBOCMF_ACQ_MAX_PAIRS <= AS_WAVE && MOBOCMF_MAX_D <= AS_WAVE, "one lane per model, one per coordinate");
-    hipLaunchKernelGGL(jes_mc_group_kernel, dim3((unsigned)T), dim3(AS_WAVE), 0, (hipStream_t)stream, moments, noise, n_boxes, K,
-                       T, S, acq, want_seeds ? seeds : (double*)nullptr, x, track ? d : 0,
-                       track ? best_v : (double*)nullptr, best_x);
-    return CHECK_LAUNCH();
+    return jes_launch(JES_COUPLED, moments, noise, n_boxes, K, T, S, nullptr, acq, 0, want_seeds, seeds, track, x, d, best_v,
+                      best_x, stream);
 }
 
 // The pair form (model 2p unconditioned, 2p + 1 conditioned): K = 1 of the above, whose checks are then this entry point's own
@@ -281,25 +250,17 @@ int mobocmf_jes_mc_group_forward(const double* moments, const double* noise, int
 int mobocmf_jes_group_forward(const double* moments, const double* noise, int32_t n_pairs, int32_t T, int32_t S,
                               double* acq, int32_t want_seeds, double* seeds, int32_t track, const double* x, int32_t d,
                               double* best_v, double* best_x, mobocmf_stream_t stream) {
-    return mobocmf_jes_mc_group_forward(moments, noise, n_pairs, 1, T, S, acq, want_seeds, seeds, track, x, d, best_v, best_x,
-                                        stream);
+    return jes_launch(JES_COUPLED, moments, noise, n_pairs, 1, T, S, nullptr, acq, 0, want_seeds, seeds, track, x, d, best_v,
+                      best_x, stream);
 }
 
-// Per black-box: the coupled entry point's checks, and the all-box mode (box_of_point NULL) writes values alone.
+// Per black-box: the all-box mode (box_of_point NULL) writes values alone.
 int mobocmf_jes_mc_box_forward(const double* moments, const double* noise, int32_t n_boxes, int32_t K, int32_t T, int32_t S,
                                const int32_t* box_of_point, double* acq, int32_t acq_ld, int32_t want_seeds, double* seeds,
                                int32_t track, const double* x, int32_t d, double* best_v, double* best_x,
                                mobocmf_stream_t stream) {
-    if (!moments || !noise || !acq || n_boxes < 1 || K < 1 || T < 1 || S < 1) return MOBOCMF_BAD_ARG;
-    if ((int64_t)n_boxes * (1 + (int64_t)K) > 2 * MOBOCMF_ACQ_MAX_PAIRS) return MOBOCMF_BAD_ARG;      // one lane per model
-    if ((int64_t)T * S > MOBOCMF_ACQ_MAX_COLUMNS) return MOBOCMF_BAD_ARG;
-    if (want_seeds < 0 || want_seeds > 1 || track < 0 || track > 1 || (want_seeds && !seeds)) return MOBOCMF_BAD_ARG;
-    if (track && (!x || !best_v || !best_x || d < 1 || d > MOBOCMF_MAX_D)) return MOBOCMF_BAD_ARG;
-    if (!box_of_point && (acq_ld < T || want_seeds || track)) return MOBOCMF_BAD_ARG;
-    hipLaunchKernelGGL(jes_mc_box_kernel, dim3((unsigned)T), dim3(AS_WAVE), 0, (hipStream_t)stream, moments, noise, n_boxes, K, T,
-                       S, (const int*)box_of_point, acq, acq_ld, want_seeds ? seeds : (double*)nullptr, x, track ? d : 0,
-                       track ? best_v : (double*)nullptr, best_x);
-    return CHECK_LAUNCH();
+    return jes_launch(box_of_point ? JES_SELECTED_BOX : JES_ALL_BOXES, moments, noise, n_boxes, K, T, S, box_of_point, acq, acq_ld,
+                      want_seeds, seeds, track, x, d, best_v, best_x, stream);
 }
 
 int mobocmf_ascent_adam_step(double* x, const double* gx, int32_t n_models, int32_t T, int32_t d, const double* lo,

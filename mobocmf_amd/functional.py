@@ -1472,18 +1472,31 @@ def _on(stream):
     return _stream() if stream is None else ctypes.c_void_p(stream.cuda_stream)
 
 
+def _jes_call(name, moments, noise, dims, acq, tail, seeds, x, best_v, best_x, stream):
+    """The one call of a JES entry point ``name``: moments, noise, ``dims`` (the box count, K where the entry point has one, T,
+    S), ``tail`` (what stands between S and want_seeds: acq, and box_of_point / acq_ld where the entry point has them), then
+    the seeds, the tracking and the stream as every one of them takes them."""
+    lib = _lib.require_device()
+    track = best_v is not None
+    _lib.check(getattr(lib, name)(_ptr(moments), _ptr(noise), *dims, *tail, int(seeds is not None), _ptr(seeds), int(track),
+                                  _ptr(x), x.shape[-1] if track else 0, _ptr(best_v), _ptr(best_x), _on(stream)), name)
+    return acq
+
+
+def _jes_boxes(who, moments, K):
+    """n_boxes of ``moments`` (n_boxes (1 + K), ...); K < 1 is the library's to refuse."""
+    if K >= 1 and moments.shape[0] % (1 + K):
+        raise _lib.MobocmfError("%s: 1 + K models per black-box (got K = %d, %d models)" % (who, K, moments.shape[0]))
+    return moments.shape[0] // max(1 + K, 1)
+
+
 def jes_group_forward(moments, noise, T, S, acq, seeds=None, x=None, best_v=None, best_x=None, stream=None):
     """mobocmf_jes_group_forward: ``acq`` (T,) = the JES value of every test point from a predict group's raw ``moments``
     (2 n_pairs, 2, T S) and ``noise`` (2 n_pairs,); ``seeds`` given: d acq.sum() / d moments written there; ``best_v`` (T,) /
     ``best_x`` (T, d) given: updated from the iterate ``x`` (T, d) where acq[t] > best_v[t].  One launch, everything in place,
     only enqueues (on ``stream``, default the current one): capturable."""
-    lib = _lib.require_device()
-    track = best_v is not None
-    _lib.check(lib.mobocmf_jes_group_forward(_ptr(moments), _ptr(noise), moments.shape[0] // 2, int(T), int(S), _ptr(acq),
-                                             int(seeds is not None), _ptr(seeds), int(track), _ptr(x),
-                                             x.shape[-1] if track else 0, _ptr(best_v), _ptr(best_x), _on(stream)),
-               "mobocmf_jes_group_forward")
-    return acq
+    return _jes_call("mobocmf_jes_group_forward", moments, noise, (moments.shape[0] // 2, int(T), int(S)), acq, (_ptr(acq),),
+                     seeds, x, best_v, best_x, stream)
 
 
 def jes_mc_group_forward(moments, noise, K, T, S, acq, seeds=None, x=None, best_v=None, best_x=None, stream=None):
@@ -1491,16 +1504,10 @@ def jes_mc_group_forward(moments, noise, K, T, S, acq, seeds=None, x=None, best_
     ``noise`` (n_boxes (1 + K),): per black-box its unconditioned surrogate, then the K conditioned ones; ``acq`` (T,) =
     sum_p (1/K) sum_k 0.5 max(log v_u,p - log v_c,pk, 0).  ``seeds``, ``x``, ``best_v``, ``best_x`` as in ``jes_group_forward``;
     with K = 1 the same bits as that.  One launch, only enqueues (on ``stream``, default the current one): capturable."""
-    lib = _lib.require_device()
     K = int(K)
-    if K >= 1 and moments.shape[0] % (1 + K):      # (K < 1 is the library's to refuse)
-        raise _lib.MobocmfError("jes_mc_group_forward: 1 + K models per black-box (got K = %d, %d models)" % (K, moments.shape[0]))
-    track = best_v is not None
-    _lib.check(lib.mobocmf_jes_mc_group_forward(_ptr(moments), _ptr(noise), moments.shape[0] // max(1 + K, 1), K, int(T), int(S),
-                                                _ptr(acq), int(seeds is not None), _ptr(seeds), int(track), _ptr(x),
-                                                x.shape[-1] if track else 0, _ptr(best_v), _ptr(best_x), _on(stream)),
-               "mobocmf_jes_mc_group_forward")
-    return acq
+    n_boxes = _jes_boxes("jes_mc_group_forward", moments, K)
+    return _jes_call("mobocmf_jes_mc_group_forward", moments, noise, (n_boxes, K, int(T), int(S)), acq, (_ptr(acq),), seeds, x,
+                     best_v, best_x, stream)
 
 
 def jes_mc_box_forward(moments, noise, K, T, S, acq, box_of_point=None, seeds=None, x=None, best_v=None, best_x=None, stream=None):
@@ -1510,11 +1517,8 @@ def jes_mc_box_forward(moments, noise, K, T, S, acq, box_of_point=None, seeds=No
     tracking.  ``box_of_point`` (T,) int32 on the device: ``acq`` (T,) = term_b[t] with b = box_of_point[t]; ``seeds`` given: the
     coupled launch's seeds for the models of box b, 0.0 for every other model; ``best_v`` / ``best_x`` / ``x`` as in
     ``jes_group_forward``.  One launch, only enqueues (on ``stream``, default the current one): capturable."""
-    lib = _lib.require_device()
     K, T = int(K), int(T)
-    if K >= 1 and moments.shape[0] % (1 + K):      # (K < 1 is the library's to refuse)
-        raise _lib.MobocmfError("jes_mc_box_forward: 1 + K models per black-box (got K = %d, %d models)" % (K, moments.shape[0]))
-    n_boxes = moments.shape[0] // max(1 + K, 1)
+    n_boxes = _jes_boxes("jes_mc_box_forward", moments, K)
     ld = 0
     if box_of_point is None:
         if acq.dim() == 1:
@@ -1527,12 +1531,8 @@ def jes_mc_box_forward(moments, noise, K, T, S, acq, box_of_point=None, seeds=No
             raise _lib.MobocmfError("jes_mc_box_forward: box_of_point (T,) int32, contiguous")
         if acq.numel() < T:
             raise _lib.MobocmfError("jes_mc_box_forward: acq (T,)")
-    track = best_v is not None
-    _lib.check(lib.mobocmf_jes_mc_box_forward(_ptr(moments), _ptr(noise), n_boxes, K, T, int(S), _ptr(box_of_point), _ptr(acq),
-                                              int(ld), int(seeds is not None), _ptr(seeds), int(track), _ptr(x),
-                                              x.shape[-1] if track else 0, _ptr(best_v), _ptr(best_x), _on(stream)),
-               "mobocmf_jes_mc_box_forward")
-    return acq
+    return _jes_call("mobocmf_jes_mc_box_forward", moments, noise, (n_boxes, K, T, int(S)), acq,
+                     (_ptr(box_of_point), _ptr(acq), int(ld)), seeds, x, best_v, best_x, stream)
 
 
 def ascent_adam_step(x, gx, lo, hi, exp_avg, exp_avg_sq, steps_done, lr, betas=(0.9, 0.999), eps=1e-8, stream=None):

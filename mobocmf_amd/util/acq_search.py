@@ -39,12 +39,17 @@ class DeviceAcqSearch:
     use_graph = True          # False: the same launches issued eagerly (tests, A/B)
     iters_per_graph = 1       # iterates unrolled into one graph (DESIGN.md 5.6 on what tools/acq_search_bench.py reports)
 
-    def __init__(self, group, bounds, num_restarts, lr, betas=(0.9, 0.999), eps=1e-8, num_pareto_samples=1):
+    def __init__(self, group, bounds, num_restarts, lr, betas=(0.9, 0.999), eps=1e-8, num_pareto_samples=1, n_searches=None):
+        """``n_searches`` = B: the engine runs B independent searches of R = ``num_restarts`` rows each, rows [p R, (p + 1) R) of
+        the group's x being search p's (the raw candidates are shared, the restarts and the winner are chosen per search).  None:
+        the coupled search, B = 1, whose results come without the leading axis of the searches."""
         _lib.require_device()
         K = self.K = int(num_pareto_samples)
         if K < 1:
             raise ValueError("DeviceAcqSearch: num_pareto_samples >= 1 (got %d)" % K)
-        if group.T != int(num_restarts) or len(group.models) % (1 + K):
+        B, R = self.B, self.R = int(n_searches or 1), int(num_restarts)
+        self._one = (lambda t: t[0]) if n_searches is None else (lambda t: t)
+        if group.T != B * R or len(group.models) % (1 + K):
             raise _lib.MobocmfError("DeviceAcqSearch: a group of (uncond, cond_1 .. cond_K) per black-box built for T = "
                                     "num_restarts test points")
         if not 1 + K <= len(group.models) <= 2 * _lib.ACQ_MAX_PAIRS:
@@ -60,17 +65,21 @@ class DeviceAcqSearch:
         self.acq, self.best_v, self.best_x = z(T), z(T), z(T, d)
         self.exp_avg, self.exp_avg_sq = z(T, d), z(T, d)
         self.steps_done = torch.zeros(1, dtype=torch.int64, device=dev)
-        self.win_v, self.win_i, self.cand = z(1), torch.zeros(1, dtype=torch.int64, device=dev), z(1, d)
+        self.win_v, self.win_i, self.cand = z(B), torch.zeros(B, dtype=torch.int64, device=dev), z(B, d)
         self._graphs, self._raw = {}, {}
         self._capture_stream = group.stream
 
     # ------------------------------------------------------------------ the launches
+    def _jes(self, grp, noise, acq, **track):
+        """The JES launch on ``grp``'s moments.  ``track`` (seeds, x, best_v, best_x): an iterate, ``acq`` (T,); none: a chunk of
+        raw candidates, ``acq`` (B, chunk) -- here B = 1, the coupled value."""
+        F.jes_mc_group_forward(grp.moments, noise, self.K, grp.T, grp.S, acq, stream=grp.stream, **track)
+
     def _score(self, seeds):
         """The forward launch and the JES kernel on the group's current x: acq, the best iterate so far, optionally the seeds."""
         g = self.group
         g._launch(_lib.STEP_FORWARD)
-        F.jes_mc_group_forward(g.moments, self.noise, self.K, self.T, g.S, self.acq, seeds=g.seeds if seeds else None, x=g.x,
-                               best_v=self.best_v, best_x=self.best_x, stream=g.stream)
+        self._jes(g, self.noise, self.acq, seeds=g.seeds if seeds else None, x=g.x, best_v=self.best_v, best_x=self.best_x)
 
     def _iterate(self):
         """One iterate: four launches (on the group's stream; None: the current one)."""
@@ -100,29 +109,31 @@ class DeviceAcqSearch:
     # ------------------------------------------------------------------ the search
     def start_from_raw(self, raw_group, Xraw):
         """Scores the raw candidates ``Xraw`` (n, d) through ``raw_group`` -- the same models for T = n test points, or for
-        T = n / c: c equal chunks, one forward launch each, where n S columns are beyond the one-launch kernels' limit -- and
-        writes the ``num_restarts`` best rows straight into the search group's x.  Returns (raw values (n,), the restarts'
-        values, their indices): device tensors of this object, overwritten by the next call.  A cooperative ``raw_group`` is
-        left frozen (see the class docstring): the caller thaws it with the search group."""
-        n, Tc = Xraw.shape[0], raw_group.T
-        if n % Tc or len(raw_group.models) != len(self.group.models) or not self.T <= n <= _lib.TOPK_MAX_N:
+        T = n / c: c equal chunks, one forward launch each, where n S columns are beyond the one-launch kernels' limit --
+        ONCE for all B searches (one JES launch per chunk: row p of ``vals`` (B, n) is search p's value at every candidate) and
+        writes each search's R best rows straight into rows [p R, (p + 1) R) of the search group's x, one selection per search.
+        Returns (vals (B, n), the restarts' values (B, R), their indices (B, R)) -- coupled: (n,), (R,), (R,) -- device tensors
+        of this object, overwritten by the next call.  A cooperative ``raw_group`` is left frozen (see the class docstring): the
+        caller thaws it with the search group."""
+        n, Tc, B, R = Xraw.shape[0], raw_group.T, self.B, self.R
+        if n % Tc or len(raw_group.models) != len(self.group.models) or not R <= n <= _lib.TOPK_MAX_N:
             raise _lib.MobocmfError("DeviceAcqSearch: the raw candidates in equal chunks of the raw group's T test points")
         if (n, Tc) not in self._raw:
             dev = self.group.device
-            self._raw[(n, Tc)] = (torch.zeros(n, dtype=torch.float64, device=dev), torch.zeros(self.T, dtype=torch.float64, device=dev),
-                                  torch.zeros(self.T, dtype=torch.int64, device=dev), raw_group.noise().detach().clone().contiguous(),
+            self._raw[(n, Tc)] = (torch.zeros(B, n, dtype=torch.float64, device=dev), torch.zeros(B, R, dtype=torch.float64, device=dev),
+                                  torch.zeros(B, R, dtype=torch.int64, device=dev), raw_group.noise().detach().clone().contiguous(),
                                   torch.zeros(n, self.d, dtype=torch.float64, device=dev))
         vals, top_v, top_i, noise, xraw = self._raw[(n, Tc)]
-        self.raw_group, self.raw_values = raw_group, vals
+        self.raw_group, self.raw_values = raw_group, self._one(vals)
         raw_group.freeze()
         xraw.copy_(Xraw.detach().reshape(n, self.d))
         for c in range(n // Tc):
             raw_group.x.copy_(xraw[c * Tc:(c + 1) * Tc])
             raw_group._launch(_lib.STEP_FORWARD)
-            F.jes_mc_group_forward(raw_group.moments, noise, self.K, Tc, raw_group.S, vals[c * Tc:(c + 1) * Tc],
-                                   stream=raw_group.stream)
-        F.select_topk(vals, self.T, top_v, top_i, x=xraw, out_x=self.group.x, stream=self.group.stream)
-        return vals, top_v, top_i
+            self._jes(raw_group, noise, vals[:, c * Tc:(c + 1) * Tc])
+        for p in range(B):
+            F.select_topk(vals[p], R, top_v[p], top_i[p], x=xraw, out_x=self.group.x[p * R:(p + 1) * R], stream=self.group.stream)
+        return self._one(vals), self._one(top_v), self._one(top_i)
 
     def run(self, x0=None, maxiter=200):
         """``x0`` (num_restarts, d): the starting points (None: what ``start_from_raw`` left in the group's x)."""
@@ -154,9 +165,12 @@ class DeviceAcqSearch:
             return self._winner()
 
     def _winner(self):
-        """The best of the restarts' best iterates: (candidate (1, d), value ()), device tensors."""
-        F.select_topk(self.best_v, 1, self.win_v, self.win_i, x=self.best_x, out_x=self.cand, stream=self.group.stream)
-        return self.cand.clone(), self.win_v[0].clone()
+        """Per search the best of its restarts' best iterates: (candidates (B, d), values (B,) -- coupled: ()), device tensors."""
+        R = self.R
+        for p in range(self.B):
+            F.select_topk(self.best_v[p * R:(p + 1) * R], 1, self.win_v[p:p + 1], self.win_i[p:p + 1],
+                          x=self.best_x[p * R:(p + 1) * R], out_x=self.cand[p:p + 1], stream=self.group.stream)
+        return self.cand.clone(), self._one(self.win_v).clone()
 
     def info_words(self):
         """The Cholesky verdicts of the models of the search group and of the raw-candidate group last used (int32 words, 0:
@@ -174,9 +188,9 @@ class DecoupledDeviceAcqSearch(DeviceAcqSearch):
     over all models is the gradient of the row's own term.  Every model is therefore evaluated at all B R rows though only R
     are its own.
 
-    ``start_from_raw`` scores the raw candidates ONCE for all boxes (the forward launches of the coupled search, then the all-box
-    mode into ``vals`` (B, n)) and picks each box's R best.  ``run`` -> (candidates (B, d), values (B,)), device tensors,
-    without synchronising."""
+    Only the JES launch differs from the coupled engine (``_jes``): ``start_from_raw`` scores the raw candidates ONCE for all
+    boxes (the forward launches of the coupled search, then the all-box mode into ``vals`` (B, n)) and picks each box's R
+    best.  ``run`` -> (candidates (B, d), values (B,)), device tensors, without synchronising."""
 
     def __init__(self, group, bounds, num_restarts, lr, betas=(0.9, 0.999), eps=1e-8, num_pareto_samples=1):
         K, R = int(num_pareto_samples), int(num_restarts)
@@ -189,53 +203,13 @@ class DecoupledDeviceAcqSearch(DeviceAcqSearch):
                                     "(black-boxes) x num_restarts test points")
         if B * R > _lib.TOPK_MAX_N or B * (1 + K) > 2 * _lib.ACQ_MAX_PAIRS:
             raise _lib.MobocmfError("DecoupledDeviceAcqSearch: at most %d rows and %d models" % (_lib.TOPK_MAX_N, 2 * _lib.ACQ_MAX_PAIRS))
-        super().__init__(group, bounds, B * R, lr, betas=betas, eps=eps, num_pareto_samples=K)
-        self.B, self.R = B, R
-        dev = group.device
-        self.box_of_point = torch.div(torch.arange(B * R, device=dev), R, rounding_mode="floor").to(torch.int32).contiguous()
-        self.win_v = torch.zeros(B, dtype=torch.float64, device=dev)
-        self.win_i = torch.zeros(B, dtype=torch.int64, device=dev)
-        self.cand = torch.zeros(B, self.d, dtype=torch.float64, device=dev)
+        super().__init__(group, bounds, R, lr, betas=betas, eps=eps, num_pareto_samples=K, n_searches=B)
+        self.box_of_point = torch.div(torch.arange(B * R, device=group.device), R, rounding_mode="floor").to(torch.int32).contiguous()
 
-    def _score(self, seeds):
-        g = self.group
-        g._launch(_lib.STEP_FORWARD)
-        F.jes_mc_box_forward(g.moments, self.noise, self.K, self.T, g.S, self.acq, box_of_point=self.box_of_point,
-                             seeds=g.seeds if seeds else None, x=g.x, best_v=self.best_v, best_x=self.best_x, stream=g.stream)
-
-    def start_from_raw(self, raw_group, Xraw):
-        """As DeviceAcqSearch.start_from_raw -- the same raw group, chunks and forward launches -- with every chunk scored for all
-        boxes in one launch (row p of ``vals`` (B, n): box p's term at every candidate) and one selection per box writing its R
-        best rows into rows [p R, (p + 1) R) of the search group's x.  Returns (vals (B, n), the restarts' values (B, R), their
-        indices (B, R))."""
-        n, Tc, B, R = Xraw.shape[0], raw_group.T, self.B, self.R
-        if n % Tc or len(raw_group.models) != len(self.group.models) or not R <= n <= _lib.TOPK_MAX_N:
-            raise _lib.MobocmfError("DecoupledDeviceAcqSearch: the raw candidates in equal chunks of the raw group's T test points")
-        if (n, Tc) not in self._raw:
-            dev = self.group.device
-            self._raw[(n, Tc)] = (torch.zeros(B, n, dtype=torch.float64, device=dev), torch.zeros(B, R, dtype=torch.float64, device=dev),
-                                  torch.zeros(B, R, dtype=torch.int64, device=dev), raw_group.noise().detach().clone().contiguous(),
-                                  torch.zeros(n, self.d, dtype=torch.float64, device=dev))
-        vals, top_v, top_i, noise, xraw = self._raw[(n, Tc)]
-        self.raw_group, self.raw_values = raw_group, vals
-        raw_group.freeze()
-        xraw.copy_(Xraw.detach().reshape(n, self.d))
-        for c in range(n // Tc):
-            raw_group.x.copy_(xraw[c * Tc:(c + 1) * Tc])
-            raw_group._launch(_lib.STEP_FORWARD)
-            F.jes_mc_box_forward(raw_group.moments, noise, self.K, Tc, raw_group.S, vals[:, c * Tc:(c + 1) * Tc],
-                                 stream=raw_group.stream)
-        for p in range(B):
-            F.select_topk(vals[p], R, top_v[p], top_i[p], x=xraw, out_x=self.group.x[p * R:(p + 1) * R], stream=self.group.stream)
-        return vals, top_v, top_i
-
-    def _winner(self):
-        """Per box the best of its restarts' best iterates: (candidates (B, d), values (B,)), device tensors."""
-        R = self.R
-        for p in range(self.B):
-            F.select_topk(self.best_v[p * R:(p + 1) * R], 1, self.win_v[p:p + 1], self.win_i[p:p + 1],
-                          x=self.best_x[p * R:(p + 1) * R], out_x=self.cand[p:p + 1], stream=self.group.stream)
-        return self.cand.clone(), self.win_v.clone()
+    def _jes(self, grp, noise, acq, **track):
+        """An iterate: every row for the box it is searched for; a chunk of raw candidates: every box's term at every row."""
+        F.jes_mc_box_forward(grp.moments, noise, self.K, grp.T, grp.S, acq, box_of_point=self.box_of_point if track else None,
+                             stream=grp.stream, **track)
 
 
 def raise_on_info(words, what):

@@ -150,6 +150,42 @@ def test_one_box_with_zero_words_is_the_coupled_entry_point_bitwise(K, T, S):
     assert bool(torch.isfinite(best["box"][0]).all())
 
 
+@pytest.mark.parametrize("n_boxes,K,T,S", [(2, 4, 5, 4), (3, 2, 9, 1), (1, 63, 3, 2)])
+def test_both_box_modes_reproduce_the_recorded_bits(n_boxes, K, T, S):
+    """tests/golden/jes_kernels_bits.npz (tools/record_jes_pair_golden.py --fixture kernels): three consecutive calls of
+    mobocmf_jes_mc_box_forward, all boxes and the selected box (blocks, tracked), recorded on an MI355X while the per-box and
+    the coupled launch were two kernels.  The regenerated inputs are the stored ones bit for bit; then the all-box rows and
+    the selected mode's acq, best_v and best_x after every call are; the selected mode's seeds are the recorded coupled seeds
+    in the own box (P2) and +0.0 elsewhere."""
+    import os
+
+    import numpy as np
+    from mobocmf_amd import functional as F
+    golden = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "jes_kernels_bits.npz"))
+    d = 3
+    g = torch.Generator().manual_seed(T)
+    box = RB.box_patterns(n_boxes, T)["blocks"]
+    own = (torch.arange(n_boxes * (1 + K))[:, None] // (1 + K) == box[None, :].long())
+    own = own[:, None, :, None].expand(n_boxes * (1 + K), 2, T, S).reshape(n_boxes * (1 + K), 2, T * S)
+    best_v = torch.full((T,), float("-inf"), dtype=torch.float64, device=DEV)
+    best_x = torch.zeros(T, d, dtype=torch.float64, device=DEV)
+    for call in range(3):
+        rec = lambda name: torch.from_numpy(golden["%d_%d_%d_%d/%d/%s" % (n_boxes, K, T, S, call, name)].copy())
+        mom, noise = R.mc_inputs(n_boxes, K, T, S, seed=50 + call, flip=call)
+        x = torch.rand(T, d, dtype=torch.float64, generator=g)
+        for name, t in (("moments", mom), ("noise", noise), ("x", x)):
+            assert torch.equal(_bits(t), rec(name)), (name, call)
+        md, nd = mom.to(DEV), noise.to(DEV)
+        rows, acq, seeds = _nan(n_boxes, T), _nan(T), torch.full_like(md, float("nan"))
+        F.jes_mc_box_forward(md, nd, K, T, S, rows)
+        F.jes_mc_box_forward(md, nd, K, T, S, acq, box_of_point=box.to(DEV), seeds=seeds, x=x.to(DEV), best_v=best_v,
+                             best_x=best_x)
+        for name, got in (("rows", rows), ("box_acq", acq), ("box_best_v", best_v), ("box_best_x", best_x)):
+            assert torch.equal(_bits(got), rec(name)), (name, call)
+        s = _bits(seeds)
+        assert torch.equal(s[own], rec("seeds")[own]) and bool((s[~own] == 0).all()), call
+
+
 def test_out_of_range_word_gives_nan_zero_seeds_and_no_tracking():
     from mobocmf_amd import functional as F
     n_boxes, K, T, S, d = 2, 2, 9, 3, 2

@@ -117,6 +117,36 @@ def test_one_sample_reproduces_the_recorded_pair_kernel(n_pairs, T, S):
     assert moved[0] == T and (T <= 5 or 0 < moved[-1] < T)
 
 
+_KERNELS = os.path.join(os.path.dirname(_GOLDEN), "jes_kernels_bits.npz")
+_kernels = {}
+
+
+@pytest.mark.parametrize("n_boxes,K,T,S", [(2, 4, 5, 4), (3, 2, 9, 1), (1, 63, 3, 2)])
+def test_coupled_launch_reproduces_the_recorded_bits(n_boxes, K, T, S):
+    """tests/golden/jes_kernels_bits.npz (tools/record_jes_pair_golden.py --fixture kernels): three consecutive tracked calls of
+    mobocmf_jes_mc_group_forward at K > 1, recorded on an MI355X while the coupled and the per-box launch were two kernels.
+    The regenerated inputs are the stored ones bit for bit (a drifting generator fails here, not silently); then acq, seeds,
+    best_v and best_x after every call are."""
+    from mobocmf_amd import functional as F
+    if not _kernels:
+        _kernels.update(np.load(_KERNELS))
+    d = 3
+    g = torch.Generator().manual_seed(T)
+    best_v = torch.full((T,), float("-inf"), dtype=torch.float64, device=DEV)
+    best_x = torch.zeros(T, d, dtype=torch.float64, device=DEV)
+    for call in range(3):
+        rec = lambda name: torch.from_numpy(_kernels["%d_%d_%d_%d/%d/%s" % (n_boxes, K, T, S, call, name)].copy())
+        mom, noise = R.mc_inputs(n_boxes, K, T, S, seed=50 + call, flip=call)
+        x = torch.rand(T, d, dtype=torch.float64, generator=g)
+        for name, t in (("moments", mom), ("noise", noise), ("x", x)):
+            assert torch.equal(_bits(t), rec(name)), (name, call)
+        md = mom.to(DEV)
+        acq, seeds = torch.full((T,), float("nan"), dtype=torch.float64, device=DEV), torch.full_like(md, float("nan"))
+        F.jes_mc_group_forward(md, noise.to(DEV), K, T, S, acq, seeds=seeds, x=x.to(DEV), best_v=best_v, best_x=best_x)
+        for name, got in (("acq", acq), ("seeds", seeds), ("best_v", best_v), ("best_x", best_x)):
+            assert torch.equal(_bits(got), rec(name)), (name, call)
+
+
 # ------------------------------------------------------------------ 3. tracking, bad arguments
 def test_jes_mc_group_forward_tracks_the_best_iterate():
     """The three-call scenario of tests/test_hip_acq_search.py: the element-wise larger value and its row stay (strict), the -inf
