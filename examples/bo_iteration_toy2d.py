@@ -122,10 +122,13 @@ if __name__ == "__main__":
                     help="with --iters > 1: warm-start every iteration after the first and train this many phase-2 epochs")
     ap.add_argument("--pareto-samples", type=int, default=1,
                     help="average the JES acquisition over this many sampled Pareto sets (one conditioned fit each)")
+    ap.add_argument("--pareto-search", choices=["grid", "evolve"], default="grid",
+                    help="how the sampled Pareto set is searched: the random grid, or NSGA-II on the GPU started from it")
     a = ap.parse_args()
     if a.warm_epochs is not None and a.iters < 2:
         ap.error("--warm-epochs needs --iters > 1: the first iteration has no predecessor to start from")
     if a.iters > 1:
-        loop(iters=a.iters, seed=a.seed, epochs=a.epochs, warm_epochs=a.warm_epochs, pareto_samples=a.pareto_samples)
+        loop(iters=a.iters, seed=a.seed, epochs=a.epochs, warm_epochs=a.warm_epochs, pareto_samples=a.pareto_samples,
+             model_kwargs={"pareto_search": a.pareto_search})
     else:
-        run(epochs=a.epochs, seed=a.seed, pareto_samples=a.pareto_samples)
+        run(epochs=a.epochs, seed=a.seed, pareto_samples=a.pareto_samples, model_kwargs={"pareto_search": a.pareto_search})

@@ -85,15 +85,16 @@ def score(fitter, grid):
 
 
 def loop_hv(iters=5, acq="jes", seed=0, out_dir=".", epochs=300, verbose=True, num_inducing=None, inducing="first",
-            warm_start=False, warm_epochs=None, pareto_samples=1, **kw):
+            warm_start=False, warm_epochs=None, pareto_samples=1, pareto_search="grid", **kw):
     """``iters`` BO iterations, each one scored and appended to ``out_dir``/hypervolumes.txt; returns the rows.
     ``warm_start``: every iteration after the first starts from the last one's unconditioned fit, ``warm_epochs`` epochs of
-    phase 2 (default: ``epochs``).  ``pareto_samples``: JES averaged over this many sampled Pareto sets."""
+    phase 2 (default: ``epochs``).  ``pareto_samples``: JES averaged over this many sampled Pareto sets.  ``pareto_search``: the fitter's
+    (``"evolve"``: NSGA-II on the GPU from the grid's rows)."""
     warm_epochs = (epochs if warm_epochs is None else warm_epochs) if warm_start else None
     previous = None
-    model_kwargs = {}
+    model_kwargs = {"pareto_search": pareto_search}
     if num_inducing is not None:
-        model_kwargs = dict(num_inducing=num_inducing,
+        model_kwargs.update(num_inducing=num_inducing,
                             inducing_selection="greedy_variance" if inducing == "greedy" else "first")
     rng = np.random.default_rng(seed)
     x = rng.uniform(size=(20, 2))
@@ -147,8 +148,11 @@ if __name__ == "__main__":
                     help="with --warm-start: phase-2 epochs of a warm refit (default: --epochs)")
     ap.add_argument("--pareto-samples", type=int, default=1,
                     help="average the JES acquisition over this many sampled Pareto sets (one conditioned fit each)")
+    ap.add_argument("--pareto-search", choices=["grid", "evolve"], default="grid",
+                    help="how the sampled Pareto set is searched: the random grid, or NSGA-II on the GPU started from it")
     a = ap.parse_args()
     if a.warm_epochs is not None and not a.warm_start:
         ap.error("--warm-epochs needs --warm-start")
     loop_hv(iters=a.iters, acq=a.acq, seed=a.seed, out_dir=a.out, epochs=a.epochs, num_inducing=a.num_inducing,
-            inducing=a.inducing, warm_start=a.warm_start, warm_epochs=a.warm_epochs, pareto_samples=a.pareto_samples)
+            inducing=a.inducing, warm_start=a.warm_start, warm_epochs=a.warm_epochs, pareto_samples=a.pareto_samples,
+            pareto_search=a.pareto_search)

@@ -344,6 +344,82 @@ int mobocmf_hypervolume_workspace_bytes(int32_t k, int64_t P, size_t* bytes);
 int mobocmf_hypervolume(int32_t k, int64_t P, const double* pts, int64_t ldp, const double* ref, double* hv, void* workspace,
                         size_t workspace_bytes, mobocmf_stream_t stream);
 
+/* ------------------------------------------------------------------ NSGA-II over chain samples (csrc/pareto_evolve.hip)
+ * The population logic of an elitist non-dominated-sorting search (Deb et al. 2002) on rows of the box [0, 1]^d whose k
+ * objectives (all minimised) and violation were computed elsewhere (mobocmf_rff_eval_chains / mobocmf_rff_feasibility).
+ * Everything is float64, deterministic and bitwise reproducible across launches: no floating-point atomics, no workgroup
+ * waits on another, every trip count is bounded by the row count.
+ *
+ * mobocmf_nsga_survive ranks n_in rows and keeps n_keep of them.
+ *   Inputs.  X [n_in x d] row-major; F [k x n_in], objective j of row i at F[j * ldf + i] (ldf >= n_in); viol [n_in], the
+ *   violation: >= 0, 0 = feasible (the caller passes MINUS the viol of mobocmf_rff_feasibility; -0.0 is 0); NULL = every row
+ *   is feasible.  A row with a NaN objective or a NaN violation is infeasible with violation +inf.
+ *   Constraint-domination.  Row i dominates row j when (a) i is feasible and j is not, or (b) both are infeasible and
+ *   viol_i < viol_j, or (c) both are feasible, F[c][i] <= F[c][j] for every c and F[c][i] < F[c][j] for some c.  Exactly equal
+ *   rows do not dominate each other.
+ *   Rank = peeling depth: rank 0 holds the rows nobody dominates; remove them and repeat for rank 1, ...
+ *   Crowding, per rank, starts at 0 and takes one term per objective c = 0, 1, ..., k - 1 in that order.  A NaN objective value
+ *   counts as +inf here.  Order the rank's rows by (value, row index); prev / next = the neighbours of a row in that order,
+ *   min / max = the first / last value.  The first and the last row add +inf; an interior row adds
+ *   (next - prev) / (max - min) -- one IEEE subtraction each, one division, then one addition to the running sum -- and adds 0
+ *   when max == min or when the quotient is NaN (inf - inf, inf / inf).
+ *   Survivors = the first n_keep rows under the key (rank ascending, crowding descending, row index ascending); equal
+ *   crowding (+inf == +inf included) falls through to the index.
+ *   Outputs, compacted in key order: X_out [n_keep x d], F_out [k x n_keep] with row stride ldf_out (>= n_keep), viol_out
+ *   [n_keep] (the violation as used: +inf for a NaN row; may be NULL when viol is NULL, else zeros are written), rank_out
+ *   (int32), crowd_out, src_out (int32: the input row a survivor came from).  X_out / F_out / viol_out may BE the inputs (same
+ *   base pointer, ldf_out == ldf): every survivor is read before any is written; any other overlap is not allowed.
+ *   generation: NULL, or a DEVICE int64 word that this launch increments by one after everything else (what
+ *   mobocmf_nsga_vary reads: a captured generation replays with a fresh generation number without the host).
+ *   n_keep == n_in is the "rank only" call.  One launch of one workgroup: the n_in x n_in dominance relation is a bit matrix
+ *   in LDS (128 KB at n_in = 1024), peeled with workgroup barriers; order positions and crowding neighbours by counting.
+ *   MOBOCMF_BAD_ARG (before any launch): k outside 1..MOBOCMF_PARETO_MAX_K, d outside 1..MOBOCMF_MAX_D, not
+ *   2 <= n_keep <= n_in <= MOBOCMF_NSGA_MAX_ROWS, ldf < n_in, ldf_out < n_keep, a NULL X, F, X_out, F_out, rank_out, crowd_out
+ *   or src_out, viol given without viol_out.
+ *
+ * mobocmf_nsga_vary makes Np children (Np even, 2 <= Np <= MOBOCMF_NSGA_MAX_ROWS) from Np ranked parents X [Np x d] with rank /
+ * crowd [Np] (what mobocmf_nsga_survive wrote).  Every uniform is u(s) = philox_uniform(seed, *generation, q * 2^32 + s): the
+ * Philox4x32-10 stream keyed by seed, counter (q * 2^32 + s, *generation), 53 bits -> (0, 1), of mobocmf_propagate_rng_forward;
+ * q = the pair, s = the slot below; *generation is the DEVICE int64 word.  Pair q < Np / 2 gives children 2 q and 2 q + 1.
+ *   Tournament.  Parent e (0, 1) is the better of rows a = min(floor(u(2 e) Np), Np - 1) and b = min(floor(u(2 e + 1) Np),
+ *   Np - 1): a wins when rank_a < rank_b, or the ranks are equal and (crowd_a > crowd_b, or crowd_b is not > crowd_a and
+ *   a <= b); else b.
+ *   Crossover (simulated binary).  The pair crosses when u(4) < p_c; then variable v crosses when u(8 + 8 v) < 0.5, with
+ *   w = u(9 + 8 v), beta = (2 w)^(1 / (eta_c + 1)) for w <= 0.5 else (1 / (2 (1 - w)))^(1 / (eta_c + 1)),
+ *   c0 = 0.5 ((1 + beta) p0 + (1 - beta) p1), c1 = 0.5 ((1 - beta) p0 + (1 + beta) p1).  Otherwise c0 = p0, c1 = p1.
+ *   Mutation (polynomial).  Variable v of child e mutates when u(10 + 8 v + 2 e) < p_m; with w = u(11 + 8 v + 2 e),
+ *   x += (2 w)^(1 / (eta_m + 1)) - 1 for w < 0.5 else x += 1 - (2 (1 - w))^(1 / (eta_m + 1)).
+ *   Then x = min(max(x, 0), 1).
+ *   Arithmetic.  Every operation above is one IEEE float64 operation as written, left to right, nothing fused, and a power
+ *   x^e (x > 0) is NOT the math library's: it is pw(x, e) = ex(e * lg(x)), made of IEEE operations only, so that two
+ *   implementations of this text agree in every bit (a child of two equal parents equals them or differs in the last place
+ *   depending on the last bit of beta, and which of the two it is decides a domination).  With L = 0.6931471805599453:
+ *     lg(x): x = m 2^n with 0.5 <= m < 1 (frexp); if m < 0.7071067811865476 then m = 2 m, n = n - 1; s = (m - 1) / (m + 1),
+ *            z = s s; P = 1 / 23; for j = 21, 19, ..., 1: P = P z + 1 / j; lg = n L + (2 s) P.
+ *     ex(y): n = rint(y * 1.4426950408889634) (to nearest, ties to even); r = y - n L; T = 1; for j = 14, 13, ..., 1:
+ *            T = 1 + (r T) / j; ex = T 2^n (ldexp).
+ *   children [Np x d] must not overlap X.  parents (NULL or int32 [Np]): parents[2 q + e] = the
+ *   tournament winner e of pair q.
+ *   MOBOCMF_BAD_ARG (before any launch): Np odd or outside its range, d outside 1..MOBOCMF_MAX_D, a NULL X, rank, crowd,
+ *   generation or children, options of another struct_size or outside their ranges. */
+#define MOBOCMF_NSGA_MAX_ROWS 1024
+typedef struct mobocmf_nsga_options {
+    uint32_t struct_size;   /* sizeof(mobocmf_nsga_options) of the caller (set by mobocmf_nsga_options_init) */
+    uint32_t reserved;      /* 0 */
+    double eta_c;           /* crossover distribution index (default 15, 0..1000) */
+    double p_c;             /* crossover probability per pair (default 0.9, 0..1) */
+    double eta_m;           /* mutation distribution index (default 20, 0..1000) */
+    double p_m;             /* mutation probability per child and variable (default 0 = 1 / d, 0..1) */
+} mobocmf_nsga_options;
+int mobocmf_nsga_options_init(mobocmf_nsga_options* opt);
+int mobocmf_nsga_survive(int32_t n_in, int32_t n_keep, int32_t d, int32_t k, const double* X, const double* F, int64_t ldf,
+                         const double* viol, double* X_out, double* F_out, int64_t ldf_out, double* viol_out,
+                         int32_t* rank_out, double* crowd_out, int32_t* src_out, int64_t* generation,
+                         mobocmf_stream_t stream);
+int mobocmf_nsga_vary(int32_t Np, int32_t d, const double* X, const int32_t* rank, const double* crowd, uint64_t seed,
+                      const int64_t* generation, const mobocmf_nsga_options* opt, double* children, int32_t* parents,
+                      mobocmf_stream_t stream);
+
 /* Inducing-point selection by greedy conditional variance: the incomplete pivoted Cholesky of K_nn under the kind-0 kernel
  * (the one mobocmf_gram_forward(kind 0) evaluates).  x [N x d] row-major (1 <= d <= MOBOCMF_MAX_D), hyp = [a, ls[0..d)].
  * Step j picks the row with the largest residual d = diag(K_nn - K_nm K_mm^-1 K_mn) over the rows picked so far -- of

@@ -123,6 +123,16 @@ class RffRefineOptions(ctypes.Structure):
     KNOBS = tuple(n for n, _ in _fields_[1:])
 
 
+NSGA_MAX_ROWS = 1024      # MOBOCMF_NSGA_MAX_ROWS
+
+
+class NsgaOptions(ctypes.Structure):
+    """mobocmf_nsga_options: the settings of mobocmf_nsga_vary, passed with the call (NULL = defaults)."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("eta_c", ctypes.c_double),
+                ("p_c", ctypes.c_double), ("eta_m", ctypes.c_double), ("p_m", ctypes.c_double)]
+    KNOBS = tuple(n for n, _ in _fields_[2:])
+
+
 class MobocmfError(RuntimeError):
     pass
 
@@ -201,6 +211,9 @@ SYMBOLS = {
     "mobocmf_pareto_mask": [_I32, _I64, _P, _I64, _I32, _P, _P, _I64, _P, _D, _P, _P, _P],
     "mobocmf_hypervolume_workspace_bytes": [_I32, _I64, ctypes.POINTER(_SZ)],
     "mobocmf_hypervolume": [_I32, _I64, _P, _I64, _P, ctypes.POINTER(_D), _P, _SZ, _P],
+    "mobocmf_nsga_options_init": [ctypes.POINTER(NsgaOptions)],
+    "mobocmf_nsga_survive": [_I32, _I32, _I32, _I32, _P, _P, _I64, _P, _P, _P, _I64, _P, _P, _P, _P, _P, _P],
+    "mobocmf_nsga_vary": [_I32, _I32, _P, _P, _P, ctypes.c_uint64, _P, ctypes.POINTER(NsgaOptions), _P, _P, _P],
     "mobocmf_select_inducing_workspace_bytes": [_I64, _I32, ctypes.POINTER(_SZ)],
     "mobocmf_select_inducing": [_I64, _I32, _P, _P, _I32, _D, _I32, _P, _P, _P, _P, _P, _P, _SZ, _P],
     "mobocmf_minibatch_permutation_host": [_I64, _I64, _I64, _P],

@@ -1915,6 +1915,93 @@ def rff_feasibility(vals, thr):
     return ok.bool(), viol
 
 
+def nsga_options(**kw):
+    """The settings of ``nsga_vary`` (mobocmf_nsga_options): the library's defaults with ``kw`` (eta_c, p_c, eta_m, p_m)
+    replaced."""
+    opt = _lib.NsgaOptions()
+    _lib.check(_lib.load().mobocmf_nsga_options_init(ctypes.byref(opt)), "mobocmf_nsga_options_init")
+    for name, v in kw.items():
+        if name not in _lib.NsgaOptions.KNOBS:
+            raise _lib.MobocmfError("nsga_options: no option %r" % name)
+        setattr(opt, name, float(v))
+    return opt
+
+
+def _nsga_opt(options):
+    return nsga_options(**options) if isinstance(options, dict) else options
+
+
+def nsga_survive(X, F, viol=None, n_keep=None, generation=None):
+    """Constraint-domination ranks, crowding distances and the ``n_keep`` best of the rows ``X`` (n_in, d) with objective values
+    ``F`` (k, n_in) (minimised) and violations ``viol`` (n_in,) (>= 0, 0 = feasible; None: all feasible), in one launch
+    (mobocmf_nsga_survive; ``n_keep`` None = n_in, rank only).  ``generation``: a device int64 word the launch increments, or
+    None.  Returns a dict of new device tensors in key order (rank, -crowding, row): ``X``, ``F``, ``viol`` (None without
+    ``viol``), ``rank`` (int32), ``crowd``, ``src`` (int32, the input row).  No autograd, no host synchronisation."""
+    lib = _lib.require_device()
+    with torch.no_grad():
+        if not (torch.is_tensor(X) and torch.is_tensor(F)) or X.dim() != 2 or F.dim() != 2 or F.shape[1] != X.shape[0] \
+                or F.device != X.device:
+            raise _lib.MobocmfError("nsga_survive: X must be (n_in, d) and F (k, n_in), on one GPU")
+        X, F = _prep(X.detach()), _prep(F.detach())
+        n_in, d = X.shape
+        k = F.shape[0]
+        n_keep = n_in if n_keep is None else int(n_keep)
+        if viol is not None:
+            if viol.numel() != n_in or viol.device != X.device:
+                raise _lib.MobocmfError("nsga_survive: viol must be (n_in,)")
+            viol = _prep(viol.detach().reshape(-1))
+        if generation is not None and (generation.dtype != torch.int64 or generation.device != X.device):
+            raise _lib.MobocmfError("nsga_survive: generation must be a device int64 word")
+        dev, m = X.device, max(n_keep, 0)
+        out = {"X": _empty(m, d, device=dev), "F": _empty(k, m, device=dev),
+               "viol": None if viol is None else _empty(m, device=dev),
+               "rank": torch.empty(m, dtype=torch.int32, device=dev), "crowd": _empty(m, device=dev),
+               "src": torch.empty(m, dtype=torch.int32, device=dev)}
+        _lib.check(lib.mobocmf_nsga_survive(n_in, n_keep, d, k, _ptr(X), _ptr(F), n_in, _ptr(viol), _ptr(out["X"]),
+                                            _ptr(out["F"]), max(m, 1), _ptr(out["viol"]), _ptr(out["rank"]), _ptr(out["crowd"]),
+                                            _ptr(out["src"]), _ptr(generation), _stream()), "mobocmf_nsga_survive")
+    return out
+
+
+def nsga_vary(X, rank, crowd, seed, generation, options=None):
+    """Np children of the ranked parents ``X`` (Np, d) with ``rank`` (int32) / ``crowd`` (Np,) (what ``nsga_survive`` returns):
+    binary tournaments, simulated binary crossover, polynomial mutation, clamped to [0, 1] (mobocmf_nsga_vary).  ``seed``: the
+    Philox key; ``generation``: a device int64 word, the Philox call counter (``nsga_survive`` increments it); ``options``:
+    ``nsga_options(...)`` or a dict of its keywords.  Returns (children (Np, d), parents (Np,) int32 -- the tournament winners,
+    two per pair).  No autograd, no host synchronisation."""
+    lib = _lib.require_device()
+    with torch.no_grad():
+        if not torch.is_tensor(X) or X.dim() != 2 or rank.numel() != X.shape[0] or crowd.numel() != X.shape[0] \
+                or rank.dtype != torch.int32 or generation.dtype != torch.int64 \
+                or len({X.device, rank.device, crowd.device, generation.device}) != 1:
+            raise _lib.MobocmfError("nsga_vary: X (Np, d), rank (Np,) int32, crowd (Np,), generation int64, on one GPU")
+        X, crowd = _prep(X.detach()), _prep(crowd.detach().reshape(-1))
+        rank = rank.contiguous()
+        Np, d = X.shape
+        children = _empty(Np, d, device=X.device)
+        parents = torch.empty(Np, dtype=torch.int32, device=X.device)
+        options = _nsga_opt(options)
+        _lib.check(lib.mobocmf_nsga_vary(Np, d, _ptr(X), _ptr(rank), _ptr(crowd), int(seed) & (2 ** 64 - 1), _ptr(generation),
+                                         None if options is None else ctypes.byref(options), _ptr(children), _ptr(parents),
+                                         _stream()), "mobocmf_nsga_vary")
+    return children, parents
+
+
+def rff_evolve(x0, params, layers, n_obj, thr, generations, seed, options=None):
+    """NSGA-II on chain samples with no host in the loop (util/pareto_evolve.py ParetoEvolve): the population ``x0`` (Np, d), Np
+    even in 4..512, evolves for ``generations`` generations, each ONE graph replay of vary -> mobocmf_rff_eval_chains on the
+    children -> mobocmf_rff_feasibility -> survive on the 2 Np rows.  ``params`` / ``layers``: the chain samples as for
+    ``rff_eval_chains``, the first ``n_obj`` are the objectives (minimised), the others constraints, feasible when sample >=
+    ``thr`` (one threshold each).  Returns a dict of device tensors: ``X`` (Np, d), ``F`` (n_obj, Np), ``viol`` (Np,) (0 =
+    feasible), ``rank`` (int32), ``crowd``, ``generation`` (int64 word), in the survivors' key order.  Nothing is read on the
+    host."""
+    from .util.pareto_evolve import ParetoEvolve
+    eng = ParetoEvolve(params, layers, n_obj, thr, x0.shape[0], x0.shape[1], seed, options=options)
+    eng.start(x0)
+    eng.run(generations)
+    return eng.result()
+
+
 def pareto_mask(vals, con_mean=None, con_var=None, noise=None, p_min=0.999):
     """The recommendation rule of the reference's BO driver in one call (mobocmf_pareto_mask): ``vals`` (k, n) objective values
     (minimised), optionally ``con_mean`` / ``con_var`` (K_con, n) Gaussian constraint predictions and ``noise`` (K_con,) to

@@ -146,9 +146,19 @@ class BlackBoxMFDGPFitter:
                  pareto_set_size=50, opt_grid_size=1000, eps=1e-8, decoupled_evals=False,
                  type_lengthscale=TL.MEDIAN, device="cuda", pareto_refine="slsqp", variational_optimizer="adam",
                  natgrad_gamma=0.1, natgrad_gamma_init=1e-4, natgrad_warmup_steps=100, natgrad_one_launch=False,
-                 **model_kwargs):
+                 pareto_search="grid", pareto_evolve_population=128, pareto_evolve_generations=100, **model_kwargs):
         if pareto_refine not in ("slsqp", "device"):
             raise ValueError("pareto_refine must be 'slsqp' or 'device' (got %r)" % (pareto_refine,))
+        if pareto_search not in ("grid", "evolve"):
+            raise ValueError("pareto_search must be 'grid' or 'evolve' (got %r)" % (pareto_search,))
+        if not 4 <= int(pareto_evolve_population) <= 512 or int(pareto_evolve_population) % 2:
+            raise ValueError("pareto_evolve_population must be even, 4..512 (got %r)" % (pareto_evolve_population,))
+        if int(pareto_evolve_generations) < 1:
+            raise ValueError("pareto_evolve_generations must be >= 1")
+        # MOOP's search: the random grid | NSGA-II on the GPU from the grid's rows (util/pareto_evolve.py)
+        self.pareto_search = pareto_search
+        self.pareto_evolve_population = int(pareto_evolve_population)
+        self.pareto_evolve_generations = int(pareto_evolve_generations)
         if variational_optimizer not in ("adam", "natgrad"):
             raise ValueError("variational_optimizer must be 'adam' or 'natgrad' (got %r)" % (variational_optimizer,))
         if natgrad_one_launch and variational_optimizer != "natgrad":
@@ -447,7 +457,8 @@ class BlackBoxMFDGPFitter:
         """One posterior function sample per black-box (top layer), then the feasible Pareto set of the sampled
         problem on a random grid + the training inputs (blackbox_mfdgp_fitter.py:181-216)."""
         from .moop import MOOP, NotFeasiblePoints
-        if self.pareto_refine == "device":      # the same function for the same generator, as tensors MOOP can refine on the GPU
+        # the same function for the same generator, as tensors MOOP can refine / evolve on the GPU
+        if self.pareto_refine == "device" or self.pareto_search == "evolve":
             from ..layers.rff import sample_chain_from_posterior
             draw = lambda h: sample_chain_from_posterior(h.mfdgp, nFeatures=nFeatures, generator=generator)
         else:
@@ -460,7 +471,7 @@ class BlackBoxMFDGPFitter:
             samples_cons = [draw(h) for h in self.mfdgp_handlers_cons.values()]
             optimizer = MOOP(samples_objs, samples_cons, input_dim=inputs.shape[1],
                              grid_size=self.opt_grid_size * inputs.shape[1], pareto_set_size=self.pareto_set_size,
-                             feasible_values=feasible, rng=rng, refine=self.pareto_refine)
+                             feasible_values=feasible, rng=rng, refine=self.pareto_refine, **self._moop_search_kwargs())
             res = optimizer.compute_pareto_solution_from_samples(inputs)
             if res is not None:
                 break
@@ -473,6 +484,10 @@ class BlackBoxMFDGPFitter:
         self.set_pareto_solution(pareto_set, pareto_front)
         return self.pareto_set, self.pareto_front, self.samples_objs, self.samples_cons
 
+    def _moop_search_kwargs(self):
+        return {"search": self.pareto_search, "evolve_population": self.pareto_evolve_population,
+                "evolve_generations": self.pareto_evolve_generations}
+
     def sample_and_store_pareto_solution(self, seed=None, **kw):
         """Pareto solution of one posterior sample of the problem, stored for the conditioned training.
 
@@ -481,6 +496,9 @@ class BlackBoxMFDGPFitter:
         procedure of ``_sample_and_store_pareto_solution_seeded``, identical on every rank and independent of the sharding;
         with a group and no seed, rank 0 draws the seed from torch's global generator and broadcasts it."""
         from .moop import NotFeasiblePoints
+        if self.pareto_search == "evolve" and not parallel._no_group():
+            raise ValueError("pareto_search='evolve' is limited to one process (surrogates sharded over a process group take "
+                             "pareto_search='grid')")
         seeded = seed is not None or not parallel._no_group()
         if seeded:
             unknown = set(kw) - {"nFeatures"}
@@ -619,7 +637,8 @@ class BlackBoxMFDGPFitter:
                                          "set_global_constraint_thresholds)" % (len(cons), feasible.shape[0]))
                     optimizer = MOOP(objs, cons, input_dim=d, grid_size=self.opt_grid_size * d,
                                      pareto_set_size=self.pareto_set_size, feasible_values=feasible,
-                                     rng=np.random.default_rng((int(seed), int(t))), refine=self.pareto_refine)
+                                     rng=np.random.default_rng((int(seed), int(t))), refine=self.pareto_refine,
+                                     **self._moop_search_kwargs())
                     res = optimizer.compute_pareto_solution_from_samples(inputs)
                 else:
                     res = optimizer.compute_pareto_solution_from_samples(inputs, allow_negative_constraints=True)

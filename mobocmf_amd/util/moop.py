@@ -19,7 +19,10 @@ How it differs inside (results equal the reference's own MOOP, pinned by tests/g
   * ``refine="device"`` (opt-in; such samples only) replaces the SLSQP run per objective by ONE launch of the multi-start
     augmented-Lagrangian refinement ``functional.rff_refine``: ``refine_starts`` starts per objective, the best feasible grid
     rows, chosen on the device from the grid values that stay there.  The results differ from the default's (other optima
-    are found, never worse than the grid's best), so the golden results are pinned with the default only.
+    are found, never worse than the grid's best), so the golden results are pinned with the default only;
+  * ``search="evolve"`` (opt-in; such samples only) runs NSGA-II on the GPU from the rows the grid stage found
+    (``_evolve_device``, util/pareto_evolve.py) and appends the feasible rows it ends with, so the front weakly dominates
+    the default's for the same ``rng``.  It combines with both ``refine`` modes.
 """
 import numpy as np
 import scipy.optimize as spo
@@ -38,11 +41,21 @@ def _weakly_dominated_by_any(front, p):
 class MOOP:
 
     def __init__(self, samples_objs, samples_cons, input_dim, grid_size=1000, pareto_set_size=None, feasible_values=0.0,
-                 min_distance_between_points=1e-6, rng=None, refine="slsqp", refine_starts=16):
+                 min_distance_between_points=1e-6, rng=None, refine="slsqp", refine_starts=16, search="grid",
+                 evolve_population=128, evolve_generations=100, evolve_seed=None):
         if refine not in ("slsqp", "device"):
             raise ValueError("refine must be 'slsqp' or 'device' (got %r)" % (refine,))
         if int(refine_starts) < 1:
             raise ValueError("refine_starts must be >= 1")
+        if search not in ("grid", "evolve"):
+            raise ValueError("search must be 'grid' or 'evolve' (got %r)" % (search,))
+        if not 4 <= int(evolve_population) <= 512 or int(evolve_population) % 2:
+            raise ValueError("evolve_population must be even, 4..512 (got %r)" % (evolve_population,))
+        if int(evolve_generations) < 1:
+            raise ValueError("evolve_generations must be >= 1")
+        self.search = search
+        self.evolve_population, self.evolve_generations = int(evolve_population), int(evolve_generations)
+        self.evolve_seed = None if evolve_seed is None else int(evolve_seed)
         self.refine = refine
         self.refine_starts = int(refine_starts)
         self.samples_objs = samples_objs
@@ -156,6 +169,42 @@ class MOOP:
         status = out["status"].cpu().numpy()
         return [x_best[j][None] for j in range(n_obj) if status[j] == 0 and f_best[j] < np.min(evals[:, j])]
 
+    # ------------------------------------------------------------------ NSGA-II from the rows found so far
+    def _evolve_device(self, grid, evals, seed):
+        """``search="evolve"``: the feasible rows assembled so far (grid, training inputs, optima) seed a population that
+        ``util.pareto_evolve.ParetoEvolve`` evolves on the GPU for ``evolve_generations`` generations.  Initial population: the
+        non-dominated rows, thinned to Np / 2 by ``compute_pareto_front_and_set_summary_y_space`` when there are more, then the
+        other rows in row order up to Np = ``evolve_population`` (with fewer rows: the largest even count; fewer than 4, or the
+        least-infeasible fallback of the grid: no evolution).  The final rows the device calls feasible and that lie farther
+        than 1e-6 from every row are appended with the values the device computed.  Returns (grid, evals)."""
+        from .pareto_evolve import ParetoEvolve
+        g = self._grid_dev
+        if g["rows"] is None or grid.shape[0] < 4:
+            return grid, evals
+        Np, n = self.evolve_population, grid.shape[0]
+        front = np.flatnonzero(self.obtain_indices_pareto(evals))
+        if front.size > Np // 2:
+            front = self.compute_pareto_front_and_set_summary_y_space(front[:, None], evals[front], Np // 2)[0][:, 0]
+        taken = np.zeros(n, dtype=bool)
+        taken[front] = True
+        rest = np.flatnonzero(~taken)[:max(Np - front.size, 0)]
+        rows = np.concatenate((front, rest))
+        rows = rows[:rows.size // 2 * 2]
+        if rows.size < 4:
+            return grid, evals
+        n_obj, n_con = len(self.samples_objs), len(self.samples_cons)
+        thr = self._thresholds(n_con, self.feasible_values)[:n_con]
+        eng = ParetoEvolve(g["params"], g["layers"], n_obj, thr, rows.size, self.input_dim, seed)
+        eng.start(torch.from_numpy(np.ascontiguousarray(grid[rows])))
+        eng.run(self.evolve_generations)
+        out = eng.result()
+        X, Fv, viol = out["X"].cpu().numpy(), out["F"].cpu().numpy().T, out["viol"].cpu().numpy()
+        new = [i for i in np.flatnonzero(viol == 0.0)
+               if not np.isnan(Fv[i]).any() and np.min(np.sqrt(((grid - X[i]) ** 2).sum(1))) > 1e-6]
+        if new:
+            grid, evals = np.vstack((grid, X[new])), np.vstack((evals, Fv[new]))
+        return grid, evals
+
     # ------------------------------------------------------------------ constrained optimum of one objective
     def _slsqp(self, obj, cons, x0, tol):
         thr = self._thresholds(len(cons), self.feasible_values)
@@ -255,6 +304,14 @@ class MOOP:
             self.rng.uniform(size=(n_rand, self.input_dim))
         grid = np.concatenate((rand, inputs))
         dev = self._batched_device()
+        if self.search == "evolve":
+            if dev is None:
+                raise ValueError("MOOP(search='evolve') needs every sample to be an RFFChainSample on one GPU "
+                                 "(layers.rff.sample_chain_from_posterior); there is no host fallback")
+            seed = self.evolve_seed               # drawn after the grid, and in this mode only: the default's draws stay
+            if seed is None:
+                seed = int(np.random.randint(0, 2 ** 63 - 1, dtype=np.int64)) if self.rng is None else \
+                    int(self.rng.integers(0, 2 ** 63 - 1))
         if self.refine == "device" and dev is None:
             raise ValueError("MOOP(refine='device') needs every sample to be an RFFChainSample on one GPU "
                              "(layers.rff.sample_chain_from_posterior); there is no host fallback")
@@ -282,6 +339,8 @@ class MOOP:
             extra = np.concatenate(extra, 0)
             grid = np.vstack((grid, extra))
             evals = np.vstack((evals, np.stack([np.asarray(obj(extra)).reshape(-1) for obj in self.samples_objs], 1)))
+        if self.search == "evolve":
+            grid, evals = self._evolve_device(grid, evals, seed)
         keep = self.obtain_indices_pareto(evals)
         pareto_set, pareto_front = grid[keep, :], evals[keep, :]
         if self.pareto_set_size is not None:
