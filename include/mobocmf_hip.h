@@ -92,7 +92,9 @@ typedef struct {
     int32_t want_dx; /* backward also returns d/dx (acquisition optimisation) */
     double jitter;   /* added to diag(K_mm); gpytorch variational_cholesky_jitter = 1e-6 */
     double min_var;  /* MultivariateNormal.variance clamp; gpytorch min_variance = 1e-10 */
-    int32_t phase;   /* MOBOCMF_PHASE_*: which half of the layer call to run (0 = both) */
+    int32_t params_const; /* 0 | 1.  1: the parameters are constants (acquisition optimisation against a fitted model) --
+                           * honoured by mobocmf_layer_panel_* and mobocmf_panel_workspace_bytes, refused by the whole-call
+                           * entry points */
     int32_t reserved;
     const mobocmf_tuning* tuning; /* kernel-selection knobs of THIS call and of the size queries made with this descriptor;
                                    * NULL = defaults */
@@ -106,22 +108,12 @@ typedef struct {
 } mobocmf_layer_desc;
 #define MOBOCMF_PROBE_EVENTS 11
 
-/* A layer call has two halves that only meet in `saved` (forward) / `scratch` (backward):
+/* A layer call has two halves:
  *   CHAIN  the M x M work that depends on the parameters alone: K_mm, its Cholesky and inverse, U = L^-1 L_S,
  *          a = L^-1 m, the KL (forward); the M x M backward chain, Cholesky backward, Gram backward of K_mm (backward);
  *   PANEL  the M x N' work: K_mn, A, C, moments (forward); dA, the weighted syrk, dK, Gram backward of K_mn (backward).
- * Forward order: CHAIN then PANEL.  Backward order: PANEL then CHAIN (same private `scratch` for both calls).
- * A caller may run the CHAIN halves of several layers on another stream, overlapping the latency-bound chain of one
- * layer with the grid-filling PANEL work of another.  Pointers a half does not touch may be NULL.
- * In a split backward the CHAIN half OVERWRITES g_zf / g_hyp with its own contribution (the caller adds the PANEL
- * half's); CHAIN_ONLY additionally treats the PANEL half's contribution as zero (no upstream mean/var gradient). */
-#define MOBOCMF_PHASE_ALL 0
-#define MOBOCMF_PHASE_CHAIN 1
-#define MOBOCMF_PHASE_PANEL 2
-#define MOBOCMF_PHASE_CHAIN_ONLY 3   /* backward only */
-#define MOBOCMF_PHASE_PANEL_INPUTS 4 /* PANEL half with the parameters held constant: backward yields g_f / g_x (and the
-                                      * K_mn share of g_zf / g_hyp) but skips the M x M contractions the CHAIN half would
-                                      * consume -- acquisition optimisation against a fixed model */
+ * mobocmf_layer_forward / _backward run both (desc->params_const must be 0); mobocmf_layers_chain_* and mobocmf_layer_panel_*
+ * below run them apart, meeting in the layer's chain block. */
 
 int mobocmf_version(void);
 /* 1 if the current HIP device is gfx950. */
@@ -130,11 +122,6 @@ int mobocmf_device_arch_ok(void);
 /* Bytes of the `saved` buffer (forward -> backward state: L, L^-1, U, K_mn, A, C, ...) and of the scratch
  * buffer (dead after each call). */
 int mobocmf_layer_workspace_bytes(const mobocmf_layer_desc* desc, size_t* saved_bytes, size_t* scratch_bytes);
-
-/* Leading bytes of `saved` that hold the CHAIN half's state (L, L^-1, U, a, ...).  They do not depend on Np: a caller
- * whose parameters are fixed (acquisition optimisation) runs the CHAIN half once and copies these bytes to the front of
- * the `saved` buffer of every later PANEL call. */
-int mobocmf_layer_chain_state_bytes(const mobocmf_layer_desc* desc, size_t* bytes);
 
 /* mean[Np], var[Np] (clamped at min_var), kl[1] = KL(q(u) || p(u)), info[1]. */
 int mobocmf_layer_forward(const mobocmf_layer_desc* desc, const double* x, const double* f, const double* Zx,
@@ -168,7 +155,12 @@ int mobocmf_layer_backward(const mobocmf_layer_desc* desc, const double* x, cons
  * had_panel[l] |= 4 (l >= 1, kind 1): zf[l] IS the variational mean m[l-1] of the previous layer of this call (the reference's
  * Z~_l = [Z_x, m_{l-1}], mfdgp_hidden_layer.py:555-556): the complete gradient of zf[l] -- this call's K_mm share plus, under
  * 2, the PANEL share found in g_zf[l] -- is ADDED to g_m[l-1] and g_zf[l] is not written; the caller hands g_m[l-1] to m[l-1]
- * and nothing to zf[l]. */
+ * and nothing to zf[l].
+ * The first `state_bytes` of a block (mobocmf_chain_block_bytes) are the CHAIN state the PANEL halves read; they do not depend
+ * on Np.  desc->params_const = 1 (PANEL calls only): the parameters are constants.  `chain_block` may then be that state alone
+ * (block_bytes >= state_bytes) and the call does not write through it -- a frozen state serves every evaluation of a search, on
+ * any number of streams; the backward yields g_f / g_x (and the K_mn share of g_zf / g_hyp) and skips H / Hc / da, which only a
+ * chain backward would consume. */
 int mobocmf_chain_block_bytes(const mobocmf_layer_desc* desc, size_t* block_bytes, size_t* state_bytes);
 int mobocmf_panel_workspace_bytes(const mobocmf_layer_desc* desc, size_t* saved_bytes, size_t* scratch_bytes);
 int mobocmf_layers_chain_forward(int32_t n, const mobocmf_layer_desc* const* desc, const double* const* Zx,
@@ -184,7 +176,6 @@ int mobocmf_layer_panel_forward(const mobocmf_layer_desc* desc, const double* x,
                                 const double* zf, const double* hyp, double* mean, double* var, void* chain_block,
                                 size_t block_bytes, void* saved, size_t saved_bytes, void* scratch, size_t scratch_bytes,
                                 mobocmf_stream_t stream);
-/* desc->phase == MOBOCMF_PHASE_PANEL_INPUTS: parameters held constant (no H / Hc / da for a chain backward). */
 int mobocmf_layer_panel_backward(const mobocmf_layer_desc* desc, const double* x, const double* f, const double* Zx,
                                  const double* zf, const double* hyp, const double* g_mean, const double* g_var,
                                  double* g_f, double* g_zf, double* g_hyp, double* g_x, void* chain_block,
@@ -194,7 +185,7 @@ int mobocmf_layer_panel_backward(const mobocmf_layer_desc* desc, const double* x
 /* cov[Np x Np] = K_nn - A^T A + C^T C (A = L^-1 K_mn, C = U^T A): the full predictive covariance of the eval branch of the
  * variational strategy (the dense matrix GPyTorch materialises in .eval(), JESMOC_MFDGP.py:42 -> mfdgp.py:248), written as
  * the full symmetric matrix with leading dimension ldcov >= Np.  Only the layer's CHAIN state is read (`chain_state` = the
- * first mobocmf_layer_chain_state_bytes of the `saved` buffer a forward / CHAIN-half call filled: L^-1 and U), so a frozen
+ * first `state_bytes` (mobocmf_chain_block_bytes) of the chain block mobocmf_layers_chain_forward filled: L^-1 and U), so a frozen
  * chain serves any number of input batches.  The contractions over the M inducing points are symmetric rank-M updates on
  * the MFMA (lower 128-tiles only), one column panel at a time: the scratch (mobocmf_predictive_covariance_workspace_bytes)
  * grows with Np x panel width, not Np^2, and Np is not capped.  Ordinary layer scratch sizes do not include it. */
@@ -1036,7 +1027,7 @@ int mobocmf_select_topk(const double* vals, int32_t n, int32_t k, const double* 
  * MOBOCMF_FROZEN_MAX_M) against their FROZEN chains, and the gradient w.r.t. the test points (csrc/frozen_predict.hip): the two
  * model evaluations of a device acquisition search at those sizes.  n models at the same kind of T test points; the parameters
  * are constants, so every layer's M x M chain exists already: chain[l] is the layer's CHAIN state, the first
- * mobocmf_layer_chain_state_bytes of the `saved` buffer a MOBOCMF_PHASE_CHAIN forward with branch = 1 filled, read only.
+ * `state_bytes` (mobocmf_chain_block_bytes) of the chain block mobocmf_layers_chain_forward with branch = 1 filled, read only.
  * The algebra is the layer's eval branch (no clamp, floor 1e-10), column by column:
  *   layer 0 at x_t:               k = k(Z, x_t), A = L^-1 k, C = U^T A, mean = a^T A, var = max(k_nn - |A|^2 + |C|^2, 1e-10)
  *   layer l >= 1 at column t S + s: f = mean_{l-1} + sqrt(var_{l-1}) samples[l][s] (layer 0's column t serves the S replicas),
@@ -1059,7 +1050,7 @@ typedef struct mobocmf_frozen_predict_model {
     int32_t L, M, d, S;
     int32_t T;                                   /* test points */
     int32_t kind[MOBOCMF_TINY_MAX_LAYERS];       /* 0, 1, 1 */
-    const void* chain[MOBOCMF_TINY_MAX_LAYERS];  /* the layer's CHAIN state (mobocmf_layer_chain_state_bytes) */
+    const void* chain[MOBOCMF_TINY_MAX_LAYERS];  /* the layer's CHAIN state (state_bytes of mobocmf_chain_block_bytes) */
     const double* Zx[MOBOCMF_TINY_MAX_LAYERS];   /* M x d (the layers share one Z_x; the pointers may be equal) */
     const double* zf[MOBOCMF_TINY_MAX_LAYERS];   /* M (layers >= 1) */
     const double* hyp[MOBOCMF_TINY_MAX_LAYERS];  /* packed constrained hyper-parameters (the layer entry points' order) */

@@ -162,8 +162,8 @@ int weighted_syrk_pair(const double* A, int64_t lda, const double* w, const doub
 
 bool valid_desc(const mobocmf_layer_desc* d) {
     return d && tuning_ok(d->tuning) && (d->kind == 0 || d->kind == 1) && d->d >= 1 && d->d <= MOBOCMF_MAX_D && d->M >= 1 && d->xdiv >= 1 &&
-           d->xdiv <= MOBOCMF_MAX_XDIV && d->Np >= 1 && d->Np % d->xdiv == 0 && (d->branch == 0 || d->branch == 1) && d->phase >= 0 &&
-           d->phase <= MOBOCMF_PHASE_PANEL_INPUTS;
+           d->xdiv <= MOBOCMF_MAX_XDIV && d->Np >= 1 && d->Np % d->xdiv == 0 && (d->branch == 0 || d->branch == 1) &&
+           (d->params_const == 0 || d->params_const == 1);
 }
 
 Dims dims_of(const mobocmf_layer_desc* d) {
@@ -202,7 +202,8 @@ struct ChainWs {
     double *Dinv, *Ld, *T, *ws, *klpart;
     int64_t ws_elems;
     // panel backward -> chain backward
-    double *H, *Hc, *da, *flag;
+    double *H, *Hc, *da;
+    int32_t* nclamped;      // chain-block layout only: the clamped-column counter of the PANEL backward, cleared by its forward
     // backward scratch
     double *W[8], *da_tot, *slabs, *hyp_part2, *df_part2, *dzf_part2;
     int64_t slab_elems;
@@ -212,7 +213,7 @@ struct ChainWs {
 // forward SCRATCH, not in the state kept for backward -- one M x N' panel less per layer (268 MB at C3, 8.6 GB at C4)
 struct PanelSaved { double *A, *C, *knn, *q, *r, *varraw; };
 struct PanelFwd { double *K, *qpart, *mupart, *rpart; };
-struct PanelBwd { double *gmu, *gv, *gv2, *cgv, *dA, *dK, *slabs, *slabs2, *dapart, *hyp_part, *df_part, *dzf_part, *dx_part; int64_t slab_elems; int32_t* blkact; };
+struct PanelBwd { double *gmu, *gv, *gv2, *cgv, *dA, *dK, *slabs, *slabs2, *dapart, *hyp_part, *df_part, *dzf_part, *dx_part; int64_t slab_elems; int32_t *blkact, *nclamped; };
 
 void carve_chain_state(Bump& b, const Dims& D, ChainWs& S) {
     int64_t mm = (int64_t)D.Mp * D.Mp;
@@ -240,7 +241,7 @@ void carve_panel_fwd(Bump& b, const Dims& D, PanelFwd& S) {
 }
 void carve_chain_bwd_in(Bump& b, const Dims& D, ChainWs& S) {
     int64_t mm = (int64_t)D.Mp * D.Mp;
-    S.H = b.take(mm); S.Hc = b.take(mm); S.da = b.take(D.Mp); S.flag = b.take(4);
+    S.H = b.take(mm); S.Hc = b.take(mm); S.da = b.take(D.Mp);
 }
 // kind-independent sizes (hyp_part2 for the largest hyper-parameter vector, the f-column partials always): the chain
 // blocks of all layers of a model have ONE size
@@ -256,6 +257,7 @@ void carve_panel_bwd(Bump& b, const Dims& D, const mobocmf_layer_desc* d, PanelB
     int64_t mm = (int64_t)D.Mp * D.Mp, mn = (int64_t)D.Mp * D.Np;
     S.gmu = b.take(D.Np); S.gv = b.take(D.Np); S.gv2 = b.take(D.Np); S.cgv = b.take(D.Np);
     S.blkact = (int32_t*)b.take((D.Np / TILE + 1) / 2);      // one word per 128 columns (moments_bwd_prep)
+    S.nclamped = (int32_t*)b.take(4);      // the clamped-column counter of a call that has none in a chain block of its own
     S.dA = b.take(mn); S.dK = b.take(mn);
     S.slab_elems = syrk_slab_elems(D.Mp, D.Np);
     S.slabs = b.take(S.slab_elems);
@@ -306,10 +308,20 @@ bool carve_chain_block(void* block, size_t bytes, const Dims& D, ChainWs& c, siz
     if (state_bytes) *state_bytes = b.off;
     carve_chain_fwd(b, D, c);
     carve_chain_bwd_in(b, D, c);
+    c.nclamped = (int32_t*)b.take(4);
     carve_chain_bwd(b, D, c);
     c.slabs = c.ws;
     c.slab_elems = c.ws_elems;
     if (used) *used = b.off;
+    return b.ok;
+}
+
+// what a PANEL call gets of its layer's chain block: the whole block, or -- constant parameters -- the state alone, read only
+// (H, Hc, da and the counter stay null: nothing is left for a chain backward, nothing is written)
+bool carve_panel_chain(const mobocmf_layer_desc* d, void* block, size_t bytes, const Dims& D, ChainWs& c) {
+    if (!d->params_const) return carve_chain_block(block, bytes, D, c);
+    Bump b(block, bytes);
+    carve_chain_state(b, D, c);
     return b.ok;
 }
 
@@ -372,7 +384,7 @@ int chain_forward(int n, const ChainWs& c, int64_t zs, const ChainIO& io, const 
 // PANEL half, forward: K_mn, A = L^-1 K (+ q, mean partials), C = U^T A (+ r partials), moments
 int panel_forward(const mobocmf_layer_desc* desc, const Dims& D, const ChainWs& c, const PanelSaved& P, const PanelFwd& F,
                   const double* x, const double* f, const double* Zx, const double* zf, const double* hyp, double* mean,
-                  double* var, bool block_layout, hipStream_t s) {
+                  double* var, hipStream_t s) {
     const int Mp = D.Mp;
     const int64_t Np = D.Np;
     GramArgs g = {};
@@ -396,48 +408,47 @@ int panel_forward(const mobocmf_layer_desc* desc, const Dims& D, const ChainWs& 
     gc.rm = ga.rm; gc.pair_mode = ga.pair_mode;
     TRY(launch_gemm(gc, false, 1, s));
     probe_at(2, s);
-    // chain-block layout: the clamped-column counter of the backward lives in the block and is cleared here
+    // (a chain block of the call's own holds the backward's clamped-column counter: cleared here)
     TRY(launch_moments_finish(F.qpart, F.mupart, F.rpart, gemm_colstat_rows(ga), Np, D.N, P.knn, desc->branch, desc->min_var, P.q, P.r,
-                              P.varraw, mean, var, block_layout ? (int32_t*)c.flag : nullptr, s));
+                              P.varraw, mean, var, c.nclamped, s));
     return MOBOCMF_OK;
 }
 
 // PANEL half, backward: dA, the weighted syrk(s) H / Hc and da (unless the parameters are constants), dK, Gram backward of
 // K_mn and k_nn.  Writes g_f, g_x and -- overwriting -- the K_mn share of g_hyp / g_zf.
 int panel_backward(const mobocmf_layer_desc* desc, const Dims& D, const ChainWs& c, const PanelSaved& P, const PanelBwd& B,
-                   bool inputs_only, bool block_layout, const double* x, const double* f, const double* Zx, const double* zf,
-                   const double* hyp, const double* g_mean, const double* g_var, double* g_f, double* g_zf, double* g_hyp,
-                   double* g_x, hipStream_t s) {
+                   const double* x, const double* f, const double* Zx, const double* zf, const double* hyp, const double* g_mean,
+                   const double* g_var, double* g_f, double* g_zf, double* g_hyp, double* g_x, hipStream_t s) {
     const int Mp = D.Mp;
     const int64_t Np = D.Np, mm = (int64_t)Mp * Mp;
-    int32_t* nclamped = (int32_t*)c.flag;
+    int32_t* nclamped = c.nclamped ? c.nclamped : B.nclamped;      // the block's, cleared by the forward, or the call's own
     double* Hc = desc->branch != 0 ? c.H : c.Hc;
     // act: one word per 128 columns, zero where every upstream gradient of the block is exactly zero (the top layer of a
     // multi-fidelity model only gets gradient from the rows scored at ITS fidelity): those blocks' shares of dA, H, da,
     // dK and the Gram backward are exactly zero and are not computed
     const int32_t* act = tune().sparse_backward ? B.blkact : nullptr;
     TRY(launch_moments_bwd_prep(g_mean, g_var, P.knn, P.q, P.varraw, desc->branch, desc->min_var, D.N, Np, B.gmu, B.gv,
-                                B.gv2, B.cgv, nclamped, block_layout ? 1 : 0, (int32_t*)act, s));
+                                B.gv2, B.cgv, nclamped, c.nclamped ? 1 : 0, (int32_t*)act, s));
     // dA = 2 U (C diag(gv)) + a gmu^T - 2 A diag(cgv)
     int da_parts = 0;
     {
         GemmArgs ga = gemm_args(c.U, Mp, P.C, Np, B.dA, Np, Mp, Np, Mp, TRI_LOWER_A, 2.0);
         ga.bscale = B.gv; ga.epi = EPI_DA; ga.avec = c.a; ga.gmu = B.gmu; ga.cgv = B.cgv; ga.Aaux = P.A;
         ga.Kreal = D.M;
-        ga.rowdot_part = inputs_only ? nullptr : B.dapart;      // da = A gmu rides in the epilogue (it reads A anyway)
+        ga.rowdot_part = desc->params_const ? nullptr : B.dapart;     // da = A gmu rides in the epilogue (it reads A anyway)
         ga.colact = act;
         ga.rm = panel_tile_rows(Mp, Np);
         set_pairing(ga);
         probe_at(3, s);
         TRY(launch_gemm(ga, false, 1, s));
         probe_at(4, s);
-        da_parts = inputs_only ? 0 : gemm_rowdot_parts(ga);      // summed in the call's last launch (below): da is read by the
+        da_parts = desc->params_const ? 0 : gemm_rowdot_parts(ga);     // summed in the call's last launch (below): da is read by the
     }                                                           // CHAIN half only
     // H = A diag(gv) A^T  (weighted syrk, split-K over N').  Both M x M contractions of the backward reduce to it:
     //   dU = 2 tril(A diag(gv) C^T) = 2 tril(H U),   dA A^T = 2 U U^T H + a da^T - 2 Hc,  Hc = A diag(cgv) A^T.
     // Hc differs from H only when clamp(k_nn - q, 0) is active in some column: its syrk is skipped on the device
     // (skip_if_zero) when no column is clamped.
-    if (!inputs_only) {
+    if (!desc->params_const) {      // constant parameters: no chain backward follows, c.H / c.Hc / c.da are not there
         probe_at(5, s);
         if (desc->branch == 0) TRY(weighted_syrk_pair(P.A, Np, B.gv, B.cgv, Mp, Np, B.slabs, B.slabs2, c.H, Hc, nclamped, act, s));
         else TRY(weighted_syrk(P.A, Np, B.gv, Mp, Np, B.slabs, c.H, nullptr, nullptr, act, s));
@@ -611,7 +622,7 @@ bool carve_cov(void* scratch, size_t bytes, const mobocmf_layer_desc* d, const D
 
 extern "C" {
 
-int mobocmf_version(void) { return 200; }
+int mobocmf_version(void) { return 201; }
 
 int mobocmf_device_arch_ok(void) {
     int dev = 0;
@@ -640,29 +651,15 @@ int mobocmf_layer_workspace_bytes(const mobocmf_layer_desc* desc, size_t* saved_
     return MOBOCMF_OK;
 }
 
-int mobocmf_layer_chain_state_bytes(const mobocmf_layer_desc* desc, size_t* bytes) {
-    if (!valid_desc(desc) || !bytes) return MOBOCMF_BAD_ARG;
-    TuneScope tune_scope(desc->tuning, desc->probe_events);
-    Dims D = dims_of(desc);
-    Bump b(nullptr, ~(size_t)0 >> 1);
-    ChainWs c;
-    carve_chain_state(b, D, c);
-    *bytes = b.off;
-    return MOBOCMF_OK;
-}
-
 int mobocmf_layer_forward(const mobocmf_layer_desc* desc, const double* x, const double* f, const double* Zx,
                           const double* zf, const double* hyp, const double* m, const double* L_S, double* mean,
                           double* var, double* kl, int32_t* info, void* saved, size_t saved_bytes, void* scratch,
                           size_t scratch_bytes, mobocmf_stream_t stream) {
-    if (!valid_desc(desc) || desc->phase == MOBOCMF_PHASE_CHAIN_ONLY || !Zx || !hyp || !saved || !scratch)
+    if (!valid_desc(desc) || desc->params_const || !x || !Zx || !hyp || !m || !L_S || !mean || !var || !kl || !info || !saved ||
+        !scratch)
         return MOBOCMF_BAD_ARG;
     TuneScope tune_scope(desc->tuning, desc->probe_events);
-    const bool do_chain = desc->phase == MOBOCMF_PHASE_ALL || desc->phase == MOBOCMF_PHASE_CHAIN;
-    const bool do_panel = desc->phase != MOBOCMF_PHASE_CHAIN;
-    if (do_chain && (!m || !L_S || !kl || !info)) return MOBOCMF_BAD_ARG;
-    if (do_panel && (!x || !mean || !var)) return MOBOCMF_BAD_ARG;
-    if (desc->kind == 1 && (!zf || (do_panel && !f))) return MOBOCMF_BAD_ARG;
+    if (desc->kind == 1 && (!zf || !f)) return MOBOCMF_BAD_ARG;
     hipStream_t s = (hipStream_t)stream;
     Dims D = dims_of(desc);
     ChainWs c = {};
@@ -670,13 +667,10 @@ int mobocmf_layer_forward(const mobocmf_layer_desc* desc, const double* x, const
     PanelFwd F;
     if (!carve_single_saved(saved, saved_bytes, D, c, P) || !carve_single_fwd(scratch, scratch_bytes, D, c, F))
         return MOBOCMF_WORKSPACE_TOO_SMALL;
-    if (do_chain) {
-        ChainIO io = {};
-        io.desc = &desc; io.Zx = &Zx; io.zf = &zf; io.hyp = &hyp; io.m = &m; io.L_S = &L_S; io.kl = &kl; io.info = &info;
-        TRY(chain_forward(1, c, 0, io, D, s));
-    }
-    if (!do_panel) return MOBOCMF_OK;
-    return panel_forward(desc, D, c, P, F, x, f, Zx, zf, hyp, mean, var, false, s);
+    ChainIO io = {};
+    io.desc = &desc; io.Zx = &Zx; io.zf = &zf; io.hyp = &hyp; io.m = &m; io.L_S = &L_S; io.kl = &kl; io.info = &info;
+    TRY(chain_forward(1, c, 0, io, D, s));
+    return panel_forward(desc, D, c, P, F, x, f, Zx, zf, hyp, mean, var, s);
 }
 
 int mobocmf_layer_backward(const mobocmf_layer_desc* desc, const double* x, const double* f, const double* Zx,
@@ -684,15 +678,11 @@ int mobocmf_layer_backward(const mobocmf_layer_desc* desc, const double* x, cons
                            const double* g_mean, const double* g_var, const double* g_kl, double* g_f, double* g_zf,
                            double* g_hyp, double* g_m, double* g_LS, double* g_x, void* saved, size_t saved_bytes,
                            void* scratch, size_t scratch_bytes, mobocmf_stream_t stream) {
-    if (!valid_desc(desc) || !Zx || !hyp || !g_hyp || !saved || !scratch) return MOBOCMF_BAD_ARG;
+    if (!valid_desc(desc) || desc->params_const || !x || !Zx || !hyp || !g_mean || !g_var || !g_kl || !g_hyp || !g_m || !g_LS ||
+        (desc->want_dx && !g_x) || !saved || !scratch)
+        return MOBOCMF_BAD_ARG;
     TuneScope tune_scope(desc->tuning, desc->probe_events);
-    const bool inputs_only = desc->phase == MOBOCMF_PHASE_PANEL_INPUTS;   // parameters are constants: no H / Hc / da
-    const bool do_panel = desc->phase == MOBOCMF_PHASE_ALL || desc->phase == MOBOCMF_PHASE_PANEL || inputs_only;
-    const bool do_chain = desc->phase == MOBOCMF_PHASE_ALL || desc->phase == MOBOCMF_PHASE_CHAIN ||
-                          desc->phase == MOBOCMF_PHASE_CHAIN_ONLY;
-    if (do_panel && (!x || !g_mean || !g_var || (desc->want_dx && !g_x))) return MOBOCMF_BAD_ARG;
-    if (do_chain && (!g_kl || !g_m || !g_LS)) return MOBOCMF_BAD_ARG;
-    if (desc->kind == 1 && (!zf || !g_zf || (do_panel && (!f || !g_f)))) return MOBOCMF_BAD_ARG;
+    if (desc->kind == 1 && (!zf || !g_zf || !f || !g_f)) return MOBOCMF_BAD_ARG;
     hipStream_t s = (hipStream_t)stream;
     Dims D = dims_of(desc);
     ChainWs c = {};
@@ -700,15 +690,12 @@ int mobocmf_layer_backward(const mobocmf_layer_desc* desc, const double* x, cons
     PanelBwd B;
     if (!carve_single_saved(saved, saved_bytes, D, c, P) || !carve_single_bwd(scratch, scratch_bytes, D, desc, c, B))
         return MOBOCMF_WORKSPACE_TOO_SMALL;
-    if (do_panel)
-        TRY(panel_backward(desc, D, c, P, B, inputs_only, false, x, f, Zx, zf, hyp, g_mean, g_var, g_f, g_zf, g_hyp, g_x, s));
-    if (!do_chain) return MOBOCMF_OK;
+    TRY(panel_backward(desc, D, c, P, B, x, f, Zx, zf, hyp, g_mean, g_var, g_f, g_zf, g_hyp, g_x, s));
     ChainIO io = {};
     io.desc = &desc; io.Zx = &Zx; io.zf = &zf; io.hyp = &hyp; io.m = &m; io.L_S = &L_S;
     io.g_kl = &g_kl; io.g_zf = &g_zf; io.g_hyp = &g_hyp; io.g_m = &g_m; io.g_LS = &g_LS;
-    const bool zero = desc->phase == MOBOCMF_PHASE_CHAIN_ONLY;     // no upstream mean/var gradient: H = Hc = 0, da = 0
-    const int acc = desc->phase == MOBOCMF_PHASE_ALL ? 1 : 0;       // split: the chain half reports its own g_hyp / g_zf
-    const bool fold = false;
+    const bool zero = false, fold = false;
+    const int acc = 1;      // the PANEL half wrote its share of g_hyp / g_zf
     return chain_backward(1, c, 0, io, D, &zero, &acc, &fold, s);
 }
 
@@ -802,14 +789,14 @@ int mobocmf_layer_panel_forward(const mobocmf_layer_desc* desc, const double* x,
     if (desc->kind == 1 && (!zf || !f)) return MOBOCMF_BAD_ARG;
     Dims D = dims_of(desc);
     ChainWs c = {};
-    if (!carve_chain_block(chain_block, block_bytes, D, c)) return MOBOCMF_WORKSPACE_TOO_SMALL;
+    if (!carve_panel_chain(desc, chain_block, block_bytes, D, c)) return MOBOCMF_WORKSPACE_TOO_SMALL;
     Bump bs(saved, saved_bytes), bf(scratch, scratch_bytes);
     PanelSaved P;
     PanelFwd F;
     carve_panel_saved(bs, D, P);
     carve_panel_fwd(bf, D, F);
     if (!bs.ok || !bf.ok) return MOBOCMF_WORKSPACE_TOO_SMALL;
-    return panel_forward(desc, D, c, P, F, x, f, Zx, zf, hyp, mean, var, true, (hipStream_t)stream);
+    return panel_forward(desc, D, c, P, F, x, f, Zx, zf, hyp, mean, var, (hipStream_t)stream);
 }
 
 int mobocmf_layer_panel_backward(const mobocmf_layer_desc* desc, const double* x, const double* f, const double* Zx,
@@ -824,15 +811,14 @@ int mobocmf_layer_panel_backward(const mobocmf_layer_desc* desc, const double* x
     if (desc->kind == 1 && (!zf || !f || !g_f || !g_zf)) return MOBOCMF_BAD_ARG;
     Dims D = dims_of(desc);
     ChainWs c = {};
-    if (!carve_chain_block(chain_block, block_bytes, D, c)) return MOBOCMF_WORKSPACE_TOO_SMALL;
+    if (!carve_panel_chain(desc, chain_block, block_bytes, D, c)) return MOBOCMF_WORKSPACE_TOO_SMALL;
     Bump bs(saved, saved_bytes), bb(scratch, scratch_bytes);
     PanelSaved P;
     PanelBwd B;
     carve_panel_saved(bs, D, P);
     carve_panel_bwd(bb, D, desc, B);
     if (!bs.ok || !bb.ok) return MOBOCMF_WORKSPACE_TOO_SMALL;
-    return panel_backward(desc, D, c, P, B, desc->phase == MOBOCMF_PHASE_PANEL_INPUTS, true, x, f, Zx, zf, hyp, g_mean, g_var,
-                          g_f, g_zf, g_hyp, g_x, (hipStream_t)stream);
+    return panel_backward(desc, D, c, P, B, x, f, Zx, zf, hyp, g_mean, g_var, g_f, g_zf, g_hyp, g_x, (hipStream_t)stream);
 }
 
 int mobocmf_predictive_covariance_workspace_bytes(const mobocmf_layer_desc* desc, size_t* scratch_bytes) {
@@ -1118,7 +1104,7 @@ int mobocmf_debug_touch_workspaces(const mobocmf_layer_desc* desc, void* saved, 
         touch(c.T, mm, &n); touch(c.ws, c.ws_elems, &n); touch(c.klpart, D.Mp, &n);
     };
     auto chain_bwd = [&](ChainWs& c) {
-        touch(c.H, mm, &n); touch(c.Hc, mm, &n); touch(c.da, D.Mp, &n); touch(c.flag, 4, &n);
+        touch(c.H, mm, &n); touch(c.Hc, mm, &n); touch(c.da, D.Mp, &n); touch((double*)c.nclamped, 4, &n);
         for (int i = 0; i < 8; ++i) touch(c.W[i], mm, &n);
         touch(c.da_tot, D.Mp, &n);
         touch(c.hyp_part2, (int64_t)D.ggrid_mm.x * D.ggrid_mm.y * hyp_len(1, MOBOCMF_MAX_D), &n);
@@ -1135,7 +1121,7 @@ int mobocmf_debug_touch_workspaces(const mobocmf_layer_desc* desc, void* saved, 
     };
     auto panel_bwd = [&](PanelBwd& B) {
         touch(B.gmu, D.Np, &n); touch(B.gv, D.Np, &n); touch(B.gv2, D.Np, &n); touch(B.cgv, D.Np, &n);
-        touch((double*)B.blkact, (D.Np / TILE + 1) / 2, &n);
+        touch((double*)B.blkact, (D.Np / TILE + 1) / 2, &n); touch((double*)B.nclamped, 4, &n);
         touch(B.dA, mn, &n); touch(B.dK, mn, &n); touch(B.slabs, B.slab_elems, &n); touch(B.slabs2, B.slab_elems, &n);
         touch(B.dapart, (D.Np <= 8192 ? D.Np / 16 : D.Np / 64) * (int64_t)D.Mp, &n);
         touch(B.hyp_part, (int64_t)D.ggrid_mn.x * D.ggrid_mn.y * D.H, &n);

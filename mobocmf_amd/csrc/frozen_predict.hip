@@ -5,8 +5,8 @@
 //
 // A search evaluates n models at the same T test points, T S columns per model -- 125 at the search's own sizes: one tile of
 // the layer path's grid-filling products -- against parameters that stay constant, so L^-1, L^-T, U, U^T and a of every layer
-// exist already (the layer's CHAIN state, mobocmf_layer_chain_state_bytes).  Every column of every layer depends on its own
-// base row only:
+// exist already (the layer's CHAIN state, state_bytes of mobocmf_chain_block_bytes).  Every column of every layer depends on
+// its own base row only:
 //
 //   a WORKGROUP owns (model, a block of base rows), runs ALL layers for those rows and their S replicas, 16 columns at a time,
 //   and sums its rows' d/dx in a fixed order.

@@ -93,19 +93,13 @@ def release_scratch(stream=None):
     small pool, so a stale entry would otherwise pin up to ~1 GB per handle for ever)."""
     if stream is None:
         _scratch.clear()
-        _side_streams.clear()
         return
     for key in [k for k in _scratch if k[1] == stream.cuda_stream]:
         del _scratch[key]
-    for key in [k for k in _side_streams if k[1] == stream.cuda_stream]:
-        del _side_streams[key]
 
 
 def hyp_len(kind, d):
     return 1 + d if kind == 0 else 5 + 2 * d
-
-
-PHASE_ALL, PHASE_CHAIN, PHASE_PANEL, PHASE_CHAIN_ONLY, PHASE_PANEL_INPUTS = 0, 1, 2, 3, 4
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -181,9 +175,9 @@ def _probe_for(layer):
     return cur[0]
 
 
-def make_desc(kind, d, M, Np, xdiv=1, branch=0, want_dx=False, jitter=JITTER, min_var=MIN_VARIANCE, phase=PHASE_ALL,
-              tune=None, probe=None):
-    """``tune``: a Tuning snapshot to carry (default: the calling thread's current one); ``probe``: a ctypes array of
+def make_desc(kind, d, M, Np, xdiv=1, branch=0, want_dx=False, jitter=JITTER, min_var=MIN_VARIANCE, tune=None,
+              probe=None, params_const=False):
+    """``params_const``: the parameters are constants (PANEL calls against a FrozenChain only); ``tune``: a Tuning snapshot to carry (default: the calling thread's current one); ``probe``: a ctypes array of
     PROBE_EVENTS hipEvent_t handles (mobocmf_layer_desc.probe_events) or None."""
     if not 1 <= d <= _lib.MAX_D:
         raise _lib.MobocmfError("mobocmf_amd: a layer takes 1..%d input dimensions (got %d): the Gram kernels keep one "
@@ -192,7 +186,7 @@ def make_desc(kind, d, M, Np, xdiv=1, branch=0, want_dx=False, jitter=JITTER, mi
         raise _lib.MobocmfError("mobocmf_amd: at most %d samples per input row (num_samples_for_acquisition / "
                                 "num_samples_for_training), got %d" % (_lib.MAX_XDIV, xdiv))
     desc = LayerDesc(kind=kind, d=d, M=M, xdiv=xdiv, Np=Np, branch=branch, want_dx=int(want_dx), jitter=jitter,
-                     min_var=min_var, phase=phase, reserved=0)
+                     min_var=min_var, params_const=int(params_const), reserved=0)
     snap = tune if tune is not None else current_tuning()
     desc.tuning = ctypes.pointer(snap)
     desc._tune = snap              # keeps the snapshot alive as long as the descriptor
@@ -272,179 +266,6 @@ class _LayerFn(torch.autograd.Function):
 
 
 # ------------------------------------------------------------------------------------------------------------
-# The same layer call in two halves (include/mobocmf_hip.h, MOBOCMF_PHASE_*): the CHAIN half depends on the
-# parameters alone, so a model launches it for every layer up front on a side stream and the latency-bound
-# M x M chains (one wavefront per Cholesky panel) run under the grid-filling PANEL work of the other layers.
-# Autograd runs each half's backward on the stream its forward ran on and orders them through the ``token``.
-# ------------------------------------------------------------------------------------------------------------
-_side_streams = {}
-
-
-def side_stream_for(main):
-    """The chain stream paired with ``main`` (one per (device, main stream))."""
-    key = (main.device.index, main.cuda_stream)
-    st = _side_streams.get(key)
-    if st is None:
-        st = torch.cuda.Stream(device=main.device)
-        _side_streams[key] = st
-    return st
-
-
-class LayerPass:
-    """State shared by the two halves of one split layer call."""
-    __slots__ = ("kind", "d", "M", "Np", "xdiv", "branch", "jitter", "min_var", "want_dx", "info", "saved", "sb", "cb",
-                 "bscratch", "main", "side", "ready", "kl", "frozen", "tune", "probe")
-
-    def desc(self, phase):
-        # one tuning snapshot (taken when the pass was created, in the forward) serves both halves, forward and backward
-        return make_desc(self.kind, self.d, self.M, self.Np, self.xdiv, self.branch, self.want_dx, self.jitter,
-                         self.min_var, phase, tune=self.tune, probe=self.probe)
-
-
-class _ChainFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, Zx, zf, hyp, m, L_S, P):
-        lib = _lib.require_device()
-        Zx, zf, hyp, m, L_S = (_prep(t) for t in (Zx, zf, hyp, m, L_S))
-        dev = Zx.device
-        desc = P.desc(PHASE_CHAIN)
-        P.sb, P.cb = workspace_bytes(desc)
-        P.saved = _poison(torch.empty(P.sb, dtype=torch.uint8, device=dev))
-        scratch = scratch_buffer(P.cb, dev)
-        kl = _empty((), device=dev)
-        token = torch.empty(1, dtype=torch.float64, device=dev)      # never read: it only orders the autograd nodes
-        rc = lib.mobocmf_layer_forward(ctypes.byref(desc), None, None, _ptr(Zx), _ptr(zf), _ptr(hyp), _ptr(m), _ptr(L_S),
-                                       None, None, _ptr(kl), _ptr(P.info), _ptr(P.saved), P.sb, _ptr(scratch),
-                                       scratch.numel(), _stream())
-        _lib.check(rc, "mobocmf_layer_forward[chain]")
-        if P.main is not None:      # allocated here (side stream), consumed on the main stream
-            for t in (P.saved, kl, token):
-                t.record_stream(P.main)
-            for t in (hyp, zf, m, L_S):     # allocated on the main stream, read here
-                if t is not None:
-                    t.record_stream(P.side)
-        ctx.P = P
-        ctx.save_for_backward(*[t for t in (Zx, zf, hyp, m, L_S) if t is not None])
-        ctx.has_f = zf is not None
-        return token, kl
-
-    @staticmethod
-    def backward(ctx, g_token, g_kl):
-        lib = _lib.require_device()
-        P = ctx.P
-        ts = list(ctx.saved_tensors)
-        if ctx.has_f:
-            Zx, zf, hyp, m, L_S = ts
-        else:
-            Zx, hyp, m, L_S = ts
-            zf = None
-        dev = Zx.device
-        M = P.M
-        phase = PHASE_CHAIN
-        scratch = P.bscratch
-        P.bscratch = None
-        if scratch is None:         # the PANEL half took no part in this backward (only the KL was differentiated)
-            scratch = _poison(torch.empty(P.cb, dtype=torch.uint8, device=dev))
-            phase = PHASE_CHAIN_ONLY
-        if g_kl is None:
-            g_kl = torch.zeros((), dtype=torch.float64, device=dev)
-        g_kl = _prep(g_kl)
-        desc = P.desc(phase)
-        new = lambda *s: _empty(*s, device=dev)
-        g_zf = new(M) if ctx.has_f else None
-        g_hyp, g_m, g_LS = new(hyp.numel()), new(M), new(M, M)
-        rc = lib.mobocmf_layer_backward(ctypes.byref(desc), None, None, _ptr(Zx), _ptr(zf), _ptr(hyp), _ptr(m),
-                                        _ptr(L_S), None, None, _ptr(g_kl), None, _ptr(g_zf), _ptr(g_hyp), _ptr(g_m),
-                                        _ptr(g_LS), None, _ptr(P.saved), P.sb, _ptr(scratch), scratch.numel(), _stream())
-        _lib.check(rc, "mobocmf_layer_backward[chain]")
-        return None, g_zf, g_hyp, g_m, g_LS, None
-
-
-class _PanelFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, f, Zx, zf, hyp, token, P):
-        lib = _lib.require_device()
-        x, f, Zx, zf, hyp = (_prep(t) for t in (x, f, Zx, zf, hyp))
-        if x.shape[0] * P.xdiv != P.Np or x.shape[1] != P.d or (P.kind == 1 and (f is None or f.numel() != P.Np)):
-            raise _lib.MobocmfError("shape mismatch between the two halves of a split layer call")
-        dev = x.device
-        desc = P.desc(PHASE_PANEL)
-        scratch = scratch_buffer(P.cb, dev)
-        mean = _empty(P.Np, device=dev)
-        var = _empty(P.Np, device=dev)
-        rc = lib.mobocmf_layer_forward(ctypes.byref(desc), _ptr(x), _ptr(f), _ptr(Zx), _ptr(zf), _ptr(hyp), None, None,
-                                       _ptr(mean), _ptr(var), None, None, _ptr(P.saved), P.sb, _ptr(scratch),
-                                       scratch.numel(), _stream())
-        _lib.check(rc, "mobocmf_layer_forward[panel]")
-        ctx.P = P
-        ctx.save_for_backward(*[t for t in (x, f, Zx, zf, hyp) if t is not None])
-        ctx.has_f = f is not None
-        return mean, var
-
-    @staticmethod
-    def backward(ctx, g_mean, g_var):
-        lib = _lib.require_device()
-        P = ctx.P
-        ts = list(ctx.saved_tensors)
-        if ctx.has_f:
-            x, f, Zx, zf, hyp = ts
-        else:
-            x, Zx, hyp = ts
-            f = zf = None
-        dev = x.device
-        g_mean, g_var = _prep(g_mean), _prep(g_var)
-        if P.frozen:        # constant parameters: nothing is handed to a CHAIN half
-            desc = P.desc(PHASE_PANEL_INPUTS)
-            scratch = scratch_buffer(P.cb, dev)
-        else:
-            desc = P.desc(PHASE_PANEL)
-            # private scratch: H, Hc, da stay in it until the CHAIN half (side stream) has consumed them
-            scratch = _poison(torch.empty(P.cb, dtype=torch.uint8, device=dev))
-            if P.side is not None:
-                scratch.record_stream(P.side)
-        new = lambda *s: _empty(*s, device=dev)
-        g_f = new(P.Np) if ctx.has_f else None
-        g_zf = new(P.M) if ctx.has_f else None
-        g_hyp = new(hyp.numel())
-        g_x = new(x.shape[0], P.d) if P.want_dx else None
-        rc = lib.mobocmf_layer_backward(ctypes.byref(desc), _ptr(x), _ptr(f), _ptr(Zx), _ptr(zf), _ptr(hyp), None, None,
-                                        _ptr(g_mean), _ptr(g_var), None, _ptr(g_f), _ptr(g_zf), _ptr(g_hyp), None, None,
-                                        _ptr(g_x), _ptr(P.saved), P.sb, _ptr(scratch), scratch.numel(), _stream())
-        _lib.check(rc, "mobocmf_layer_backward[panel]")
-        if P.frozen:
-            return g_x, g_f, None, None, None, None, None
-        P.bscratch = scratch
-        # the token gradient is a real tensor here: the CHAIN half may run on another stream, and the autograd engine
-        # orders the two streams through the tensors that flow between the nodes
-        return g_x, g_f, None, g_zf, g_hyp, torch.zeros(1, dtype=torch.float64, device=dev), None
-
-
-def layer_chain(Zx, zf, hyp, m, L_S, kind, Np, xdiv=1, branch=0, jitter=JITTER, min_var=MIN_VARIANCE, want_dx=False,
-                info_out=None, main=None, side=None):
-    """CHAIN half of a layer call for N' = Np rows: returns (LayerPass, token); ``LayerPass.kl`` holds the KL.  Call it
-    under ``torch.cuda.stream(side)`` with ``main`` = the stream the PANEL half will run on (or both None: same stream)."""
-    P = LayerPass()
-    P.kind, P.d, P.M, P.Np, P.xdiv, P.branch = kind, Zx.shape[1], Zx.shape[0], Np, xdiv, branch
-    P.jitter, P.min_var, P.want_dx = jitter, min_var, want_dx
-    P.info = info_out if info_out is not None else torch.zeros((), dtype=torch.int32, device=Zx.device)
-    P.bscratch, P.main, P.side, P.frozen = None, main, side, False
-    P.tune, P.probe = current_tuning(), _probe_for(None)
-    token, P.kl = _ChainFn.apply(Zx, zf, hyp, m, L_S, P)
-    P.ready = None
-    if side is not None:
-        P.ready = torch.cuda.Event()
-        P.ready.record(side)
-    return P, token
-
-
-def layer_panel(P, token, x, f, Zx, zf, hyp):
-    """PANEL half: mean (N'), var (N').  Waits (stream-side) for the CHAIN half of the same pass."""
-    if P.ready is not None:
-        torch.cuda.current_stream(x.device).wait_event(P.ready)
-    return _PanelFn.apply(x, f, Zx, zf, hyp, token, P)
-
-
-# ------------------------------------------------------------------------------------------------------------
 # All layers of a model in one batch of CHAIN launches (include/mobocmf_hip.h, mobocmf_layers_chain_*): the chain is a
 # serial string of latency-bound M x M kernels, the layers' chains do not depend on each other, so one z-batched
 # sequence divides its length by the number of layers.  One autograd node carries every layer's chain; the per-layer
@@ -457,7 +278,11 @@ class ChainBatch:
 
     def chain_desc(self, z):
         return make_desc(self.kinds[z], self.ds[z], self.M, 1, 1, self.branch, False, self.jitters[z], self.min_var,
-                         PHASE_CHAIN, tune=self.tune)
+                         tune=self.tune)
+
+    def panel_desc(self, z, Np, xdiv, want_dx):
+        return make_desc(self.kinds[z], self.ds[z], self.M, Np, xdiv, self.branch, want_dx, self.jitters[z], self.min_var,
+                         tune=self.tune, probe=_probe_for(z))
 
     def block(self, z):
         return self.blocks[z * self.stride:z * self.stride + self.block_bytes]
@@ -568,17 +393,18 @@ def layers_chain(layers_params, kinds, branch, jitters, infos, min_var=MIN_VARIA
 
 
 class _PanelBatchedFn(torch.autograd.Function):
+    """The PANEL half of one layer against its chain: slot ``z`` of a ChainBatch, or a FrozenChain (``token`` None, ``z`` not
+    used) -- then the chain state is only read and the gradients stop at x and f."""
+
     @staticmethod
     def forward(ctx, x, f, Zx, zf, hyp, token, CB, z, xdiv, want_dx):
         lib = _lib.require_device()
         x, f, Zx, zf, hyp = (_prep(t) for t in (x, f, Zx, zf, hyp))
         Np = x.shape[0] * xdiv
-        kind = CB.kinds[z]
-        if x.shape[1] != CB.ds[z] or (kind == 1 and (f is None or f.numel() != Np)):
-            raise _lib.MobocmfError("shape mismatch between the chain batch and a panel call")
+        desc = CB.panel_desc(z, Np, xdiv, want_dx)
+        if x.shape[1] != desc.d or (desc.kind == 1 and (f is None or f.numel() != Np)):
+            raise _lib.MobocmfError("shape mismatch between the chain and a panel call")
         dev = x.device
-        desc = make_desc(kind, CB.ds[z], CB.M, Np, xdiv, CB.branch, want_dx, CB.jitters[z], CB.min_var, PHASE_PANEL,
-                         tune=CB.tune, probe=_probe_for(z))
         sb, cb = ctypes.c_size_t(), ctypes.c_size_t()
         _lib.check(lib.mobocmf_panel_workspace_bytes(ctypes.byref(desc), ctypes.byref(sb), ctypes.byref(cb)),
                    "mobocmf_panel_workspace_bytes")
@@ -607,7 +433,7 @@ class _PanelBatchedFn(torch.autograd.Function):
             f = zf = None
         dev = x.device
         g_mean, g_var = _prep(g_mean), _prep(g_var)
-        scratch = scratch_buffer(ctx.cb, dev)      # H / Hc / da go to the chain block, nothing of the scratch is kept
+        scratch = scratch_buffer(ctx.cb, dev)      # H / Hc / da (if any) go to the chain block, nothing of the scratch is kept
         new = lambda *s: _empty(*s, device=dev)
         g_f = new(desc.Np) if ctx.has_f else None
         g_zf = new(CB.M) if ctx.has_f else None
@@ -619,6 +445,8 @@ class _PanelBatchedFn(torch.autograd.Function):
                                               _ptr(blk), blk.numel(), _ptr(ctx.saved_ws), ctx.sb, _ptr(scratch),
                                               scratch.numel(), _stream())
         _lib.check(rc, "mobocmf_layer_panel_backward")
+        if desc.params_const:
+            return g_x, g_f, None, None, None, None, None, None, None, None
         CB.had_panel[z] = 1
         # the K_mn share of g_hyp / g_zf is handed to the chain node (which adds its K_mm share into the same buffers), and
         # None for the token: the edge to the chain node orders the backward passes, no gradient has to flow through it
@@ -632,12 +460,20 @@ def layer_panel_batched(CB, z, x, f, Zx, zf, hyp, xdiv=1, want_dx=False):
 
 
 class FrozenChain:
-    """CHAIN state of one layer for FIXED parameters (acquisition optimisation): computed once, then copied to the
-    front of the ``saved`` buffer of every PANEL call; gradients flow to the layer inputs only."""
+    """CHAIN state of one layer for FIXED parameters (acquisition optimisation): computed once, then read in place by every
+    PANEL call (any number of them, on any stream); gradients flow to the layer inputs only."""
     __slots__ = ("kind", "d", "M", "branch", "jitter", "min_var", "state", "kl", "info", "Zx", "zf", "hyp")
+
+    def panel_desc(self, z, Np, xdiv, want_dx):
+        return make_desc(self.kind, self.d, self.M, Np, xdiv, self.branch, want_dx, self.jitter, self.min_var,
+                         probe=_probe_for(None), params_const=True)
+
+    def block(self, z):
+        return self.state
 
 
 def freeze_chain(Zx, zf, hyp, m, L_S, kind, branch=1, jitter=JITTER, min_var=MIN_VARIANCE):
+    """The FrozenChain of one layer: a one-layer chain batch into a temporary block, of which the state is kept."""
     lib = _lib.require_device()
     with torch.no_grad():
         Zx, zf, hyp, m, L_S = (_prep(None if t is None else t.detach()) for t in (Zx, zf, hyp, m, L_S))
@@ -645,34 +481,25 @@ def freeze_chain(Zx, zf, hyp, m, L_S, kind, branch=1, jitter=JITTER, min_var=MIN
         fc.kind, fc.d, fc.M, fc.branch, fc.jitter, fc.min_var = kind, Zx.shape[1], Zx.shape[0], branch, jitter, min_var
         fc.Zx, fc.zf, fc.hyp = Zx, zf, hyp
         dev = Zx.device
-        desc = make_desc(kind, fc.d, fc.M, 1, 1, branch, False, jitter, min_var, PHASE_CHAIN)
-        nb = ctypes.c_size_t()
-        _lib.check(lib.mobocmf_layer_chain_state_bytes(ctypes.byref(desc), ctypes.byref(nb)), "chain_state_bytes")
-        sb, cb = workspace_bytes(desc)
-        saved = _poison(torch.empty(sb, dtype=torch.uint8, device=dev))
-        scratch = scratch_buffer(cb, dev)
+        desc = make_desc(kind, fc.d, fc.M, 1, 1, branch, False, jitter, min_var)
+        bb, st = ctypes.c_size_t(), ctypes.c_size_t()
+        _lib.check(lib.mobocmf_chain_block_bytes(ctypes.byref(desc), ctypes.byref(bb), ctypes.byref(st)),
+                   "mobocmf_chain_block_bytes")
+        stride = (bb.value + 255) // 256 * 256
+        block = _poison(torch.empty(stride, dtype=torch.uint8, device=dev))
         fc.kl = _empty((), device=dev)
         fc.info = torch.zeros((), dtype=torch.int32, device=dev)
-        rc = lib.mobocmf_layer_forward(ctypes.byref(desc), None, None, _ptr(Zx), _ptr(zf), _ptr(hyp), _ptr(m), _ptr(L_S),
-                                       None, None, _ptr(fc.kl), _ptr(fc.info), _ptr(saved), sb, _ptr(scratch),
-                                       scratch.numel(), _stream())
-        _lib.check(rc, "mobocmf_layer_forward[chain]")
-        fc.state = saved[:nb.value].clone()
+        T = lambda t: _table([0 if t is None else t.data_ptr()])
+        rc = lib.mobocmf_layers_chain_forward(1, _desc_table([desc]), T(Zx), T(zf), T(hyp), T(m), T(L_S), T(fc.kl), T(fc.info),
+                                              _ptr(block), stride, block.numel(), _stream())
+        _lib.check(rc, "mobocmf_layers_chain_forward")
+        fc.state = block[:st.value].clone()
     return fc
 
 
 def layer_panel_frozen(fc, x, f, xdiv=1, want_dx=False):
     """mean (N'), var (N') against a FrozenChain; differentiable w.r.t. f (and x if want_dx) only."""
-    P = LayerPass()
-    P.kind, P.d, P.M, P.Np, P.xdiv, P.branch = fc.kind, fc.d, fc.M, x.shape[0] * xdiv, xdiv, fc.branch
-    P.jitter, P.min_var, P.want_dx, P.info = fc.jitter, fc.min_var, want_dx, fc.info
-    P.bscratch = P.main = P.side = P.ready = None
-    P.kl, P.frozen = fc.kl, True
-    P.tune, P.probe = current_tuning(), _probe_for(None)
-    P.sb, P.cb = workspace_bytes(P.desc(PHASE_PANEL))
-    P.saved = _poison(torch.empty(P.sb, dtype=torch.uint8, device=x.device))
-    P.saved[:fc.state.numel()].copy_(fc.state)
-    return _PanelFn.apply(x, f, fc.Zx, fc.zf, fc.hyp, None, P)
+    return _PanelBatchedFn.apply(x, f, fc.Zx, fc.zf, fc.hyp, None, fc, 0, xdiv, want_dx)
 
 
 def layer_forward(x, f, Zx, zf, hyp, m, L_S, kind, xdiv=1, branch=0, jitter=JITTER, min_var=MIN_VARIANCE,

@@ -284,24 +284,6 @@ class MFDGPHiddenLayer(nn.Module):
     _info = None
     _shortcut_last = False
 
-    def launch_chain(self, n_rows, xdiv, want_dx, main, side):
-        """CHAIN half of the next call of this layer on ``n_rows`` rows (K_mm, Cholesky, L^-1, U, a, KL), issued
-        under ``torch.cuda.stream(side)``; hands back what ``__call__(..., chain=...)`` needs for the PANEL half."""
-        vs = self.variational_strategy
-        vd = vs._variational_distribution
-        Zx, zf = vs.Zx, vs.zf
-        if self._info is None or self._info.device != Zx.device:
-            self._info = torch.zeros((), dtype=torch.int32, device=Zx.device)
-        with torch.cuda.stream(main):
-            hyp = gp.pack_hypers(self.covar_module, self.kind)     # constraint transforms stay on the main stream
-            ev = torch.cuda.Event()
-            ev.record(main)
-        side.wait_event(ev)
-        P, token = F.layer_chain(Zx, zf, hyp, vd.variational_mean, vd.chol_variational_covar, self.kind, n_rows,
-                                 xdiv=xdiv, branch=0 if self.training else 1, jitter=vs.jitter_val, want_dx=want_dx,
-                                 info_out=self._info, main=main, side=side)
-        return P, token, hyp
-
     def freeze_chain(self):
         """CHAIN half for the current (fixed) parameters, with the psd_safe_cholesky jitter ladder of ``_moments``."""
         vs = self.variational_strategy
@@ -335,21 +317,18 @@ class MFDGPHiddenLayer(nn.Module):
         else:
             hit = bool(torch.equal(x, vs.Zx) and (f is None or torch.equal(f, vs.zf)))
             self._shortcut_last = hit
+        # ``chain``: a FrozenChain (MFDGP.frozen_chains), this layer's slot (ChainBatch, z, hyp) of a chain batch, or None
+        frozen = isinstance(chain, F.FrozenChain)
         if hit:
-            if isinstance(chain, tuple) and isinstance(chain[0], F.ChainBatch):
+            if chain is not None and not frozen:
                 vs._kl_cache = chain[0].kls[chain[1]]      # the batch has this layer's KL already
             return vd.variational_mean, F.shortcut_var(vd.chol_variational_covar)
-        if isinstance(chain, F.FrozenChain):
+        if frozen:
             return F.layer_panel_frozen(chain, x, f, xdiv=xdiv, want_dx=want_dx)
-        if isinstance(chain, tuple) and isinstance(chain[0], F.ChainBatch):      # all layers' chains in one batch
+        if chain is not None:
             CB, z, hyp = chain
             mean, var = F.layer_panel_batched(CB, z, x, f, vs.Zx, vs.zf, hyp, xdiv=xdiv, want_dx=want_dx)
             vs._kl_cache = CB.kls[z]
-            return mean, var
-        if chain is not None:
-            P, token, hyp = chain
-            mean, var = F.layer_panel(P, token, x, f, vs.Zx, vs.zf, hyp)
-            vs._kl_cache = P.kl
             return mean, var
         mean, var, kl = self._moments(x, f, xdiv, want_dx)
         vs._kl_cache = kl

@@ -301,7 +301,7 @@ class MFDGP(nn.Module):
         if self._frozen is not None:
             chains = self._frozen_chains(num_layers)
         else:
-            chains = self._batched_chains(inputs, num_layers) or self._launch_chains(inputs, num_layers, S, want_dx, rows)
+            chains = self._batched_chains(inputs, num_layers) or [None] * num_layers
         for i in range(num_layers):
             hidden_layer = getattr(self, self.name_hidden_layer + str(i))
             x_i = inputs if rows is None else inputs[:rows[i]]
@@ -319,7 +319,6 @@ class MFDGP(nn.Module):
             l_outputs[i] = output_layer
         return l_outputs
 
-    _warned_off = False
     _frozen = None
 
     @contextlib.contextmanager
@@ -343,6 +342,7 @@ class MFDGP(nn.Module):
                 self._frozen[key] = layer.freeze_chain()
             out.append(self._frozen[key])
         return out
+
     batch_chains = True                   # all layers' CHAIN halves as one z-batched sequence of launches (fast path)
 
     def _batched_chains(self, inputs, num_layers):
@@ -352,7 +352,7 @@ class MFDGP(nn.Module):
         per-call host checks (``set_check_pd(False)``: graphed step / bench / fitter fast path) and with one M for all
         layers; otherwise None (the layers then run one by one)."""
         layers = [getattr(self, self.name_hidden_layer + str(i)) for i in range(num_layers)]
-        if not (self.batch_chains and not self.overlap_chains and inputs.is_cuda and 2 <= num_layers <= 4
+        if not (self.batch_chains and inputs.is_cuda and 2 <= num_layers <= 4
                 and not any(l.check_pd for l in layers)):
             return None
         params, kinds, jit, infos, hyps = [], [], [], [], []
@@ -373,31 +373,6 @@ class MFDGP(nn.Module):
             infos.append(layer._info)
         CB = F.layers_chain(params, kinds, 0 if self.training else 1, jit, infos)
         return [(CB, z, hyps[z]) for z in range(num_layers)]
-
-    overlap_chains = False                # opt-in (HIP-graph replay of forked captures is slower on ROCm 7.2)
-    OVERLAP_MAX_ROWS = 1 << 21            # above this the private backward scratch per layer is not worth its memory
-
-    def _launch_chains(self, inputs, num_layers, S, want_dx, rows=None):
-        """The parameter-only (CHAIN) half of every layer, issued up front on a side stream so the latency-bound M x M
-        work of layer l runs under the grid-filling panel work of the other layers -- forward here, and backward through
-        autograd, which replays each half on the stream its forward used.  Only without per-call host checks
-        (``set_check_pd(False)``: graphed / bench / fitter fast path); otherwise the layers run serially."""
-        layers = [getattr(self, self.name_hidden_layer + str(i)) for i in range(num_layers)]
-        if not (self.overlap_chains and inputs.is_cuda and num_layers > 1 and not any(l.check_pd for l in layers)
-                and inputs.shape[0] * S <= self.OVERLAP_MAX_ROWS):      # (rows: an upper bound)
-            return [None] * num_layers
-        main = torch.cuda.current_stream(inputs.device)
-        side = F.side_stream_for(main)
-        if not MFDGP._warned_off and hasattr(torch.autograd.graph, "set_warn_on_accumulate_grad_stream_mismatch"):
-            # parameters feed both halves, i.e. both streams, on purpose; the engine orders the accumulation
-            torch.autograd.graph.set_warn_on_accumulate_grad_stream_mismatch(False)
-            MFDGP._warned_off = True
-        chains = []
-        with torch.cuda.stream(side):
-            for i, layer in enumerate(layers):
-                nb = inputs.shape[0] if rows is None else rows[i]
-                chains.append(layer.launch_chain(nb * (1 if i == 0 else S), 1 if i == 0 else S, want_dx, main, side))
-        return chains
 
     def fix_variational_hypers(self, value):
         for i in range(self.num_hidden_layers):

@@ -205,3 +205,20 @@ def test_predictive_covariance_matches_oracle(kind, d, M, nbase, xdiv):
     fc = F.freeze_chain(g(Zx), g(zf), _pack(kind, hyp).to(dev), g(m), g(L_S), kind, branch=1)
     _, cov2 = F.predictive_covariance(g(x), g(f), g(Zx), g(zf), _pack(kind, hyp).to(dev), None, None, kind, xdiv=xdiv, chain=fc)
     assert torch.equal(cov, cov2)
+
+
+def test_frozen_chain_and_its_panel_calls_reproduce_the_recorded_bits():
+    """functional.freeze_chain, layer_panel_frozen with its backward, and predictive_covariance at M = 20 and 150, both kinds,
+    both branches, N' = 35 and 1000: bit for bit what tools/record_frozen_layer_golden.py recorded (tests/frozen_layer_cases.py
+    has the calls) -- and a PANEL call, forward or backward, leaves the frozen state as it found it."""
+    import os
+
+    from tests import frozen_layer_cases as C
+    ref = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "frozen_layer_bits.npz"))
+    got, state_after = C.layer_arrays()
+    assert sorted(got) == sorted(k for k in ref.files if k.startswith("M")) and len(got) == 84
+    for k, v in got.items():
+        assert torch.equal(v, torch.from_numpy(ref[k])), k
+    assert "M20/k0/b0/state" in state_after
+    for k, v in state_after.items():
+        assert torch.equal(v, got[k]), k

@@ -127,9 +127,9 @@ def test_every_group_class_gates_with_its_own_why_not():
 def _fake_chain(kind, M, d):
     """A FrozenChain of host tensors with the library's own state size (nothing is computed)."""
     lib = _lib.load()
-    desc = F.make_desc(kind, d, M, 1, 1, 1, False, F.JITTER, F.MIN_VARIANCE, F.PHASE_CHAIN)
-    nb = ctypes.c_size_t()
-    _lib.check(lib.mobocmf_layer_chain_state_bytes(ctypes.byref(desc), ctypes.byref(nb)), "chain_state_bytes")
+    desc = F.make_desc(kind, d, M, 1, 1, 1, False, F.JITTER, F.MIN_VARIANCE)
+    bb, nb = ctypes.c_size_t(), ctypes.c_size_t()
+    _lib.check(lib.mobocmf_chain_block_bytes(ctypes.byref(desc), ctypes.byref(bb), ctypes.byref(nb)), "chain_block_bytes")
     Mp = (M + 127) // 128 * 128
     assert nb.value == (6 * Mp * Mp + 2 * Mp) * 8      # L, L^-1, L^-T, U, U^T, L_S, then a and m: the order the kernel indexes
     fc = F.FrozenChain()

@@ -40,7 +40,7 @@ int main(int argc, char** argv) {
         d.want_dx = (int32_t)U(0, 1);
         d.jitter = 1e-6;
         d.min_var = 1e-10;
-        d.phase = (int32_t)U(0, 4);
+        d.params_const = (int32_t)U(0, 1);
         bool ok = d.d <= MOBOCMF_MAX_D && d.xdiv <= MOBOCMF_MAX_XDIV;
         // the tuning travels in the descriptor: NULL (defaults) or a record with random valid knobs -- the sizes reported and the
         // regions carved below are both derived from it; now and then a record that must be refused
@@ -70,22 +70,29 @@ int main(int argc, char** argv) {
             case 0: d.kind = 2; ok = false; break;
             case 1: d.Np += 1; if (d.Np % d.xdiv) ok = false; break;
             case 2: d.M = 0; ok = false; break;
-            case 3: d.phase = 5; ok = false; break;
+            case 3: d.params_const = 2; ok = false; break;
             case 4: d.branch = 2; ok = false; break;
             case 5: d.xdiv = 0; ok = false; break;
             default: break;
         }
-        size_t sv = 0, sc = 0, bb = 0, st = 0, ps = 0, pc = 0, cs = 0, cv = 0;
+        size_t sv = 0, sc = 0, bb = 0, st = 0, ps = 0, pc = 0, cv = 0;
         const int rc = mobocmf_layer_workspace_bytes(&d, &sv, &sc);
         REQUIRE((rc == MOBOCMF_OK) == ok);
         REQUIRE((mobocmf_chain_block_bytes(&d, &bb, &st) == MOBOCMF_OK) == ok);
         REQUIRE((mobocmf_panel_workspace_bytes(&d, &ps, &pc) == MOBOCMF_OK) == ok);
-        REQUIRE((mobocmf_layer_chain_state_bytes(&d, &cs) == MOBOCMF_OK) == ok);
         REQUIRE((mobocmf_predictive_covariance_workspace_bytes(&d, &cv) == MOBOCMF_OK) == ok);
         REQUIRE(mobocmf_layer_workspace_bytes(&d, nullptr, &sc) == MOBOCMF_BAD_ARG);
         if (!ok) { ++invalid; continue; }
         ++valid;
-        REQUIRE(cs == st && cs <= sv && st <= bb && ps <= sv);
+        REQUIRE(st > 0 && st <= sv && st <= bb && ps <= sv);
+        {   // constant parameters: the PANEL workspaces are reported, and are no smaller (the same carve serves both)
+            mobocmf_layer_desc dc = d, dv = d;
+            dc.params_const = 1;
+            dv.params_const = 0;
+            size_t cps = 0, cpc = 0, vps = 0, vpc = 0;
+            REQUIRE(mobocmf_panel_workspace_bytes(&dc, &cps, &cpc) == MOBOCMF_OK);
+            REQUIRE(mobocmf_panel_workspace_bytes(&dv, &vps, &vpc) == MOBOCMF_OK && cps >= vps && cpc >= vpc);
+        }
         {   // syrk workspace: multiples of 128 only
             const int32_t Mr = (int32_t)((d.M + 127) / 128 * 128);
             const int64_t Kd = (d.Np + 127) / 128 * 128;
