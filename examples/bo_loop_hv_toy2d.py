@@ -65,13 +65,14 @@ def fit_only(x, fid, epochs, seed, device="cuda", model_kwargs=None, previous=No
     return fitter
 
 
-def score(fitter, grid):
-    """The six numbers of one iteration (toy_synthetic_2D_JESMOCMF.py:537-618) on the true high-fidelity functions."""
+def score(fitter, grid, recommend_search="grid"):
+    """The six numbers of one iteration (toy_synthetic_2D_JESMOCMF.py:537-618) on the true high-fidelity functions.
+    ``recommend_search``: ``recommend``'s ``search`` ("evolve": NSGA-II on the GPU over the predictions, from the grid's rows)."""
     bb = blackboxes()
     objs = [hi for _, hi, is_con in bb.values() if not is_con]
     cons = [hi for _, hi, is_con in bb.values() if is_con]
     ind = HV(ref_point=REF_POINT)
-    rec_set, _, _ = fitter.recommend(grid, min_feasible_prob=0.999)
+    rec_set, _, _ = fitter.recommend(grid, min_feasible_prob=0.999, search=recommend_search)
     true_cons = np.stack([c(rec_set) for c in cons], 1) if rec_set.shape[0] else np.zeros((0, len(cons)))
     feasible = not np.any(true_cons < 0)
     num_ini = rec_set.shape[0]
@@ -85,11 +86,12 @@ def score(fitter, grid):
 
 
 def loop_hv(iters=5, acq="jes", seed=0, out_dir=".", epochs=300, verbose=True, num_inducing=None, inducing="first",
-            warm_start=False, warm_epochs=None, pareto_samples=1, pareto_search="grid", **kw):
+            warm_start=False, warm_epochs=None, pareto_samples=1, pareto_search="grid", recommend_search="grid", **kw):
     """``iters`` BO iterations, each one scored and appended to ``out_dir``/hypervolumes.txt; returns the rows.
     ``warm_start``: every iteration after the first starts from the last one's unconditioned fit, ``warm_epochs`` epochs of
     phase 2 (default: ``epochs``).  ``pareto_samples``: JES averaged over this many sampled Pareto sets.  ``pareto_search``: the fitter's
-    (``"evolve"``: NSGA-II on the GPU from the grid's rows)."""
+    (``"evolve"``: NSGA-II on the GPU from the grid's rows).  ``recommend_search``: how the recommendation that is scored is
+    searched (``score``)."""
     warm_epochs = (epochs if warm_epochs is None else warm_epochs) if warm_start else None
     previous = None
     model_kwargs = {"pareto_search": pareto_search}
@@ -120,7 +122,7 @@ def loop_hv(iters=5, acq="jes", seed=0, out_dir=".", epochs=300, verbose=True, n
                                               model_kwargs=model_kwargs, previous=previous, warm_epochs=warm_epochs,
                                               pareto_samples=pareto_samples, **kw)
             previous = jes.blackbox_mfdgp_fitter_uncond if warm_start else None
-        row = score(fitter, grid)
+        row = score(fitter, grid, recommend_search)
         with open(path, "a") as f:
             print("%lf %lf %lf %lf %lf %lf" % row, file=f)
         rows.append(row)
@@ -150,9 +152,12 @@ if __name__ == "__main__":
                     help="average the JES acquisition over this many sampled Pareto sets (one conditioned fit each)")
     ap.add_argument("--pareto-search", choices=["grid", "evolve"], default="grid",
                     help="how the sampled Pareto set is searched: the random grid, or NSGA-II on the GPU started from it")
+    ap.add_argument("--recommend-search", choices=["grid", "evolve"], default="grid",
+                    help="how the scored recommendation is searched: the random grid, or NSGA-II on the GPU over the "
+                         "surrogates' predictions started from it")
     a = ap.parse_args()
     if a.warm_epochs is not None and not a.warm_start:
         ap.error("--warm-epochs needs --warm-start")
     loop_hv(iters=a.iters, acq=a.acq, seed=a.seed, out_dir=a.out, epochs=a.epochs, num_inducing=a.num_inducing,
             inducing=a.inducing, warm_start=a.warm_start, warm_epochs=a.warm_epochs, pareto_samples=a.pareto_samples,
-            pareto_search=a.pareto_search)
+            pareto_search=a.pareto_search, recommend_search=a.recommend_search)

@@ -411,6 +411,37 @@ int mobocmf_nsga_vary(int32_t Np, int32_t d, const double* X, const int32_t* ran
                       const int64_t* generation, const mobocmf_nsga_options* opt, double* children, int32_t* parents,
                       mobocmf_stream_t stream);
 
+/* ------------------------------------------------------------------ the recommendation's NSGA operands (csrc/recommend.hip)
+ * What mobocmf_nsga_survive ranks when the rows are scored by fitted surrogates instead of chain samples (BlackBoxMFDGPFitter.
+ * recommend(search="evolve")): the objectives are the surrogates' top-fidelity predictive means, the violation grades the
+ * feasibility rule of mobocmf_pareto_mask.  It turns a predict group's raw top-layer moments into F and viol in ONE launch on
+ * `stream`; no atomics, a fixed summation order (two calls on the same inputs are bitwise equal); it allocates nothing, reads
+ * nothing on the host and keeps no state: capturable.
+ *   moments  (n_obj + n_con, 2, T S): per model its means, then its variances WITHOUT noise, column t S + s (the moments of a
+ *            predict group); the n_obj objectives come first, then the n_con constraints.
+ *   scale    NULL, or (n_obj + n_con, 2): (shift, factor) per model -- recommend's output_scaling (mean, std).
+ * Per model and test point t -- every operation below is one IEEE float64 operation as written, nothing fused:
+ *   S = 1:  mbar = mu_0, v = var_0 exactly.
+ *   else:   a = 0, q = 0; for s = 0 .. S - 1 in order: a = a + mu_s, q = q + (var_s + mu_s * mu_s);
+ *           mbar = a / S, v = q / S - mbar * mbar.
+ *   scale:  mbar = mbar * factor + shift, v = (v * factor) * factor.
+ * Objective j (minimised): F[j * ldf + t] = mbar_j (ldf >= T).
+ * Constraint c: z = mbar / sqrt(v).  It is feasible iff 0.5 erfc(-(z / sqrt(2))) > p_min -- the rule of mobocmf_pareto_mask on
+ *   noise-free variances: v < 0 is infeasible, at v == 0 the sign of mbar decides.  viol_c = 0 when feasible, else
+ *   max(z_min - z, DBL_MIN); viol_c = +inf when v < 0 or z is NaN.  viol[t] = sum_c viol_c, summed from 0.0 in the order of c
+ *   (n_con = 0: 0.0, and viol may be NULL).
+ *   z_min: the caller passes Phi^-1(p_min).  It only GRADES infeasible rows -- a violation measured in probability is flat where
+ *   Phi saturates, and a constraint-domination search among infeasible rows needs a slope -- and never decides feasibility:
+ *   viol[t] == 0 exactly where every constraint passes the rule above.
+ * sqrt and the division of z are the only operations the stated order does not pin to the bit.
+ * One launch of T workgroups of one wavefront: a lane per model sums its S samples in order, one lane adds the constraints'
+ * terms in order.
+ * MOBOCMF_BAD_ARG (on the host, before any HIP call): moments or F NULL; n_obj outside 1..MOBOCMF_PARETO_MAX_K; n_con < 0;
+ * n_obj + n_con > 64; T < 1; S < 1; T S > MOBOCMF_ACQ_MAX_COLUMNS; ldf < T; viol NULL with n_con > 0; p_min not inside (0, 1);
+ * z_min not finite. */
+int mobocmf_recommend_scores(const double* moments, int32_t n_obj, int32_t n_con, int32_t T, int32_t S, const double* scale,
+                             double p_min, double z_min, double* F, int64_t ldf, double* viol, mobocmf_stream_t stream);
+
 /* Inducing-point selection by greedy conditional variance: the incomplete pivoted Cholesky of K_nn under the kind-0 kernel
  * (the one mobocmf_gram_forward(kind 0) evaluates).  x [N x d] row-major (1 <= d <= MOBOCMF_MAX_D), hyp = [a, ls[0..d)].
  * Step j picks the row with the largest residual d = diag(K_nn - K_nm K_mm^-1 K_mn) over the rows picked so far -- of

@@ -213,6 +213,7 @@ SYMBOLS = {
     "mobocmf_nsga_options_init": [ctypes.POINTER(NsgaOptions)],
     "mobocmf_nsga_survive": [_I32, _I32, _I32, _I32, _P, _P, _I64, _P, _P, _P, _I64, _P, _P, _P, _P, _P, _P],
     "mobocmf_nsga_vary": [_I32, _I32, _P, _P, _P, ctypes.c_uint64, _P, ctypes.POINTER(NsgaOptions), _P, _P, _P],
+    "mobocmf_recommend_scores": [_P, _I32, _I32, _I32, _I32, _P, _D, _D, _P, _I64, _P, _P],
     "mobocmf_select_inducing_workspace_bytes": [_I64, _I32, ctypes.POINTER(_SZ)],
     "mobocmf_select_inducing": [_I64, _I32, _P, _P, _I32, _D, _I32, _P, _P, _P, _P, _P, _P, _SZ, _P],
     "mobocmf_minibatch_permutation_host": [_I64, _I64, _I64, _P],

@@ -1829,6 +1829,53 @@ def rff_evolve(x0, params, layers, n_obj, thr, generations, seed, options=None):
     return eng.result()
 
 
+def recommend_z_min(p_min):
+    """Phi^-1(p_min): the ``z_min`` of ``recommend_scores`` for the feasibility probability ``p_min`` (0.0 for a ``p_min``
+    outside (0, 1): the library refuses that one itself)."""
+    import statistics
+    p_min = float(p_min)
+    return statistics.NormalDist().inv_cdf(p_min) if 0.0 < p_min < 1.0 else 0.0
+
+
+def recommend_scores(moments, n_obj, T, S, scale=None, p_min=0.999, z_min=None, F=None, viol=None, stream=None):
+    """mobocmf_recommend_scores: a predict group's raw ``moments`` (n_obj + n_con, 2, T S) -- objectives first -- as the operands of
+    ``nsga_survive``: ``F`` (n_obj, T) the predictive means over the S samples (minimised), ``viol`` (T,) the graded violation of
+    ``pareto_mask``'s rule on noise-free variances, 0 exactly where every constraint has Phi(mbar / sqrt(v)) > ``p_min``, else
+    sum_c max(z_min - z_c, DBL_MIN) over the failing constraints (+inf for v < 0 or a NaN).  ``scale`` (n_obj + n_con, 2): (shift,
+    factor) per model; ``z_min`` None: Phi^-1(p_min).  ``F`` / ``viol`` given: written in place (``F`` may be a column slice of a
+    wider array: unit column stride), else new tensors (``viol`` None without constraints).  One launch, only enqueues (on
+    ``stream``, default the current one): capturable.  Returns (F, viol)."""
+    lib = _lib.require_device()
+    with torch.no_grad():
+        if not torch.is_tensor(moments) or moments.dim() != 3 or moments.shape[1] != 2 or not moments.is_contiguous() \
+                or moments.dtype != torch.float64 or not moments.is_cuda:
+            raise _lib.MobocmfError("recommend_scores: moments must be a contiguous (n_obj + n_con, 2, T S) float64 tensor on a GPU")
+        n_obj, T, S = int(n_obj), int(T), int(S)
+        n_con = moments.shape[0] - n_obj
+        if T >= 1 and S >= 1 and moments.shape[2] != T * S:
+            raise _lib.MobocmfError("recommend_scores: moments has %d columns, not T S = %d" % (moments.shape[2], T * S))
+        dev = moments.device
+        if scale is not None:
+            scale = _prep(torch.as_tensor(scale, dtype=torch.float64, device=dev))
+            if tuple(scale.shape) != (moments.shape[0], 2):
+                raise _lib.MobocmfError("recommend_scores: scale must be (n_obj + n_con, 2)")
+        if F is None:
+            F = _empty(max(n_obj, 0), max(T, 0), device=dev)
+        elif F.dim() != 2 or F.shape[0] != n_obj or F.shape[1] < T or F.dtype != torch.float64 or F.device != dev \
+                or (F.shape[1] > 1 and F.stride(1) != 1):
+            raise _lib.MobocmfError("recommend_scores: F must be (n_obj, >= T) float64 with unit column stride")
+        if viol is None and n_con > 0:
+            viol = _empty(max(T, 0), device=dev)
+        elif viol is not None and (viol.dim() != 1 or viol.numel() < T or viol.dtype != torch.float64 or viol.device != dev
+                                   or not viol.is_contiguous()):
+            raise _lib.MobocmfError("recommend_scores: viol must be a contiguous (>= T,) float64 tensor")
+        ldf = F.shape[1] if F.shape[0] < 2 else F.stride(0)
+        _lib.check(lib.mobocmf_recommend_scores(_ptr(moments), n_obj, n_con, T, S, _ptr(scale), float(p_min),
+                                                recommend_z_min(p_min) if z_min is None else float(z_min), _ptr(F), ldf,
+                                                _ptr(viol), _on(stream)), "mobocmf_recommend_scores")
+    return F, viol
+
+
 def pareto_mask(vals, con_mean=None, con_var=None, noise=None, p_min=0.999):
     """The recommendation rule of the reference's BO driver in one call (mobocmf_pareto_mask): ``vals`` (k, n) objective values
     (minimised), optionally ``con_mean`` / ``con_var`` (K_con, n) Gaussian constraint predictions and ``noise`` (K_con,) to

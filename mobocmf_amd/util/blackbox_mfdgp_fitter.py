@@ -859,7 +859,87 @@ class BlackBoxMFDGPFitter:
         return report if self.verbose else None
 
     # ------------------------------------------------------------------ recommendation (the reference's BO driver)
-    def recommend(self, grid, min_feasible_prob=0.999, output_scaling=None):
+    def recommend(self, grid, min_feasible_prob=0.999, output_scaling=None, search="grid", evolve_population=128,
+                  evolve_generations=100, evolve_seed=0):
+        """The recommended Pareto set of the BO loop.  ``search="grid"``: the rule of ``_recommend_grid`` on the rows of ``grid``.
+        ``search="evolve"``: the grid stage first; then NSGA-II on the GPU over the same predictions under the same feasibility
+        rule (util/recommend_evolve.py, a generation per graph replay) from a population of ``evolve_population`` grid rows --
+        the grid's front, thinned to half the population by ``MOOP.compute_pareto_front_and_set_summary_y_space`` when it has
+        more rows, then the other rows by (violation ascending, row index); the largest even count; with fewer than 4 rows no
+        evolution -- for ``evolve_generations`` generations with the Philox key ``evolve_seed``.  The final rows the device calls
+        feasible that lie farther than 1e-6 from every grid row are appended to the grid and the grid stage decides over the
+        union: the returned set obeys exactly the grid mode's rule, and every row of the grid's front is in it or dominated by
+        one of its rows.  One process only; surrogates no predict group takes raise ValueError (there is no host fallback).
+
+        Returns (pareto_set, predicted_front, info) as ``_recommend_grid``; with "evolve" the kept grid rows come first, in row
+        order, then the kept evolved rows; ``info["mask"]`` stays the mask over the grid's rows, the counts are those of the
+        union, and ``info`` gains ``population`` (Np, d) the final population, ``evolved_mask`` (Np,) its rows in the returned
+        set, ``num_evolved``, ``generations`` and ``engine`` (the predict group's class name; None without evolution)."""
+        if search not in ("grid", "evolve"):
+            raise ValueError("search must be 'grid' or 'evolve' (got %r)" % (search,))
+        if not 4 <= int(evolve_population) <= 512 or int(evolve_population) % 2:
+            raise ValueError("evolve_population must be even, 4..512 (got %r)" % (evolve_population,))
+        if int(evolve_generations) < 1:
+            raise ValueError("evolve_generations must be >= 1")
+        if search == "grid":
+            return self._recommend_grid(grid, min_feasible_prob, output_scaling)
+        if parallel.world()[1] != 1:
+            raise ValueError("recommend: search='evolve' runs in one process only")
+        return self._recommend_evolve(grid, min_feasible_prob, output_scaling, int(evolve_population), int(evolve_generations),
+                                      int(evolve_seed))
+
+    def _recommend_evolve(self, grid, p_min, output_scaling, Np, generations, seed):
+        from .moop import MOOP
+        from .recommend_evolve import RecommendEvolve
+        _, grid_front, info = self._recommend_grid(grid, p_min, output_scaling)
+        grid_np = np.ascontiguousarray(grid.detach().cpu().numpy() if torch.is_tensor(grid) else np.asarray(grid),
+                                       dtype=np.float64)
+        n, d = grid_np.shape
+        pop = min(Np, n) // 2 * 2
+        new, X, generations_run, engine = np.zeros(0, dtype=np.int64), np.zeros((0, d)), 0, None
+        if pop >= 4:
+            # objectives, then constraints, each in global-index order: the order of the grid stage
+            hs = sorted(self._handlers(), key=lambda e: (e[0] != "OBJ", self._global_index(e[2], e[1])))
+            names = {id(h): name for name, h in list(self.mfdgp_handlers_objs.items()) + list(self.mfdgp_handlers_cons.items())}
+            scale = None
+            if output_scaling is not None:
+                scale = [[float(output_scaling[names[id(h)]][0]), float(output_scaling[names[id(h)]][1])] for _, _, h in hs]
+            eng = RecommendEvolve([h.mfdgp for _, _, h in hs], self.num_obj, self.num_fidelities - 1, pop, d, seed, p_min=p_min,
+                                  scale=scale)
+            try:
+                _, viol = eng.score(grid_np)
+                viol = viol.cpu().numpy()
+                front = np.flatnonzero(info["mask"])
+                if front.size > pop // 2:
+                    front = MOOP.compute_pareto_front_and_set_summary_y_space(None, front[:, None], grid_front, pop // 2)[0][:, 0]
+                rest = np.setdiff1d(np.arange(n), front)
+                rest = rest[np.lexsort((rest, viol[rest]))][:pop - front.size]
+                eng.start(torch.from_numpy(grid_np[np.concatenate((front, rest))]))
+                eng.run(generations)
+                out = eng.result()
+                X, Fv, ev = (out[key].cpu().numpy() for key in ("X", "F", "viol"))
+            except BaseException:      # (the group must not keep chains of parameters that may change)
+                eng.group.thaw()
+                raise
+            eng.finish()
+            new = np.array([i for i in np.flatnonzero(ev == 0.0)
+                            if not np.isnan(Fv[:, i]).any() and np.min(np.sqrt(((grid_np - X[i]) ** 2).sum(1))) > 1e-6],
+                           dtype=np.int64)
+            generations_run, engine = generations, type(eng.group).__name__
+        evolved_mask = np.zeros(X.shape[0], dtype=bool)
+        if new.size:
+            union = np.vstack((grid_np, X[new]))
+            pareto_set, front_vals, info = self._recommend_grid(union, p_min, output_scaling)
+            evolved_mask[new] = info["mask"][n:]
+            info = dict(info, mask=info["mask"][:n])
+        else:
+            pareto_set = grid_np[info["mask"]]
+            front_vals = grid_front
+        info.update(population=X, evolved_mask=evolved_mask, num_evolved=int(evolved_mask.sum()), generations=generations_run,
+                    engine=engine)
+        return pareto_set, front_vals, info
+
+    def _recommend_grid(self, grid, min_feasible_prob=0.999, output_scaling=None):
         """The recommended Pareto set of the reference's BO loop (toy_synthetic_2D_JESMOCMF.py:537-573): every black-box's
         top-fidelity ``predict_for_acquisition`` moments on ``grid`` (n, d), the top layer's likelihood noise subtracted from
         the constraint variances, optionally un-standardised (``output_scaling``: black-box name -> (mean, std); means
