@@ -208,6 +208,32 @@ int mobocmf_gram_forward_rep(int32_t kind, int32_t d, const double* x1, const do
                              const double* f2, int64_t nbase2, int32_t xdiv, const double* hyp, double* K, int64_t ldk,
                              double* knn, mobocmf_stream_t stream);
 
+/* The Gram backward of the same launch, alone: given G = dL/dK [n1 x nbase2 * xdiv] (row-major, ldk >= nbase2 * xdiv) and
+ * gknn = dL/dknn (nbase2 * xdiv values, or NULL), the gradients of L with respect to hyp, f1, f2 and x2.  Arguments as in
+ * mobocmf_gram_forward_rep: rows are x1 / f1, columns the rows of x2 replicated xdiv-fold with f2.  This is the launch that
+ * ends a layer's PANEL backward (the Gram kernel writes per-workgroup partial sums, one reduction launch adds them up), the
+ * replica fast paths included (kind 1, xdiv 8 / 16 with f2 and G 16-byte aligned and ldk even; anything else takes the
+ * general path, same values up to summation order).
+ *   G             rows >= n1 are never read.  col_activity (may be NULL = all active): one word per 128 columns,
+ *                 ceil(nbase2 * xdiv / 128) words; the columns of a block whose word is zero are never read and count as exact
+ *                 zeros (the block was never written, it may hold anything).
+ *   gknn          is read at EVERY column, whatever col_activity says (a layer's is zero in inactive blocks).
+ *   g_hyp         [1 + d] (kind 0) or [5 + 2 d] (kind 1), OVERWRITTEN, like every output.
+ *   g_f1, g_f2    [n1], [nbase2 * xdiv]: kind 1 only (kind 0: not touched, may be NULL).  g_f2 is exactly 0 in an inactive
+ *                 block when gknn is NULL or zero there.
+ *   g_x2          [nbase2 x d], the gradient with respect to the column-side inputs; NULL = it is not formed.
+ *   workspace     the partial sums, >= the bytes mobocmf_gram_backward_workspace_bytes reports for the same shape and
+ *                 want_dx = (g_x2 != NULL); MOBOCMF_WORKSPACE_TOO_SMALL below that.  Nothing beyond the reported size is written.
+ * geometry (may be NULL) receives the launch: [0] workgroups along the columns (128 base rows each), [1] along the rows,
+ * [2] rows of x1 per workgroup (8, 16 or 32).  The partial counts the reduction sees follow from it: [0] * [1] for g_hyp,
+ * [1] for g_f2 and g_x2, [0] for g_f1. */
+int mobocmf_gram_backward_workspace_bytes(int32_t kind, int32_t d, int64_t n1, int64_t nbase2, int32_t xdiv, int32_t want_dx,
+                                          size_t* bytes, int32_t* geometry);
+int mobocmf_gram_backward(int32_t kind, int32_t d, const double* x1, const double* f1, int64_t n1, const double* x2,
+                          const double* f2, int64_t nbase2, int32_t xdiv, const double* hyp, const double* G, int64_t ldk,
+                          const double* gknn, const int32_t* col_activity, double* g_hyp, double* g_f1, double* g_f2,
+                          double* g_x2, void* workspace, size_t workspace_bytes, mobocmf_stream_t stream);
+
 /* One random-Fourier-feature function sample of a layer evaluated at n points (mfdgp_hidden_layer.py:326-337, :402-444; the
  * Pareto-grid evaluation of moop.py:232-272), without materialising the F x n feature matrix:
  *   kind 0:  out[i] = sum_j theta[j] s0 cos(W1[j].x_i + b1[j])

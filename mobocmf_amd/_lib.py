@@ -222,6 +222,8 @@ SYMBOLS = {
     "mobocmf_minibatch_accumulate": [_I64, _I64, _P, _P, _P, _P, _P],
     "mobocmf_gram_forward": [_I32, _I32, _P, _P, _I64, _P, _P, _I64, _P, _P, _I64, _P],
     "mobocmf_gram_forward_rep": [_I32, _I32, _P, _P, _I64, _P, _P, _I64, _I32, _P, _P, _I64, _P, _P],
+    "mobocmf_gram_backward_workspace_bytes": [_I32, _I32, _I64, _I64, _I32, _I32, ctypes.POINTER(_SZ), ctypes.POINTER(_I32)],
+    "mobocmf_gram_backward": [_I32, _I32, _P, _P, _I64, _P, _P, _I64, _I32, _P, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _SZ, _P],
     "mobocmf_check_info": [_P, ctypes.POINTER(_I32), _P],
     "mobocmf_natgrad_workspace_bytes": [_I32, _I32, ctypes.POINTER(_SZ)],
     "mobocmf_natgrad_step": [_I32, _I32, _P, _P, _P, _P, _D, _D, _I32, _D, _P, _P, _P, _P, _SZ, ctypes.POINTER(Tuning), _P],

@@ -622,7 +622,7 @@ bool carve_cov(void* scratch, size_t bytes, const mobocmf_layer_desc* d, const D
 
 extern "C" {
 
-int mobocmf_version(void) { return 201; }
+int mobocmf_version(void) { return 202; }
 
 int mobocmf_device_arch_ok(void) {
     int dev = 0;
@@ -1022,6 +1022,63 @@ int mobocmf_gram_forward_rep(int32_t kind, int32_t d, const double* x1, const do
     g.x = x2; g.f = f2; g.nbase = nbase2; g.Zx = x1; g.zf = f1; g.M = (int)n1; g.hyp = hyp;
     g.K = K; g.ldk = ldk; g.Mp = (int)round_up(n1, 32); g.Np = nbase2 * xdiv; g.knn = knn; g.jitter = 0.0; g.is_kmm = 0;
     return launch_gram_fwd(g, (hipStream_t)stream);
+}
+
+// The Gram backward alone: the shapes of mobocmf_gram_forward_rep, the partials carved out of the caller's workspace in the
+// layout gram_grid gives (hyp | df | dzf | dx, as carve_panel_bwd lays them out).
+static bool gram_bwd_shape_ok(int32_t kind, int32_t d, int64_t n1, int64_t nbase2, int32_t xdiv) {
+    return (kind == 0 || kind == 1) && d >= 1 && d <= MOBOCMF_MAX_D && n1 >= 1 && nbase2 >= 1 && xdiv >= 1 &&
+           xdiv <= MOBOCMF_MAX_XDIV && n1 <= 0x7fffffff - 32 && nbase2 <= 0x7fffffff;
+}
+static void gram_bwd_carve(Bump& b, GramArgs& g, bool want_dx, dim3* grid) {
+    gram_grid(g, grid);
+    g.hyp_part = b.take((int64_t)grid->x * grid->y * hyp_len(g.kind, g.d));
+    g.df_part = g.kind == 1 ? b.take((int64_t)grid->y * g.Np) : nullptr;
+    g.dzf_part = g.kind == 1 ? b.take((int64_t)grid->x * g.Mp) : nullptr;
+    g.dx_part = want_dx ? b.take((int64_t)grid->y * g.nbase * g.d) : nullptr;
+}
+
+int mobocmf_gram_backward_workspace_bytes(int32_t kind, int32_t d, int64_t n1, int64_t nbase2, int32_t xdiv, int32_t want_dx,
+                                          size_t* bytes, int32_t* geometry) {
+    if (!gram_bwd_shape_ok(kind, d, n1, nbase2, xdiv) || !bytes) return MOBOCMF_BAD_ARG;
+    GramArgs g = {};
+    g.kind = kind; g.d = d; g.xdiv = xdiv; g.nbase = nbase2; g.Mp = (int)round_up(n1, 32); g.Np = nbase2 * xdiv;
+    Bump b(nullptr, ~(size_t)0 >> 1);
+    dim3 grid;
+    gram_bwd_carve(b, g, want_dx != 0, &grid);
+    *bytes = b.off;
+    if (geometry) { geometry[0] = (int32_t)grid.x; geometry[1] = (int32_t)grid.y; geometry[2] = g.Mp / (int32_t)grid.y; }
+    return MOBOCMF_OK;
+}
+
+int mobocmf_gram_backward(int32_t kind, int32_t d, const double* x1, const double* f1, int64_t n1, const double* x2,
+                          const double* f2, int64_t nbase2, int32_t xdiv, const double* hyp, const double* G, int64_t ldk,
+                          const double* gknn, const int32_t* col_activity, double* g_hyp, double* g_f1, double* g_f2,
+                          double* g_x2, void* workspace, size_t workspace_bytes, mobocmf_stream_t stream) {
+    if (!gram_bwd_shape_ok(kind, d, n1, nbase2, xdiv) || !x1 || !x2 || !hyp || !G || !g_hyp || !workspace ||
+        ldk < nbase2 * xdiv || (kind == 1 && (!f1 || !f2 || !g_f1 || !g_f2)))
+        return MOBOCMF_BAD_ARG;
+    const bool want_dx = g_x2 != nullptr;
+    GramArgs g = {};
+    g.kind = kind; g.d = d; g.xdiv = xdiv; g.zdiv = 1;
+    g.x = x2; g.f = f2; g.nbase = nbase2; g.Zx = x1; g.zf = f1; g.M = (int)n1; g.hyp = hyp;
+    g.ldk = ldk; g.Mp = (int)round_up(n1, 32); g.Np = nbase2 * xdiv; g.G = G; g.gknn = gknn; g.colact = col_activity;
+    Bump b(workspace, workspace_bytes);
+    dim3 grid;
+    gram_bwd_carve(b, g, want_dx, &grid);
+    if (!b.ok) return MOBOCMF_WORKSPACE_TOO_SMALL;
+    hipStream_t s = (hipStream_t)stream;
+    TRY(launch_gram_bwd(g, want_dx, s));
+    const int H = hyp_len(kind, d);
+    SumTask tk[4];
+    int nt = 0;
+    tk[nt++] = {g.hyp_part, (int64_t)grid.x * grid.y, H, nullptr, 0, 0, g_hyp, H, 0};
+    if (kind == 1) {
+        tk[nt++] = {g.df_part, grid.y, g.Np, nullptr, 0, 0, g_f2, g.Np, 0};
+        tk[nt++] = {g.dzf_part, grid.x, g.Mp, nullptr, 0, 0, g_f1, n1, 0};
+    }
+    if (want_dx) tk[nt++] = {g.dx_part, grid.y, nbase2 * d, nullptr, 0, 0, g_x2, nbase2 * d, 0};
+    return launch_sum_partials_multi(tk, nt, s);
 }
 
 int mobocmf_gemm_f64_epilogue(int32_t tri, int32_t epi, int32_t Mr, int64_t Nc, int64_t Kd, const double* A, int64_t lda,

@@ -277,6 +277,265 @@ def gram_violations(got, K, W, c=None):
     return int(bad.sum()), float(ratio.max()) if ratio.size else 0.0
 
 
+# ---- Gram backward (gram.hip: gram_bwd_kernel + sum_partials_multi_kernel; include/mobocmf_hip.h, mobocmf_gram_backward)
+# With L = sum G . K + sum gknn . knn every output component theta is a sum of ADDENDS G_mn dterm_mn/dtheta over (m, n, term)
+# (plus gknn_n dknn_n/dtheta, exponent 0), the three terms and their exponents being those of gram_hp.  The addends cancel
+# (sum |addend| / |sum| of 20 .. 2e5), so the bound is on the sum of their magnitudes, never on the value:
+#     |got - ref| <= 2^-53 (c W + D A),    A = sum |G| |dterm/dtheta|,    W = sum (2 + |arg_term|) |G| |dterm/dtheta|.
+# c W covers the evaluation of each addend (exponent, exp, the products); c = GRAM_BWD_C = 4 x GRAM_BWD_RATIO_MEASURED, the
+# ratio being the worst err / (2^-53 W) of the float64 CPU restatement gram_bwd_f64 below (these statements in float64 with
+# numpy's pairwise sums) over the cases of tests/test_kernel_reference_cpu.py::test_gram_backward_constant_is_the_measured_one,
+# recorded rounded up.  Measured 4.05 (kind 1, d = 32; 0.7 .. 1.4 at d <= 3, 2.3 .. 2.9 at d = 8, 9).  Autograd over the oracle
+# is NOT the restatement: it forms x / ls - z / ls, which loses 2 u |x| / |x - z| of the d/dx and d/dls addends -- err / (2^-53 W)
+# of 1e3 .. 2e4 at gram_case's near-coincident columns -- while the device, like gram_bwd_f64, takes the difference first.
+# D A covers the additions on the device, first order, worst case: D (gram_bwd_depth) is the number of roundings a partial sum
+# holding the addend can pass through.
+GRAM_BWD_RATIO_MEASURED = 4.1
+GRAM_BWD_C = 4.0 * GRAM_BWD_RATIO_MEASURED
+GRAM_BWD_NBASE2 = (1, 127, 129, 257)
+GRAM_BWD_OUTPUTS = ("hyp", "g_f1", "g_f2", "g_x2")
+
+
+def gram_bwd_inputs(n1, Np, seed=0, active=None):
+    """(G [n1 x Np], gknn [Np]) standard normal; gknn zero in the inactive 128-column blocks, as a layer's is."""
+    rng = np.random.default_rng(77 + seed)
+    G, gk = rng.standard_normal((n1, Np)), rng.standard_normal(Np)
+    if active is not None:
+        gk = np.where(column_mask(active, Np), gk, 0.0)
+    return G, gk
+
+
+def column_mask(active, Np):
+    """bool [Np] from one activity word per 128 columns."""
+    assert len(active) == (Np + 127) // 128
+    return np.repeat(np.asarray(active) != 0, 128)[:Np]
+
+
+def sum_form(P, length):
+    """The form launch_sum_partials_multi picks for a task of P partials and ``length`` outputs: 0 serial (one thread adds
+    the P partials in turn), 1 wide (P >= 64 and length <= 4096: 256 threads stride over the partials, a wavefront butterfly,
+    four wavefront sums), 2 four-way (P >= 16: four threads take every fourth partial, combined pairwise)."""
+    return 1 if (P >= 64 and length <= 4096) else (2 if P >= 16 else 0)
+
+
+def sum_depth(P, length):
+    """Additions a partial can pass through in that reduction.  serial: v = 0, v += part[p]: P.  wide: ceil(P / 256) strided
+    adds, six butterfly steps, sh[0] + sh[1] + sh[2] + sh[3]: ceil(P / 256) + 9.  four-way: ceil(P / 4) strided adds, then
+    (s0 + s1) + (s2 + s3): ceil(P / 4) + 2."""
+    form = sum_form(P, length)
+    return -(-P // 256) + 9 if form == 1 else (-(-P // 4) + 2 if form == 2 else P)
+
+
+GRAM_BWD_MULS = 6
+
+
+def gram_bwd_tasks(kind, d, n1, nbase2, xdiv, geometry):
+    """{output: (P, length)} of the reduction tasks mobocmf_gram_backward launches, from the geometry of the size query."""
+    gx, gy, _ = geometry
+    t = {"hyp": (gx * gy, 1 + d if kind == 0 else 5 + 2 * d), "g_x2": (gy, nbase2 * d)}
+    if kind == 1:
+        t["g_f2"], t["g_f1"] = (gy, nbase2 * xdiv), (gx, n1)
+    return t
+
+
+def gram_bwd_depth(kind, d, n1, nbase2, xdiv, geometry):
+    """D per output: the roundings a partial sum that holds a given addend can pass through on the device, read off
+    gram_bwd_kernel (gm = geometry[2] rows of x1 per workgroup, walked serially by a thread that owns one base row and its
+    xdiv replicas) and sum_partials_multi_kernel.  Additions:
+      hyp   the replica sums (Gsum; S1 .. S4, G2s): xdiv; nu zf S1 + af S2: 1; the thread's accumulator (s_a1 .., aL1, aL2)
+            over its rows: gm (the k_nn addends enter it first: xdiv + gm, no more); wave_sum: 6; red[0] + red[1]: 1; the
+            reduction over grid x * grid y partials.                                       xdiv + gm + 8 + sum_depth
+      g_f1  the replica sums: xdiv; aE1 nu S1 + c_b S3: 1; wave_sum: 6; the two wavefronts' LDS atomic adds into a zeroed
+            slot: 2; the reduction over grid x partials.                                   xdiv + 9 + sum_depth
+      g_f2  Gv c_a - T c_b: 1; the general path's acc = 0 + that: 1; the column's accumulator over the rows: gm; the k_nn
+            term: 1; the reduction over grid y partials.                                   gm + 3 + sum_depth
+      g_x2  the replica sums and nu zf S1 + af S2: xdiv + 1; W1 t1 il1 + W2 t2 il2: 1; aX over the rows: gm; the reduction
+            over grid y partials.                                                          xdiv + gm + 2 + sum_depth
+    Products applied to a sum of addends round it once more each; the most any output sees is six (aE1 * (nu * zf * S1 + ..),
+    W1 * t1 * t1, the final * il1): GRAM_BWD_MULS, added to every D.  Products inside one addend belong to c W."""
+    gm = geometry[2]
+    tasks = gram_bwd_tasks(kind, d, n1, nbase2, xdiv, geometry)
+    chain = {"hyp": xdiv + gm + 8, "g_f1": xdiv + 9, "g_f2": gm + 3, "g_x2": xdiv + gm + 2}
+    return {k: chain[k] + GRAM_BWD_MULS + sum_depth(*pl) for k, pl in tasks.items()}
+
+
+def _gram_bwd(kind, c, xdiv, G, gknn, active, T):
+    """The gradients and their weights in the number format ``T`` converts to: {output: (value, W, A)}."""
+    x1, x2, hyp = T(c["x1"]), T(c["x2"]), T(c["hyp"])
+    n1, d = x1.shape
+    nb = x2.shape[0]
+    Np = nb * xdiv
+    G = np.asarray(G, np.float64)
+    assert G.shape == (n1, Np)
+    if active is not None:
+        G = np.where(column_mask(active, Np)[None, :], G, 0.0)        # inactive blocks may hold NaN: they count as zero
+    G = T(G).reshape(n1, nb, xdiv)
+    aG = np.abs(G)
+    Gs, aGs = G.sum(2), aG.sum(2)
+    half = T(0.5)
+    diff = [x1[:, None, k] - x2[None, :, k] for k in range(d)]         # d matrices n1 x nb
+
+    def arg(ls):
+        s = 0
+        for k in range(d):
+            t = diff[k] / ls[k]
+            s = s + t * t
+        return half * s
+
+    def red(terms, axes):
+        """terms: (signed weight G or Gs, its magnitude, d term / d theta, 2 + |arg|) -> (value, W, A) summed over ``axes``."""
+        v = sum((g * dt).sum(axes) for g, _, dt, _ in terms)
+        A = sum((a * np.abs(dt)).sum(axes) for _, a, dt, _ in terms)
+        W = sum((w * a * np.abs(dt)).sum(axes) for _, a, dt, w in terms)
+        return [v, W, A]
+
+    ALL2, ALL3 = (0, 1), (0, 1, 2)
+    if kind == 0:
+        alpha, ls = hyp[0], hyp[1:1 + d]
+        g1 = arg(ls)
+        E, w = np.exp(-g1), 2 + g1
+        K = alpha * E
+        hy = [red([(Gs, aGs, E, w)], ALL2)]
+        gx = []
+        for k in range(d):
+            t = diff[k] / ls[k]
+            hy.append(red([(Gs, aGs, K * t * t / ls[k], w)], ALL2))
+            gx.append(red([(Gs, aGs, K * diff[k] / (ls[k] * ls[k]), w)], 0))
+        out = {"hyp": tuple(np.array([h[i] for h in hy], dtype=x1.dtype) for i in range(3)),
+               "g_x2": tuple(np.stack([g[i] for g in gx], 1) for i in range(3))}
+        return _gram_bwd_knn(kind, c, out, gknn, T)
+    a1, af, nu, a2, lsf = hyp[:5]
+    ls1, ls2 = hyp[5:5 + d], hyp[5 + d:5 + 2 * d]
+    f1, f2 = T(c["f1"]), T(c["f2"]).reshape(nb, xdiv)
+    g1, g2 = arg(ls1), arg(ls2)
+    E1, E2 = np.exp(-g1)[:, :, None], np.exp(-g2)
+    fdif = f2[None, :, :] - f1[:, None, None]
+    gf = half * (fdif / lsf) ** 2
+    Ef = np.exp(-gf)
+    p = f1[:, None, None] * f2[None, :, :]
+    w1 = (2 + g1)[:, :, None] + 0 * gf
+    w2, w3 = w1 + gf, 2 + g2
+    T1, T2, T3 = a1 * E1 * nu * p, a1 * E1 * af * Ef, a2 * E2
+    hy = [red([(G, aG, E1 * nu * p, w1), (G, aG, E1 * af * Ef, w2)], ALL3),
+          red([(G, aG, a1 * E1 * Ef, w2)], ALL3),
+          red([(G, aG, a1 * E1 * p, w1)], ALL3),
+          red([(Gs, aGs, E2, w3)], ALL2),
+          red([(G, aG, T2 * (2 * gf) / lsf, w2)], ALL3)]
+    # the x-only factors: per (row, base row) the replica sums of G (T1 + T2), of their magnitudes and of the weighted ones
+    Qv, QA, QW = (G * (T1 + T2)).sum(2), (aG * (np.abs(T1) + np.abs(T2))).sum(2), (aG * (w1 * np.abs(T1) + w2 * np.abs(T2))).sum(2)
+    R3 = aGs * np.abs(T3)
+    l1, l2, gx = [], [], []
+    for k in range(d):
+        r1, r2 = (diff[k] / ls1[k]) ** 2 / ls1[k], (diff[k] / ls2[k]) ** 2 / ls2[k]
+        l1.append([(Qv * r1).sum(), (QW * r1).sum(), (QA * r1).sum()])
+        l2.append(red([(Gs, aGs, T3 * r2, w3)], ALL2))
+        s1, s2 = diff[k] / (ls1[k] * ls1[k]), diff[k] / (ls2[k] * ls2[k])
+        gx.append([(Qv * s1 + Gs * T3 * s2).sum(0), (QW * np.abs(s1) + w3 * R3 * np.abs(s2)).sum(0),
+                   (QA * np.abs(s1) + R3 * np.abs(s2)).sum(0)])
+    hy = hy + l1 + l2
+    dT2 = T2 * fdif / (lsf * lsf)
+    gf1 = red([(G, aG, a1 * E1 * nu * f2[None, :, :], w1), (G, aG, dT2, w2)], (1, 2))
+    gf2 = [a.reshape(Np) for a in red([(G, aG, a1 * E1 * nu * f1[:, None, None] + 0 * gf, w1), (G, aG, -dT2, w2)], 0)]
+    out = {"hyp": tuple(np.array([h[i] for h in hy], dtype=x1.dtype) for i in range(3)),
+           "g_f1": tuple(gf1), "g_f2": tuple(gf2), "g_x2": tuple(np.stack([g[i] for g in gx], 1) for i in range(3))}
+    return _gram_bwd_knn(kind, c, out, gknn, T)
+
+
+def _gram_bwd_knn(kind, c, ref, gknn, T):
+    """``ref`` (the G part) plus the addends gknn_n dknn_n / dtheta (exponent 0: weight 2), knn = alpha (kind 0) or
+    a1 (nu f^2 + af) + a2: into alpha, or into a1 (two terms), af, nu, a2 and g_f2."""
+    if gknn is None:
+        return ref
+    gk, hyp = T(gknn), T(c["hyp"])
+    ref = {k: tuple(a.copy() for a in v) for k, v in ref.items()}
+
+    def add(o, i, dknn):
+        v, W, A = o
+        t = gk * dknn
+        if i is None:
+            v += t; W += 2 * np.abs(t); A += np.abs(t)
+        else:
+            v[i] += t.sum(); W[i] += 2 * np.abs(t).sum(); A[i] += np.abs(t).sum()
+
+    if kind == 0:
+        add(ref["hyp"], 0, 1 + 0 * gk)
+        return ref
+    a1, af, nu = hyp[0], hyp[1], hyp[2]
+    f = T(c["f2"])
+    add(ref["hyp"], 0, nu * f * f)
+    add(ref["hyp"], 0, af + 0 * gk)
+    add(ref["hyp"], 1, a1 + 0 * gk)
+    add(ref["hyp"], 2, a1 * f * f)
+    add(ref["hyp"], 3, 1 + 0 * gk)
+    add(ref["g_f2"], None, 2 * a1 * nu * f)
+    return ref
+
+
+def gram_bwd_hp(kind, c, xdiv, G, gknn=None, active=None):
+    """{output: (gradient, W, A)} in longdouble for ``c`` = gram_case(...): 'hyp' [1 + d | 5 + 2 d], 'g_f1' [n1] and 'g_f2'
+    [nbase2 xdiv] (kind 1), 'g_x2' [nbase2 x d].  G [n1 x nbase2 xdiv] float64; the columns of 128-blocks that ``active`` (one
+    word per block) marks inactive count as zero whatever they hold; gknn [nbase2 xdiv] or None enters at every column."""
+    assert HAVE_LONGDOUBLE
+    return _gram_bwd(kind, c, xdiv, G, gknn, active, ld)
+
+
+def gram_bwd_hp_with_knn(kind, c, ref, gknn):
+    """gram_bwd_hp(..., gknn) from ``ref`` = gram_bwd_hp(..., None) of the same case: the k_nn addends do not depend on G."""
+    return _gram_bwd_knn(kind, c, ref, gknn, ld)
+
+
+def gram_bwd_f64(kind, c, xdiv, G, gknn=None, active=None):
+    """The same statements in float64 (numpy's pairwise sums): one of the two restatements behind GRAM_BWD_RATIO_MEASURED."""
+    return _gram_bwd(kind, c, xdiv, G, gknn, active, lambda a: np.asarray(a, np.float64))
+
+
+def gram_bwd_hp_blocks(kind, c, xdiv, blocks, Gb, gkb):
+    """The reference of a wide launch of which only the 128-column blocks ``blocks`` (sorted) are active: Gb [n1 x 128
+    len(blocks)] and gkb hold G and gknn on those columns, gknn is zero elsewhere.  Needs 128 % xdiv == 0 and a width that is a
+    multiple of 128 (a block then owns whole base rows).  Returns the dict of gram_bwd_hp at the full width, zeros (value and
+    weights) outside the blocks."""
+    nb = c["x2"].shape[0]
+    Np = nb * xdiv
+    assert 128 % xdiv == 0 and Np % 128 == 0
+    cols = np.concatenate([np.arange(128 * b, 128 * b + 128) for b in blocks])
+    rows = cols[::xdiv] // xdiv
+    sub = dict(c, x2=c["x2"][rows], f2=None if kind == 0 else c["f2"][cols])
+    r = gram_bwd_hp(kind, sub, xdiv, Gb, gkb)
+    out = {"hyp": r["hyp"]}
+    if kind == 1:
+        out["g_f1"] = r["g_f1"]
+        out["g_f2"] = tuple(_scatter(Np, cols, a) for a in r["g_f2"])
+    out["g_x2"] = tuple(_scatter((nb, c["x2"].shape[1]), rows, a) for a in r["g_x2"])
+    return out
+
+
+def _scatter(shape, idx, a):
+    full = np.zeros(shape, np.longdouble)
+    full[idx] = a
+    return full
+
+
+def gram_bwd_violations(got, ref, D, c=None):
+    """Components outside |got - ref| <= 2^-53 (c W + D A), or, where W < 1e-290 (zero included), outside |got - ref| <= 1e-300
+    -- gram_violations' rule for the underflowing elements.  (|got| <= 1e-300 there would refuse the reference itself: at d = 32
+    the exponents straddle float64's range and hundreds of components have a W, and a value, between 1e-300 and 1e-290.)
+    Returns (count, worst err / (2^-53 W), worst fraction of the bound) over the outputs of ``ref``."""
+    c = GRAM_BWD_C if c is None else c
+    bad, ratio, frac = 0, 0.0, 0.0
+    for k, (v, W, A) in ref.items():
+        g = ld(got[k]).reshape(np.shape(v))
+        err = np.abs(g - v)
+        tiny = W < ld(1e-290)
+        safe = np.where(tiny, 1, W)
+        r = np.where(tiny, 0, err / (ld(U) * safe))
+        fr = np.where(tiny, 0, err / (ld(U) * (c * safe + D[k] * np.where(tiny, 1, A))))
+        with np.errstate(invalid="ignore"):
+            b = np.where(tiny, ~(err <= ld(1e-300)), ~(fr <= 1))       # a NaN is outside
+        bad += int(np.sum(b))
+        ratio, frac = max(ratio, float(np.nanmax(r, initial=0.0))), max(frac, float(np.nanmax(fr, initial=0.0)))
+    return bad, ratio, frac
+
+
 # ---- fused ELBO (variational_elbo_mf.py:24-51; include/mobocmf_hip.h, mobocmf_elbo_forward)
 LOG_2PI = ld(2) * np.arctan(ld(1)) * 4
 LOG_2PI = np.log(LOG_2PI)
@@ -678,6 +937,62 @@ def gram_rep(kind, d, x1, f1, n1, x2, f2, nbase2, xdiv, hyp, K, ldk, knn=None):
     rc = lib().mobocmf_gram_forward_rep(kind, d, _p(x1), _p(f1), n1, _p(x2), _p(f2), nbase2, xdiv, _p(hyp), _p(K), ldk,
                                         _p(knn), _stream())
     _lib.check(rc, "mobocmf_gram_forward_rep")
+
+
+def gram_bwd_geometry(kind, d, n1, nbase2, xdiv, want_dx):
+    """(workspace bytes, (grid x, grid y, rows per workgroup)) of mobocmf_gram_backward: a host computation, no device needed."""
+    from mobocmf_amd import _lib
+    nb, geo = ctypes.c_size_t(), (ctypes.c_int32 * 3)()
+    _lib.check(_lib.load().mobocmf_gram_backward_workspace_bytes(kind, d, n1, nbase2, xdiv, int(want_dx), ctypes.byref(nb), geo),
+               "mobocmf_gram_backward_workspace_bytes")
+    return nb.value, tuple(geo)
+
+
+class GramBwd:
+    """What gram_bwd leaves behind: the outputs as float64 numpy ('hyp', 'g_f1', 'g_f2', 'g_x2'; absent ones missing),
+    ``geometry`` and ``untouched``: every guard double behind an output and behind the workspace is still NaN."""
+
+
+def gram_bwd(kind, d, x1, f1, n1, x2, f2, nbase2, xdiv, hyp, G, ldk, gknn=None, colact=None, want_dx=True, guard=8,
+             ws_bytes=None, check=True):
+    """mobocmf_gram_backward with the pointers as given (f2 / G may be views that are only 8-byte aligned): outputs and a
+    workspace of exactly the reported size (``ws_bytes``: that size instead) NaN before the call, ``guard`` NaN doubles
+    behind each.  Returns a GramBwd, or the status if ``check`` is False and the call is refused."""
+    from mobocmf_amd import _lib
+    nbytes, geo = gram_bwd_geometry(kind, d, n1, nbase2, xdiv, want_dx)
+    assert nbytes % 8 == 0
+    Np = nbase2 * xdiv
+    new = lambda n: torch.full((n + guard,), NAN, dtype=torch.float64, device="cuda")
+    lens = {"hyp": 1 + d if kind == 0 else 5 + 2 * d}
+    if kind == 1:
+        lens["g_f1"], lens["g_f2"] = n1, Np
+    if want_dx:
+        lens["g_x2"] = nbase2 * d
+    buf = {k: new(n) for k, n in lens.items()}
+    use = nbytes if ws_bytes is None else ws_bytes
+    ws = new(max(nbytes, use) // 8)
+    rc = lib().mobocmf_gram_backward(kind, d, _p(x1), _p(f1), n1, _p(x2), _p(f2), nbase2, xdiv, _p(hyp), _p(G), ldk, _p(gknn),
+                                     _p(colact), _p(buf["hyp"]), _p(buf.get("g_f1")), _p(buf.get("g_f2")), _p(buf.get("g_x2")),
+                                     _p(ws), use, _stream())
+    if not check and rc != 0:
+        return rc
+    _lib.check(rc, "mobocmf_gram_backward")
+    r = GramBwd()
+    r.geometry = geo
+    r.out = {k: buf[k][:n].cpu().numpy() for k, n in lens.items()}
+    r.untouched = all(bool(torch.isnan(buf[k][n:]).all()) for k, n in lens.items()) and bool(torch.isnan(ws[nbytes // 8:]).all())
+    # the workspace's own slack: the partials (hyp | df | dzf | dx, in the header's geometry) start on 256-byte boundaries
+    gx, gy, _ = geo
+    parts = [gx * gy * lens["hyp"]] + ([gy * Np, gx * ((n1 + 31) // 32 * 32)] if kind == 1 else []) + ([gy * nbase2 * d] if want_dx else [])
+    off = 0
+    for n in parts:
+        end = off + (n + 31) // 32 * 32
+        r.untouched = r.untouched and bool(torch.isnan(ws[off + n:end]).all())
+        off = end
+    assert off == nbytes // 8, (off, nbytes)
+    if "g_x2" in r.out:
+        r.out["g_x2"] = r.out["g_x2"].reshape(nbase2, d)
+    return r
 
 
 def _tab(ts):

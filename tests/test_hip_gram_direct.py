@@ -1,7 +1,8 @@
 """The Gram kernels directly: every forward instantiation (kind x d-bucket x replica path) through
-mobocmf_gram_forward_rep against an extended-precision reference with a componentwise bound, and the backward
-instantiations the layer tests did not reach (kind 1, every d-bucket, xdiv 8 / 16, with and without d/dx, and the general
-path an f that is only 8-byte aligned falls back to) through the layer against its oracle.
+mobocmf_gram_forward_rep against an extended-precision reference with a componentwise bound; every backward instantiation
+(kind x d-bucket x d/dx x replica path), its column-activity path, its three launch geometries and the three forms of its
+reduction through mobocmf_gram_backward against an extended-precision reference with a bound on the sum of the addends'
+magnitudes (kernel_reference.py, "Gram backward"); and the backward once more through the layer against its oracle.
 
 Forward bound per element: c (2 + |arg|) 2^-53 |term|, summed over the terms of kind 1, with arg the exponent's magnitude
 (lengthscales down to 0.05: |arg| reaches the thousands and float64 underflows) and c = kernel_reference.GRAM_C, four times
@@ -120,3 +121,204 @@ def test_layer_backward_replica_paths(d, xdiv, want_dx, offset_f):
         _close(xg.grad, x.grad, 1e-7, "g_x")
     else:
         assert xg.grad is None
+
+
+# ------------------------------------------------------------------------------------ backward, direct (mobocmf_gram_backward)
+# Bound per output component: 2^-53 (c W + D A), c = kernel_reference.GRAM_BWD_C, D = kernel_reference.gram_bwd_depth of the
+# geometry the size query reports; components whose W is below 1e-290 must be within 1e-300 of the reference.
+def _colact(active):
+    return None if active is None else torch.tensor(list(active), dtype=torch.int32, device=DEV)
+
+
+def _bwd_check(kind, d, n1, nbase2, xdiv, res, ref, want_dx, what):
+    """All outputs of one call against ``ref``; returns (err / (2^-53 W), fraction of the bound), the worst of each."""
+    want = {"hyp", "g_x2"} if kind == 0 else set(R.GRAM_BWD_OUTPUTS)
+    want -= set() if want_dx else {"g_x2"}
+    assert set(res.out) == want, what
+    assert res.untouched, what + ": a write beyond an output's or the workspace's extent"
+    D = R.gram_bwd_depth(kind, d, n1, nbase2, xdiv, res.geometry)
+    bad, ratio, frac = R.gram_bwd_violations(res.out, {k: ref[k] for k in want}, D)
+    print(f"{what}: worst err / (2^-53 W) {ratio:.2f}, {frac:.3f} of the bound (c = {R.GRAM_BWD_C}, D = {D})")
+    assert bad == 0, what + f": {bad} components outside the bound, worst {frac:.3g} of it"
+    return ratio, frac
+
+
+def _G_store(n1, Np, G, pad=0, offset=0):
+    """G inside a NaN store of round_up(n1, 32) rows: the rows >= n1 and the slack stay NaN (neither is read)."""
+    S = R.Strided((n1 + 31) // 32 * 32, Np, pad, offset)
+    S.view[:n1].copy_(dev(G))
+    return S
+
+
+@pytest.mark.parametrize("xdiv", R.GRAM_XDIV)
+@pytest.mark.parametrize("d", R.GRAM_D)
+@pytest.mark.parametrize("kind", [0, 1])
+def test_gram_backward_componentwise(kind, d, xdiv):
+    """Every instantiation: with and without d/dx, with and without gknn, 1 .. 3 workgroups of 128 base rows, 1 .. 5 of 8 rows
+    of x1.  Kind 1 at xdiv 8 / 16 also the three ways off the vector path (f2 or G only 8-byte aligned, an odd ldk).  That the
+    general instantiation ran there cannot be shown from outside: the geometry is the same, both instantiations add the same
+    values in the same order (bitwise equal results), and the hardware serves a 16-byte load from an 8-byte aligned address --
+    what is shown is that the values are right and nothing beyond the extents is touched."""
+    worst = (0.0, 0.0)
+    for n1 in R.GRAM_N1:
+        for nbase2 in R.GRAM_BWD_NBASE2:
+            c = R.gram_case(kind, d, n1, nbase2, xdiv)
+            Np = nbase2 * xdiv
+            G, gk = R.gram_bwd_inputs(n1, Np, seed=n1 + nbase2)
+            ref0 = R.gram_bwd_hp(kind, c, xdiv, G)
+            ref1 = R.gram_bwd_hp_with_knn(kind, c, ref0, gk)
+            x1, f1, x2, hyp, gkd = dev(c["x1"]), dev(c["f1"]), dev(c["x2"]), dev(c["hyp"]), dev(gk)
+            f2 = dev(c["f2"])
+            variants = [(0, 0, 0, dx, kn) for dx in (True, False) for kn in (True, False)]
+            if kind == 1 and xdiv in (8, 16):
+                variants += [(1, 0, 0, True, True), (0, 1, 0, False, True), (0, 0, 1, True, False)]
+            for f_off, g_off, pad, want_dx, with_knn in variants:
+                what = (f"kind={kind} d={d} xdiv={xdiv} n1={n1} nbase2={nbase2} dx={want_dx} gknn={with_knn} "
+                        f"f2 offset={f_off} G offset={g_off} ldk=w+{pad}")
+                Gs = _G_store(n1, Np, G, pad, g_off)
+                assert Gs.view.data_ptr() % 16 == 8 * g_off and Gs.ld == Np + pad
+                fv = _offset(c["f2"], 1) if f_off else f2
+                res = R.gram_bwd(kind, d, x1, f1, n1, x2, fv, nbase2, xdiv, hyp, Gs.view, Gs.ld, gkd if with_knn else None,
+                                 None, want_dx)
+                worst = tuple(map(max, worst, _bwd_check(kind, d, n1, nbase2, xdiv, res, ref1 if with_knn else ref0, want_dx, what)))
+    print(f"backward kind={kind} d={d} xdiv={xdiv}: worst ratio {worst[0]:.2f} (c = {R.GRAM_BWD_C}), {worst[1]:.3f} of the bound")
+
+
+# xdiv -> base rows giving a width that is / is not a multiple of 128.  8 and 16 divide 128 (a row's replicas share a block:
+# the vector instantiations' all-or-nothing mask); 3 and 48 do not (replicas straddle block boundaries, per-replica mask)
+_ACT_NBASE = {1: (384, 385), 3: (256, 257), 8: (160, 150), 16: (160, 150), 48: (40, 41)}
+_ACT_PATTERNS = dict(R.ACTIVITY, scattered=lambda n: [1 if i % 3 == 1 or i == n - 1 else 0 for i in range(n)])
+
+
+@pytest.mark.parametrize("pattern", list(_ACT_PATTERNS))
+@pytest.mark.parametrize("kind,xdiv", [(0, 1), (0, 3), (1, 3), (1, 8), (1, 16), (1, 48)])
+def test_gram_backward_column_activity(kind, xdiv, pattern):
+    """Inactive 128-column blocks of G hold NaN and count as exact zeros; gknn is zero there, as a layer's is."""
+    d, n1 = 3, 33
+    worst = (0.0, 0.0)
+    for nbase2 in _ACT_NBASE[xdiv]:
+        Np = nbase2 * xdiv
+        act = _ACT_PATTERNS[pattern]((Np + 127) // 128)
+        mask = R.column_mask(act, Np)
+        c = R.gram_case(kind, d, n1, nbase2, xdiv)
+        G, gk = R.gram_bwd_inputs(n1, Np, seed=xdiv, active=act)
+        ref = R.gram_bwd_hp(kind, c, xdiv, G, gk, act)
+        Gn = np.where(mask[None, :], G, np.nan)
+        assert np.isnan(Gn).sum() == n1 * int((~mask).sum()) and not gk[~mask].any()
+        for want_dx in (True, False):
+            what = f"kind={kind} xdiv={xdiv} nbase2={nbase2} Np={Np} {pattern} dx={want_dx}"
+            Gs = _G_store(n1, Np, Gn)
+            res = R.gram_bwd(kind, d, dev(c["x1"]), dev(c["f1"]), n1, dev(c["x2"]), dev(c["f2"]), nbase2, xdiv, dev(c["hyp"]),
+                             Gs.view, Gs.ld, dev(gk), _colact(act), want_dx)
+            worst = tuple(map(max, worst, _bwd_check(kind, d, n1, nbase2, xdiv, res, ref, want_dx, what)))
+            if kind == 1:
+                z = res.out["g_f2"][~mask]
+                assert z.size == int((~mask).sum()) and not z.any() and not np.isnan(z).any(), what + ": g_f2 of an inactive block"
+            if pattern == "none":
+                assert all(not v.any() and not np.isnan(v).any() for v in res.out.values()), what + ": exact zeros everywhere"
+    print(f"backward activity kind={kind} xdiv={xdiv} {pattern}: worst ratio {worst[0]:.2f}, {worst[1]:.3f} of the bound")
+
+
+# (n1, nbase2) -> (rows per workgroup, reduction form of the hyp, g_f1, g_f2, g_x2 tasks; 0 serial, 1 wide, 2 four-way), at
+# kind 0 / xdiv 1 and kind 1 / xdiv 8 alike (kind 0 has no g_f1 / g_f2).  gram_rows_per_block: 32 rows from grid x * Mp >= 32768,
+# 16 from 16384, else 8.
+_GEOMETRY = {
+    (512, 8192): (32, (1, 1, 2, 2)),      # 64 x 16 workgroups
+    (256, 8192): (16, (1, 1, 2, 2)),      # 64 x 16
+    (512, 512): (8, (1, 0, 1, 1)),        # 4 x 64: 64 partials per column and <= 4096 columns -- the wide form for g_f2 / g_x2
+    (33, 2048): (8, (1, 2, 0, 0)),        # 16 x 8
+    (64, 384): (8, (2, 0, 0, 0)),         # 3 x 8
+    (31, 129): (8, (0, 0, 0, 0)),         # 2 x 4
+}
+
+
+def test_gram_backward_geometry_cases_cover_every_rule():
+    assert {g for g, _ in _GEOMETRY.values()} == {8, 16, 32}
+    for task in range(4):
+        assert {f[task] for _, f in _GEOMETRY.values()} == {0, 1, 2}, task
+
+
+@pytest.mark.parametrize("kind,xdiv", [(0, 1), (1, 8)])
+@pytest.mark.parametrize("n1,nbase2", list(_GEOMETRY))
+def test_gram_backward_launch_geometry(n1, nbase2, kind, xdiv):
+    """The three rows-per-workgroup values and the three reduction forms of every task, asserted from the geometry the size
+    query reports.  The launch has the full grid; at most 8 column blocks are active (the first and the last among them), so
+    the reference covers n1 x 1024 elements.  (512, 512) at kind 0 is the one dense case."""
+    d = 2
+    Np = nbase2 * xdiv
+    nblk = (Np + 127) // 128
+    gm, forms = _GEOMETRY[(n1, nbase2)]
+    _, geo = R.gram_bwd_geometry(kind, d, n1, nbase2, xdiv, True)
+    tasks = R.gram_bwd_tasks(kind, d, n1, nbase2, xdiv, geo)
+    assert geo == ((nbase2 + 127) // 128, (n1 + 31) // 32 * 32 // gm, gm)
+    got_forms = {k: R.sum_form(*pl) for k, pl in tasks.items()}
+    want_forms = dict(zip(("hyp", "g_f1", "g_f2", "g_x2"), forms))
+    assert got_forms == {k: want_forms[k] for k in tasks}, (geo, tasks)
+    c = R.gram_case(kind, d, n1, nbase2, xdiv)
+    what = f"kind={kind} xdiv={xdiv} n1={n1} nbase2={nbase2} geometry={geo}"
+    Gd = torch.full((n1, Np), R.NAN, dtype=torch.float64, device=DEV)           # n1 is a multiple of 32 or the store is small
+    if nblk <= 8 or Np % 128:
+        act = None
+        G, gk = R.gram_bwd_inputs(n1, Np, seed=5)
+        ref = R.gram_bwd_hp(kind, c, xdiv, G, gk)
+        Gd.copy_(dev(G))
+    else:
+        blocks = sorted({0, nblk - 1} | {(nblk * i) // 7 + (i % 2) for i in range(1, 7)})
+        assert len(blocks) == 8 and blocks[-1] == nblk - 1
+        act = [1 if b in blocks else 0 for b in range(nblk)]
+        Gb, gkb = R.gram_bwd_inputs(n1, 128 * len(blocks), seed=5)
+        ref = R.gram_bwd_hp_blocks(kind, c, xdiv, blocks, Gb, gkb)
+        cols = torch.as_tensor(np.concatenate([np.arange(128 * b, 128 * b + 128) for b in blocks]), device=DEV)
+        Gd[:, cols] = dev(Gb)
+        gk = np.zeros(Np)
+        gk[cols.cpu().numpy()] = gkb
+    res = R.gram_bwd(kind, d, dev(c["x1"]), dev(c["f1"]), n1, dev(c["x2"]), dev(c["f2"]), nbase2, xdiv, dev(c["hyp"]), Gd, Np,
+                     dev(gk), _colact(act), True)
+    assert res.geometry == geo
+    ratio, frac = _bwd_check(kind, d, n1, nbase2, xdiv, res, ref, True, what)
+    if act is not None and kind == 1:
+        assert not res.out["g_f2"][~R.column_mask(act, Np)].any(), what
+
+
+def test_gram_backward_refuses_bad_arguments():
+    from mobocmf_amd import _lib
+    import ctypes
+    kind, d, n1, nbase2, xdiv = 1, 3, 31, 127, 8
+    c = R.gram_case(kind, d, n1, nbase2, xdiv)
+    Np = nbase2 * xdiv
+    G, gk = R.gram_bwd_inputs(n1, Np)
+    a = dict(x1=dev(c["x1"]), f1=dev(c["f1"]), x2=dev(c["x2"]), f2=dev(c["f2"]), hyp=dev(c["hyp"]), G=dev(G))
+
+    def call(ldk=Np, ws_bytes=None, **kw):
+        v = dict(a, kind=kind, d=d, n1=n1, nbase2=nbase2, xdiv=xdiv)
+        v.update(kw)
+        return R.gram_bwd(v["kind"], v["d"], v["x1"], v["f1"], v["n1"], v["x2"], v["f2"], v["nbase2"], v["xdiv"], v["hyp"], v["G"],
+                          ldk, dev(gk), None, True, ws_bytes=ws_bytes, check=False)
+
+    nbytes, _ = R.gram_bwd_geometry(kind, d, n1, nbase2, xdiv, True)
+    assert not isinstance(call(), int)
+    assert call(ws_bytes=nbytes - 8) == _lib.WORKSPACE_TOO_SMALL and call(ws_bytes=0) == _lib.WORKSPACE_TOO_SMALL
+    nodx, _ = R.gram_bwd_geometry(kind, d, n1, nbase2, xdiv, False)
+    assert nodx < nbytes and call(ws_bytes=nodx) == _lib.WORKSPACE_TOO_SMALL           # the d/dx partials count
+    assert call(ldk=Np - 1) == _lib.BAD_ARG
+    for k in ("x1", "f1", "x2", "f2", "hyp", "G"):
+        assert call(**{k: None}) == _lib.BAD_ARG, k
+    lib, nb, geo = R.lib(), ctypes.c_size_t(), (ctypes.c_int32 * 3)()
+    q = lambda kind=kind, d=d, n1=n1, nbase2=nbase2, xdiv=xdiv, out=ctypes.byref(nb): \
+        lib.mobocmf_gram_backward_workspace_bytes(kind, d, n1, nbase2, xdiv, 1, out, geo)
+    assert q() == _lib.OK and nb.value == nbytes and q(out=None) == _lib.BAD_ARG
+    for kw in (dict(kind=2), dict(kind=-1), dict(d=0), dict(d=33), dict(n1=0), dict(nbase2=0), dict(xdiv=0), dict(xdiv=49)):
+        assert q(**kw) == _lib.BAD_ARG, kw
+        # the launch refuses the same shapes, every pointer given, before it looks at the workspace (of no bytes here)
+        out = [torch.empty(n, dtype=torch.float64, device=DEV) for n in (64, n1, Np, nbase2 * d, 8)]
+        rc = lib.mobocmf_gram_backward(kw.get("kind", kind), kw.get("d", d), R._p(a["x1"]), R._p(a["f1"]), kw.get("n1", n1),
+                                       R._p(a["x2"]), R._p(a["f2"]), kw.get("nbase2", nbase2), kw.get("xdiv", xdiv), R._p(a["hyp"]),
+                                       R._p(a["G"]), Np * 8, None, None, R._p(out[0]), R._p(out[1]), R._p(out[2]), R._p(out[3]),
+                                       R._p(out[4]), 0, R._stream())
+        assert rc == _lib.BAD_ARG, kw
+    # kind 0 needs neither f nor the f gradients
+    c0 = R.gram_case(0, d, n1, nbase2, 1)
+    G0, _ = R.gram_bwd_inputs(n1, nbase2)
+    r = R.gram_bwd(0, d, dev(c0["x1"]), None, n1, dev(c0["x2"]), None, nbase2, 1, dev(c0["hyp"]), dev(G0), nbase2, None, None, False)
+    assert set(r.out) == {"hyp"} and r.untouched
+

@@ -156,6 +156,129 @@ def test_gram_constant_is_the_measured_one():
     assert R.GRAM_C == 4.0 * R.GRAM_RATIO_MEASURED
 
 
+# ---------------------------------------------------------------------------------------------------------- Gram backward
+def _autograd_gram_bwd(kind, c, xdiv, G, gknn, active):
+    """float64 torch autograd of sum G . gram + sum gknn . gram_diag over the oracle: {output: gradient} as numpy."""
+    t = lambda a: torch.tensor(a, dtype=torch.float64)
+    d = c["x1"].shape[1]
+    Np = c["x2"].shape[0] * xdiv
+    Gm = np.asarray(G, np.float64)
+    if active is not None:
+        Gm = np.where(R.column_mask(active, Np)[None, :], Gm, 0.0)
+    h = t(c["hyp"]).requires_grad_(True)
+    x2 = t(c["x2"]).requires_grad_(True)
+    xr = x2.repeat_interleave(xdiv, 0)
+    if kind == 0:
+        hyp = {"alpha": h[0], "ls": h[1:]}
+        X1, X2, leaves = t(c["x1"]), xr, (h, x2)
+    else:
+        hyp = {"a1": h[0], "af": h[1], "nu": h[2], "a2": h[3], "lsf": h[4], "ls1": h[5:5 + d], "ls2": h[5 + d:]}
+        f1, f2 = t(c["f1"]).requires_grad_(True), t(c["f2"]).requires_grad_(True)
+        X1, X2, leaves = torch.cat([t(c["x1"]), f1[:, None]], 1), torch.cat([xr, f2[:, None]], 1), (h, x2, f1, f2)
+    L = (t(Gm) * O.gram(hyp, X1, X2)).sum()
+    if gknn is not None:
+        L = L + (t(gknn) * O.gram_diag(hyp, X2)).sum()
+    g = torch.autograd.grad(L, leaves)
+    out = {"hyp": g[0].numpy(), "g_x2": g[1].numpy()}
+    if kind == 1:
+        out["g_f1"], out["g_f2"] = g[2].numpy(), g[3].numpy()
+    return out
+
+
+def _gram_bwd_cpu_cases():
+    """(kind, d, xdiv, with gknn, activity) at 33 x 129 base rows: both kinds, every d, xdiv 1 and 3, with and without gknn,
+    and one activity mask per (kind, d) -- 387 columns are four blocks, the last a partial one."""
+    for kind in (0, 1):
+        for d in R.GRAM_D:
+            for xdiv in (1, 3):
+                for with_knn in (False, True):
+                    yield kind, d, xdiv, with_knn, None
+            yield kind, d, 3, True, [1, 0, 0, 1]
+
+
+def _apart(c, seed):
+    """``c`` with the columns gram_case put next to rows of x1 (|x - z| ~ 1e-3) moved to fresh uniform points.  The oracle
+    forms x / ls - z / ls: an absolute rounding of 2 u |x| / ls, which is 2 u |x| / |x - z| RELATIVE to the d/dx and d/dls addends
+    G K (x - z) / ls^2 -- with |x - z| down to 1e-4 in one coordinate that alone is 1e-12 .. 1e-11 of A (measured: up to 5.3e-12 A
+    at d = 32), the oracle's own error and no statement about the reference.  The formulas are compared where the oracle is
+    accurate; the constant and the cancellation are measured on gram_case as it is."""
+    c = dict(c, x2=c["x2"].copy())
+    k = min(c["x1"].shape[0], c["x2"].shape[0], 5)
+    c["x2"][:k] = np.random.default_rng(4242 + seed).random((k, c["x2"].shape[1]))
+    return c
+
+
+@pytest.fixture(scope="module")
+def gram_bwd_cpu():
+    """Per case of _gram_bwd_cpu_cases: (reference, numpy float64 restatement) on gram_case, (reference, autograd) on the same
+    case with the near-coincident columns moved apart; computed once."""
+    res = {}
+    for kind, d, xdiv, with_knn, act in _gram_bwd_cpu_cases():
+        c = R.gram_case(kind, d, 33, 129, xdiv)
+        G, gk = R.gram_bwd_inputs(33, 129 * xdiv, seed=d + xdiv, active=act)
+        gk = gk if with_knn else None
+        ca = _apart(c, d)
+        res[(kind, d, xdiv, with_knn, None if act is None else tuple(act))] = (
+            R.gram_bwd_hp(kind, c, xdiv, G, gk, act), R.gram_bwd_f64(kind, c, xdiv, G, gk, act),
+            R.gram_bwd_hp(kind, ca, xdiv, G, gk, act), _autograd_gram_bwd(kind, ca, xdiv, G, gk, act))
+    return res
+
+
+def test_gram_backward_reference_matches_autograd(gram_bwd_cpu):
+    """The longdouble reference equals float64 autograd of the oracle's gram (+ gram_diag) to 1e-12 A per component, every
+    output of every case; an inactive block of G may hold NaN."""
+    for key, (_, _, ref, auto) in gram_bwd_cpu.items():
+        assert set(ref) == set(auto) == ({"hyp", "g_x2"} if key[0] == 0 else set(R.GRAM_BWD_OUTPUTS)), key
+        for k, (v, W, A) in ref.items():
+            err = np.abs(R.ld(auto[k]).reshape(v.shape) - v)
+            assert bool(np.all(err <= R.ld(1e-12) * A)), (key, k, float(np.max(err / np.maximum(A, R.ld(1e-300)))))
+            assert bool(np.all(W >= 2 * A)) and bool(np.all(A >= np.abs(v) * (1 - 1e-15)))
+    c = R.gram_case(1, 3, 33, 129, 3)
+    G, gk = R.gram_bwd_inputs(33, 387, seed=6, active=[1, 0, 0, 1])
+    Gn = G.copy()
+    Gn[:, 128:384] = np.nan
+    a, b = R.gram_bwd_hp(1, c, 3, G, gk, [1, 0, 0, 1]), R.gram_bwd_hp(1, c, 3, Gn, gk, [1, 0, 0, 1])
+    assert all(np.array_equal(a[k][i], b[k][i]) for k in a for i in range(3))
+    assert not a["g_f2"][2][128:384].any() and a["g_f2"][2][:128].all()
+
+
+def test_gram_backward_constant_is_the_measured_one(gram_bwd_cpu):
+    """Worst err / (2^-53 W) of the float64 restatement (kernel_reference.gram_bwd_f64: direct differences, as the device
+    forms them) over the cases above: GRAM_BWD_RATIO_MEASURED covers it and is not stale (within a factor of two);
+    GRAM_BWD_C is four times it."""
+    worst = {}
+    for key, (ref, f64, _, _) in gram_bwd_cpu.items():
+        bad, ratio, _ = R.gram_bwd_violations({k: v[0] for k, v in f64.items()}, ref, {k: 0 for k in ref}, c=np.inf)
+        assert bad == 0, key
+        worst[key[:2]] = max(worst.get(key[:2], 0.0), ratio)
+    w = max(worst.values())
+    print("gram backward ratios", {k: round(v, 2) for k, v in worst.items()}, "worst", w)
+    assert w <= R.GRAM_BWD_RATIO_MEASURED <= 2.0 * w, worst
+    assert R.GRAM_BWD_C == 4.0 * R.GRAM_BWD_RATIO_MEASURED
+
+
+def test_gram_backward_bound_bites_where_the_layer_tolerance_does_not(gram_bwd_cpu):
+    """Some component of each kind cancels by more than a factor 100 (A / |ref|): a bound on 2^-53 A there is orders of
+    magnitude below 1e-7 of the value's norm."""
+    for kind in (0, 1):
+        canc = max(float(np.max(np.where(np.abs(v) > 0, A / np.where(np.abs(v) > 0, np.abs(v), 1), 0)))
+                   for key, (ref, _, _, _) in gram_bwd_cpu.items() if key[0] == kind for v, W, A in ref.values())
+        print(f"kind {kind}: worst cancellation {canc:.3g}")
+        assert canc > 100
+
+
+def test_gram_backward_depth_follows_the_launch():
+    """gram_bwd_depth on the geometry the size query reports: the three reduction forms and the formula per output."""
+    assert [R.sum_form(*a) for a in ((15, 10), (16, 10), (63, 10), (64, 4096), (64, 4097), (1024, 3))] == [0, 2, 2, 1, 2, 1]
+    assert [R.sum_depth(*a) for a in ((15, 10), (16, 10), (63, 10), (64, 4096), (1024, 3), (257, 3))] == [15, 6, 18, 10, 13, 11]
+    nbytes, geo = R.gram_bwd_geometry(1, 3, 33, 257, 8, True)
+    assert geo == (3, 8, 8) and nbytes % 256 == 0
+    D = R.gram_bwd_depth(1, 3, 33, 257, 8, geo)
+    assert D == {"hyp": 8 + 8 + 8 + 6 + (6 + 2), "g_f1": 8 + 9 + 6 + 3, "g_f2": 8 + 3 + 6 + 8, "g_x2": 8 + 8 + 2 + 6 + 8}
+    _, geo = R.gram_bwd_geometry(0, 2, 512, 8192, 1, True)
+    assert geo == (64, 16, 32) and R.gram_bwd_depth(0, 2, 512, 8192, 1, geo) == {"hyp": 1 + 32 + 8 + 6 + 13, "g_x2": 1 + 32 + 2 + 6 + 6}
+
+
 # ---------------------------------------------------------------------------------------------------------- ELBO reference
 def test_elbo_reference_matches_a_float64_restatement():
     rng = np.random.default_rng(4)
