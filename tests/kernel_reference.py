@@ -10,6 +10,9 @@ Three things live here so that the CPU proof (tests/test_kernel_reference_cpu.py
   componentwise bounds the rounding tests assert;
 * callers of the product / Gram / ELBO entry points that pass pointers, leading dimensions and tunings through unchanged
   (functional._prep would make every operand contiguous).
+
+At the end: the variational layer as a whole -- well-conditioned cases, a dtype-generic reference with its magnitude shadow,
+the measured constants of the layer bound and direct callers of the whole-call and the split layer entry points.
 """
 import ctypes
 
@@ -242,9 +245,14 @@ def gram_case(kind, d, n1, nbase2, xdiv, seed=0):
 def gram_hp(kind, c, xdiv):
     """(K, sum_t (2 + |arg_t|) |term_t|, knn) in longdouble: rows = x1, columns = x2 rows replicated xdiv times."""
     assert HAVE_LONGDOUBLE
-    x1, x2, hyp = ld(c["x1"]), ld(c["x2"]), ld(c["hyp"])
+    return _gram(kind, c, xdiv, ld)[:3]
+
+
+def _gram(kind, c, xdiv, T):
+    """gram_hp's statements in the number format ``T`` converts to, and sum_t |term_t| as a fourth result."""
+    x1, x2, hyp = T(c["x1"]), T(c["x2"]), T(c["hyp"])
     d = x1.shape[1]
-    half = ld(0.5)
+    half = T(0.5)
 
     def arg(a, b, ls):
         t = (a[:, None, :] - b[None, :, :]) / ls
@@ -253,9 +261,9 @@ def gram_hp(kind, c, xdiv):
     if kind == 0:
         a1 = np.repeat(arg(x1, x2, hyp[1:1 + d]), xdiv, axis=1)
         K = hyp[0] * np.exp(-a1)
-        return K, (2 + a1) * np.abs(K), np.full(K.shape[1], hyp[0])
+        return K, (2 + a1) * np.abs(K), np.full(K.shape[1], hyp[0]), np.abs(K)
     a1_, af_, nu, a2_, lsf = hyp[:5]
-    f1, f2 = ld(c["f1"]), ld(c["f2"])
+    f1, f2 = T(c["f1"]), T(c["f2"])
     g1 = np.repeat(arg(x1, x2, hyp[5:5 + d]), xdiv, axis=1)
     g2 = np.repeat(arg(x1, x2, hyp[5 + d:5 + 2 * d]), xdiv, axis=1)
     gf = half * ((f1[:, None] - f2[None, :]) / lsf) ** 2
@@ -263,7 +271,7 @@ def gram_hp(kind, c, xdiv):
     T2 = a1_ * np.exp(-(g1 + gf)) * af_
     T3 = a2_ * np.exp(-g2)
     W = (2 + g1) * np.abs(T1) + (2 + g1 + gf) * np.abs(T2) + (2 + g2) * np.abs(T3)
-    return T1 + T2 + T3, W, a1_ * (nu * f2 * f2 + af_) + a2_
+    return T1 + T2 + T3, W, a1_ * (nu * f2 * f2 + af_) + a2_, np.abs(T1) + np.abs(T2) + np.abs(T3)
 
 
 def gram_violations(got, K, W, c=None):
@@ -365,11 +373,11 @@ def _gram_bwd(kind, c, xdiv, G, gknn, active, T):
     n1, d = x1.shape
     nb = x2.shape[0]
     Np = nb * xdiv
-    G = np.asarray(G, np.float64)
+    G = T(G)                                                           # (a longdouble G -- the layer reference's dK -- stays one)
     assert G.shape == (n1, Np)
     if active is not None:
-        G = np.where(column_mask(active, Np)[None, :], G, 0.0)        # inactive blocks may hold NaN: they count as zero
-    G = T(G).reshape(n1, nb, xdiv)
+        G = np.where(column_mask(active, Np)[None, :], G, T(0.0))     # inactive blocks may hold NaN: they count as zero
+    G = G.reshape(n1, nb, xdiv)
     aG = np.abs(G)
     Gs, aGs = G.sum(2), aG.sum(2)
     half = T(0.5)
@@ -1126,3 +1134,547 @@ def mf_combine(Ks, Kn, s1, s2, l1, l2, ntab, diag, out, n1, n2, rows_p, cols_p):
     rc = lib().mobocmf_mf_kernel_combine(n1, n2, Ks.ptr, Kn.ptr, Ks.ld, _p(s1), _p(s2), _p(l1), _p(l2), _p(ntab), float(diag),
                                          out.ptr, out.ld, rows_p, cols_p, _stream())
     _lib.check(rc, "mobocmf_mf_kernel_combine")
+
+
+# ------------------------------------------------------------------------------- the variational layer: cases and reference
+# (api.hip: chain_forward / panel_forward / panel_backward / chain_backward; DESIGN.md, "The layer bound".)
+#
+# layer_ref runs the DEVICE's algebraic form -- explicit X = L^-1, A = X K_mn, a = X m, U = X L_S, mean = A^T a, C = U^T A, q, r,
+# var, KL; backwards dC, dA, da, dU, dK_mn = X^T dA, g_m, g_LS, Y, dL, Phi(L^T dL), dK_mm = sym(X^T Phi X), the Gram backwards
+# -- in the number format asked for: numpy.longdouble is the reference, numpy.float64 the restatement.  Its SHADOW S is the
+# same chain of statements with every operand replaced by its magnitude and every subtraction by an addition: the leaves are
+# |m|, |L_S|, |g_mean|, |g_var|, |g_kl|, sum_t |term_t| of K_mn, |L| of the factor (a Cholesky factor is determined by K_mm to
+# within |L||L^T|: its own magnitude is its scale), the comparison inverse of |L| (forward substitution with additions:
+# >= |L^-1| entrywise, the scale of Higham's |X||L||X|) and |log .| in the KL.  The Gram-derived outputs take the A output of
+# _gram_bwd (sum |G||d term / d theta|) fed with the shadow of dK.  The gate is |got - ref| <= C_g u S per component, and
+# components with S = 0 (the strict upper triangle of g_LS, gradients of columns that got none) must be exactly zero.
+#
+# C_g is not fitted to the device.  Per output group two float64 algorithms are measured against the longdouble reference on
+# every case the GPU tests run (tests/test_layer_reference_cpu.py, on every run): the float64 run of layer_ref, and float64
+# autograd over oracle.layer_moments + kl_layer (triangular solves, no explicit inverse).  LAYER_RATIO_MEASURED records the
+# larger of the two worst ratios err / (u S), rounded up; C_g = 4 x that, the room DESIGN 5.5 gives the Gram constants for a
+# third summation order, FMA and the reciprocal-root Cholesky.
+LAYER_GROUPS = {"forward": ("mean", "var", "kl"), "chain": ("g_m", "g_LS"), "gram": ("g_hyp", "g_x", "g_f", "g_zf")}
+# Measured: forward 13.1 (oracle; restatement 6.0), chain 128.7 (oracle; restatement 75.7: both g_LS of the kind 1, M = 128
+# case when only the KL is differentiated -- g_LS = g_kl (tril(K_mm^-1 L_S) - diag(1 / LS_ii)) cancels on the diagonal and
+# carries the factor's forward error, which |L| as a leaf does not scale with; 47 at M = 129 under the KL alone, at most 27
+# with all three upstream gradients), gram 95.4 (oracle: its x / ls - z / ls; restatement 13.8).  The figures move by a few per
+# cent with the BLAS blocking of the host, so they are recorded a quarter above the measurement: another blocking stays
+# inside [recorded / 2, recorded].
+LAYER_RATIO_MEASURED = {"forward": 17.0, "chain": 165.0, "gram": 125.0}
+LAYER_C = {k: 4.0 * v for k, v in LAYER_RATIO_MEASURED.items()}
+LAYER_COND_MAX = 1e3
+LAYER_MARGIN = 1e-9
+CLAMP_JITTER = -2e-3
+
+
+def layer_group(name):
+    return next(g for g, names in LAYER_GROUPS.items() if name in names)
+
+
+def hyp_dict(kind, hyp, d):
+    """The oracle's hyper-parameter dict from the packed vector (include/mobocmf_hip.h, mobocmf_layer_desc)."""
+    if kind == 0:
+        return {"alpha": hyp[0], "ls": hyp[1:1 + d]}
+    return {"a1": hyp[0], "af": hyp[1], "nu": hyp[2], "a2": hyp[3], "lsf": hyp[4], "ls1": hyp[5:5 + d], "ls2": hyp[5 + d:5 + 2 * d]}
+
+
+_layer_cases = {}
+
+
+def layer_case(kind, d, M, nbase, xdiv, seed=0, clamp=0, floor=False, branch=0, want_dx=1):
+    """One well-conditioned layer problem as a dict of float64 numpy arrays and the descriptor's scalars (cached, read-only).
+    Z_x: a lattice of spacing h jittered by 0.15 h (d <= 3) or uniform points (d > 3: they are far apart anyway), lengthscales
+    0.55 .. 0.8 h resp. 0.25 .. 0.32, so that K_mm is diagonally dominant: cond(K_mm + jitter I) <= 1e3 (asserted by the CPU
+    test, as are the margins below).  The data rows sit 0.6 lengthscales from randomly chosen inducing rows: K_mn has entries
+    of order one.  ``clamp`` = k > 0: the first k base rows lie ON inducing rows (row i on Z[i % M], f on zf) and jitter =
+    CLAMP_JITTER < 0, so that q > k_nn there (training branch: clamp(k_nn - q, 0) active in those columns, and in any other that lies as close).  ``floor``:
+    min_var is raised to half the median variance -- the columns below sit on the floor.  Upstream gradients g_mean, g_var
+    standard normal, g_kl = 0.37."""
+    key = (kind, d, M, nbase, xdiv, seed, clamp, floor, branch, want_dx)
+    if key in _layer_cases:
+        return _layer_cases[key]
+    rng = np.random.default_rng(100003 * kind + 1009 * M + 31 * nbase + 7 * d + xdiv + 131071 * seed)
+    if d <= 3:
+        side = int(np.ceil(M ** (1.0 / d)))
+        h = 1.0 / side
+        grid = np.stack(np.meshgrid(*[np.arange(side)] * d, indexing="ij"), -1).reshape(-1, d)
+        Zx = (grid[rng.permutation(len(grid))[:M]] + 0.5 + 0.15 * rng.uniform(-1, 1, (M, d))) * h
+        ls = lambda: h * rng.uniform(0.55, 0.8, d)
+    else:
+        Zx = rng.random((M, d))
+        ls = lambda: rng.uniform(0.25, 0.32, d)
+    Np = nbase * xdiv
+    if kind == 0:
+        hyp = np.concatenate([[0.7 + rng.random()], ls()])
+        zf = f = None
+        lsx = hyp[1:]
+    else:
+        lsx = ls()
+        hyp = np.concatenate([[0.6 + rng.random(), 0.5 + rng.random(), 0.5 + rng.random(), 0.05 + 0.1 * rng.random(),
+                               0.7 + rng.random()], lsx, ls()])
+        zf = 0.5 * rng.standard_normal(M)
+        f = rng.standard_normal(Np)
+    near = rng.integers(0, M, nbase)
+    x = Zx[near] + 0.6 * lsx * rng.standard_normal((nbase, d)) / np.sqrt(d)
+    if clamp:
+        assert branch == 0 and clamp <= nbase
+        rows = np.arange(clamp) % M
+        x[:clamp] = Zx[rows]
+        if kind == 1:
+            f[:clamp * xdiv] = np.repeat(zf[rows], xdiv)
+    c = dict(kind=kind, d=d, M=M, nbase=nbase, xdiv=xdiv, Np=Np, branch=branch, want_dx=want_dx, clamp=clamp, floor=floor,
+             jitter=CLAMP_JITTER if clamp else 1e-6, min_var=1e-10, x=x, f=f, Zx=Zx, zf=zf, hyp=hyp,
+             m=0.3 * rng.standard_normal(M), L_S=0.2 * np.eye(M) + 0.05 * np.tril(rng.standard_normal((M, M))),
+             g_mean=rng.standard_normal(Np), g_var=rng.standard_normal(Np), g_kl=0.37, key=key)
+    if floor:
+        c["min_var"] = 0.5 * float(np.median(_layer_forward(c, _f64)[0]["varraw"]))
+    for v in c.values():
+        if isinstance(v, np.ndarray):
+            v.setflags(write=False)
+    _layer_cases[key] = c
+    return c
+
+
+def with_upstream(c, g_mean=None, g_var=None, g_kl=0.0, tag=None):
+    """A copy of the case with other upstream gradients (None: exact zeros -- the entry points take no NULL there)."""
+    z = np.zeros(c["Np"])
+    return dict(c, g_mean=z if g_mean is None else g_mean, g_var=z if g_var is None else g_var, g_kl=float(g_kl),
+                key=c["key"] + (tag,))
+
+
+def _f64(a):
+    return np.asarray(a, np.float64)
+
+
+def _chol_columns(K):
+    """The Cholesky factor by a plain column loop in K's number format."""
+    n = K.shape[0]
+    L = np.zeros_like(K)
+    for j in range(n):
+        s = K[j, j] - L[j, :j] @ L[j, :j]
+        assert s > 0, (j, float(s))
+        L[j, j] = np.sqrt(s)
+        if j + 1 < n:
+            L[j + 1:, j] = (K[j + 1:, j] - L[j + 1:, :j] @ L[j, :j]) / L[j, j]
+    return L
+
+
+def _tri_inverse(L, shadow=False):
+    """L^-1 by forward substitution, row by row (tri_inverse_hp's statements) in L's number format; ``shadow``: the
+    subtraction becomes an addition -- the inverse of the comparison matrix of |L|."""
+    n = L.shape[0]
+    X = np.zeros_like(L)
+    sg = 1 if shadow else -1
+    for i in range(n):
+        if i:
+            X[i, :i] = sg * (L[i, :i] @ X[:i, :i]) / L[i, i]
+        X[i, i] = 1 / L[i, i]
+    return X
+
+
+def _gram_operands(c):
+    return (dict(x1=c["Zx"], f1=c["zf"], x2=c["Zx"], f2=c["zf"], hyp=c["hyp"]),
+            dict(x1=c["Zx"], f1=c["zf"], x2=c["x"], f2=c["f"], hyp=c["hyp"]))
+
+
+def _layer_forward(c, T):
+    """(state, shadow state) of the forward in the number format ``T`` converts to."""
+    M = c["M"]
+    cmm, cmn = _gram_operands(c)
+    Kmm = _gram(c["kind"], cmm, 1, T)[0] + T(c["jitter"]) * np.eye(M, dtype=T(0.0).dtype)
+    Kmn, _, knn, Kabs = _gram(c["kind"], cmn, c["xdiv"], T)
+    L = _chol_columns(Kmm)
+    m, LS = T(c["m"]), np.tril(T(c["L_S"]))
+    out = []
+    for sh in (False, True):
+        ab = np.abs if sh else (lambda v: v)
+        X = _tri_inverse(ab(L), sh)
+        A, a, U = X @ (Kabs if sh else Kmn), X @ ab(m), X @ ab(LS)
+        mean, C = A.T @ a, U.T @ A
+        q, r = (A * A).sum(0), (C * C).sum(0)
+        s = knn + q if sh else knn - q
+        pos = s > 0
+        if c["branch"] == 0 and not sh:
+            s = np.where(pos, s, 0)
+        varraw = s + r
+        lgL, lgS = np.log(np.diag(L)), np.log(np.diag(LS) ** 2)
+        kl = T(0.5) * (2 * ab(lgL).sum() + (ab(lgS).sum() if sh else -lgS.sum()) + (U * U).sum() + (a * a).sum() + (M if sh else -M))
+        out.append(dict(L=ab(L), X=X, A=A, a=a, U=U, C=C, LS=ab(LS), q=q, r=r, knn=knn, pos=pos, varraw=varraw, mean=mean,
+                        var=varraw if sh else np.maximum(varraw, T(c["min_var"])), kl=kl, Kmm=Kmm))
+    return out
+
+
+def _layer_backward(c, st, sst, T, phi_diag=0.5):
+    """(gradients, their shadows) from the forward states.  ``phi_diag``: the factor on Phi's diagonal (1/2; the CPU test's
+    mutation drops it)."""
+    kind, xdiv = c["kind"], c["xdiv"]
+    cmm, cmn = _gram_operands(c)
+    gm, gkl = T(c["g_mean"]), T(c["g_kl"])
+    gv = np.where(st["varraw"] > T(c["min_var"]), T(c["g_var"]), 0)            # clamp_min passes gradient above the floor only
+    cgv = gv if c["branch"] else np.where(st["pos"], gv, 0)
+    res = []
+    for sh, s in ((False, st), (True, sst)):
+        ab = np.abs if sh else (lambda v: v)
+        sg = 1 if sh else -1
+        X, A, a, U, C, L, LS = (s[k] for k in ("X", "A", "a", "U", "C", "L", "LS"))
+        g, w, cw, k = ab(gm), ab(gv), ab(cgv), ab(gkl)
+        dC = 2 * C * w[None, :]
+        dA = U @ dC + np.outer(a, g) + sg * 2 * A * cw[None, :]
+        da = A @ g + k * a
+        dU = np.tril(A @ dC.T) + k * U
+        dKmn = X.T @ dA
+        g_m = X.T @ da
+        g_LS = np.tril(X.T @ dU)
+        g_LS[np.diag_indices_from(g_LS)] += sg * k / np.diag(LS)
+        Y = dA @ A.T + np.outer(da, a) + dU @ U.T
+        dL = sg * np.tril(X.T @ Y)
+        dL[np.diag_indices_from(dL)] += k / np.diag(L)
+        P = np.tril(L.T @ dL)
+        P[np.diag_indices_from(P)] *= T(phi_diag)
+        Sm = X.T @ P @ X
+        dKmm = T(0.5) * (Sm + Sm.T)
+        pick = 2 if sh else 0
+        bmn = _gram_bwd(kind, cmn, xdiv, dKmn, cw, None, T)
+        bmm = _gram_bwd(kind, cmm, 1, dKmm, None, None, T)
+        o = dict(g_m=g_m, g_LS=g_LS, g_hyp=bmn["hyp"][pick] + bmm["hyp"][pick],
+                 g_hyp_mn=bmn["hyp"][pick], g_hyp_mm=bmm["hyp"][pick])
+        if c["want_dx"]:
+            o["g_x"] = bmn["g_x2"][pick]
+        if kind == 1:
+            o["g_f"] = bmn["g_f2"][pick]
+            o["g_zf_mn"], o["g_zf_mm"] = bmn["g_f1"][pick], bmm["g_f1"][pick] + bmm["g_f2"][pick]
+            o["g_zf"] = o["g_zf_mn"] + o["g_zf_mm"]
+        res.append(o)
+    return res
+
+
+_layer_fwd_cache, _layer_ref_cache = {}, {}
+
+
+def layer_ref(c, dtype=np.longdouble, shadow=False):
+    """{output: value} of the layer ``c`` = layer_case(...) in ``dtype`` -- mean, var [N'], kl, g_m [M], g_LS [M x M, lower],
+    g_hyp, g_x [nbase x d] (want_dx), g_f [N'], g_zf [M] (kind 1), and the two shares g_hyp_mn / g_hyp_mm, g_zf_mn / g_zf_mm
+    of the PANEL and the CHAIN backward -- or, ``shadow``, the magnitude shadow S of each.  Cached per case and upstream."""
+    assert dtype is not np.longdouble or HAVE_LONGDOUBLE
+    key = (c["key"], np.dtype(dtype).name)
+    if key not in _layer_ref_cache:
+        T = lambda a: np.asarray(a, dtype)
+        fkey = (c["key"][:10], np.dtype(dtype).name)                       # the forward does not depend on the upstream
+        if fkey not in _layer_fwd_cache:
+            _layer_fwd_cache[fkey] = _layer_forward(c, T)
+        st, sst = _layer_fwd_cache[fkey]
+        g, sg = _layer_backward(c, st, sst, T)
+        fw = lambda s: {k: s[k] for k in ("mean", "var", "kl", "q", "knn", "varraw", "r")}
+        _layer_ref_cache[key] = (dict(fw(st), **g), dict(fw(sst), **sg))
+    return _layer_ref_cache[key][1 if shadow else 0]
+
+
+def layer_oracle(c):
+    """The same outputs by float64 autograd over oracle.layer_moments + kl_layer (triangular solves, no explicit inverse)."""
+    from oracle import mfdgp_oracle as O
+    kind, d, xdiv = c["kind"], c["d"], c["xdiv"]
+    t = lambda a: torch.tensor(np.array(a), dtype=torch.float64)
+    x, m, LS, hyp = t(c["x"]).requires_grad_(True), t(c["m"]).requires_grad_(True), t(c["L_S"]).requires_grad_(True), t(c["hyp"]).requires_grad_(True)
+    f, zf = (t(c["f"]).requires_grad_(True), t(c["zf"]).requires_grad_(True)) if kind == 1 else (None, None)
+    xr = x.repeat_interleave(xdiv, 0)
+    Zx = t(c["Zx"])
+    Xt = xr if kind == 0 else torch.cat([xr, f[:, None]], 1)
+    Zt = Zx if kind == 0 else torch.cat([Zx, zf[:, None]], 1)
+    hd = hyp_dict(kind, hyp, d)
+    mean, var, _ = O.layer_moments(hd, Xt, Zt, m, LS, jitter=c["jitter"], training=(c["branch"] == 0), shortcut=False)
+    var = var.clamp_min(c["min_var"])                                      # the oracle's own floor is 1e-10 <= min_var
+    kl = O.kl_layer(hd, Zt, m, LS, jitter=c["jitter"])
+    ((t(c["g_mean"]) * mean).sum() + (t(c["g_var"]) * var).sum() + c["g_kl"] * kl).backward()
+    n = lambda v: v.detach().numpy()
+    out = dict(mean=n(mean), var=n(var), kl=n(kl), g_m=n(m.grad), g_LS=np.tril(n(LS.grad)), g_hyp=n(hyp.grad), g_x=n(x.grad))
+    if kind == 1:
+        out["g_f"], out["g_zf"] = n(f.grad), n(zf.grad)
+    return out
+
+
+def layer_names(c):
+    return ("mean", "var", "kl", "g_m", "g_LS", "g_hyp") + (("g_x",) if c["want_dx"] else ()) + (("g_f", "g_zf") if c["kind"] == 1 else ())
+
+
+def layer_ratios(got, ref, S, names):
+    """{output: (worst |got - ref| / (u S) over the components with S > 0, number of components with S = 0 that are not
+    exactly zero -- NaN included)}."""
+    out = {}
+    for k in names:
+        g, r, s = ld(got[k]).reshape(np.shape(ref[k])), ld(ref[k]), ld(S[k])
+        err = np.abs(g - r)
+        pos = s > 0
+        with np.errstate(invalid="ignore"):
+            ratio = np.where(pos, err / np.where(pos, ld(U) * s, 1), 0)
+            ratio = np.where(np.isnan(ratio), np.inf, ratio)
+        out[k] = (float(np.max(ratio, initial=0.0)), int(np.sum(~pos & ~(g == 0))))
+    return out
+
+
+def layer_gate(got, ref, S, names, C=None):
+    """(violations, {group: worst ratio}, report) of the gate |got - ref| <= C_g u S, S = 0 => exactly zero."""
+    C = LAYER_C if C is None else C
+    rat = layer_ratios(got, ref, S, names)
+    worst, bad = {}, []
+    for k, (r, nz) in rat.items():
+        g = layer_group(k)
+        worst[g] = max(worst.get(g, 0.0), r)
+        if not r <= C[g] or nz:
+            bad.append((k, r, nz))
+    report = "  ".join("%s %.2f u S = %.0f%% of the gate" % (g, w, 100 * w / C[g]) for g, w in worst.items())
+    return bad, worst, report
+
+
+# The cases the GPU conformance tests run and the CPU test proves the conditions and the constants on:
+# (kind, d, M, nbase, xdiv, seed, clamp, floor, branch, want_dx).  M: 8 / 127 / 128 (kl_one, substitution Cholesky, Mp = 128),
+# 129 (kl_part, blocked Cholesky, Mp = 256), 257 (Mp = 384: an odd row-block count), 400 (Mp = 512: the k-sliced dual syrk);
+# N' = nbase xdiv: 12 (one partial block), 128 (exact), 129 (127 padding columns), 300 (several partial rows); clamp = 128
+# columns at M = 8: every column of the first block clamped.
+LAYER_CASES = [
+    (0, 2, 8, 12, 1, 0, 0, False, 0, 1), (0, 2, 8, 300, 1, 0, 128, False, 0, 1), (0, 9, 8, 128, 1, 0, 0, True, 1, 0),
+    (0, 2, 8, 129, 1, 1, 0, True, 0, 0), (0, 2, 127, 129, 1, 0, 0, False, 0, 1), (0, 9, 127, 12, 1, 0, 0, False, 1, 0),
+    (0, 2, 127, 300, 1, 0, 10, True, 0, 0), (0, 2, 128, 128, 1, 0, 0, False, 0, 0), (0, 2, 128, 300, 1, 0, 5, True, 0, 1),
+    (0, 9, 128, 12, 1, 0, 0, False, 1, 1), (0, 2, 129, 300, 1, 0, 0, False, 0, 1), (0, 9, 129, 129, 1, 0, 0, True, 1, 1),
+    (0, 2, 129, 12, 1, 0, 4, False, 0, 0), (0, 2, 257, 128, 1, 0, 0, False, 0, 1), (0, 9, 257, 300, 1, 0, 20, False, 0, 0),
+    (0, 2, 257, 129, 1, 0, 0, True, 1, 1), (0, 2, 400, 300, 1, 0, 30, False, 0, 1),
+    (1, 2, 8, 4, 3, 0, 0, False, 0, 1), (1, 2, 8, 100, 3, 0, 43, False, 0, 1), (1, 9, 8, 16, 8, 0, 0, True, 1, 0),
+    (1, 2, 8, 129, 1, 1, 0, True, 0, 0), (1, 2, 127, 43, 3, 0, 0, False, 0, 1), (1, 9, 127, 12, 1, 0, 0, False, 1, 0),
+    (1, 2, 127, 100, 3, 0, 8, True, 0, 0), (1, 2, 128, 16, 8, 0, 0, False, 0, 0), (1, 2, 128, 100, 3, 0, 5, True, 0, 1),
+    (1, 9, 128, 4, 3, 0, 0, False, 1, 1), (1, 2, 129, 300, 1, 0, 0, False, 0, 1), (1, 9, 129, 43, 3, 0, 0, True, 1, 1),
+    (1, 2, 129, 4, 3, 0, 2, False, 0, 0), (1, 2, 257, 16, 8, 0, 0, False, 0, 1), (1, 9, 257, 100, 3, 0, 10, False, 0, 0),
+    (1, 2, 257, 129, 1, 0, 0, True, 1, 1), (1, 2, 400, 100, 3, 0, 20, False, 0, 1),
+]
+LAYER_ACTIVITY_CASES = [(0, 2, 129, 640, 1, 0, 0, False, 0, 1), (1, 2, 129, 80, 8, 0, 0, False, 0, 1)]          # N' = 640: five blocks
+LAYER_SPLIT_CASES = [(0, 2, 129, 300, 1, 0, 0, False, 0, 1), (1, 2, 129, 300, 1, 0, 0, False, 0, 1), (1, 2, 129, 43, 3, 1, 0, False, 0, 1)]
+LAYER_SPLIT_ONE = (1, 2, 8, 4, 3, 0, 0, False, 0, 1)
+LAYER_TUNING_CASES = [c for c in LAYER_CASES if c[2] in (257, 400) and c[1] == 2 and c[8] == 0]
+LAYER_UPSTREAM_CASES = [(0, 2, 129, 300, 1, 0, 0, False, 0, 1), (1, 2, 8, 100, 3, 0, 43, False, 0, 1), (1, 2, 128, 100, 3, 0, 5, True, 0, 1)]
+LAYER_ACTIVITY = {"first": [1, 0, 0, 0, 0], "one_column": [0, 0, 1, 0, 0], "scattered": [0, 1, 0, 1, 0]}
+
+
+def activity_case(c, pattern):
+    """``c`` (N' = 640) with whole 128-blocks of exactly zero upstream gradients: 'first' -- only the first block active;
+    'one_column' -- nothing but g_mean of column 300; 'scattered' -- blocks 1 and 3."""
+    mask = column_mask(LAYER_ACTIVITY[pattern], c["Np"])
+    if pattern == "one_column":
+        one = np.arange(c["Np"]) == 300
+        return with_upstream(c, np.where(one, c["g_mean"], 0.0), None, 0.0, tag=pattern), mask
+    return with_upstream(c, np.where(mask, c["g_mean"], 0.0), np.where(mask, c["g_var"], 0.0), c["g_kl"], tag=pattern), mask
+
+
+def all_layer_cases():
+    seen, out = set(), []
+    for k in LAYER_CASES + LAYER_ACTIVITY_CASES + LAYER_SPLIT_CASES + [LAYER_SPLIT_ONE] + LAYER_UPSTREAM_CASES:
+        if k not in seen:
+            seen.add(k)
+            out.append(k)
+    return out
+
+
+# ---- direct callers of the layer entry points: pointers and the descriptor (tuning, jitter, min_var, branch, want_dx) pass
+# through unchanged; outputs, saved, scratch and chain blocks are NaN before the call; every output has GUARD doubles behind it
+GUARD = 8
+WORKSPACE_TOO_SMALL = 2                 # MOBOCMF_WORKSPACE_TOO_SMALL
+
+
+class LayerCall:
+    """What a direct layer call leaves behind: ``out`` {name: float64 numpy}, ``rc``, ``info``, ``untouched`` (every guard double
+    bitwise as it was), the device buffers a later call of the sequence needs."""
+
+
+def _dev(a):
+    return None if a is None else torch.as_tensor(np.ascontiguousarray(a), dtype=torch.float64).cuda()
+
+
+def _out(n):
+    return torch.full((n + GUARD,), NAN, dtype=torch.float64, device="cuda")
+
+
+def _collect(r, bufs, lens):
+    torch.cuda.synchronize()
+    nan_bits = torch.full((GUARD,), NAN, dtype=torch.float64, device="cuda").view(torch.int64)
+    r.untouched = all(bool(torch.equal(bufs[k][n:].view(torch.int64), nan_bits)) for k, n in lens.items())
+    r.out = {k: bufs[k][:n].cpu().numpy() for k, n in lens.items()}
+    r.bufs = bufs
+    return r
+
+
+def layer_desc(c, tune=None, params_const=0, **over):
+    from mobocmf_amd import _lib
+    d = _lib.LayerDesc(kind=c["kind"], d=c["d"], M=c["M"], xdiv=c["xdiv"], Np=c["Np"], branch=c["branch"], want_dx=c["want_dx"],
+                       jitter=c["jitter"], min_var=c["min_var"], params_const=params_const, reserved=0)
+    for k, v in over.items():
+        setattr(d, k, v)
+    if tune is not None:
+        d.tuning = ctypes.pointer(tune)
+    d._tune = tune                                                          # keeps it alive with the descriptor
+    return d
+
+
+def layer_inputs(c):
+    return {k: _dev(c[k]) for k in ("x", "f", "Zx", "zf", "hyp", "m", "L_S")}
+
+
+def _sizes(fn, desc):
+    a, b = ctypes.c_size_t(), ctypes.c_size_t()
+    rc = getattr(lib(), fn)(ctypes.byref(desc), ctypes.byref(a), ctypes.byref(b))
+    assert a.value % 8 == 0 and b.value % 8 == 0
+    return rc, a.value, b.value
+
+
+def _grad_lens(c, names):
+    n = {"g_hyp": len(c["hyp"]), "g_m": c["M"], "g_LS": c["M"] * c["M"], "g_x": c["nbase"] * c["d"], "g_f": c["Np"], "g_zf": c["M"]}
+    return {k: n[k] for k in names if (k != "g_x" or c["want_dx"]) and (k not in ("g_f", "g_zf") or c["kind"] == 1)}
+
+
+def _shape_out(c, out):
+    if "g_LS" in out:
+        out["g_LS"] = out["g_LS"].reshape(c["M"], c["M"])
+    if "g_x" in out:
+        out["g_x"] = out["g_x"].reshape(c["nbase"], c["d"])
+    if "kl" in out:
+        out["kl"] = out["kl"][0]
+    return out
+
+
+def layer_forward_direct(c, tune=None, desc=None, saved_short=0, size_desc=None):
+    """mobocmf_layer_forward with the sizes mobocmf_layer_workspace_bytes reports for the same descriptor (``size_desc``: for
+    that one -- a descriptor the size query itself refuses can still be handed to the call)."""
+    r = LayerCall()
+    r.c, r.desc, r.inp = c, desc if desc is not None else layer_desc(c, tune), layer_inputs(c)
+    r.size_rc = _sizes("mobocmf_layer_workspace_bytes", r.desc)[0]
+    r.rc, r.sb, r.cb = _sizes("mobocmf_layer_workspace_bytes", r.desc if size_desc is None else size_desc)
+    assert r.rc == 0
+    r.saved, scratch = _nan_bytes(r.sb), _nan_bytes(r.cb)
+    lens = {"mean": c["Np"], "var": c["Np"], "kl": 1}
+    bufs = {k: _out(n) for k, n in lens.items()}
+    info = torch.full((1,), -77, dtype=torch.int32, device="cuda")
+    i = r.inp
+    r.rc = lib().mobocmf_layer_forward(ctypes.byref(r.desc), _p(i["x"]), _p(i["f"]), _p(i["Zx"]), _p(i["zf"]), _p(i["hyp"]), _p(i["m"]),
+                                       _p(i["L_S"]), _p(bufs["mean"]), _p(bufs["var"]), _p(bufs["kl"]), _p(info), _p(r.saved),
+                                       r.sb - saved_short, _p(scratch), r.cb, _stream())
+    _collect(r, bufs, lens)
+    r.info = int(info[0])
+    _shape_out(c, r.out)
+    return r
+
+
+def layer_backward_direct(fw, c=None, null=()):
+    """mobocmf_layer_backward over the forward ``fw`` with the upstream gradients of ``c`` (default: the forward's case);
+    ``null``: names among g_mean / g_var passed as NULL."""
+    c = fw.c if c is None else c
+    r = LayerCall()
+    lens = _grad_lens(c, ("g_hyp", "g_m", "g_LS", "g_x", "g_f", "g_zf"))
+    bufs = {k: _out(n) for k, n in lens.items()}
+    scratch = _nan_bytes(fw.cb)
+    up = {k: None if k in null else _dev(c[k]) for k in ("g_mean", "g_var")}
+    gkl = _dev(np.array([c["g_kl"]]))
+    i = fw.inp
+    r.rc = lib().mobocmf_layer_backward(ctypes.byref(fw.desc), _p(i["x"]), _p(i["f"]), _p(i["Zx"]), _p(i["zf"]), _p(i["hyp"]), _p(i["m"]),
+                                        _p(i["L_S"]), _p(up["g_mean"]), _p(up["g_var"]), _p(gkl), _p(bufs.get("g_f")), _p(bufs.get("g_zf")),
+                                        _p(bufs["g_hyp"]), _p(bufs["g_m"]), _p(bufs["g_LS"]), _p(bufs.get("g_x")), _p(fw.saved), fw.sb,
+                                        _p(scratch), fw.cb, _stream())
+    _collect(r, bufs, lens)
+    _shape_out(c, r.out)
+    return r
+
+
+def _desc_table(descs):
+    from mobocmf_amd import _lib
+    return (ctypes.POINTER(_lib.LayerDesc) * len(descs))(*[ctypes.pointer(d) for d in descs])
+
+
+def chain_forward_direct(cs, tune=None, descs=None):
+    """mobocmf_layers_chain_forward of the layers ``cs`` (equal M) into NaN-filled chain blocks of the size and stride
+    mobocmf_chain_block_bytes reports (the chain's descriptors: N' = xdiv = 1, as functional.ChainBatch.chain_desc)."""
+    r = LayerCall()
+    n = len(cs)
+    r.cs, r.tune = cs, tune
+    r.descs = descs if descs is not None else [layer_desc(c, tune, Np=1, xdiv=1, want_dx=0) for c in cs]
+    r.rc, r.bb, r.st = _sizes("mobocmf_chain_block_bytes", r.descs[0])
+    if r.rc:
+        return r
+    r.stride = (r.bb + 255) // 256 * 256
+    r.blocks = _nan_bytes(n * r.stride)
+    r.inp = [layer_inputs(c) for c in cs]
+    kls = [_out(1) for _ in cs]
+    infos = [torch.full((1,), -77, dtype=torch.int32, device="cuda") for _ in cs]
+    T = lambda k: _tab([i[k] for i in r.inp])
+    r.rc = lib().mobocmf_layers_chain_forward(n, _desc_table(r.descs), T("Zx"), T("zf"), T("hyp"), T("m"), T("L_S"), _tab(kls), _tab(infos),
+                                              _p(r.blocks), r.stride, r.blocks.numel(), _stream())
+    torch.cuda.synchronize()
+    nan_bits = torch.full((GUARD,), NAN, dtype=torch.float64, device="cuda").view(torch.int64)
+    r.untouched = all(bool(torch.equal(k[1:].view(torch.int64), nan_bits)) for k in kls)
+    r.kl = [float(k[0]) for k in kls]
+    r.info = [int(i[0]) for i in infos]
+    return r
+
+
+def chain_block(ch, z, state_only=False):
+    return ch.blocks[z * ch.stride:z * ch.stride + (ch.st if state_only else ch.bb)]
+
+
+def panel_forward_direct(ch, z, c, params_const=0, block=None):
+    """mobocmf_layer_panel_forward of layer ``z`` of the chain call ``ch`` (``block``: that byte tensor instead of the layer's
+    chain block -- the state alone under params_const)."""
+    r = LayerCall()
+    r.c, r.z, r.inp = c, z, ch.inp[z]
+    r.desc = layer_desc(c, ch.tune, params_const)
+    r.block = chain_block(ch, z) if block is None else block
+    r.rc, r.sb, r.cb = _sizes("mobocmf_panel_workspace_bytes", r.desc)
+    if r.rc:
+        return r
+    r.saved, scratch = _nan_bytes(r.sb), _nan_bytes(r.cb)
+    r.x, r.f = _dev(c["x"]), _dev(c["f"])
+    lens = {"mean": c["Np"], "var": c["Np"]}
+    bufs = {k: _out(n) for k, n in lens.items()}
+    i = r.inp
+    r.rc = lib().mobocmf_layer_panel_forward(ctypes.byref(r.desc), _p(r.x), _p(r.f), _p(i["Zx"]), _p(i["zf"]), _p(i["hyp"]), _p(bufs["mean"]),
+                                             _p(bufs["var"]), _p(r.block), r.block.numel(), _p(r.saved), r.sb, _p(scratch), r.cb, _stream())
+    return _collect(r, bufs, lens)
+
+
+def panel_backward_direct(pf, c=None):
+    """mobocmf_layer_panel_backward over the panel forward ``pf``: g_f, g_x and the K_mn shares of g_hyp / g_zf."""
+    c = pf.c if c is None else c
+    r = LayerCall()
+    lens = _grad_lens(c, ("g_hyp", "g_x", "g_f", "g_zf"))
+    bufs = {k: _out(n) for k, n in lens.items()}
+    scratch = _nan_bytes(pf.cb)
+    gm, gv = _dev(c["g_mean"]), _dev(c["g_var"])
+    i = pf.inp
+    r.rc = lib().mobocmf_layer_panel_backward(ctypes.byref(pf.desc), _p(pf.x), _p(pf.f), _p(i["Zx"]), _p(i["zf"]), _p(i["hyp"]), _p(gm), _p(gv),
+                                              _p(bufs.get("g_f")), _p(bufs.get("g_zf")), _p(bufs["g_hyp"]), _p(bufs.get("g_x")), _p(pf.block),
+                                              pf.block.numel(), _p(pf.saved), pf.sb, _p(scratch), pf.cb, _stream())
+    _collect(r, bufs, lens)
+    _shape_out(c, r.out)
+    return r
+
+
+def chain_backward_direct(ch, g_kl, had_panel, shares=None):
+    """mobocmf_layers_chain_backward.  ``shares``[z]: the LayerCall of layer z's panel backward, whose g_hyp / g_zf buffers are
+    handed over (had_panel 2: accumulated into) -- None: fresh NaN buffers.  Returns one LayerCall per layer."""
+    n = len(ch.cs)
+    outs, lens, bufs = [], [], []
+    for z, c in enumerate(ch.cs):
+        l = _grad_lens(c, ("g_hyp", "g_m", "g_LS", "g_zf"))
+        b = {k: _out(m) for k, m in l.items()}
+        if shares is not None and shares[z] is not None:
+            b["g_hyp"] = shares[z].bufs["g_hyp"]
+            if "g_zf" in b:
+                b["g_zf"] = shares[z].bufs["g_zf"]
+        lens.append(l)
+        bufs.append(b)
+    gk = [_dev(np.array([g])) for g in g_kl]
+    T = lambda k: _tab([i[k] for i in ch.inp])
+    B = lambda k: _tab([b.get(k) for b in bufs])
+    rc = lib().mobocmf_layers_chain_backward(n, _desc_table(ch.descs), T("Zx"), T("zf"), T("hyp"), _tab(gk), (ctypes.c_int32 * n)(*had_panel),
+                                             B("g_zf"), B("g_hyp"), B("g_m"), B("g_LS"), _p(ch.blocks), ch.stride, ch.blocks.numel(), _stream())
+    for z, c in enumerate(ch.cs):
+        r = LayerCall()
+        r.rc = rc
+        _collect(r, bufs[z], lens[z])
+        _shape_out(c, r.out)
+        outs.append(r)
+    return outs
