@@ -124,11 +124,18 @@ if __name__ == "__main__":
                     help="average the JES acquisition over this many sampled Pareto sets (one conditioned fit each)")
     ap.add_argument("--pareto-search", choices=["grid", "evolve"], default="grid",
                     help="how the sampled Pareto set is searched: the random grid, or NSGA-II on the GPU started from it")
+    ap.add_argument("--learn-inducing", action="store_true",
+                    help="train the inducing inputs too (one shared Z_x per surrogate; captured layer-path steps)")
     a = ap.parse_args()
+    if a.learn_inducing and a.warm_epochs is not None:
+        ap.error("--learn-inducing does not combine with --warm-epochs (the posterior warm start needs fixed inducing inputs)")
     if a.warm_epochs is not None and a.iters < 2:
         ap.error("--warm-epochs needs --iters > 1: the first iteration has no predecessor to start from")
+    mk = {"pareto_search": a.pareto_search}
+    if a.learn_inducing:
+        mk["learn_inducing_locations"] = True
     if a.iters > 1:
         loop(iters=a.iters, seed=a.seed, epochs=a.epochs, warm_epochs=a.warm_epochs, pareto_samples=a.pareto_samples,
-             model_kwargs={"pareto_search": a.pareto_search})
+             model_kwargs=mk)
     else:
-        run(epochs=a.epochs, seed=a.seed, pareto_samples=a.pareto_samples, model_kwargs={"pareto_search": a.pareto_search})
+        run(epochs=a.epochs, seed=a.seed, pareto_samples=a.pareto_samples, model_kwargs=mk)

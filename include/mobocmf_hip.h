@@ -234,6 +234,55 @@ int mobocmf_gram_backward(int32_t kind, int32_t d, const double* x1, const doubl
                           const double* gknn, const int32_t* col_activity, double* g_hyp, double* g_f1, double* g_f2,
                           double* g_x2, void* workspace, size_t workspace_bytes, mobocmf_stream_t stream);
 
+/* The ROW-side input gradient of the same launch, the one output mobocmf_gram_backward does not form: g_x1 [n1 x d] =
+ * dL/dx1 for L = sum G . K -- the gradient with respect to the inducing inputs Z_x when the rows are the inducing points.
+ * Arguments as in mobocmf_gram_backward (rows x1 / f1, columns the rows of x2 replicated xdiv-fold with f2; G, ldk and
+ * col_activity as there: rows >= n1 of G and the columns of inactive blocks are never read).  n1 <= 65535 * 64.
+ *   symmetric     1 = the K_mm mode: n1 == nbase2, xdiv == 1 (MOBOCMF_BAD_ARG otherwise), x2 / f2 hold the values of x1 / f1
+ *                 and G is symmetric; g_x1 is then the gradient with respect to the shared argument, row side plus column
+ *                 side (twice the row side; the diagonal contributes nothing).  0 = the row side alone.
+ *   g_x1          OVERWRITTEN.  Deterministic: per-chunk partial sums and one reduction launch, no atomics; two calls on
+ *                 the same inputs give the same bits.
+ *   workspace     >= the bytes mobocmf_gram_backward_rows_workspace_bytes reports; MOBOCMF_WORKSPACE_TOO_SMALL below that.
+ *                 Nothing beyond the reported size is written.
+ * geometry (may be NULL) receives the launch: [0] column chunks = partials per output the reduction adds, [1] row groups
+ * (64 rows each), [2] base columns per chunk (four wavefronts, [2] / 4 base columns each, walked in tiles of 32 columns). */
+int mobocmf_gram_backward_rows_workspace_bytes(int32_t kind, int32_t d, int64_t n1, int64_t nbase2, int32_t xdiv, size_t* bytes,
+                                               int32_t* geometry);
+int mobocmf_gram_backward_rows(int32_t kind, int32_t d, const double* x1, const double* f1, int64_t n1, const double* x2,
+                               const double* f2, int64_t nbase2, int32_t xdiv, const double* hyp, const double* G, int64_t ldk,
+                               const int32_t* col_activity, int32_t symmetric, double* g_x1, void* workspace,
+                               size_t workspace_bytes, mobocmf_stream_t stream);
+
+/* The backward halves with the gradient of the inducing inputs Z_x [M x d] as one more output.  Each takes the arguments of
+ * the entry point it extends plus g_Zx and a workspace of its own (zws, zws_bytes), runs exactly that entry point's launches
+ * -- every other output has the plain call's bits -- and then the row-side Gram backward on the dL/dK_mn (PANEL) or the
+ * symmetrised dL/dK_mm (CHAIN) those launches left in the scratch / chain block.
+ *   mobocmf_layer_backward_z          g_Zx = K_mn share + K_mm share, OVERWRITTEN; zws >= panel_bytes + chain_bytes.
+ *   mobocmf_layer_panel_backward_z    g_Zx = the K_mn share, OVERWRITTEN; zws >= panel_bytes.  params_const = 1 is refused.
+ *   mobocmf_layers_chain_backward_z   g_Zx = host array of n device pointers, each [M x d]: the K_mm shares, OVERWRITTEN;
+ *                                     zws >= n * chain_bytes.
+ * panel_bytes / chain_bytes: mobocmf_inducing_grad_workspace_bytes.  zws must not overlap the call's saved / scratch bytes or
+ * chain blocks (MOBOCMF_BAD_ARG).  For layers >= 1 the gradient holds for a Z_x shared by all layers of the model (Z~_l =
+ * [Z_x, m_{l-1}]): the caller adds the layers' shares. */
+int mobocmf_inducing_grad_workspace_bytes(const mobocmf_layer_desc* desc, size_t* panel_bytes, size_t* chain_bytes);
+int mobocmf_layer_backward_z(const mobocmf_layer_desc* desc, const double* x, const double* f, const double* Zx,
+                             const double* zf, const double* hyp, const double* m, const double* L_S,
+                             const double* g_mean, const double* g_var, const double* g_kl, double* g_f, double* g_zf,
+                             double* g_hyp, double* g_m, double* g_LS, double* g_x, double* g_Zx, void* saved,
+                             size_t saved_bytes, void* scratch, size_t scratch_bytes, void* zws, size_t zws_bytes,
+                             mobocmf_stream_t stream);
+int mobocmf_layer_panel_backward_z(const mobocmf_layer_desc* desc, const double* x, const double* f, const double* Zx,
+                                   const double* zf, const double* hyp, const double* g_mean, const double* g_var,
+                                   double* g_f, double* g_zf, double* g_hyp, double* g_x, double* g_Zx, void* chain_block,
+                                   size_t block_bytes, void* saved, size_t saved_bytes, void* scratch, size_t scratch_bytes,
+                                   void* zws, size_t zws_bytes, mobocmf_stream_t stream);
+int mobocmf_layers_chain_backward_z(int32_t n, const mobocmf_layer_desc* const* desc, const double* const* Zx,
+                                    const double* const* zf, const double* const* hyp, const double* const* g_kl,
+                                    const int32_t* had_panel, double* const* g_zf, double* const* g_hyp, double* const* g_m,
+                                    double* const* g_LS, double* const* g_Zx, void* blocks, size_t block_stride,
+                                    size_t blocks_bytes, void* zws, size_t zws_bytes, mobocmf_stream_t stream);
+
 /* One random-Fourier-feature function sample of a layer evaluated at n points (mfdgp_hidden_layer.py:326-337, :402-444; the
  * Pareto-grid evaluation of moop.py:232-272), without materialising the F x n feature matrix:
  *   kind 0:  out[i] = sum_j theta[j] s0 cos(W1[j].x_i + b1[j])

@@ -224,6 +224,12 @@ SYMBOLS = {
     "mobocmf_gram_forward_rep": [_I32, _I32, _P, _P, _I64, _P, _P, _I64, _I32, _P, _P, _I64, _P, _P],
     "mobocmf_gram_backward_workspace_bytes": [_I32, _I32, _I64, _I64, _I32, _I32, ctypes.POINTER(_SZ), ctypes.POINTER(_I32)],
     "mobocmf_gram_backward": [_I32, _I32, _P, _P, _I64, _P, _P, _I64, _I32, _P, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _SZ, _P],
+    "mobocmf_gram_backward_rows_workspace_bytes": [_I32, _I32, _I64, _I64, _I32, ctypes.POINTER(_SZ), ctypes.POINTER(_I32)],
+    "mobocmf_gram_backward_rows": [_I32, _I32, _P, _P, _I64, _P, _P, _I64, _I32, _P, _P, _I64, _P, _I32, _P, _P, _SZ, _P],
+    "mobocmf_inducing_grad_workspace_bytes": [ctypes.POINTER(LayerDesc), ctypes.POINTER(_SZ), ctypes.POINTER(_SZ)],
+    "mobocmf_layer_backward_z": [ctypes.POINTER(LayerDesc)] + [_P] * 17 + [_P, _SZ, _P, _SZ, _P, _SZ, _P],
+    "mobocmf_layer_panel_backward_z": [ctypes.POINTER(LayerDesc)] + [_P] * 12 + [_P, _SZ, _P, _SZ, _P, _SZ, _P, _SZ, _P],
+    "mobocmf_layers_chain_backward_z": [_I32] + [_P] * 11 + [_P, _SZ, _SZ, _P, _SZ, _P],
     "mobocmf_check_info": [_P, ctypes.POINTER(_I32), _P],
     "mobocmf_natgrad_workspace_bytes": [_I32, _I32, ctypes.POINTER(_SZ)],
     "mobocmf_natgrad_step": [_I32, _I32, _P, _P, _P, _P, _D, _D, _I32, _D, _P, _P, _P, _P, _SZ, ctypes.POINTER(Tuning), _P],

@@ -586,6 +586,45 @@ int chain_backward(int n, const ChainWs& c, int64_t zs, const ChainIO& io, const
     return launch_sum_partials_multi(tk, nt, s);
 }
 
+// ---- Row-side Gram backward (gram_rows.hip): the gradient with respect to the inducing inputs Z_x.  The `_z` entry points run
+// it on what the backward halves above leave behind: B.dK = dL/dK_mn in the call's scratch (PANEL) and Gm = sym dL/dK_mm in
+// the chain block (CHAIN).  Its partials live in a workspace of the caller's that is neither.
+bool gram_rows_shape_ok(int32_t kind, int32_t d, int64_t n1, int64_t nbase2, int32_t xdiv) {
+    return (kind == 0 || kind == 1) && d >= 1 && d <= MOBOCMF_MAX_D && n1 >= 1 && nbase2 >= 1 && xdiv >= 1 &&
+           xdiv <= MOBOCMF_MAX_XDIV && n1 <= (int64_t)65535 * 64 && nbase2 <= 0x7fffffff;
+}
+int64_t gram_rows_part_elems(int32_t d, int64_t n1, int64_t nbase2, int32_t xdiv, int64_t* chunks_out = nullptr) {
+    int64_t chunks;
+    int groups, wb;
+    gram_rows_geometry(n1, nbase2, xdiv, &chunks, &groups, &wb);
+    if (chunks_out) *chunks_out = chunks;
+    return chunks * n1 * d;
+}
+int gram_rows_partials(int kind, int d, const double* x1, const double* f1, int64_t n1, const double* x2, const double* f2,
+                       int64_t nbase2, int xdiv, const double* hyp, const double* G, int64_t ldk, const int32_t* colact,
+                       int symmetric, double* part, hipStream_t s) {
+    GramRowsArgs g = {};
+    g.kind = kind; g.d = d; g.xdiv = xdiv; g.symmetric = symmetric;
+    g.x1 = x1; g.f1 = f1; g.n1 = n1; g.x2 = x2; g.f2 = f2; g.nbase2 = nbase2;
+    g.hyp = hyp; g.G = G; g.ldk = ldk; g.colact = colact; g.part = part;
+    return launch_gram_bwd_rows(g, s);
+}
+bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
+    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+    return a && b && pa < pb + nb && pb < pa + na;
+}
+// the PANEL half's share: partials of dK (as panel_backward left it) into `part`
+int panel_rows_partials(const mobocmf_layer_desc* desc, const Dims& D, const PanelBwd& B, const double* x, const double* f,
+                        const double* Zx, const double* zf, const double* hyp, double* part, hipStream_t s) {
+    return gram_rows_partials(desc->kind, desc->d, Zx, zf, D.M, x, f, D.nbase, desc->xdiv, hyp, B.dK, D.Np,
+                              tune().sparse_backward ? B.blkact : nullptr, 0, part, s);
+}
+// the CHAIN half's share of layer z: partials of Gm (as chain_backward left it: its W[2]) into `part`
+int chain_rows_partials(const mobocmf_layer_desc* desc, const Dims& D, const ChainWs& c, int z, int64_t zs, const double* Zx,
+                        const double* zf, const double* hyp, double* part, hipStream_t s) {
+    return gram_rows_partials(desc->kind, desc->d, Zx, zf, D.M, Zx, zf, D.M, 1, hyp, c.W[2] + z * zs, D.Mp, nullptr, 1, part, s);
+}
+
 bool same_chain_shape(int n, const mobocmf_layer_desc* const* d) {
     for (int z = 0; z < n; ++z)
         if (!valid_desc(d[z]) || d[z]->M != d[0]->M) return false;
@@ -622,7 +661,7 @@ bool carve_cov(void* scratch, size_t bytes, const mobocmf_layer_desc* d, const D
 
 extern "C" {
 
-int mobocmf_version(void) { return 202; }
+int mobocmf_version(void) { return 203; }
 
 int mobocmf_device_arch_ok(void) {
     int dev = 0;
@@ -673,12 +712,15 @@ int mobocmf_layer_forward(const mobocmf_layer_desc* desc, const double* x, const
     return panel_forward(desc, D, c, P, F, x, f, Zx, zf, hyp, mean, var, s);
 }
 
-int mobocmf_layer_backward(const mobocmf_layer_desc* desc, const double* x, const double* f, const double* Zx,
-                           const double* zf, const double* hyp, const double* m, const double* L_S,
-                           const double* g_mean, const double* g_var, const double* g_kl, double* g_f, double* g_zf,
-                           double* g_hyp, double* g_m, double* g_LS, double* g_x, void* saved, size_t saved_bytes,
-                           void* scratch, size_t scratch_bytes, mobocmf_stream_t stream) {
-    if (!valid_desc(desc) || desc->params_const || !x || !Zx || !hyp || !g_mean || !g_var || !g_kl || !g_hyp || !g_m || !g_LS ||
+// want_z (the `_z` variant): after each half the row-side Gram backward runs on the dK / Gm it left behind; g_Zx receives
+// the two shares in one reduction launch.  Without it the launches are exactly the plain call's.
+static int layer_backward_impl(const mobocmf_layer_desc* desc, const double* x, const double* f, const double* Zx,
+                               const double* zf, const double* hyp, const double* m, const double* L_S,
+                               const double* g_mean, const double* g_var, const double* g_kl, double* g_f, double* g_zf,
+                               double* g_hyp, double* g_m, double* g_LS, double* g_x, void* saved, size_t saved_bytes,
+                               void* scratch, size_t scratch_bytes, bool want_z, double* g_Zx, void* zws, size_t zws_bytes,
+                               mobocmf_stream_t stream) {
+    if ((want_z && (!g_Zx || !zws)) || !valid_desc(desc) || desc->params_const || !x || !Zx || !hyp || !g_mean || !g_var || !g_kl || !g_hyp || !g_m || !g_LS ||
         (desc->want_dx && !g_x) || !saved || !scratch)
         return MOBOCMF_BAD_ARG;
     TuneScope tune_scope(desc->tuning, desc->probe_events);
@@ -690,13 +732,59 @@ int mobocmf_layer_backward(const mobocmf_layer_desc* desc, const double* x, cons
     PanelBwd B;
     if (!carve_single_saved(saved, saved_bytes, D, c, P) || !carve_single_bwd(scratch, scratch_bytes, D, desc, c, B))
         return MOBOCMF_WORKSPACE_TOO_SMALL;
+    Bump bz(zws, zws_bytes);
+    int64_t chp = 0, chc = 0;
+    double *zp = nullptr, *zc = nullptr;
+    if (want_z) {
+        if (ranges_overlap(zws, zws_bytes, scratch, scratch_bytes) || ranges_overlap(zws, zws_bytes, saved, saved_bytes))
+            return MOBOCMF_BAD_ARG;
+        zp = bz.take(gram_rows_part_elems(desc->d, D.M, D.nbase, desc->xdiv, &chp));
+        zc = bz.take(gram_rows_part_elems(desc->d, D.M, D.M, 1, &chc));
+        if (!bz.ok) return MOBOCMF_WORKSPACE_TOO_SMALL;
+    }
     TRY(panel_backward(desc, D, c, P, B, x, f, Zx, zf, hyp, g_mean, g_var, g_f, g_zf, g_hyp, g_x, s));
+    if (want_z) TRY(panel_rows_partials(desc, D, B, x, f, Zx, zf, hyp, zp, s));
     ChainIO io = {};
     io.desc = &desc; io.Zx = &Zx; io.zf = &zf; io.hyp = &hyp; io.m = &m; io.L_S = &L_S;
     io.g_kl = &g_kl; io.g_zf = &g_zf; io.g_hyp = &g_hyp; io.g_m = &g_m; io.g_LS = &g_LS;
     const bool zero = false, fold = false;
     const int acc = 1;      // the PANEL half wrote its share of g_hyp / g_zf
-    return chain_backward(1, c, 0, io, D, &zero, &acc, &fold, s);
+    TRY(chain_backward(1, c, 0, io, D, &zero, &acc, &fold, s));
+    if (!want_z) return MOBOCMF_OK;
+    TRY(chain_rows_partials(desc, D, c, 0, 0, Zx, zf, hyp, zc, s));
+    const int64_t len = (int64_t)D.M * desc->d;
+    const SumTask tk = {zp, chp, len, zc, chc, len, g_Zx, len, 0, nullptr};
+    return launch_sum_partials_multi(&tk, 1, s);
+}
+
+int mobocmf_layer_backward(const mobocmf_layer_desc* desc, const double* x, const double* f, const double* Zx,
+                           const double* zf, const double* hyp, const double* m, const double* L_S,
+                           const double* g_mean, const double* g_var, const double* g_kl, double* g_f, double* g_zf,
+                           double* g_hyp, double* g_m, double* g_LS, double* g_x, void* saved, size_t saved_bytes,
+                           void* scratch, size_t scratch_bytes, mobocmf_stream_t stream) {
+    return layer_backward_impl(desc, x, f, Zx, zf, hyp, m, L_S, g_mean, g_var, g_kl, g_f, g_zf, g_hyp, g_m, g_LS, g_x, saved,
+                               saved_bytes, scratch, scratch_bytes, false, nullptr, nullptr, 0, stream);
+}
+
+int mobocmf_layer_backward_z(const mobocmf_layer_desc* desc, const double* x, const double* f, const double* Zx,
+                             const double* zf, const double* hyp, const double* m, const double* L_S,
+                             const double* g_mean, const double* g_var, const double* g_kl, double* g_f, double* g_zf,
+                             double* g_hyp, double* g_m, double* g_LS, double* g_x, double* g_Zx, void* saved,
+                             size_t saved_bytes, void* scratch, size_t scratch_bytes, void* zws, size_t zws_bytes,
+                             mobocmf_stream_t stream) {
+    return layer_backward_impl(desc, x, f, Zx, zf, hyp, m, L_S, g_mean, g_var, g_kl, g_f, g_zf, g_hyp, g_m, g_LS, g_x, saved,
+                               saved_bytes, scratch, scratch_bytes, true, g_Zx, zws, zws_bytes, stream);
+}
+
+int mobocmf_inducing_grad_workspace_bytes(const mobocmf_layer_desc* desc, size_t* panel_bytes, size_t* chain_bytes) {
+    if (!valid_desc(desc) || !panel_bytes || !chain_bytes) return MOBOCMF_BAD_ARG;
+    Dims D = dims_of(desc);
+    Bump bp(nullptr, ~(size_t)0 >> 1), bc(nullptr, ~(size_t)0 >> 1);
+    bp.take(gram_rows_part_elems(desc->d, D.M, D.nbase, desc->xdiv));
+    bc.take(gram_rows_part_elems(desc->d, D.M, D.M, 1));
+    *panel_bytes = bp.off;
+    *chain_bytes = bc.off;
+    return MOBOCMF_OK;
 }
 
 // ------------------------------------------------------------------------------------------------- multi-layer forms
@@ -748,12 +836,12 @@ int mobocmf_layers_chain_forward(int32_t n, const mobocmf_layer_desc* const* des
     return chain_forward(n, c, (int64_t)(block_stride / sizeof(double)), io, D, (hipStream_t)stream);
 }
 
-int mobocmf_layers_chain_backward(int32_t n, const mobocmf_layer_desc* const* desc, const double* const* Zx,
-                                  const double* const* zf, const double* const* hyp, const double* const* g_kl,
-                                  const int32_t* had_panel, double* const* g_zf, double* const* g_hyp, double* const* g_m,
-                                  double* const* g_LS, void* blocks, size_t block_stride, size_t blocks_bytes,
-                                  mobocmf_stream_t stream) {
-    if (n < 1 || n > MAX_ZL || !desc || !Zx || !zf || !hyp || !g_kl || !had_panel || !g_zf || !g_hyp || !g_m || !g_LS ||
+static int layers_chain_backward_impl(int32_t n, const mobocmf_layer_desc* const* desc, const double* const* Zx,
+                                      const double* const* zf, const double* const* hyp, const double* const* g_kl,
+                                      const int32_t* had_panel, double* const* g_zf, double* const* g_hyp, double* const* g_m,
+                                      double* const* g_LS, void* blocks, size_t block_stride, size_t blocks_bytes, bool want_z,
+                                      double* const* g_Zx, void* zws, size_t zws_bytes, mobocmf_stream_t stream) {
+    if ((want_z && (!g_Zx || !zws)) || n < 1 || n > MAX_ZL || !desc || !Zx || !zf || !hyp || !g_kl || !had_panel || !g_zf || !g_hyp || !g_m || !g_LS ||
         !blocks || (block_stride & 255))
         return MOBOCMF_BAD_ARG;
     if (!same_chain_shape(n, desc)) return MOBOCMF_BAD_ARG;
@@ -777,7 +865,46 @@ int mobocmf_layers_chain_backward(int32_t n, const mobocmf_layer_desc* const* de
     ChainIO io = {};
     io.desc = desc; io.Zx = Zx; io.zf = zf; io.hyp = hyp;
     io.g_kl = g_kl; io.g_zf = g_zf; io.g_hyp = g_hyp; io.g_m = g_m; io.g_LS = g_LS;
-    return chain_backward(n, c, (int64_t)(block_stride / sizeof(double)), io, D, zero, acc, fold, (hipStream_t)stream);
+    const int64_t zs = (int64_t)(block_stride / sizeof(double));
+    hipStream_t s = (hipStream_t)stream;
+    Bump bz(zws, zws_bytes);
+    double* zc[MAX_ZL] = {};
+    int64_t chc[MAX_ZL] = {};
+    if (want_z) {
+        if (ranges_overlap(zws, zws_bytes, blocks, blocks_bytes)) return MOBOCMF_BAD_ARG;
+        for (int z = 0; z < n; ++z) {
+            if (!g_Zx[z]) return MOBOCMF_BAD_ARG;
+            zc[z] = bz.take(gram_rows_part_elems(desc[z]->d, D.M, D.M, 1, &chc[z]));
+        }
+        if (!bz.ok) return MOBOCMF_WORKSPACE_TOO_SMALL;
+    }
+    TRY(chain_backward(n, c, zs, io, D, zero, acc, fold, s));
+    if (!want_z) return MOBOCMF_OK;
+    SumTask tk[MAX_ZL];
+    for (int z = 0; z < n; ++z) {
+        TRY(chain_rows_partials(desc[z], D, c, z, zs, Zx[z], zf[z], hyp[z], zc[z], s));
+        const int64_t len = (int64_t)D.M * desc[z]->d;
+        tk[z] = {zc[z], chc[z], len, nullptr, 0, 0, g_Zx[z], len, 0, nullptr};
+    }
+    return launch_sum_partials_multi(tk, n, s);
+}
+
+int mobocmf_layers_chain_backward(int32_t n, const mobocmf_layer_desc* const* desc, const double* const* Zx,
+                                  const double* const* zf, const double* const* hyp, const double* const* g_kl,
+                                  const int32_t* had_panel, double* const* g_zf, double* const* g_hyp, double* const* g_m,
+                                  double* const* g_LS, void* blocks, size_t block_stride, size_t blocks_bytes,
+                                  mobocmf_stream_t stream) {
+    return layers_chain_backward_impl(n, desc, Zx, zf, hyp, g_kl, had_panel, g_zf, g_hyp, g_m, g_LS, blocks, block_stride,
+                                      blocks_bytes, false, nullptr, nullptr, 0, stream);
+}
+
+int mobocmf_layers_chain_backward_z(int32_t n, const mobocmf_layer_desc* const* desc, const double* const* Zx,
+                                    const double* const* zf, const double* const* hyp, const double* const* g_kl,
+                                    const int32_t* had_panel, double* const* g_zf, double* const* g_hyp, double* const* g_m,
+                                    double* const* g_LS, double* const* g_Zx, void* blocks, size_t block_stride,
+                                    size_t blocks_bytes, void* zws, size_t zws_bytes, mobocmf_stream_t stream) {
+    return layers_chain_backward_impl(n, desc, Zx, zf, hyp, g_kl, had_panel, g_zf, g_hyp, g_m, g_LS, blocks, block_stride,
+                                      blocks_bytes, true, g_Zx, zws, zws_bytes, stream);
 }
 
 int mobocmf_layer_panel_forward(const mobocmf_layer_desc* desc, const double* x, const double* f, const double* Zx,
@@ -799,12 +926,12 @@ int mobocmf_layer_panel_forward(const mobocmf_layer_desc* desc, const double* x,
     return panel_forward(desc, D, c, P, F, x, f, Zx, zf, hyp, mean, var, (hipStream_t)stream);
 }
 
-int mobocmf_layer_panel_backward(const mobocmf_layer_desc* desc, const double* x, const double* f, const double* Zx,
-                                 const double* zf, const double* hyp, const double* g_mean, const double* g_var,
-                                 double* g_f, double* g_zf, double* g_hyp, double* g_x, void* chain_block,
-                                 size_t block_bytes, void* saved, size_t saved_bytes, void* scratch, size_t scratch_bytes,
-                                 mobocmf_stream_t stream) {
-    if (!valid_desc(desc) || !x || !Zx || !hyp || !g_mean || !g_var || !g_hyp || !chain_block || !saved || !scratch ||
+static int layer_panel_backward_impl(const mobocmf_layer_desc* desc, const double* x, const double* f, const double* Zx,
+                                     const double* zf, const double* hyp, const double* g_mean, const double* g_var,
+                                     double* g_f, double* g_zf, double* g_hyp, double* g_x, void* chain_block,
+                                     size_t block_bytes, void* saved, size_t saved_bytes, void* scratch, size_t scratch_bytes,
+                                     bool want_z, double* g_Zx, void* zws, size_t zws_bytes, mobocmf_stream_t stream) {
+    if ((want_z && (!g_Zx || !zws || (desc && desc->params_const))) || !valid_desc(desc) || !x || !Zx || !hyp || !g_mean || !g_var || !g_hyp || !chain_block || !saved || !scratch ||
         (desc->want_dx && !g_x))
         return MOBOCMF_BAD_ARG;
     TuneScope tune_scope(desc->tuning, desc->probe_events);
@@ -818,7 +945,41 @@ int mobocmf_layer_panel_backward(const mobocmf_layer_desc* desc, const double* x
     carve_panel_saved(bs, D, P);
     carve_panel_bwd(bb, D, desc, B);
     if (!bs.ok || !bb.ok) return MOBOCMF_WORKSPACE_TOO_SMALL;
-    return panel_backward(desc, D, c, P, B, x, f, Zx, zf, hyp, g_mean, g_var, g_f, g_zf, g_hyp, g_x, (hipStream_t)stream);
+    hipStream_t s = (hipStream_t)stream;
+    Bump bz(zws, zws_bytes);
+    int64_t chp = 0;
+    double* zp = nullptr;
+    if (want_z) {
+        if (ranges_overlap(zws, zws_bytes, scratch, scratch_bytes) || ranges_overlap(zws, zws_bytes, chain_block, block_bytes) ||
+            ranges_overlap(zws, zws_bytes, saved, saved_bytes))
+            return MOBOCMF_BAD_ARG;
+        zp = bz.take(gram_rows_part_elems(desc->d, D.M, D.nbase, desc->xdiv, &chp));
+        if (!bz.ok) return MOBOCMF_WORKSPACE_TOO_SMALL;
+    }
+    TRY(panel_backward(desc, D, c, P, B, x, f, Zx, zf, hyp, g_mean, g_var, g_f, g_zf, g_hyp, g_x, s));
+    if (!want_z) return MOBOCMF_OK;
+    TRY(panel_rows_partials(desc, D, B, x, f, Zx, zf, hyp, zp, s));
+    const int64_t len = (int64_t)D.M * desc->d;
+    const SumTask tk = {zp, chp, len, nullptr, 0, 0, g_Zx, len, 0, nullptr};
+    return launch_sum_partials_multi(&tk, 1, s);
+}
+
+int mobocmf_layer_panel_backward(const mobocmf_layer_desc* desc, const double* x, const double* f, const double* Zx,
+                                 const double* zf, const double* hyp, const double* g_mean, const double* g_var,
+                                 double* g_f, double* g_zf, double* g_hyp, double* g_x, void* chain_block,
+                                 size_t block_bytes, void* saved, size_t saved_bytes, void* scratch, size_t scratch_bytes,
+                                 mobocmf_stream_t stream) {
+    return layer_panel_backward_impl(desc, x, f, Zx, zf, hyp, g_mean, g_var, g_f, g_zf, g_hyp, g_x, chain_block, block_bytes,
+                                     saved, saved_bytes, scratch, scratch_bytes, false, nullptr, nullptr, 0, stream);
+}
+
+int mobocmf_layer_panel_backward_z(const mobocmf_layer_desc* desc, const double* x, const double* f, const double* Zx,
+                                   const double* zf, const double* hyp, const double* g_mean, const double* g_var,
+                                   double* g_f, double* g_zf, double* g_hyp, double* g_x, double* g_Zx, void* chain_block,
+                                   size_t block_bytes, void* saved, size_t saved_bytes, void* scratch, size_t scratch_bytes,
+                                   void* zws, size_t zws_bytes, mobocmf_stream_t stream) {
+    return layer_panel_backward_impl(desc, x, f, Zx, zf, hyp, g_mean, g_var, g_f, g_zf, g_hyp, g_x, chain_block, block_bytes,
+                                     saved, saved_bytes, scratch, scratch_bytes, true, g_Zx, zws, zws_bytes, stream);
 }
 
 int mobocmf_predictive_covariance_workspace_bytes(const mobocmf_layer_desc* desc, size_t* scratch_bytes) {
@@ -1079,6 +1240,37 @@ int mobocmf_gram_backward(int32_t kind, int32_t d, const double* x1, const doubl
     }
     if (want_dx) tk[nt++] = {g.dx_part, grid.y, nbase2 * d, nullptr, 0, 0, g_x2, nbase2 * d, 0};
     return launch_sum_partials_multi(tk, nt, s);
+}
+
+int mobocmf_gram_backward_rows_workspace_bytes(int32_t kind, int32_t d, int64_t n1, int64_t nbase2, int32_t xdiv, size_t* bytes,
+                                               int32_t* geometry) {
+    if (!gram_rows_shape_ok(kind, d, n1, nbase2, xdiv) || !bytes) return MOBOCMF_BAD_ARG;
+    int64_t chunks;
+    int groups, wb;
+    gram_rows_geometry(n1, nbase2, xdiv, &chunks, &groups, &wb);
+    Bump b(nullptr, ~(size_t)0 >> 1);
+    b.take(chunks * n1 * d);
+    *bytes = b.off;
+    if (geometry) { geometry[0] = (int32_t)chunks; geometry[1] = groups; geometry[2] = 4 * wb; }
+    return MOBOCMF_OK;
+}
+
+int mobocmf_gram_backward_rows(int32_t kind, int32_t d, const double* x1, const double* f1, int64_t n1, const double* x2,
+                               const double* f2, int64_t nbase2, int32_t xdiv, const double* hyp, const double* G, int64_t ldk,
+                               const int32_t* col_activity, int32_t symmetric, double* g_x1, void* workspace,
+                               size_t workspace_bytes, mobocmf_stream_t stream) {
+    if (!gram_rows_shape_ok(kind, d, n1, nbase2, xdiv) || !x1 || !x2 || !hyp || !G || !g_x1 || !workspace ||
+        ldk < nbase2 * xdiv || (kind == 1 && (!f1 || !f2)) || (symmetric != 0 && symmetric != 1) ||
+        (symmetric && (n1 != nbase2 || xdiv != 1)))
+        return MOBOCMF_BAD_ARG;
+    int64_t chunks;
+    Bump b(workspace, workspace_bytes);
+    double* part = b.take(gram_rows_part_elems(d, n1, nbase2, xdiv, &chunks));
+    if (!b.ok) return MOBOCMF_WORKSPACE_TOO_SMALL;
+    hipStream_t s = (hipStream_t)stream;
+    TRY(gram_rows_partials(kind, d, x1, f1, n1, x2, f2, nbase2, xdiv, hyp, G, ldk, col_activity, symmetric, part, s));
+    const SumTask tk = {part, chunks, n1 * d, nullptr, 0, 0, g_x1, n1 * d, 0, nullptr};
+    return launch_sum_partials_multi(&tk, 1, s);
 }
 
 int mobocmf_gemm_f64_epilogue(int32_t tri, int32_t epi, int32_t Mr, int64_t Nc, int64_t Kd, const double* A, int64_t lda,

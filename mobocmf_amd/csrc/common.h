@@ -156,6 +156,28 @@ struct SumTask {
 };
 int launch_sum_partials_multi(const SumTask* tasks, int n, hipStream_t s);
 
+// ------------------------------------------------------------------ Gram, row-side input gradient (gram_rows.hip)
+struct GramRowsArgs {
+    int kind, d, xdiv;
+    int symmetric;        // 1: K_mm mode (x2 == x1, f2 == f1, xdiv == 1, G symmetric): the partials hold row side + column side
+    const double* x1;     // [n1 x d]     row side: the inputs the gradient is taken for
+    const double* f1;     // [n1] (kind 1)
+    int64_t n1;
+    const double* x2;     // [nbase2 x d] column side
+    const double* f2;     // [nbase2*xdiv] (kind 1)
+    int64_t nbase2;
+    const double* hyp;
+    const double* G;      // dL/dK [n1 x nbase2*xdiv], ld = ldk; rows >= n1 are never read
+    int64_t ldk;
+    const int32_t* colact; // per 128 columns of G (GramArgs.colact), or null
+    double* part;         // [chunks][n1*d]: one partial of every output per column chunk
+    int wb;               // base columns per wavefront (set by the launcher: gram_rows_geometry's rule)
+};
+// chunks = workgroups along the columns = partials per output, groups = workgroups along the rows (64 rows each), wb = base
+// columns per wavefront (a chunk has 4 wb)
+void gram_rows_geometry(int64_t n1, int64_t nbase2, int xdiv, int64_t* chunks, int* groups, int* wb);
+int launch_gram_bwd_rows(const GramRowsArgs& g, hipStream_t s);      // writes g.part; the caller reduces the chunks
+
 // ------------------------------------------------------------------ Cholesky and triangular inverse (chol.hip)
 int launch_trtri(const double* L, int64_t ld, int Mp, const double* Dinv, double* Linv, double* T, double* ws,
                  int64_t ws_elems, hipStream_t s);

@@ -204,6 +204,19 @@ def workspace_bytes(desc):
     return a.value, b.value
 
 
+def _inducing_grad_ws(descs, panel, chain, device):
+    """The workspace of a `_z` backward call (the inducing-input gradient's partial sums): a buffer of its own -- the call's
+    scratch and chain blocks hold the dK / Gm it reads -- from torch's allocator (no host sync, capturable)."""
+    lib = _lib.load()
+    total = 0
+    for desc in descs:
+        a, b = ctypes.c_size_t(), ctypes.c_size_t()
+        _lib.check(lib.mobocmf_inducing_grad_workspace_bytes(ctypes.byref(desc), ctypes.byref(a), ctypes.byref(b)),
+                   "mobocmf_inducing_grad_workspace_bytes")
+        total += (a.value if panel else 0) + (b.value if chain else 0)
+    return _poison(torch.empty(total, dtype=torch.uint8, device=device))
+
+
 class _LayerFn(torch.autograd.Function):
     """(mean, var, kl) of one variational layer; see include/mobocmf_hip.h."""
 
@@ -257,6 +270,15 @@ class _LayerFn(torch.autograd.Function):
         g_zf = new(M) if ctx.has_f else None
         g_hyp, g_m, g_LS = new(hyp.numel()), new(M), new(M, M)
         g_x = new(x.shape[0], d) if desc.want_dx else None
+        if ctx.needs_input_grad[2]:      # learnable inducing inputs: the same launches, then the row-side Gram backward
+            g_Zx = new(M, d)
+            zws = _inducing_grad_ws([desc], True, True, dev)
+            rc = lib.mobocmf_layer_backward_z(ctypes.byref(desc), _ptr(x), _ptr(f), _ptr(Zx), _ptr(zf), _ptr(hyp), _ptr(m),
+                                              _ptr(L_S), _ptr(g_mean), _ptr(g_var), _ptr(g_kl), _ptr(g_f), _ptr(g_zf),
+                                              _ptr(g_hyp), _ptr(g_m), _ptr(g_LS), _ptr(g_x), _ptr(g_Zx), _ptr(ctx.saved_ws),
+                                              ctx.sb, _ptr(scratch), scratch.numel(), _ptr(zws), zws.numel(), _stream())
+            _lib.check(rc, "mobocmf_layer_backward_z")
+            return (g_x, g_f, g_Zx, g_zf, g_hyp, g_m, g_LS, None, None, None, None, None, None, None)
         rc = lib.mobocmf_layer_backward(ctypes.byref(desc), _ptr(x), _ptr(f), _ptr(Zx), _ptr(zf), _ptr(hyp), _ptr(m),
                                         _ptr(L_S), _ptr(g_mean), _ptr(g_var), _ptr(g_kl), _ptr(g_f), _ptr(g_zf),
                                         _ptr(g_hyp), _ptr(g_m), _ptr(g_LS), _ptr(g_x), _ptr(ctx.saved_ws), ctx.sb,
@@ -363,14 +385,25 @@ class _ChainsFn(torch.autograd.Function):
             if ctx.fold[z]:
                 had[z] |= 4
         T = lambda ts: _table([0 if t is None else t.data_ptr() for t in ts])
-        rc = lib.mobocmf_layers_chain_backward(n, _desc_table(ctx.descs), T([p[0] for p in per]), T([p[1] for p in per]),
-                                               T([p[2] for p in per]), T(gk), (ctypes.c_int32 * n)(*had),
-                                               T(g_zf), T(g_hyp), T(g_m), T(g_LS), _ptr(CB.blocks), CB.stride,
-                                               CB.blocks.numel(), _stream())
-        _lib.check(rc, "mobocmf_layers_chain_backward")
+        g_Zx = [None] * n
+        if any(ctx.needs_input_grad[1 + 5 * z] for z in range(n)):      # learnable inducing inputs: the K_mm shares
+            g_Zx = [new(CB.M, CB.ds[z]) for z in range(n)]
+            zws = _inducing_grad_ws(ctx.descs, False, True, dev)
+            rc = lib.mobocmf_layers_chain_backward_z(n, _desc_table(ctx.descs), T([p[0] for p in per]), T([p[1] for p in per]),
+                                                     T([p[2] for p in per]), T(gk), (ctypes.c_int32 * n)(*had),
+                                                     T(g_zf), T(g_hyp), T(g_m), T(g_LS), T(g_Zx), _ptr(CB.blocks), CB.stride,
+                                                     CB.blocks.numel(), _ptr(zws), zws.numel(), _stream())
+            _lib.check(rc, "mobocmf_layers_chain_backward_z")
+        else:
+            rc = lib.mobocmf_layers_chain_backward(n, _desc_table(ctx.descs), T([p[0] for p in per]), T([p[1] for p in per]),
+                                                   T([p[2] for p in per]), T(gk), (ctypes.c_int32 * n)(*had),
+                                                   T(g_zf), T(g_hyp), T(g_m), T(g_LS), _ptr(CB.blocks), CB.stride,
+                                                   CB.blocks.numel(), _stream())
+            _lib.check(rc, "mobocmf_layers_chain_backward")
         out = [None]
         for z in range(n):
-            out += [None, None if ctx.fold[z] else g_zf[z], g_hyp[z], g_m[z], g_LS[z]]
+            out += [g_Zx[z] if ctx.needs_input_grad[1 + 5 * z] else None, None if ctx.fold[z] else g_zf[z], g_hyp[z], g_m[z],
+                    g_LS[z]]
         return tuple(out)
 
 
@@ -440,18 +473,28 @@ class _PanelBatchedFn(torch.autograd.Function):
         g_hyp = new(hyp.numel())
         g_x = new(x.shape[0], desc.d) if desc.want_dx else None
         blk = CB.block(z)
-        rc = lib.mobocmf_layer_panel_backward(ctypes.byref(desc), _ptr(x), _ptr(f), _ptr(Zx), _ptr(zf), _ptr(hyp),
-                                              _ptr(g_mean), _ptr(g_var), _ptr(g_f), _ptr(g_zf), _ptr(g_hyp), _ptr(g_x),
-                                              _ptr(blk), blk.numel(), _ptr(ctx.saved_ws), ctx.sb, _ptr(scratch),
-                                              scratch.numel(), _stream())
-        _lib.check(rc, "mobocmf_layer_panel_backward")
+        g_Zx = None
+        if ctx.needs_input_grad[2] and not desc.params_const:      # learnable inducing inputs: the K_mn share
+            g_Zx = new(CB.M, desc.d)
+            zws = _inducing_grad_ws([desc], True, False, dev)
+            rc = lib.mobocmf_layer_panel_backward_z(ctypes.byref(desc), _ptr(x), _ptr(f), _ptr(Zx), _ptr(zf), _ptr(hyp),
+                                                    _ptr(g_mean), _ptr(g_var), _ptr(g_f), _ptr(g_zf), _ptr(g_hyp), _ptr(g_x),
+                                                    _ptr(g_Zx), _ptr(blk), blk.numel(), _ptr(ctx.saved_ws), ctx.sb,
+                                                    _ptr(scratch), scratch.numel(), _ptr(zws), zws.numel(), _stream())
+            _lib.check(rc, "mobocmf_layer_panel_backward_z")
+        else:
+            rc = lib.mobocmf_layer_panel_backward(ctypes.byref(desc), _ptr(x), _ptr(f), _ptr(Zx), _ptr(zf), _ptr(hyp),
+                                                  _ptr(g_mean), _ptr(g_var), _ptr(g_f), _ptr(g_zf), _ptr(g_hyp), _ptr(g_x),
+                                                  _ptr(blk), blk.numel(), _ptr(ctx.saved_ws), ctx.sb, _ptr(scratch),
+                                                  scratch.numel(), _stream())
+            _lib.check(rc, "mobocmf_layer_panel_backward")
         if desc.params_const:
             return g_x, g_f, None, None, None, None, None, None, None, None
         CB.had_panel[z] = 1
         # the K_mn share of g_hyp / g_zf is handed to the chain node (which adds its K_mm share into the same buffers), and
         # None for the token: the edge to the chain node orders the backward passes, no gradient has to flow through it
         CB.panel_g[z] = (g_hyp, g_zf)
-        return g_x, g_f, None, None, None, None, None, None, None, None
+        return g_x, g_f, g_Zx, None, None, None, None, None, None, None
 
 
 def layer_panel_batched(CB, z, x, f, Zx, zf, hyp, xdiv=1, want_dx=False):

@@ -40,6 +40,19 @@ class UnwhitenedVariationalStrategy(nn.Module):
         state.pop("_Zx_contig", None)
         return state
 
+    def share_inducing_inputs(self, param):
+        """Learnable inducing inputs (MFDGP(learn_inducing_locations=True)): ``.Zx`` becomes ``param``, the model's ONE
+        nn.Parameter Z_x [M x d] -- the very tensor, held by reference and not registered here, so it shows up once in the
+        model's parameters() / state_dict() and keeps its identity through .double() / .to() (both convert a parameter in
+        place), deepcopy and pickling (both keep shared references).  Layer 0 drops its buffer of the same shape:
+        ``_inducing_points`` IS the parameter from now on, for every reader.  Layers >= 1 keep their (M, d + 1) buffer --
+        its x columns are the initial values and are not read any more."""
+        assert tuple(param.shape) == (self._inducing_points.shape[0], self.model.input_dims - self.model.kind)
+        self.__dict__["_shared_Zx"] = param
+        if self.model.kind == 0:
+            del self._buffers["_inducing_points"]
+            self.__dict__["_inducing_points"] = param
+
     @property
     def inducing_points(self):
         return self._inducing_points
@@ -85,6 +98,9 @@ class MFDGUnwhitenedVariationalStrategy(UnwhitenedVariationalStrategy):
         """The x columns of Z~ as a CONTIGUOUS tensor (the C-ABI takes dense rows): the column slice of the stored
         (M, d + 1) matrix is copied once and reused while that matrix is unchanged (same storage, same version counter) --
         not twice per forward."""
+        shared = self.__dict__.get("_shared_Zx")
+        if shared is not None:
+            return shared
         if self.previous_layer is None:
             return self._inducing_points
         Z = self._inducing_points

@@ -51,8 +51,16 @@ class MFDGP(nn.Module):
                  num_samples_for_acquisition=25, previously_trained_model=None, ini_inducing_using_layer_0=False,
                  use_only_highest_fidelity=False, init_params_to_prior_and_fix_them=False,
                  num_inducing=None, inducing_points=None, num_samples_for_training=1, median_mode="reference",
-                 inducing_selection="first", inducing_tol=0.0, inducing_device=None, warm_start="hypers"):
+                 inducing_selection="first", inducing_tol=0.0, inducing_device=None, warm_start="hypers",
+                 learn_inducing_locations=False):
         super().__init__()
+        if learn_inducing_locations and use_only_highest_fidelity:
+            raise ValueError("learn_inducing_locations=True needs ONE Z_x shared by all layers (Z~_l = [Z_x, m_{l-1}]): not with "
+                             "use_only_highest_fidelity=True, whose layers have inducing inputs of their own")
+        if learn_inducing_locations and warm_start == "posterior":
+            raise ValueError("warm_start='posterior' extends the previous q(u) to inducing inputs that BEGIN with the previous "
+                             "ones: not defined with learn_inducing_locations=True (the previous ones have moved)")
+        self.learn_inducing_locations = bool(learn_inducing_locations)
         if warm_start not in ("hypers", "posterior"):
             raise ValueError("warm_start must be 'hypers' or 'posterior', got %r" % (warm_start,))
         if warm_start == "posterior":
@@ -116,6 +124,13 @@ class MFDGP(nn.Module):
             likelihood = gp.GaussianLikelihood(noise_constraint=gp.Interval(lower_bound=1e-8, upper_bound=0.1 * y_std))
             likelihood.noise = 1e-2 * y_high_std if i == self.num_fidelities - 1 else 1e-6
             setattr(self, self.name_hidden_layer_likelihood + str(i), likelihood)
+        if self.learn_inducing_locations:
+            # one parameter Z_x [M x d], started from the inducing inputs chosen above (given, the first M rows, or greedy
+            # variance); every layer's strategy returns this very tensor from .Zx, autograd adds the layers' shares
+            Z0 = hidden_layers[0].variational_strategy._inducing_points
+            self.inducing_inputs = nn.Parameter(Z0.detach().clone())
+            for layer in hidden_layers:
+                layer.variational_strategy.share_inducing_inputs(self.inducing_inputs)
         self.variational_strategy = _DeepGPVariationalStrategy(self)
         if warm_start == "posterior":
             self._carry_over_posterior(previously_trained_model)
@@ -386,6 +401,8 @@ class MFDGP(nn.Module):
         for layer in self._layers():
             for _, param in layer.covar_module.named_parameters():
                 param.requires_grad = not value
+        if getattr(self, "learn_inducing_locations", False):      # the conditioned fit keeps Z_x constant, as it keeps the kernel
+            self.inducing_inputs.requires_grad = not value
 
     # ------------------------------------------------------------------ prediction
     def predict(self, test_x, fidelity_layer=0, want_dx=False, _xdiv=None):

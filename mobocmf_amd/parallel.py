@@ -504,6 +504,9 @@ class RowShardedELBOStep(_graphed_base()):
     exchanges = True
 
     def __init__(self, model, elbo, x, y, fidelities, lr, fixed_eps=None, **kw):
+        if getattr(model, "learn_inducing_locations", False):
+            raise ValueError("RowShardedELBOStep: learnable inducing inputs (learn_inducing_locations=True) are not supported "
+                             "by the row-sharded step")
         idx = shard_rows(x.shape[0], device=x.device)
         S = model.num_samples_for_training
         if fixed_eps is not None:

@@ -146,7 +146,13 @@ class BlackBoxMFDGPFitter:
                  pareto_set_size=50, opt_grid_size=1000, eps=1e-8, decoupled_evals=False,
                  type_lengthscale=TL.MEDIAN, device="cuda", pareto_refine="slsqp", variational_optimizer="adam",
                  natgrad_gamma=0.1, natgrad_gamma_init=1e-4, natgrad_warmup_steps=100, natgrad_one_launch=False,
-                 pareto_search="grid", pareto_evolve_population=128, pareto_evolve_generations=100, **model_kwargs):
+                 pareto_search="grid", pareto_evolve_population=128, pareto_evolve_generations=100,
+                 learn_inducing_locations=False, **model_kwargs):
+        # True: every surrogate owns one trainable Z_x (MFDGP(learn_inducing_locations=True)); it trains through the captured
+        # layer-path steps (the one-launch steps treat Z as a constant) and belongs to the Adam group
+        self.learn_inducing_locations = bool(learn_inducing_locations)
+        if self.learn_inducing_locations:
+            model_kwargs["learn_inducing_locations"] = True
         if pareto_refine not in ("slsqp", "device"):
             raise ValueError("pareto_refine must be 'slsqp' or 'device' (got %r)" % (pareto_refine,))
         if pareto_search not in ("grid", "evolve"):
@@ -257,6 +263,8 @@ class BlackBoxMFDGPFitter:
 
     def _one_launch_allowed(self):
         """The one-launch steps are tried first: always with Adam, with natural gradients only on request."""
+        if getattr(self, "learn_inducing_locations", False):      # TinyELBOStep / CoopELBOStep hold Z_x as a constant
+            return False
         return not self._natgrad() or getattr(self, "natgrad_one_launch", False)
 
     def _optimizer_kwargs(self):

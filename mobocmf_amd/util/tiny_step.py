@@ -100,7 +100,7 @@ def structure_fits(model, L, d, max_m, training, on_gpu=True):
             Zl = vs._inducing_points
             if layer.kind != (0 if l == 0 else 1) or vs.jitter_val != jit or Zl.shape[0] != M or (training and not layer.training):
                 return False
-            if l and not torch.equal(Zl[:, :-1], Z0):      # layers >= 1 share Z_x; their f column is m_{l-1} (F9)
+            if l and vs.Zx is not Z0 and not torch.equal(Zl[:, :-1], Z0):      # layers >= 1 share Z_x; their f column is m_{l-1} (F9)
                 return False
             lik = _likelihood(model, l)
             c = lik.raw_noise_constraint

@@ -11,7 +11,7 @@ trap 'rm -rf "$B"' EXIT
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 SAN="-fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer -O1 -g"
 pids=""
-for f in gemm_f64 chol gram elementwise rff natgrad frozen_predict tiny_step coop_step api; do
+for f in gemm_f64 chol gram gram_rows elementwise rff natgrad frozen_predict tiny_step coop_step api; do
   $HIPCC --offload-arch=gfx950 -fno-gpu-sanitize $SAN -DMOBOCMF_HOST_FUZZ -fPIC -std=c++17 -Wno-unused-result -c mobocmf_amd/csrc/$f.hip -o $B/$f.o &
   pids="$pids $!"
 done
