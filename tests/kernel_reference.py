@@ -12,7 +12,9 @@ Three things live here so that the CPU proof (tests/test_kernel_reference_cpu.py
   (functional._prep would make every operand contiguous).
 
 At the end: the variational layer as a whole -- well-conditioned cases, a dtype-generic reference with its magnitude shadow,
-the measured constants of the layer bound and direct callers of the whole-call and the split layer entry points.
+the measured constants of the layer bound and direct callers of the whole-call and the split layer entry points; then the
+whole model of the one-launch steps as a composition of the same layer statements, with its composed shadow, its cases,
+its measured constants per depth and the direct callers of mobocmf_tiny_elbo_step / mobocmf_coop_elbo_step.
 """
 import ctypes
 
@@ -367,8 +369,10 @@ def gram_bwd_depth(kind, d, n1, nbase2, xdiv, geometry):
     return {k: chain[k] + GRAM_BWD_MULS + sum_depth(*pl) for k, pl in tasks.items()}
 
 
-def _gram_bwd(kind, c, xdiv, G, gknn, active, T):
-    """The gradients and their weights in the number format ``T`` converts to: {output: (value, W, A)}."""
+def _gram_bwd(kind, c, xdiv, G, gknn, active, T, sf2=None):
+    """The gradients and their weights in the number format ``T`` converts to: {output: (value, W, A)}.  ``sf2`` [nbase2 xdiv]
+    (kind 1, the model's composed shadow): f2 itself carries an error of u sf2, so every addend |G| |d term / d theta| of W and
+    A is joined by |G| |d^2 term / d theta d f2| sf2; the values are untouched."""
     x1, x2, hyp = T(c["x1"]), T(c["x2"]), T(c["hyp"])
     n1, d = x1.shape
     nb = x2.shape[0]
@@ -390,11 +394,14 @@ def _gram_bwd(kind, c, xdiv, G, gknn, active, T):
             s = s + t * t
         return half * s
 
-    def red(terms, axes):
+    def red(terms, axes, extra=()):
         """terms: (signed weight G or Gs, its magnitude, d term / d theta, 2 + |arg|) -> (value, W, A) summed over ``axes``."""
         v = sum((g * dt).sum(axes) for g, _, dt, _ in terms)
         A = sum((a * np.abs(dt)).sum(axes) for _, a, dt, _ in terms)
         W = sum((w * a * np.abs(dt)).sum(axes) for _, a, dt, w in terms)
+        for a, dt, w in extra:                                         # (magnitude, d / d f2 of an addend's factor, 2 + |arg|)
+            A = A + (a * np.abs(dt)).sum(axes)
+            W = W + (w * a * np.abs(dt)).sum(axes)
         return [v, W, A]
 
     ALL2, ALL3 = (0, 1), (0, 1, 2)
@@ -424,13 +431,28 @@ def _gram_bwd(kind, c, xdiv, G, gknn, active, T):
     w1 = (2 + g1)[:, :, None] + 0 * gf
     w2, w3 = w1 + gf, 2 + g2
     T1, T2, T3 = a1 * E1 * nu * p, a1 * E1 * af * Ef, a2 * E2
-    hy = [red([(G, aG, E1 * nu * p, w1), (G, aG, E1 * af * Ef, w2)], ALL3),
-          red([(G, aG, a1 * E1 * Ef, w2)], ALL3),
-          red([(G, aG, a1 * E1 * p, w1)], ALL3),
+    e0 = e1 = e2 = e4 = xg1 = xg2 = ()
+    if sf2 is not None:
+        # d / d f2 of every factor that holds f2: p = f1 f2 -> f1; Ef -> -Ef rr with rr = (f2 - f1) / lsf^2; the lsf addend
+        # T2 (f2 - f1)^2 / lsf^3 and the f addends T2 rr by the product rule, each part taken by its magnitude
+        aS = aG * T(sf2).reshape(nb, xdiv)[None, :, :]
+        f1b, rr = f1[:, None, None] + 0 * gf, fdif / (lsf * lsf)
+        e0 = ((aS, E1 * nu * f1b, w1), (aS, E1 * af * Ef * rr, w2))
+        e1 = ((aS, a1 * E1 * Ef * rr, w2),)
+        e2 = ((aS, a1 * E1 * f1b, w1),)
+        e4 = ((aS, T2 * 2 * fdif / lsf ** 3, w2), (aS, T2 * rr * (2 * gf) / lsf, w2))
+        xg2 = ((aS, T2 / (lsf * lsf), w2), (aS, T2 * rr * rr, w2))
+        xg1 = ((aS, a1 * E1 * nu + 0 * gf, w1),) + xg2
+    hy = [red([(G, aG, E1 * nu * p, w1), (G, aG, E1 * af * Ef, w2)], ALL3, e0),
+          red([(G, aG, a1 * E1 * Ef, w2)], ALL3, e1),
+          red([(G, aG, a1 * E1 * p, w1)], ALL3, e2),
           red([(Gs, aGs, E2, w3)], ALL2),
-          red([(G, aG, T2 * (2 * gf) / lsf, w2)], ALL3)]
+          red([(G, aG, T2 * (2 * gf) / lsf, w2)], ALL3, e4)]
     # the x-only factors: per (row, base row) the replica sums of G (T1 + T2), of their magnitudes and of the weighted ones
     Qv, QA, QW = (G * (T1 + T2)).sum(2), (aG * (np.abs(T1) + np.abs(T2))).sum(2), (aG * (w1 * np.abs(T1) + w2 * np.abs(T2))).sum(2)
+    if sf2 is not None:
+        d1, d2 = np.abs(a1 * E1 * nu * f1b), np.abs(T2 * rr)
+        QA, QW = QA + (aS * (d1 + d2)).sum(2), QW + (aS * (w1 * d1 + w2 * d2)).sum(2)
     R3 = aGs * np.abs(T3)
     l1, l2, gx = [], [], []
     for k in range(d):
@@ -442,40 +464,47 @@ def _gram_bwd(kind, c, xdiv, G, gknn, active, T):
                    (QA * np.abs(s1) + R3 * np.abs(s2)).sum(0)])
     hy = hy + l1 + l2
     dT2 = T2 * fdif / (lsf * lsf)
-    gf1 = red([(G, aG, a1 * E1 * nu * f2[None, :, :], w1), (G, aG, dT2, w2)], (1, 2))
-    gf2 = [a.reshape(Np) for a in red([(G, aG, a1 * E1 * nu * f1[:, None, None] + 0 * gf, w1), (G, aG, -dT2, w2)], 0)]
+    gf1 = red([(G, aG, a1 * E1 * nu * f2[None, :, :], w1), (G, aG, dT2, w2)], (1, 2), xg1)
+    gf2 = [a.reshape(Np) for a in red([(G, aG, a1 * E1 * nu * f1[:, None, None] + 0 * gf, w1), (G, aG, -dT2, w2)], 0, xg2)]
     out = {"hyp": tuple(np.array([h[i] for h in hy], dtype=x1.dtype) for i in range(3)),
            "g_f1": tuple(gf1), "g_f2": tuple(gf2), "g_x2": tuple(np.stack([g[i] for g in gx], 1) for i in range(3))}
-    return _gram_bwd_knn(kind, c, out, gknn, T)
+    return _gram_bwd_knn(kind, c, out, gknn, T, sf2)
 
 
-def _gram_bwd_knn(kind, c, ref, gknn, T):
+def _gram_bwd_knn(kind, c, ref, gknn, T, sf2=None):
     """``ref`` (the G part) plus the addends gknn_n dknn_n / dtheta (exponent 0: weight 2), knn = alpha (kind 0) or
-    a1 (nu f^2 + af) + a2: into alpha, or into a1 (two terms), af, nu, a2 and g_f2."""
+    a1 (nu f^2 + af) + a2: into alpha, or into a1 (two terms), af, nu, a2 and g_f2.  ``sf2``: as in _gram_bwd -- the weights
+    gain |gknn| |d^2 knn / dtheta df| sf2 (``ddf``)."""
     if gknn is None:
         return ref
     gk, hyp = T(gknn), T(c["hyp"])
     ref = {k: tuple(a.copy() for a in v) for k, v in ref.items()}
 
-    def add(o, i, dknn):
+    def add(o, i, dknn, ddf=None):
         v, W, A = o
         t = gk * dknn
         if i is None:
             v += t; W += 2 * np.abs(t); A += np.abs(t)
         else:
             v[i] += t.sum(); W[i] += 2 * np.abs(t).sum(); A[i] += np.abs(t).sum()
+        if sf2 is not None and ddf is not None:
+            e = np.abs(gk * ddf) * T(sf2)
+            if i is None:
+                W += 2 * e; A += e
+            else:
+                W[i] += 2 * e.sum(); A[i] += e.sum()
 
     if kind == 0:
         add(ref["hyp"], 0, 1 + 0 * gk)
         return ref
     a1, af, nu = hyp[0], hyp[1], hyp[2]
     f = T(c["f2"])
-    add(ref["hyp"], 0, nu * f * f)
+    add(ref["hyp"], 0, nu * f * f, 2 * nu * f)
     add(ref["hyp"], 0, af + 0 * gk)
     add(ref["hyp"], 1, a1 + 0 * gk)
-    add(ref["hyp"], 2, a1 * f * f)
+    add(ref["hyp"], 2, a1 * f * f, 2 * a1 * f)
     add(ref["hyp"], 3, 1 + 0 * gk)
-    add(ref["g_f2"], None, 2 * a1 * nu * f)
+    add(ref["g_f2"], None, 2 * a1 * nu * f, 2 * a1 * nu + 0 * f)
     return ref
 
 
@@ -1278,12 +1307,31 @@ def _gram_operands(c):
             dict(x1=c["Zx"], f1=c["zf"], x2=c["x"], f2=c["f"], hyp=c["hyp"]))
 
 
+def _gram_df2_abs(c, xdiv, T):
+    """(sum_t |d term_t / d f2| of K [n1 x nbase2 xdiv], |d knn / d f2|) of a kind 1 Gram case, in ``T``'s number format."""
+    x1, x2, hyp, f1, f2 = T(c["x1"]), T(c["x2"]), T(c["hyp"]), T(c["f1"]), T(c["f2"])
+    d = x1.shape[1]
+    a1, af, nu, _, lsf = hyp[:5]
+    t = (x1[:, None, :] - x2[None, :, :]) / hyp[5:5 + d]
+    g1 = np.repeat(T(0.5) * (t * t).sum(-1), xdiv, axis=1)
+    fd = f2[None, :] - f1[:, None]
+    gf = T(0.5) * (fd / lsf) ** 2
+    return (np.abs(a1 * np.exp(-g1) * nu * f1[:, None]) + np.abs(a1 * np.exp(-(g1 + gf)) * af * fd / (lsf * lsf)),
+            np.abs(2 * a1 * nu * f2))
+
+
 def _layer_forward(c, T):
-    """(state, shadow state) of the forward in the number format ``T`` converts to."""
+    """(state, shadow state) of the forward in the number format ``T`` converts to.  As a layer of a model (_model_run) ``c``
+    may hold "sf", the shadow of its f column [N']: f then carries an error of u sf, which the leaves it enters -- K_mn and
+    k_nn -- pass on through their derivatives, |d K / d f| sf joining sum |term| and |d knn / d f| sf joining k_nn."""
     M = c["M"]
     cmm, cmn = _gram_operands(c)
     Kmm = _gram(c["kind"], cmm, 1, T)[0] + T(c["jitter"]) * np.eye(M, dtype=T(0.0).dtype)
     Kmn, _, knn, Kabs = _gram(c["kind"], cmn, c["xdiv"], T)
+    sknn = knn
+    if c.get("sf") is not None:
+        dK, dknn = _gram_df2_abs(cmn, c["xdiv"], T)
+        Kabs, sknn = Kabs + dK * T(c["sf"])[None, :], knn + dknn * T(c["sf"])
     L = _chol_columns(Kmm)
     m, LS = T(c["m"]), np.tril(T(c["L_S"]))
     out = []
@@ -1293,7 +1341,7 @@ def _layer_forward(c, T):
         A, a, U = X @ (Kabs if sh else Kmn), X @ ab(m), X @ ab(LS)
         mean, C = A.T @ a, U.T @ A
         q, r = (A * A).sum(0), (C * C).sum(0)
-        s = knn + q if sh else knn - q
+        s = sknn + q if sh else knn - q
         pos = s > 0
         if c["branch"] == 0 and not sh:
             s = np.where(pos, s, 0)
@@ -1307,7 +1355,8 @@ def _layer_forward(c, T):
 
 def _layer_backward(c, st, sst, T, phi_diag=0.5):
     """(gradients, their shadows) from the forward states.  ``phi_diag``: the factor on Phi's diagonal (1/2; the CPU test's
-    mutation drops it)."""
+    mutation drops it).  As a layer of a model ``c`` may hold "s_g_mean" / "s_g_var", the SHADOWS of its upstream gradients,
+    which then stand where |g_mean| / |g_var| stand for a layer by itself, and "sf" (see _layer_forward)."""
     kind, xdiv = c["kind"], c["xdiv"]
     cmm, cmn = _gram_operands(c)
     gm, gkl = T(c["g_mean"]), T(c["g_kl"])
@@ -1319,6 +1368,10 @@ def _layer_backward(c, st, sst, T, phi_diag=0.5):
         sg = 1 if sh else -1
         X, A, a, U, C, L, LS = (s[k] for k in ("X", "A", "a", "U", "C", "L", "LS"))
         g, w, cw, k = ab(gm), ab(gv), ab(cgv), ab(gkl)
+        if sh and c.get("s_g_mean") is not None:                              # a layer of a model: the shadows handed down
+            g = T(c["s_g_mean"])
+            w = np.where(st["varraw"] > T(c["min_var"]), T(c["s_g_var"]), 0)
+            cw = w if c["branch"] else np.where(st["pos"], w, 0)
         dC = 2 * C * w[None, :]
         dA = U @ dC + np.outer(a, g) + sg * 2 * A * cw[None, :]
         da = A @ g + k * a
@@ -1335,7 +1388,7 @@ def _layer_backward(c, st, sst, T, phi_diag=0.5):
         Sm = X.T @ P @ X
         dKmm = T(0.5) * (Sm + Sm.T)
         pick = 2 if sh else 0
-        bmn = _gram_bwd(kind, cmn, xdiv, dKmn, cw, None, T)
+        bmn = _gram_bwd(kind, cmn, xdiv, dKmn, cw, None, T, c.get("sf") if sh else None)
         bmm = _gram_bwd(kind, cmm, 1, dKmm, None, None, T)
         o = dict(g_m=g_m, g_LS=g_LS, g_hyp=bmn["hyp"][pick] + bmm["hyp"][pick],
                  g_hyp_mn=bmn["hyp"][pick], g_hyp_mm=bmm["hyp"][pick])
@@ -1678,3 +1731,570 @@ def chain_backward_direct(ch, g_kl, had_panel, shares=None):
         _shape_out(c, r.out)
         outs.append(r)
     return outs
+
+
+# ------------------------------------------------------------------------------------ the one-launch steps: the whole model
+# (tiny_step.hip, coop_step.hip; include/mobocmf_hip.h, mobocmf_tiny_model; DESIGN.md, "The model bound".)
+#
+# model_ref composes the layer statements above -- _layer_forward / _layer_backward, called on every layer of a model -- as
+# oracle.model_forward / oracle.elbo do: softplus of the packed raw vector, Z~_l = [Z_x, m_{l-1}], f = mean + sqrt(var) eps with
+# the S-fold replication between layer 0 and layer 1, layer l on the first rows[l] rows, the data term of the rows of level l
+# (row weights, the mean over S), kl_scale sum KL, seeds at the top layer's columns; backwards the ELBO's gradients, the
+# propagation (g_f -> g_mean, g_var of the layer below) and g_zf[l] -> g_m[l-1], the softplus and Interval derivatives.
+#
+# Its SHADOW composes the same way, and at every joint it hands over the shadow of the quantity, not its magnitude: S(f) =
+# S(mean) + S(var) |eps| / (2 sqrt(var)) + |mean| + sqrt(var) |eps|, S(g_mean) = |data term| + |seed| + sum S(g_f), and so on.
+# A first-order shadow with exact leaves does not see the error of f: layer l reads f as an input of K_mn and k_nn, so u S(f)
+# reaches everything behind them through dK / df.  The shadow is EXTENDED by that term rather than the constants enlarged:
+# the leaf sum |term| of K_mn gains |dK / df| S(f), k_nn gains |dk_nn / df| S(f) (_layer_forward, "sf"), and every addend
+# |G| |dterm / dtheta| of the Gram backward gains |G| |d^2 term / dtheta df| S(f) (_gram_bwd, sf2).  With S(f) = 0 the model's
+# shadow of a layer is layer_ref's.
+MODEL_GROUPS = {"forward": ("out", "top_mean", "top_var"), "chain": ("g_m", "g_LS"), "gram": ("g_hyp", "g_x"), "noise": ("g_noise",)}
+MODEL_NOISE_LO = 1e-4
+# C_g per depth L and group, by the rule of LAYER_C: measured by tests/test_model_reference_cpu.py on every case of the GPU file
+# as the larger worst err / (u S) of the float64 run of model_ref and of float64 autograd over the oracle, recorded a quarter
+# above the measurement, times 4.  Measured (restatement / oracle, the case of the larger one):
+#   L = 1  forward 6.21 / 24.64 (M16_L1_d1_N129: the oracle's x / ls - z / ls on a lattice of spacing 1 / 16), chain 8.44 / 8.85
+#          (M32_L1_d8_544), gram 1.30 / 7.24 (M7_L1_d2, the input gradient), noise 0.93 / 0.56 (M1_L1_d1)
+#   L = 2  forward 3.61 / 3.90 (M127_L2_d8_N144), chain 5.61 / 9.83 (M16_L2_d8_wide), gram 0.41 / 1.50 (M16_L2_d8_S3, the input
+#          gradient), noise 0.75 / 0.75 (M32_L2_d8_S3)
+#   L = 3  forward 2.12 / 3.13 (M16_L3_d8_S8), chain 7.06 / 6.95 (clamp_M20), gram 1.35 / 5.18 (M16_L3_d8_S8), noise 0.67 / 0.83
+# The oracle's figures depend on the host CPU's vector kernels and BLAS (not on the thread count): another host gave 5.94 (L = 2
+# forward), 21.67 (L = 2 chain), 7.53 (L = 1 gram), 1.29 (L = 3 noise) -- all at most 0.44 of C_g.
+# At L = 1 the model adds the ELBO and one softplus derivative to a layer, and its figures sit BELOW LAYER_RATIO_MEASURED (17 /
+# 165 / 125) because its cases are the one-launch kernels' sizes: the layer's worst ratios come from M = 128 .. 257 at d = 9 and
+# from the KL differentiated alone, which no model case does.
+MODEL_RATIO_MEASURED = {1: {"forward": 31.0, "chain": 11.1, "gram": 9.1, "noise": 1.16},
+                        2: {"forward": 4.9, "chain": 12.3, "gram": 1.9, "noise": 0.95},
+                        3: {"forward": 3.9, "chain": 8.8, "gram": 6.5, "noise": 1.05}}
+MODEL_C = {L: {k: 4.0 * v for k, v in t.items()} for L, t in MODEL_RATIO_MEASURED.items()}
+
+
+def model_group(name):
+    base = name.rstrip("0123456789")
+    return next(g for g, names in MODEL_GROUPS.items() if base in names)
+
+
+_model_cases, _model_ref_cache = {}, {}
+
+
+def _inv_softplus(h):
+    return h + np.log(-np.expm1(-h))
+
+
+def model_case(L, d, M, rows, S, seed=0, clamp=0, weights=False, seeds=None, predict=False):
+    """One well-conditioned whole-model problem (cached, read-only): L layers sharing Z_x -- layer_case's jittered lattice (d <=
+    3) or uniform points, and its lengthscale ranges, so that cond(K_mm + jitter I) <= LAYER_COND_MAX for every Z~_l = [Z_x,
+    m_{l-1}] (asserted by the CPU test).  ``rows`` = (N, rows[1], ...), descending: the rows are in the kernels' order, row b
+    has the level of the last layer whose prefix holds it -- rows[l] == rows[l+1] leaves level l without a row.  y of order one;
+    explicit eps[l] (rows[l] S); noise Interval(MODEL_NOISE_LO, hi) on the layers with l + seed even, hi <= lo (raw is tau) on
+    the others; kl_scale = 0.7.  ``clamp`` = k: the first k rows lie ON inducing rows -- x on Z_x[b % M], and eps chosen so
+    that f = m_{l-1}[b % M] in the layers above -- under jitter = CLAMP_JITTER.  ``weights``: row_weight in [0.5, 2], every
+    fourth row 0.  ``seeds``: "both" | "mean" | "var" -- seed_gmean / seed_gvar standard normal (the other one zeros),
+    seed_scale = -0.75.  ``predict``: the eval branch at N test points: rows[l] = N, no row scored (fid = -1), kl_scale = 0,
+    eps[l] = S fixed samples tiled over the points, and every third row's seeds zero."""
+    rows = tuple(int(r) for r in rows)
+    key = ("model", L, d, M, rows, S, seed, clamp, weights, seeds, predict)
+    if key in _model_cases:
+        return _model_cases[key]
+    assert len(rows) == L and all(rows[l] >= rows[l + 1] >= 1 for l in range(L - 1)) and not (predict and clamp)
+    rng = np.random.default_rng(7919 * L + 1009 * M + 31 * rows[0] + 7 * d + S + 131071 * seed)
+    if d <= 3:
+        side = int(np.ceil(M ** (1.0 / d)))
+        h = 1.0 / side
+        grid = np.stack(np.meshgrid(*[np.arange(side)] * d, indexing="ij"), -1).reshape(-1, d)
+        Zx = (grid[rng.permutation(len(grid))[:M]] + 0.5 + 0.15 * rng.uniform(-1, 1, (M, d))) * h
+        ls = lambda: h * rng.uniform(0.55, 0.8, d)
+    else:
+        Zx = rng.random((M, d))
+        ls = lambda: rng.uniform(0.25, 0.32, d)
+    N = rows[0]
+    hyp = [np.concatenate([[0.7 + rng.random()], ls()])]
+    for l in range(1, L):
+        hyp.append(np.concatenate([[0.6 + rng.random(), 0.5 + rng.random(), 0.5 + rng.random(), 0.05 + 0.1 * rng.random(),
+                                    0.7 + rng.random()], ls(), ls()]))
+    x = Zx[rng.integers(0, M, N)] + 0.6 * hyp[0][1:] * rng.standard_normal((N, d)) / np.sqrt(d)
+    if clamp:
+        assert clamp <= N
+        x[:clamp] = Zx[np.arange(clamp) % M]
+    fid = np.full(N, -1.0) if predict else np.array([sum(rows[l] > b for l in range(L)) - 1.0 for b in range(N)])
+    y = np.sin(3 * x.sum(1)) + 0.3 * fid + 0.1 * rng.standard_normal(N)
+    interval = [(l + seed) % 2 == 0 for l in range(L)]
+    c = dict(L=L, d=d, M=M, rows=rows, S=S, N=N, branch=int(predict), predict=predict, clamp=clamp, key=key,
+             jitter=CLAMP_JITTER if clamp else 1e-6, kl_scale=0.0 if predict else 0.7, x=x, y=y, fid=fid, Zx=Zx,
+             raw=[_inv_softplus(h_) for h_ in hyp], m=[0.5 * rng.standard_normal(M) for _ in range(L)],
+             L_S=[0.2 * np.eye(M) + 0.05 * np.tril(rng.standard_normal((M, M))) for _ in range(L)],
+             noise_lo=[MODEL_NOISE_LO if i else 0.0 for i in interval], noise_hi=[0.3 + 0.2 * l if i else 0.0 for l, i in enumerate(interval)],
+             raw_noise=[0.5 * rng.standard_normal() if i else 0.05 + 0.1 * rng.random() for i in interval],
+             row_weight=None, seed_gmean=None, seed_gvar=None, seed_scale=0.0)
+    if predict:
+        c["samples"] = [None] + [rng.standard_normal(S) for _ in range(1, L)]
+        c["eps"] = [None] + [np.tile(s, N) for s in c["samples"][1:]]
+    else:
+        c["eps"] = [None] + [rng.standard_normal(rows[l] * S) for l in range(1, L)]
+    if weights:
+        c["row_weight"] = np.where(np.arange(N) % 4 == 3, 0.0, rng.uniform(0.5, 2.0, N))
+    if seeds:
+        nt = rows[-1] * (S if L > 1 else 1)
+        on = (np.arange(nt) // (S if L > 1 else 1)) % 3 != 1 if predict else np.ones(nt, bool)
+        c["seed_gmean"] = np.where(on, rng.standard_normal(nt), 0.0) if seeds in ("both", "mean") else np.zeros(nt)
+        c["seed_gvar"] = np.where(on, rng.standard_normal(nt), 0.0) if seeds in ("both", "var") else np.zeros(nt)
+        c["seed_scale"] = -0.75
+    for l in range(1, L if clamp else 0):                       # f = m_{l-1} on the clamped rows of the layers above
+        _, st, _ = _model_forward(c, _f64, stop=l)[-1]
+        k = min(clamp, rows[l])
+        cols, fdiv = np.arange(k * S), S if l == 1 else 1
+        e = c["eps"][l].copy()
+        e[cols] = (c["m"][l - 1][(cols // S) % M] - st["mean"][cols // fdiv]) / np.sqrt(st["var"][cols // fdiv])
+        c["eps"][l] = e
+    for v in list(c.values()):
+        for a in (v if isinstance(v, list) else [v]):
+            if isinstance(a, np.ndarray):
+                a.setflags(write=False)
+    _model_cases[key] = c
+    return c
+
+
+def _softplus(x):
+    return np.where(x > 20, x, np.log1p(np.exp(np.minimum(x, 20))))
+
+
+def model_layer(mc, l, T, f=None, sf=None):
+    """Layer ``l`` of the model as a case of the layer statements (layer_case's fields) in ``T``'s number format."""
+    nb, xdiv = mc["rows"][l], (mc["S"] if l else 1)
+    return dict(kind=int(l > 0), d=mc["d"], M=mc["M"], nbase=nb, xdiv=xdiv, Np=nb * xdiv, branch=mc["branch"], want_dx=int(mc["predict"]),
+                jitter=mc["jitter"], min_var=1e-10, x=mc["x"][:nb], f=f, sf=sf, Zx=mc["Zx"], zf=T(mc["m"][l - 1]) if l else None,
+                hyp=_softplus(T(mc["raw"][l])), m=mc["m"][l], L_S=mc["L_S"][l])
+
+
+def _model_forward(mc, T, stop=None):
+    """[(layer case, state, shadow state)] of the layers 0 .. stop - 1 (all): the propagation with its shadow."""
+    L, S, rows = mc["L"], mc["S"], mc["rows"]
+    out, f, sf = [], None, None
+    for l in range(L if stop is None else stop):
+        lc = model_layer(mc, l, T, f, sf)
+        st, sst = _layer_forward(lc, T)
+        out.append((lc, st, sst))
+        if l + 1 < L:
+            idx = np.arange(rows[l + 1] * S) // (S if l == 0 else 1)
+            mean, sd, e = st["mean"][idx], np.sqrt(st["var"][idx]), T(mc["eps"][l + 1])
+            f = mean + sd * e
+            sf = sst["mean"][idx] + sst["var"][idx] * np.abs(e) / (2 * sd) + np.abs(mean) + sd * np.abs(e)
+    return out
+
+
+def _noise(mc, l, T):
+    """(tau, d tau / d raw) of layer l."""
+    lo, hi, raw = T(mc["noise_lo"][l]), T(mc["noise_hi"][l]), T(mc["raw_noise"][l])
+    if not mc["noise_hi"][l] > mc["noise_lo"][l]:
+        return raw, T(1.0)
+    sg = 1 / (1 + np.exp(-raw))
+    return lo + (hi - lo) * sg, (hi - lo) * sg * (1 - sg)
+
+
+def model_layout(mc):
+    """[(name, start, stop)] of the flat vector (mobocmf_tiny_flat_len): per layer [packed hyper-parameters | m | L_S], then
+    raw_noise of every layer."""
+    out, o, M = [], 0, mc["M"]
+    for l in range(mc["L"]):
+        for name, n in (("g_hyp%d" % l, len(mc["raw"][l])), ("g_m%d" % l, M), ("g_LS%d" % l, M * M)):
+            out.append((name, o, o + n))
+            o += n
+    return out + [("g_noise", o, o + mc["L"])]
+
+
+def model_split(mc, flat):
+    return {k: (flat[a:b].reshape(mc["M"], mc["M"]) if k.startswith("g_LS") else flat[a:b]) for k, a, b in model_layout(mc)}
+
+
+def model_names(mc, what):
+    """The outputs a mode leaves: ``what`` = 'forward' | 'gradients' | 'input'."""
+    fw = ("out", "top_mean", "top_var")
+    return fw + {"forward": (), "input": ("g_x",), "gradients": tuple(k for k, _, _ in model_layout(mc))}[what]
+
+
+def _model_run(mc, T, loss_only=False):
+    """(values, shadows, forward states) of the whole model in ``T``'s number format; ``loss_only``: the scalar the gradients
+    are of, -ELBO + seed_scale (<seed_gmean, top mean> + <seed_gvar, top var>), from the forward alone."""
+    L, S, rows, N = mc["L"], mc["S"], mc["rows"], mc["N"]
+    dt = T(0.0).dtype
+    fw = _model_forward(mc, T)
+    y, fid, ks = T(mc["y"]), mc["fid"], T(mc["kl_scale"])
+    w = T(np.ones(N) if mc["row_weight"] is None else mc["row_weight"])
+    half, log2pi = T(0.5), T(LOG_2PI)
+    data = sdata = kl = skl = T(0.0)
+    ups, gn, sgn = [], np.zeros(L, dt), np.zeros(L, dt)
+    for l, (lc, st, sst) in enumerate(fw):
+        div, nn = lc["xdiv"], lc["Np"]
+        b = np.arange(nn) // div
+        mask = fid[b] == float(l)
+        tau, chain = _noise(mc, l, T)
+        dlt, var = y[b] - st["mean"], st["var"]
+        sq = dlt * dlt + var
+        ssq = dlt * dlt + 2 * np.abs(dlt) * (np.abs(y[b]) + sst["mean"]) + var + sst["var"]
+        wb = w[b] / div
+        data = data + np.where(mask, -wb * half * (sq / tau + np.log(tau) + log2pi), 0).sum()
+        sdata = sdata + np.where(mask, wb * half * (ssq / tau + np.abs(np.log(tau)) + log2pi), 0).sum()
+        kl, skl = kl + st["kl"], skl + sst["kl"]
+        # d(-ELBO) / d(mean, var, raw_noise) of the rows of level l
+        gm, sgm = np.where(mask, -wb * dlt / tau, 0), np.where(mask, wb * (np.abs(y[b]) + sst["mean"]) / tau, 0)
+        gv = np.where(mask, half * wb / tau, 0)
+        gn[l] = np.where(mask, -wb * half * (sq / (tau * tau) - 1 / tau), 0).sum() * chain
+        sgn[l] = np.where(mask, wb * half * (ssq / (tau * tau) + 1 / tau), 0).sum() * np.abs(chain)
+        ups.append([gm, gv, sgm, gv.copy()])
+    res = dict(out=np.array([data - ks * kl, ks * kl, -(data - ks * kl)], dt), top_mean=fw[-1][1]["mean"], top_var=fw[-1][1]["var"])
+    sha = dict(out=np.array([sdata + ks * skl, ks * skl, sdata + ks * skl], dt), top_mean=fw[-1][2]["mean"], top_var=fw[-1][2]["var"])
+    if mc["seed_gmean"] is not None:
+        sc = T(mc["seed_scale"])
+        for i, k in enumerate(("seed_gmean", "seed_gvar")):
+            ups[-1][i] = ups[-1][i] + sc * T(mc[k])
+            ups[-1][2 + i] = ups[-1][2 + i] + np.abs(sc * T(mc[k]))
+    if loss_only:
+        seed = 0 if mc["seed_gmean"] is None else sc * ((T(mc["seed_gmean"]) * res["top_mean"]).sum() + (T(mc["seed_gvar"]) * res["top_var"]).sum())
+        return res["out"][2] + seed
+    gx, sgx = np.zeros((N, mc["d"]), dt), np.zeros((N, mc["d"]), dt)
+    flat, sflat = {}, {}
+    zshare = (None, None)
+    for l in range(L - 1, -1, -1):
+        lc, st, sst = fw[l]
+        gm, gv, sgm, sgv = ups[l]
+        g, sg = _layer_backward(dict(lc, g_mean=gm, g_var=gv, g_kl=ks, s_g_mean=sgm, s_g_var=sgv), st, sst, T)
+        sig = 1 / (1 + np.exp(-T(mc["raw"][l])))
+        flat["g_hyp%d" % l], sflat["g_hyp%d" % l] = g["g_hyp"] * sig, sg["g_hyp"] * sig
+        flat["g_m%d" % l], sflat["g_m%d" % l] = g["g_m"], sg["g_m"]
+        if zshare[0] is not None:                                          # g_zf of the layer above: Z~_{l+1} = [Z_x, m_l]
+            flat["g_m%d" % l], sflat["g_m%d" % l] = g["g_m"] + zshare[0], sg["g_m"] + zshare[1]
+        flat["g_LS%d" % l], sflat["g_LS%d" % l] = g["g_LS"], sg["g_LS"]
+        if mc["predict"]:
+            gx[:rows[l]] += g["g_x"]
+            sgx[:rows[l]] += sg["g_x"]
+        if l:
+            zshare = (g["g_zf"], sg["g_zf"])
+            res["g_zf%d" % l], sha["g_zf%d" % l] = zshare
+            ncn, fdiv = lc["Np"], S if l == 1 else 1                       # this layer's columns feed on the layer below
+            k = ncn // fdiv
+            _, stb, sstb = fw[l - 1]
+            idx = np.arange(ncn) // fdiv
+            sd, var, e = np.sqrt(stb["var"][idx]), stb["var"][idx], T(mc["eps"][l])
+            fold = lambda a: a.reshape(k, fdiv).sum(1)
+            ups[l - 1][0][:k] += fold(g["g_f"])
+            ups[l - 1][1][:k] += fold(g["g_f"] * e * half / sd)
+            ups[l - 1][2][:k] += fold(sg["g_f"])
+            ups[l - 1][3][:k] += fold(sg["g_f"] * np.abs(e) * half / sd + np.abs(g["g_f"] * e) * sstb["var"][idx] / (4 * var * sd))
+    flat["g_noise"], sflat["g_noise"] = gn, sgn
+    for d_, s_ in ((res, flat), (sha, sflat)):
+        d_.update(s_)
+        d_["grad"] = np.concatenate([np.ravel(s_[k]) for k, _, _ in model_layout(mc)])
+    if mc["predict"]:
+        res["g_x"], sha["g_x"] = gx, sgx
+    return res, sha, fw
+
+
+def model_ref(mc, dtype=np.longdouble, shadow=False):
+    """{output: value} of the model ``mc`` = model_case(...) in ``dtype`` -- out [3], top_mean, top_var [rows[L-1] S], the flat
+    gradient 'grad' of d(-ELBO + seed term) / d(raw parameters) in mobocmf_tiny_flat_len's layout and its blocks g_hyp<l>, g_m<l>,
+    g_LS<l> [M x M, lower], g_noise [L], g_zf<l> [M], the share of g_m<l-1> that Z~_l = [Z_x, m_{l-1}] sends down; prediction cases: g_x [N x d] -- or, ``shadow``, the composed shadow S of each.  Cached."""
+    assert dtype is not np.longdouble or HAVE_LONGDOUBLE
+    key = (mc["key"], np.dtype(dtype).name)
+    if key not in _model_ref_cache:
+        _model_ref_cache[key] = _model_run(mc, lambda a: np.asarray(a, dtype))[:2]
+    return _model_ref_cache[key][1 if shadow else 0]
+
+
+def model_oracle(mc):
+    """The same outputs by float64 autograd over the oracle: oracle.elbo for the plain ELBO; with row weights or seeds its
+    statements (model_forward, expected_log_prob, kl_layer) with the weights and the seed term; prediction cases through
+    oracle.predict (eval_mode, the call inside predict_for_acquisition, whose per-point averages the per-column seeds cannot
+    address) less the likelihood noise."""
+    from oracle import mfdgp_oracle as O
+    L, S, N, d, rows = mc["L"], mc["S"], mc["N"], mc["d"], mc["rows"]
+    t = lambda a: torch.tensor(np.array(a), dtype=torch.float64)
+    leaf = lambda a: t(a).requires_grad_(True)
+    raw, m, LS, rn = [leaf(a) for a in mc["raw"]], [leaf(a) for a in mc["m"]], [leaf(a) for a in mc["L_S"]], [leaf(a) for a in mc["raw_noise"]]
+    x = leaf(mc["x"])
+    noise = [O.interval(r, lo, hi) if hi > lo else r for r, lo, hi in zip(rn, mc["noise_lo"], mc["noise_hi"])]
+    state = {"Zx": t(mc["Zx"]), "noise": noise,
+             "layers": [{"hyp": hyp_dict(int(l > 0), O.softplus(raw[l]), d), "m": m[l], "L_S": LS[l]} for l in range(L)]}
+    nt = rows[-1] * (S if L > 1 else 1)
+    seed = lambda mean, var: mc["seed_scale"] * ((t(mc["seed_gmean"]) * mean[:nt]).sum() + (t(mc["seed_gvar"]) * var[:nt]).sum())
+    n = lambda v: v.detach().numpy()
+    if mc["predict"]:
+        state["samples"] = [None] + [t(s) for s in mc["samples"][1:]]
+        Xt = x.repeat_interleave(S if L > 1 else 1, 0)
+        mean, var = O.predict(state, Xt, L - 1, training=False, eval_mode=True, jitter=mc["jitter"])
+        var = var - noise[L - 1].detach()
+        out = dict(out=np.zeros(3), top_mean=n(mean), top_var=n(var))
+        if mc["seed_gmean"] is not None:
+            seed(mean, var).backward()
+            out["g_x"] = n(x.grad)
+        return out
+    eps = [None] + [t(np.concatenate([mc["eps"][l], np.zeros((N - rows[l]) * S)])) for l in range(1, L)]
+    y, fid = t(mc["y"]), t(mc["fid"])
+    outs = O.model_forward(state, x, eps=eps, S=S, training=True, jitter=mc["jitter"], shortcut=False)
+    if mc["row_weight"] is None and mc["seed_gmean"] is None:
+        e, skl = O.elbo(state, x, y, fid, eps=eps, S=S, num_data=N / mc["kl_scale"], jitter=mc["jitter"], shortcut=False)
+        loss = -e
+    else:
+        w = t(np.ones(N) if mc["row_weight"] is None else mc["row_weight"])
+        data = 0.0
+        for l, (mean, var) in enumerate(outs):
+            div = S if l else 1
+            mask = (fid == l).repeat_interleave(div)
+            if int(mask.sum()):
+                data = data + (w.repeat_interleave(div) * O.expected_log_prob(y.repeat_interleave(div), mean, var, noise[l]))[mask].sum() / div
+        skl = mc["kl_scale"] * sum(O.kl_layer(state["layers"][l]["hyp"], O.inducing_inputs(state, l), m[l], LS[l], mc["jitter"]) for l in range(L))
+        e = data - skl
+        loss = -e
+        if mc["seed_gmean"] is not None:
+            loss = loss + seed(*outs[-1])
+    loss.backward()
+    z = lambda p: np.zeros(p.shape) if p.grad is None else n(p.grad)
+    out = dict(out=np.array([float(e.detach()), float(skl.detach()), -float(e.detach())]), top_mean=n(outs[-1][0])[:nt], top_var=n(outs[-1][1])[:nt],
+               g_noise=np.array([float(z(r)) for r in rn]))
+    for l in range(L):
+        out["g_hyp%d" % l], out["g_m%d" % l], out["g_LS%d" % l] = z(raw[l]), z(m[l]), np.tril(z(LS[l]))
+    return out
+
+
+def model_gate(got, ref, S, names, C):
+    """(violations [(name, ratio, non-zeros where S = 0)], {group: worst ratio}, report) of the gate |got - ref| <= C_g u S per
+    component with exact zeros where S = 0; ``C``: MODEL_C[L]."""
+    rat = layer_ratios(got, ref, S, names)
+    worst, bad = {}, []
+    for k, (r, nz) in rat.items():
+        g = model_group(k)
+        worst[g] = max(worst.get(g, 0.0), r)
+        if not r <= C[g] or nz:
+            bad.append((k, r, nz))
+    report = "  ".join("%s %.2f u S = %.0f%% of the gate" % (g, w_, 100 * w_ / C[g]) for g, w_ in worst.items())
+    return bad, worst, report
+
+
+# The cases the one-launch conformance tests run and the CPU test proves the conditions and the constants on: model_case's
+# arguments by name.  tiny_step.hip (launch code at the end of the file): MR = 16 up to M = 16, else 32; 512 threads beyond
+# M * (widest layer's columns) = 512; the panel pool in LDS while tiny_pool_in_lds() holds.  coop_step.hip (cgeom_of): Mp = M
+# rounded up to 16; H inside the backward phase up to 8 column blocks of 16 (N' <= 128), else k-sliced, ks = ceil(N'p / 256)
+# capped at 4.  Multi-layer cases at M >= 16 use d = 8 where they can: at d <= 2 a lattice point has 2 .. 8 near neighbours,
+# the comparison inverse of |L| grows with M and the composed shadow of the lower layers' gradients with it (DESIGN.md).
+def _mc(L, d, M, rows, S, **kw):
+    return dict(L=L, d=d, M=M, rows=rows, S=S, **kw)
+
+
+MODEL_TINY_CASES = {
+    "M1_L1_d1": _mc(1, 1, 1, (3,), 1),                               # MR 16, 256 threads, pool in LDS
+    "M7_L2_d2_S3": _mc(2, 2, 7, (12, 5), 3),                         # a prefix layer
+    "M16_L3_d8_S8": _mc(3, 8, 16, (20, 9, 1), 8),                    # a top layer of one row; 16 * 72 columns: 512 threads
+    "M16_L1_d2": _mc(1, 2, 16, (30,), 1),                            # 480 elements: 256 threads
+    "M16_L2_d8_wide": _mc(2, 8, 16, (200, 10), 1),                   # 18 630 pool doubles: panels in `work`
+    "M17_L2_d1": _mc(2, 1, 17, (9, 9), 1),                           # MR 32; level 0 has no row
+    "M20_L3_d2_S3": _mc(3, 2, 20, (12, 4, 4), 3),                    # level 1 has no row
+    "M32_L2_d8_S3": _mc(2, 8, 32, (40, 20), 3),                      # MR 32, 512 threads, panels in `work`
+    "M32_L1_d8_512": _mc(1, 8, 32, (16,), 1),                        # exactly 512 elements: still 256 threads
+    "M32_L1_d8_544": _mc(1, 8, 32, (17,), 1),                        # 544: 512 threads, pool in LDS
+}
+MODEL_COOP_CASES = {
+    "M5_L3_d2": _mc(3, 2, 5, (12, 12, 5), 1),                        # all layers' m in one wavefront of the gradient assembly; N' = 12
+    "M16_L1_d1_N129": _mc(1, 1, 16, (129,), 1),                      # nine column blocks, the last of one column: ks 1
+    "M17_L2_d8_N130": _mc(2, 8, 17, (130, 40), 1),
+    "M48_L2_d8_S8": _mc(2, 8, 48, (64, 20), 8),                      # layer 1: N' = 160
+    "M64_L2_d2_N128": _mc(2, 2, 64, (128, 16), 1),                   # N' = 128: the widest layer that forms H in the backward phase
+    "M65_L2_d8_N272": _mc(2, 8, 65, (272, 100), 1),                  # ks 2
+    "M127_L2_d8_N144": _mc(2, 8, 127, (144, 144), 1),                # ks 1 in both layers; level 0 has no row
+    "M128_L3_d8_S2": _mc(3, 8, 128, (130, 40, 12), 2),
+    "M16_L2_d8_N1040": _mc(2, 8, 16, (1040, 30), 1),                 # ks capped at 4
+    "M128_L1_d2_N129": _mc(1, 2, 128, (129,), 1),
+}
+MODEL_FEATURE_CASES = {
+    "clamp": _mc(2, 2, 7, (12, 5), 3, clamp=3), "weights_seeds": _mc(2, 2, 7, (12, 5), 3, weights=True, seeds="both"),
+    "seed_mean": _mc(2, 2, 7, (12, 5), 3, seeds="mean"), "seed_var": _mc(2, 2, 7, (12, 5), 3, seeds="var"),
+    "clamp_M20": _mc(3, 8, 20, (24, 10, 3), 2, clamp=5, weights=True, seeds="both"),
+}
+MODEL_PREDICT_CASES = {
+    "M7_L1_d2": _mc(1, 2, 7, (10,), 1, predict=True, seeds="both"), "M16_L2_d8_S3": _mc(2, 8, 16, (9, 9), 3, predict=True, seeds="both"),
+    "M20_L3_d2_S8": _mc(3, 2, 20, (5, 5, 5), 8, predict=True, seeds="both"),
+    "M65_L2_d8_S8": _mc(2, 8, 65, (20, 20), 8, predict=True, seeds="both"),          # coop only: N' = 160
+}
+MODEL_UPDATE_CASES = {"tiny": "M7_L2_d2_S3", "coop": "M17_L2_d8_N130"}
+MODEL_GROUP_CASES = {"tiny": ("M7_L2_d2_S3", "M32_L2_d8_S3", "M16_L3_d8_S8"), "coop": ("M5_L3_d2", "M17_L2_d8_N130", "M64_L2_d2_N128")}
+
+
+def all_model_cases():
+    out = {}
+    for table in (MODEL_TINY_CASES, MODEL_COOP_CASES, MODEL_FEATURE_CASES, MODEL_PREDICT_CASES):
+        out.update(table)
+    return out
+
+
+def named_model_case(name):
+    return model_case(**all_model_cases()[name])
+
+
+def tiny_geometry(mcs):
+    """(MR, threads, pool in LDS) of a mobocmf_tiny_elbo_step launch over ``mcs``, restated from tiny_step.hip: geom_of (pool_len),
+    lds_bytes, LDS_BUDGET and the launch code of mobocmf_tiny_elbo_step."""
+    HS, NVEC = 5 + 2 * 8, 11
+    mmax = max(c["M"] for c in mcs)
+    MR = 16 if mmax <= 16 else 32
+    ms = MR * (MR + 1)
+    lds = 8 * (12 * ms + 3 * MR * 9 + 2 * 3 * HS + 3 * 16 + 3 * 3 * MR + 2 * MR + 8 * (HS + 1) + 24 + 32 + 16)
+    cols = lambda c: [r * (c["S"] if l else 1) for l, r in enumerate(c["rows"])]
+    pool = max(sum(cols(c)) * (2 * c["M"] + NVEC) + 3 * max(c["M"], 8) * max(cols(c)) for c in mcs)
+    cmax = max(max(cols(c)) for c in mcs)
+    return MR, 512 if mmax * cmax > 512 else 256, lds + 8 * pool <= 160 * 1024 - 512
+
+
+def coop_geometry(mc):
+    """Per layer (hblk, ks) of mobocmf_coop_elbo_step, restated from cgeom_of (coop_step.hip)."""
+    out = []
+    for l, r in enumerate(mc["rows"]):
+        ncp = (r * (mc["S"] if l else 1) + 15) // 16 * 16
+        hblk = ncp // 16 <= 8
+        out.append((hblk, ncp // 16 if hblk else min(4, max(1, (ncp + 255) // 256))))
+    return out
+
+
+# ---- direct callers of the one-launch steps: mobocmf_tiny_model records filled through the ctypes definitions of _lib, the
+# table uploaded, the launch through the C ABI.  work, grad, out, top_mean / top_var are NaN before every launch and have GUARD
+# doubles behind them; info is poisoned; sync_words are zeroed once, as the header prescribes, and the status word is read back.
+STEP_GRADIENTS, STEP_UPDATE, STEP_FORWARD, STEP_INPUT_GRADIENTS, STEP_CHAIN_VALID = 0, 1, 2, 3, 16
+INFO_POISON = -77
+ADAM = dict(lr=1e-2, beta1=0.9, beta2=0.999, eps=1e-8)
+TRAIN_ALL = 0x3FF                         # raw[l][0..6], m, L_S, raw_noise
+
+
+class OneLaunch:
+    """A group of models set up for mobocmf_tiny_elbo_step (``coop`` False) or mobocmf_coop_elbo_step: ``state[i]`` {name: device
+    tensor} -- inputs, parameters, Adam state, steps_done, rng words -- and ``outs[i]`` (work, grad, out, top_mean, top_var,
+    info).  ``launch(mode)`` poisons the outputs, launches and collects: ``rc``, ``status`` (coop: the status word), ``wgs_used``,
+    and per model ``res[i]`` {out, top_mean, top_var, grad, info} as numpy, ``guards[i]`` (every guard bitwise untouched),
+    ``written[i]`` (names of the outputs that are no longer all poison)."""
+
+    def __init__(self, mcs, coop, adam_seed=None, steps=0, trainable=None, over=None):
+        from mobocmf_amd import _lib
+        self.mcs, self.coop, self.n = list(mcs), coop, len(mcs)
+        self.host = (_lib.TinyModel * self.n)()
+        self.state, self.outs, self.lens = [], [], []
+        L_ = lib()
+        for i, mc in enumerate(self.mcs):
+            rec, L, M, d, S, N = self.host[i], mc["L"], mc["M"], mc["d"], mc["S"], mc["N"]
+            rec.L, rec.M, rec.d, rec.S, rec.N, rec.branch = L, M, d, S, N, mc["branch"]
+            rec.kl_scale, rec.jitter, rec.seed_scale = mc["kl_scale"], mc["jitter"], mc["seed_scale"]
+            t = {k: _dev(mc[k]) for k in ("x", "y", "fid", "Zx", "row_weight", "seed_gmean", "seed_gvar") if mc[k] is not None}
+            for l in range(L):
+                rec.rows[l] = mc["rows"][l]
+                rec.trainable[l] = TRAIN_ALL if trainable is None else trainable[i][l]
+                rec.noise_lo[l], rec.noise_hi[l] = mc["noise_lo"][l], mc["noise_hi"][l]
+                off = 0
+                for s, n in enumerate([1, d] if l == 0 else [1, 1, 1, 1, 1, d, d]):
+                    t["raw%d_%d" % (l, s)] = _dev(mc["raw"][l][off:off + n])
+                    rec.raw[l][s] = t["raw%d_%d" % (l, s)].data_ptr()
+                    off += n
+                t["m%d" % l], t["L_S%d" % l], t["raw_noise%d" % l] = _dev(mc["m"][l]), _dev(mc["L_S"][l]), _dev(np.array([mc["raw_noise"][l]]))
+                rec.m[l], rec.L_S[l], rec.raw_noise[l] = (t[k % l].data_ptr() for k in ("m%d", "L_S%d", "raw_noise%d"))
+                if l:
+                    t["eps%d" % l] = _dev(mc["eps"][l])
+                    t["rng%d" % l] = torch.tensor([12345 + l, 7, 3], dtype=torch.int64, device="cuda")      # eps replaces the draw
+                    rec.eps[l], rec.rng[l] = t["eps%d" % l].data_ptr(), t["rng%d" % l].data_ptr()
+            for k in ("x", "y", "fid", "Zx", "row_weight", "seed_gmean", "seed_gvar"):
+                setattr(rec, k, t[k].data_ptr() if k in t else None)
+            flat, wb = ctypes.c_int64(), ctypes.c_size_t()
+            assert L_.mobocmf_tiny_flat_len(ctypes.byref(rec), ctypes.byref(flat)) == 0 and flat.value == model_layout(mc)[-1][2]
+            assert getattr(L_, "mobocmf_coop_work_bytes" if coop else "mobocmf_tiny_work_bytes")(ctypes.byref(rec), ctypes.byref(wb)) == 0
+            assert wb.value % 8 == 0
+            if adam_seed is None:
+                am, av = np.zeros(flat.value), np.zeros(flat.value)
+            else:
+                rng = np.random.default_rng(adam_seed + i)
+                am, av = 0.01 * rng.standard_normal(flat.value), 1e-4 * rng.random(flat.value) + 1e-6
+            t["adam_m"], t["adam_v"] = _dev(am), _dev(av)
+            t["steps_done"] = torch.tensor([steps], dtype=torch.int64, device="cuda")
+            rec.adam_m, rec.adam_v, rec.steps_done = t["adam_m"].data_ptr(), t["adam_v"].data_ptr(), t["steps_done"].data_ptr()
+            nt = mc["rows"][-1] * (S if L > 1 else 1)
+            lens = dict(work=wb.value // 8, grad=max(flat.value, N * d) if mc["predict"] else flat.value, out=3, top_mean=nt, top_var=nt)
+            o = {k: _out(n) for k, n in lens.items()}
+            o["info"] = torch.full((L + GUARD,), INFO_POISON, dtype=torch.int32, device="cuda")
+            for k in o:
+                setattr(rec, k, o[k].data_ptr())
+            self.state.append(t)
+            self.outs.append(o)
+            self.lens.append(lens)
+        if over is not None:
+            over(self.host)
+        self.table = torch.frombuffer(bytearray(bytes(self.host)), dtype=torch.uint8).cuda()
+        self.sync = torch.zeros(16 * (self.n + 1), dtype=torch.int64, device="cuda") if coop else None
+        torch.cuda.synchronize()
+
+    def snapshot(self):
+        torch.cuda.synchronize()
+        return [{k: v.clone() for k, v in t.items()} for t in self.state]
+
+    def changed(self, before):
+        """Per model the names of the state tensors whose bytes differ from the snapshot ``before``."""
+        torch.cuda.synchronize()
+        bits = lambda v: v.view(torch.int64)
+        return [sorted(k for k, v in t.items() if not torch.equal(bits(v), bits(before[i][k]))) for i, t in enumerate(self.state)]
+
+    def launch(self, mode, wgs_per_model=0, keep=()):
+        """``keep``: outputs NOT poisoned before this launch (MOBOCMF_STEP_CHAIN_VALID reads the `work` of the launch before)."""
+        for o in self.outs:
+            for k, v in o.items():
+                if k not in keep:
+                    v.fill_(INFO_POISON if k == "info" else NAN)
+        torch.cuda.synchronize()
+        host, table, a = ctypes.cast(self.host, ctypes.c_void_p), ctypes.c_void_p(self.table.data_ptr()), ADAM
+        if self.coop:
+            used = ctypes.c_int32(-1)
+            self.rc = lib().mobocmf_coop_elbo_step(host, table, self.n, wgs_per_model, _p(self.sync), a["lr"], a["beta1"], a["beta2"], a["eps"],
+                                                   mode, ctypes.byref(used), _stream())
+            self.wgs_used = used.value
+        else:
+            self.rc = lib().mobocmf_tiny_elbo_step(host, table, self.n, a["lr"], a["beta1"], a["beta2"], a["eps"], mode, _stream())
+        torch.cuda.synchronize()
+        self.status = int(self.sync[16 * self.n + 1]) if self.coop else 0
+        nan_bits = torch.full((GUARD,), NAN, dtype=torch.float64, device="cuda").view(torch.int64)
+        self.res, self.guards, self.written = [], [], []
+        for i, (mc, o, lens) in enumerate(zip(self.mcs, self.outs, self.lens)):
+            lens = dict(lens)
+            if mode & ~STEP_CHAIN_VALID == STEP_INPUT_GRADIENTS:
+                lens["grad"] = mc["N"] * mc["d"]
+            ok = all(bool(torch.equal(o[k][n:n + GUARD].view(torch.int64), nan_bits)) for k, n in lens.items())
+            ok = ok and bool((o["info"][mc["L"]:] == INFO_POISON).all())
+            if mode & ~STEP_CHAIN_VALID == STEP_INPUT_GRADIENTS:                  # nothing of grad beyond N d either
+                ok = ok and bool(torch.isnan(o["grad"][lens["grad"]:]).all())
+            self.guards.append(ok)
+            self.written.append(sorted(k for k in lens if not bool(torch.isnan(o[k][:lens[k]]).all()))
+                                + (["info"] if not bool((o["info"] == INFO_POISON).all()) else []))
+            r = {k: o[k][:n].cpu().numpy() for k, n in lens.items() if k != "work"}
+            r["info"] = o["info"][:mc["L"]].cpu().numpy()
+            if "grad" in r and mode & ~STEP_CHAIN_VALID == STEP_INPUT_GRADIENTS:
+                r["g_x"] = r.pop("grad").reshape(mc["N"], mc["d"])
+            self.res.append(r)
+        return self
+
+    def params(self, i):
+        """The flat vector of the parameters of model i, the layout of grad / adam_m / adam_v."""
+        t, mc = self.state[i], self.mcs[i]
+        parts = []
+        for l in range(mc["L"]):
+            parts += [t["raw%d_%d" % (l, s)] for s in range(2 if l == 0 else 7)] + [t["m%d" % l], t["L_S%d" % l].reshape(-1)]
+        return torch.cat(parts + [t["raw_noise%d" % l] for l in range(mc["L"])]).cpu().numpy()
+
+
+def tiny_direct(mcs, mode, **kw):
+    """mobocmf_tiny_elbo_step over the models ``mcs`` in ``mode``; keywords: OneLaunch's.  Returns the OneLaunch."""
+    return OneLaunch(mcs, False, **kw).launch(mode)
+
+
+def coop_direct(mcs, mode, wgs_per_model=0, **kw):
+    """mobocmf_coop_elbo_step likewise, with ``wgs_per_model`` workgroups per model (0: the library's choice)."""
+    return OneLaunch(mcs, True, **kw).launch(mode, wgs_per_model)
+
+
+def model_got(mc, r, what):
+    """The outputs of ``r`` = OneLaunch.res[i] under model_names(mc, what)'s names."""
+    out = {k: r[k] for k in ("out", "top_mean", "top_var")}
+    if what == "gradients":
+        out.update(model_split(mc, r["grad"]))
+    elif what == "input":
+        out["g_x"] = r["g_x"]
+    return out
