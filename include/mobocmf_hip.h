@@ -1112,6 +1112,29 @@ int mobocmf_jes_mc_box_forward(const double* moments, const double* noise, int32
                                int32_t track, const double* x, int32_t d, double* best_v, double* best_x,
                                mobocmf_stream_t stream);
 
+/* MES of every test point from the moments of exact-GP surrogates (the comparison baseline, MESMOC_MFGP: the expressions of
+ * its _MES_MFGP.forward operation for operation), in the position mobocmf_jes_group_forward has in an iterate.
+ *   moments  (n_obj + n_con, 2, T): per model its latent means then its variances, objectives first
+ *   noise    (n_obj + n_con): the models' likelihood noise;   best (n_obj + n_con): best value per objective, threshold per
+ *            constraint
+ * With s = sqrt(var), z = (best - mean) / s, Phi(z) = 0.5 (1 + erf(z / sqrt 2)), phi(z) = exp(-z^2 / 2) / sqrt(2 pi), E = FLT_EPSILON:
+ *   objective p:   cdf = min(Phi(z), 1 - E);  r = phi(z) / (1 - cdf);  vt = var max(1 + (z - r) r, E) + noise
+ *                  term_p = max(0.5 log(var + noise) - 0.5 log(vt), 0)
+ *   constraint c:  pf_c = 1 - Phi(z)
+ *   acq[t] = (sum_p term_p, in the order of p) * (prod_c pf_c, in the order of c; 1 when n_con = 0)
+ * A negative variance gives a NaN value.  want_seeds = 1: seeds (the layout of moments) = d acq[t] / d (mean, var) of every
+ * model, the derivative automatic differentiation forms of the expressions above: each of the three clamps passes a gradient
+ * where it does not bind (equality passes); under a binding min(., 1 - E) the cdf is a constant while phi still varies; a
+ * constraint's seed carries the product over the OTHER constraints, formed explicitly in the order of c and never by division.
+ * want_seeds = 0 gives the same acq bits.  track = 1: exactly the rule of mobocmf_jes_group_forward.
+ * One launch of T workgroups of one wavefront: a lane per model, the sum and the products by one lane in a fixed order, no atomics.
+ * MOBOCMF_BAD_ARG: moments, noise, best or acq NULL; n_obj < 1; n_con < 0; n_obj + n_con > 2 MOBOCMF_ACQ_MAX_PAIRS; T < 1 or
+ * > MOBOCMF_ACQ_MAX_COLUMNS; a flag other than 0 / 1; want_seeds with seeds NULL; track with x, best_v or best_x NULL or d
+ * outside 1..MOBOCMF_MAX_D. */
+int mobocmf_mes_group_forward(const double* moments, const double* noise, const double* best, int32_t n_obj, int32_t n_con,
+                              int32_t T, double* acq, int32_t want_seeds, double* seeds, int32_t track, const double* x,
+                              int32_t d, double* best_v, double* best_x, mobocmf_stream_t stream);
+
 /* One projected Adam ASCENT step on the iterate x (T x d): g[t][j] = -sum_i gx[i][t][j] over the n_models slices of the group's
  * input gradients gx (n_models, T, d) in the order of i, then the update of mobocmf_adam_multi (the same expressions in the same
  * order: with n_models = 1 the same bits) with the bias corrections of step steps_done[0] + 1, then x[t][j] clamped to
@@ -1189,6 +1212,59 @@ int mobocmf_frozen_predict(const mobocmf_frozen_predict_model* host_models, cons
 int mobocmf_frozen_predict_split_work_bytes(const mobocmf_frozen_predict_model* model, int32_t mode, size_t* bytes);
 int mobocmf_frozen_predict_split(const mobocmf_frozen_predict_model* host_models, const mobocmf_frozen_predict_model* dev_models,
                                  int32_t n_models, int32_t mode, mobocmf_stream_t stream);
+
+/* ---- Predictive moments of fitted EXACT-GP surrogates (the multi-fidelity baselines: two ARD-RBF kernels, a signal and a
+ * noise one, combined by level factors) against a factorisation formed ONCE, and the gradient w.r.t. the test points
+ * (csrc/exact_predict.hip): the two model evaluations of the MES baseline's device acquisition search.  n_models models at the
+ * same T test points x; the models of a group may differ in n.  Linv and a are what mobocmf_exact_gp_factor leaves in its
+ * state (L^-1, n x n lower with leading dimension ld, and a = L^-1 y), read only.  Per model and test point t:
+ *   k_r  = sig[level] sig[lev_r] os_s exp(-1/2 sum_j ((x_tj - X_rj) / ls_s,j)^2)
+ *        + ntab[min(level, lev_r)] os_n exp(-1/2 sum_j ((x_tj - X_rj) / ls_n,j)^2)                       r < n
+ *   w    = Linv k      mean = a^T w      var = kss - |w|^2           (no clamp, no floor)
+ * mode MOBOCMF_STEP_FORWARD: top_mean / top_var (T) <- the latent moments WITHOUT likelihood noise.
+ * mode MOBOCMF_STEP_INPUT_GRADIENTS: the same, and with c = seed_gmean[t] a - 2 seed_gvar[t] w, e = Linv^T c:
+ *   grad[t][j] = sum_r e_r dk_r/dx_tj,   dk_r/dx_tj = -(x_tj - X_rj) (signal term / ls_s,j^2 + noise term / ls_n,j^2),
+ *   summed over r in ascending order.  The launch forms its panels itself: it does not depend on an earlier FORWARD launch.
+ * One launch on `stream`; a workgroup owns (model, a block of 16 test points) and nothing is shared between workgroups: no
+ * in-launch wait, no atomics, no status word; two calls on the same inputs are bitwise equal; capturable (the FIRST call per
+ * device and mode sets a function attribute and belongs outside a capture).  Both triangular products run on
+ * v_mfma_f64_16x16x4_f64 with the k and w panels ([n][16] each) in LDS.  The kernel reads the descriptors from DEVICE memory
+ * (dev_models); host_models is the same array in host memory, for validation and launch geometry.  Rows beyond T and padded
+ * training rows are never written.  The levels are device data: a lev_r outside [0, n_levels) makes that model's moments NaN
+ * and is never used as an index.
+ * Limits: 1 <= n <= MOBOCMF_EXACT_PREDICT_MAX_N (two 16-column panels are 128 KB of LDS); 1 <= d <= MOBOCMF_MAX_D; 1 <= T <=
+ * MOBOCMF_TOPK_MAX_N; 1 <= n_levels <= MOBOCMF_EXACT_PREDICT_MAX_LEVELS; 0 <= level < n_levels; ld >= n; 1 <= n_models <=
+ * 2 MOBOCMF_ACQ_MAX_PAIRS.  MOBOCMF_BAD_ARG otherwise, for a NULL pointer among those the mode reads, or for another mode -- on
+ * the host, before any HIP call.
+ * mobocmf_exact_predict_work_bytes: the bytes of `work` a launch of `mode` needs -- 0 for both modes of this version (the
+ * panels never leave LDS); work may then be NULL. */
+#define MOBOCMF_EXACT_PREDICT_MAX_N 512
+#define MOBOCMF_EXACT_PREDICT_MAX_LEVELS 8
+typedef struct mobocmf_exact_predict_model {
+    int32_t n, d, T;                 /* training rows, input columns (without the fidelity column), test points */
+    int32_t n_levels, level;         /* fidelity levels, and the level the test points are evaluated at */
+    int32_t reserved;
+    int64_t ld;                      /* leading dimension of Linv */
+    const double* xtr;               /* n x d training inputs */
+    const int32_t* lev;              /* n: their levels */
+    const double* sig;               /* n_levels: signal factor per level (all ones for the min-level kernel) */
+    const double* ntab;              /* n_levels: noise factor per min-level */
+    const double* hyp_s;             /* 1 + d: [outputscale, lengthscale[0..d)] of the signal ARD-RBF */
+    const double* hyp_n;             /* 1 + d: the noise ARD-RBF's */
+    const double* Linv;              /* n x n lower, leading dimension ld */
+    const double* a;                 /* n: L^-1 y */
+    double kss;                      /* prior variance at `level`: sig[level]^2 os_s + ntab[level] os_n */
+    const double* x;                 /* T x d, shared by the models of a group */
+    double* top_mean;                /* T */
+    double* top_var;
+    const double* seed_gmean;        /* T (MOBOCMF_STEP_INPUT_GRADIENTS) */
+    const double* seed_gvar;
+    double* grad;                    /* T x d (MOBOCMF_STEP_INPUT_GRADIENTS) */
+    void* work;                      /* mobocmf_exact_predict_work_bytes (NULL when that is 0) */
+} mobocmf_exact_predict_model;
+int mobocmf_exact_predict_work_bytes(const mobocmf_exact_predict_model* model, int32_t mode, size_t* bytes);
+int mobocmf_exact_predict(const mobocmf_exact_predict_model* host_models, const mobocmf_exact_predict_model* dev_models,
+                          int32_t n_models, int32_t mode, mobocmf_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -88,6 +88,21 @@ class FrozenPredictModel(ctypes.Structure):
                 ("work", ctypes.c_void_p)]
 
 
+EXACT_PREDICT_MAX_N, EXACT_PREDICT_MAX_LEVELS = 512, 8      # MOBOCMF_EXACT_PREDICT_MAX_N / MOBOCMF_EXACT_PREDICT_MAX_LEVELS
+
+
+class ExactPredictModel(ctypes.Structure):
+    """mobocmf_exact_predict_model: one exact-GP surrogate of mobocmf_exact_predict (the kernel reads the array from DEVICE memory)."""
+    _fields_ = [("n", ctypes.c_int32), ("d", ctypes.c_int32), ("T", ctypes.c_int32), ("n_levels", ctypes.c_int32),
+                ("level", ctypes.c_int32), ("reserved", ctypes.c_int32), ("ld", ctypes.c_int64),
+                ("xtr", ctypes.c_void_p), ("lev", ctypes.c_void_p), ("sig", ctypes.c_void_p), ("ntab", ctypes.c_void_p),
+                ("hyp_s", ctypes.c_void_p), ("hyp_n", ctypes.c_void_p), ("Linv", ctypes.c_void_p), ("a", ctypes.c_void_p),
+                ("kss", ctypes.c_double),
+                ("x", ctypes.c_void_p), ("top_mean", ctypes.c_void_p), ("top_var", ctypes.c_void_p),
+                ("seed_gmean", ctypes.c_void_p), ("seed_gvar", ctypes.c_void_p), ("grad", ctypes.c_void_p),
+                ("work", ctypes.c_void_p)]
+
+
 class NatgradSmallLayer(ctypes.Structure):
     """mobocmf_natgrad_small_layer: one layer of mobocmf_natgrad_small_step (the kernel reads the array from DEVICE memory)."""
     _fields_ = [("M", ctypes.c_int32), ("n_guard_info", ctypes.c_int32), ("m", ctypes.c_void_p), ("L_S", ctypes.c_void_p),
@@ -244,6 +259,9 @@ SYMBOLS = {
     "mobocmf_frozen_predict": [_P, _P, _I32, _I32, _P],
     "mobocmf_frozen_predict_split_work_bytes": [ctypes.POINTER(FrozenPredictModel), _I32, ctypes.POINTER(_SZ)],
     "mobocmf_frozen_predict_split": [_P, _P, _I32, _I32, _P],
+    "mobocmf_exact_predict_work_bytes": [ctypes.POINTER(ExactPredictModel), _I32, ctypes.POINTER(_SZ)],
+    "mobocmf_exact_predict": [_P, _P, _I32, _I32, _P],
+    "mobocmf_mes_group_forward": [_P, _P, _P, _I32, _I32, _I32, _P, _I32, _P, _I32, _P, _I32, _P, _P, _P],
 }
 ACQ_MAX_PAIRS, TOPK_MAX_K, TOPK_MAX_N = 32, 64, 4096      # MOBOCMF_ACQ_MAX_PAIRS / MOBOCMF_TOPK_MAX_K / MOBOCMF_TOPK_MAX_N
 ACQ_MAX_COLUMNS = 1 << 24                                 # MOBOCMF_ACQ_MAX_COLUMNS

@@ -1,7 +1,8 @@
 // The device side of the acquisition search (JESMOC_MFDGP(search="device"), util/acq_search.py): what stands between the two
 // one-launch model evaluations of an iterate -- the JES value of every test point from the predict group's raw moments with its
 // gradient w.r.t. those moments and the best-iterate tracking, the projected Adam ascent step on the iterate -- and the
-// selection of the k best of n values (the restarts among the raw candidates, the winner among the restarts).
+// selection of the k best of n values (the restarts among the raw candidates, the winner among the restarts).  The MES value
+// of the exact-GP baselines (MESMOC_MFGP(search="device"), mobocmf_mes_group_forward) stands in the JES position of the same chain.
 //
 // All of them are latency-bound glue on a few hundred to a few thousand doubles: each is ONE launch, has no atomics and sums in a
 // fixed order (two calls on the same inputs are bitwise equal), reads nothing on the host and keeps no state: capturable.
@@ -137,6 +138,87 @@ jes_kernel(const double* __restrict__ moments, const double* __restrict__ noise,
     if (MODE != JES_ALL_BOXES && s_win && m < d) best_x[(int64_t)t * d + m] = x[(int64_t)t * d + m];
 }
 
+// MES on the exact-GP baselines (mobocmf_mes_group_forward): the JES kernel's shape -- ONE wavefront per test point, lane m forms
+// the value of model m (an objective's truncated-Gaussian entropy term, a constraint's probability of feasibility) and its
+// derivative w.r.t. that model's own mean and variance, the values meet in LDS, lane 0 adds the terms in the order of p,
+// multiplies the probabilities in the order of c, writes acq[t] and tracks; every lane then scales its own derivative by what
+// the product rule leaves for it, formed from the parked values in the same orders (a constraint: the product over the OTHER
+// constraints).  Nothing is fused: the value is the host statement operation for operation.
+__global__ void __launch_bounds__(AS_WAVE)
+mes_kernel(const double* __restrict__ moments, const double* __restrict__ noise, const double* __restrict__ best, int n_obj,
+           int n_con, int T, double* __restrict__ acq, double* __restrict__ seeds, const double* __restrict__ x, int d,
+           double* __restrict__ best_v, double* __restrict__ best_x) {
+#pragma clang fp contract(off)
+    __shared__ double s_val[AS_WAVE];
+    __shared__ int s_win;
+    constexpr double E = 1.1920928955078125e-07, SQRT2 = 1.4142135623730951, SQRT_2PI = 2.5066282746310002;
+    const int t = blockIdx.x, m = threadIdx.x, n_models = n_obj + n_con;
+    const bool mine = m < n_models, con = m >= n_obj;
+    double gm = 0.0, gv = 0.0;      // d (this model's value) / d (its mean, its variance)
+    if (mine) {
+        const double mean = moments[(int64_t)m * 2 * T + t], var = moments[(int64_t)m * 2 * T + T + t];
+        const double s = sqrt(var), z = (best[m] - mean) / s;
+        const double Phi = 0.5 * (1.0 + erf(z / SQRT2));
+        const double pdf = exp(-0.5 * z * z) / SQRT_2PI;
+        const double dz_dm = -1.0 / s, dz_dv = -0.5 * z / var;
+        double val;
+        if (con) {
+            val = 1.0 - Phi;
+            gm = -pdf * dz_dm;
+            gv = -pdf * dz_dv;
+        } else {
+            const double cmax = 1.0 - E, tau = noise[m];
+            const bool bind = Phi > cmax;                    // (a NaN stays a NaN, as torch.clamp)
+            const double cdf = bind ? cmax : Phi;
+            const double r = pdf / (1.0 - cdf);
+            const double u = 1.0 + (z - r) * r;
+            const bool floor = u < E;
+            const double g = floor ? E : u;
+            const double vt = var * g + tau;
+            const double diff = 0.5 * log(var + tau) - 0.5 * log(vt);
+            val = diff < 0.0 ? 0.0 : diff;
+            if (seeds && diff >= 0.0) {                      // torch.clamp's backward: equality passes, a NaN passes nothing
+                const double dr_dz = -z * r + (bind ? 0.0 : r * r);      // under the binding clamp the cdf is a constant
+                const double du_dz = floor ? 0.0 : r + (z - 2.0 * r) * dr_dz;
+                const double dlogvt_dz = 0.5 / vt * var * du_dz;
+                gm = -(dlogvt_dz * dz_dm);
+                gv = 0.5 / (var + tau) - 0.5 / vt * g - dlogvt_dz * dz_dv;
+            }
+        }
+        s_val[m] = val;
+    }
+    __syncthreads();
+    if (m == 0) {
+        double sum = 0.0, feas = 1.0;
+        for (int p = 0; p < n_obj; ++p) sum += s_val[p];
+        for (int c = 0; c < n_con; ++c) feas *= s_val[n_obj + c];
+        const double a = sum * feas;
+        acq[t] = a;
+        int win = 0;
+        if (best_v && a > best_v[t]) {      // strict; a NaN never wins
+            best_v[t] = a;
+            win = 1;
+        }
+        s_win = win;
+    }
+    if (seeds && mine) {
+        double scale = 1.0;      // d acq / d (this model's value)
+        if (con) {
+            double sum = 0.0;
+            for (int p = 0; p < n_obj; ++p) sum += s_val[p];
+            for (int c = 0; c < n_con; ++c)
+                if (n_obj + c != m) scale *= s_val[n_obj + c];
+            scale = sum * scale;
+        } else {
+            for (int c = 0; c < n_con; ++c) scale *= s_val[n_obj + c];
+        }
+        seeds[(int64_t)m * 2 * T + t] = scale * gm;
+        seeds[(int64_t)m * 2 * T + T + t] = scale * gv;
+    }
+    __syncthreads();
+    if (s_win && m < d) best_x[(int64_t)t * d + m] = x[(int64_t)t * d + m];
+}
+
 // One workgroup.  Every thread reads the step count, the workgroup meets, thread 0 advances it: no trailing launch.
 __global__ void __launch_bounds__(AS_BLOCK)
 ascent_adam_kernel(double* __restrict__ x, const double* __restrict__ gx, int n_models, int n, int d,
@@ -261,6 +343,18 @@ int mobocmf_jes_mc_box_forward(const double* moments, const double* noise, int32
                                mobocmf_stream_t stream) {
     return jes_launch(box_of_point ? JES_SELECTED_BOX : JES_ALL_BOXES, moments, noise, n_boxes, K, T, S, box_of_point, acq, acq_ld,
                       want_seeds, seeds, track, x, d, best_v, best_x, stream);
+}
+
+int mobocmf_mes_group_forward(const double* moments, const double* noise, const double* best, int32_t n_obj, int32_t n_con,
+                              int32_t T, double* acq, int32_t want_seeds, double* seeds, int32_t track, const double* x,
+                              int32_t d, double* best_v, double* best_x, mobocmf_stream_t stream) {
+    if (!moments || !noise || !best || !acq || n_obj < 1 || n_con < 0 || T < 1 || T > MOBOCMF_ACQ_MAX_COLUMNS) return MOBOCMF_BAD_ARG;
+    if ((int64_t)n_obj + n_con > 2 * MOBOCMF_ACQ_MAX_PAIRS) return MOBOCMF_BAD_ARG;      // one lane per model
+    if (want_seeds < 0 || want_seeds > 1 || track < 0 || track > 1 || (want_seeds && !seeds)) return MOBOCMF_BAD_ARG;
+    if (track && (!x || !best_v || !best_x || d < 1 || d > MOBOCMF_MAX_D)) return MOBOCMF_BAD_ARG;
+    hipLaunchKernelGGL(mes_kernel, dim3((unsigned)T), dim3(AS_WAVE), 0, (hipStream_t)stream, moments, noise, best, n_obj, n_con,
+                       T, acq, want_seeds ? seeds : (double*)nullptr, x, track ? d : 0, track ? best_v : (double*)nullptr, best_x);
+    return CHECK_LAUNCH();
 }
 
 int mobocmf_ascent_adam_step(double* x, const double* gx, int32_t n_models, int32_t T, int32_t d, const double* lo,

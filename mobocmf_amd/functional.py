@@ -1428,6 +1428,33 @@ def select_topk(vals, k, out_vals, out_idx, x=None, out_x=None, stream=None):
     return out_vals, out_idx
 
 
+def mes_group_forward(moments, noise, best, n_obj, n_con, T, acq, seeds=None, x=None, best_v=None, best_x=None, stream=None):
+    """mobocmf_mes_group_forward: ``acq`` (T,) = the MES value of every test point from the latent ``moments``
+    (n_obj + n_con, 2, T) of exact-GP surrogates, objectives first, their likelihood ``noise`` and ``best`` (best value per
+    objective, threshold per constraint): (sum of the objectives' terms) x (product of the constraints' probabilities of
+    feasibility), the expressions of MESMOC_MFGP's ``_MES_MFGP.forward``.  ``seeds``, ``x``, ``best_v``, ``best_x`` as in
+    ``jes_group_forward``.  One launch, only enqueues (on ``stream``, default the current one): capturable."""
+    return _jes_call("mobocmf_mes_group_forward", moments, noise, (_ptr(best), int(n_obj), int(n_con), int(T)), acq, (_ptr(acq),),
+                     seeds, x, best_v, best_x, stream)
+
+
+def exact_predict_work_bytes(model, mode):
+    """mobocmf_exact_predict_work_bytes of one ``_lib.ExactPredictModel`` record: the bytes of its ``work`` for ``mode``."""
+    nb = ctypes.c_size_t()
+    _lib.check(_lib.load().mobocmf_exact_predict_work_bytes(ctypes.byref(model), int(mode), ctypes.byref(nb)),
+               "mobocmf_exact_predict_work_bytes")
+    return nb.value
+
+
+def exact_predict_launch(host_models, dev_table, mode, stream=None):
+    """mobocmf_exact_predict: ``host_models`` a ctypes array of ``_lib.ExactPredictModel``, ``dev_table`` the same bytes in a
+    device uint8 tensor; ``mode`` _lib.STEP_FORWARD or _lib.STEP_INPUT_GRADIENTS.  One launch, only enqueues (on ``stream``,
+    default the current one): capturable after the first call of each mode."""
+    lib = _lib.require_device()
+    _lib.check(lib.mobocmf_exact_predict(ctypes.cast(host_models, ctypes.c_void_p), _ptr(dev_table), len(host_models), int(mode),
+                                         _on(stream)), "mobocmf_exact_predict")
+
+
 def check_info(info):
     """Synchronising: raises if the last Cholesky reported a non-positive pivot."""
     lib = _lib.require_device()

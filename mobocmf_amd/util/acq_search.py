@@ -14,6 +14,9 @@ caller fetches the winner.
 
 ``DecoupledDeviceAcqSearch`` runs the searches of all black-boxes of a fidelity at once, each for its own JES term
 (``JESMOC_MFDGP.get_nextpoint_decoupled``): the same chain with mobocmf_jes_mc_box_forward in the JES position.
+
+``MesDeviceAcqSearch`` is the coupled search of the MES baseline over exact-GP surrogates (``MESMOC_MFGP(search="device")``): the
+same chain over an ExactGPPredictGroup (util/exact_predict.py) with mobocmf_mes_group_forward in the JES position.
 """
 import torch
 
@@ -49,11 +52,7 @@ class DeviceAcqSearch:
             raise ValueError("DeviceAcqSearch: num_pareto_samples >= 1 (got %d)" % K)
         B, R = self.B, self.R = int(n_searches or 1), int(num_restarts)
         self._one = (lambda t: t[0]) if n_searches is None else (lambda t: t)
-        if group.T != B * R or len(group.models) % (1 + K):
-            raise _lib.MobocmfError("DeviceAcqSearch: a group of (uncond, cond_1 .. cond_K) per black-box built for T = "
-                                    "num_restarts test points")
-        if not 1 + K <= len(group.models) <= 2 * _lib.ACQ_MAX_PAIRS:
-            raise _lib.MobocmfError("DeviceAcqSearch: 1 + K..%d models per group" % (2 * _lib.ACQ_MAX_PAIRS))
+        self._check_group(group)
         dev, T, d = group.device, group.T, group.d
         self.group, self.T, self.d = group, T, d
         self.lo = bounds[0].detach().to(dev, torch.float64).contiguous()
@@ -69,9 +68,19 @@ class DeviceAcqSearch:
         self._graphs, self._raw = {}, {}
         self._capture_stream = group.stream
 
+    def _check_group(self, group):
+        """What the acquisition launch (``_jes``) asks of the group's models; a subclass with another launch has another rule."""
+        K = self.K
+        if group.T != self.B * self.R or len(group.models) % (1 + K):
+            raise _lib.MobocmfError("DeviceAcqSearch: a group of (uncond, cond_1 .. cond_K) per black-box built for T = "
+                                    "num_restarts test points")
+        if not 1 + K <= len(group.models) <= 2 * _lib.ACQ_MAX_PAIRS:
+            raise _lib.MobocmfError("DeviceAcqSearch: 1 + K..%d models per group" % (2 * _lib.ACQ_MAX_PAIRS))
+
     # ------------------------------------------------------------------ the launches
     def _jes(self, grp, noise, acq, **track):
-        """The JES launch on ``grp``'s moments.  ``track`` (seeds, x, best_v, best_x): an iterate, ``acq`` (T,); none: a chunk of
+        """The acquisition launch of an iterate -- here the JES launch on ``grp``'s moments; a subclass puts its own in this
+        position (MesDeviceAcqSearch).  ``track`` (seeds, x, best_v, best_x): an iterate, ``acq`` (T,); none: a chunk of
         raw candidates, ``acq`` (B, chunk) -- here B = 1, the coupled value."""
         F.jes_mc_group_forward(grp.moments, noise, self.K, grp.T, grp.S, acq, stream=grp.stream, **track)
 
@@ -210,6 +219,33 @@ class DecoupledDeviceAcqSearch(DeviceAcqSearch):
         """An iterate: every row for the box it is searched for; a chunk of raw candidates: every box's term at every row."""
         F.jes_mc_box_forward(grp.moments, noise, self.K, grp.T, grp.S, acq, box_of_point=self.box_of_point if track else None,
                              stream=grp.stream, **track)
+
+
+class MesDeviceAcqSearch(DeviceAcqSearch):
+    """The coupled MES search of the exact-GP baseline (``MESMOC_MFGP(search="device")``): ``group`` is an ExactGPPredictGroup
+    (util/exact_predict.py) over the ``n_obj`` objectives' models, then the ``n_con`` constraints' models, built for T =
+    ``num_restarts`` test points; ``best`` (n_obj + n_con,): best value per objective, threshold per constraint.  The iterate is
+    the same chain of four launches -- group STEP_FORWARD -> mobocmf_mes_group_forward -> group STEP_INPUT_GRADIENTS ->
+    mobocmf_ascent_adam_step -- captured once and replayed; ``start_from_raw``, ``run`` and the winner are the base class's."""
+
+    def __init__(self, group, bounds, num_restarts, lr, best, n_obj, n_con, betas=(0.9, 0.999), eps=1e-8):
+        self.n_obj, self.n_con = int(n_obj), int(n_con)
+        super().__init__(group, bounds, num_restarts, lr, betas=betas, eps=eps)
+        self.best = torch.as_tensor(best, dtype=torch.float64).detach().reshape(-1).to(group.device).contiguous()
+        if self.best.numel() != self.n_obj + self.n_con:
+            raise _lib.MobocmfError("MesDeviceAcqSearch: one best value per objective and one threshold per constraint")
+
+    def _check_group(self, group):
+        if group.T != self.R or group.S != 1:
+            raise _lib.MobocmfError("MesDeviceAcqSearch: a group with S = 1 built for T = num_restarts test points")
+        if self.n_obj < 1 or self.n_con < 0 or len(group.models) != self.n_obj + self.n_con or \
+                len(group.models) > 2 * _lib.ACQ_MAX_PAIRS:
+            raise _lib.MobocmfError("MesDeviceAcqSearch: n_obj >= 1 objectives then n_con >= 0 constraints, at most %d models"
+                                    % (2 * _lib.ACQ_MAX_PAIRS))
+
+    def _jes(self, grp, noise, acq, **track):
+        """The MES launch in the JES position (``acq`` (T,) of an iterate, or (1, chunk) of raw candidates)."""
+        F.mes_group_forward(grp.moments, noise, self.best, self.n_obj, self.n_con, grp.T, acq, stream=grp.stream, **track)
 
 
 def raise_on_info(words, what):
