@@ -1266,6 +1266,110 @@ int mobocmf_exact_predict_work_bytes(const mobocmf_exact_predict_model* model, i
 int mobocmf_exact_predict(const mobocmf_exact_predict_model* host_models, const mobocmf_exact_predict_model* dev_models,
                           int32_t n_models, int32_t mode, mobocmf_stream_t stream);
 
+/* ---- Fitting the EXACT-GP surrogates on the device (csrc/exact_fit.hip): the launches of one Adam step on -log N(y | 0, K)
+ * that are not the factorisation's, for n_models models at once (util/exact_fit.py: ExactGPFitStep captures the step once and
+ * replays it).  Per model: x the n x d training inputs WITHOUT the fidelity column, lev their levels, and six parameter slots
+ * (MOBOCMF_EXACT_FIT_P_*) each with its raw tensor and the constraint it carries: value = raw (IDENTITY), lo + softplus(raw)
+ * (SOFTPLUS, torch's threshold 20), lo + (hi - lo) sigmoid(raw) (SIGMOID).  With tau, os_s, ls_s, os_n, ls_n, rho the values:
+ *   E^k_ij = exp(-1/2 sum_c ((x_ic - x_jc) / ls_kc)^2)                                                  k in {s, n}
+ *   K_ij   = sig[l_i] sig[l_j] os_s E^s_ij + ntab[min(l_i, l_j)] os_n E^n_ij + tau [i == j]
+ *   KERNEL_MIN: sig = 1, ntab[t] = t.   KERNEL_LIN: sig[l] = prod_{q < l} rho_q,
+ *                                       ntab[t] = [t >= 1] + sum_{k = 3}^{n_levels - 2} [t + 1 >= k] rho_{k-2}^2
+ *   G = dmll / dK = (alpha alpha^T - K^-1) / 2,  alpha = L^-T a
+ * mobocmf_exact_fit_covariance: K (n x n, tau on the diagonal) from the CURRENT raw parameters into the model's work area, ld
+ *   npad = n rounded up to 128, zeros in the padding and identity on the padded diagonal: the input of mobocmf_exact_gp_factor,
+ *   which the caller runs per model with mll / info / state where the descriptor says (Linv, a: inside that state).
+ * mobocmf_exact_fit_prepare: LiT = Linv^T (npad x npad, the whole padded matrix) and alpha (npad, zero beyond n) into the work
+ *   area.  The caller then forms Kinv = LiT LiT^T with mobocmf_gemm_f64 (tri = 2, trans_b = 1) into the work area.
+ * mobocmf_exact_fit_gradient: a workgroup owns (model, strip of MOBOCMF_EXACT_FIT_STRIP rows i) and STORES, into row `strip`
+ *   of the slab, its share of the MOBOCMF_EXACT_FIT_SUMS sums  sum_ij G_ij dK_ij / dvalue  -- G formed on the fly, both
+ *   exponentials formed again -- in this order:
+ *     [0] os_s   sum G sig_i sig_j E^s                     [1 + c] ls_s,c  sum G sig_i sig_j os_s E^s (x_ic - x_jc)^2 / ls_sc^3
+ *     [33] os_n  sum G ntab[min] E^n                       [34 + c] ls_n,c the same with ntab[min] os_n E^n and ls_nc
+ *     [66] tau   tr G       [67 + l] sig[l]  2 sum_{i: l_i = l} sum_j G sig_j os_s E^s       [75 + t] ntab[t]  sum_{min = t} G os_n E^n
+ *   (entries of coordinates >= d are 0).  Wavefront shuffles, then LDS in wavefront order: no atomics.
+ * mobocmf_exact_fit_update, MOBOCMF_EXACT_FIT_STEP, one workgroup per model, in this order: sums the slab strip by strip (also
+ *   left in `sums` of the work area); reads loss = -mll[0] and info[0]; a stopped model (words[STOPPED_AT] >= 0): nothing; loss
+ *   non-finite or info != 0: words[STOPPED_AT] = words[IT], losses[IT] = NaN, parameters untouched (info < 0, an abandoned
+ *   in-launch wait of the factorisation, also sets the sticky words[ABANDONED]); else losses[IT] = loss, and if there is no best
+ *   yet or loss < stats[0]: stats[0] = loss, words[BEST_IT] = IT, best <- raw (BEFORE the update); then the chain rule (through
+ *   sig and ntab to rho by prefix and running products, no division; through the constraint's slope to raw; the sign of -mll)
+ *   into grad, torch-default Adam on raw / exp_avg / exp_avg_sq with step count IT + 1 (the expressions of mobocmf_adam_multi),
+ *   and words[IT] += 1.  MOBOCMF_EXACT_FIT_FINISH (after one more covariance + factorisation): stats[1] = the final loss,
+ *   words[FINAL_INFO] = info; if a best exists and the final loss is non-finite, info != 0 or loss > stats[0]: raw <- best and
+ *   words[RESTORED] = 1.  The caller initialises words (IT 0, STOPPED_AT -1, BEST_IT -1, the others 0), losses (NaN) and the
+ *   Adam state (0).
+ * Work area (doubles, mobocmf_exact_fit_work_bytes): K | LiT | Kinv (npad^2 each) | alpha (npad) | slab (ceil(n / 16) x 83) |
+ * sums (83).  One launch each on `stream`, nothing shared between the workgroups of different models, no in-launch wait; two
+ * runs are bitwise equal; capturable.  The kernels read the descriptors from DEVICE memory (dev_models); host_models is the
+ * same array in host memory, for validation and launch geometry.  A level outside [0, n_levels) makes K and the sums NaN and is
+ * never used as an index.
+ * Limits: 1 <= n <= MOBOCMF_EXACT_FIT_MAX_N; 1 <= d <= MOBOCMF_MAX_D; 1 <= n_levels <= MOBOCMF_EXACT_FIT_MAX_LEVELS; 1 <=
+ * n_models <= MOBOCMF_EXACT_FIT_MAX_MODELS; numel = 1 (noise, outputscales), d (lengthscales), n_levels - 1 (rho, KERNEL_LIN; 0
+ * and no pointers for KERNEL_MIN); cap >= 1.  MOBOCMF_BAD_ARG otherwise, for a NULL pointer or for another mode, on the host
+ * before any HIP call. */
+#define MOBOCMF_EXACT_FIT_MAX_N 512
+#define MOBOCMF_EXACT_FIT_MAX_LEVELS 8
+#define MOBOCMF_EXACT_FIT_MAX_MODELS (2 * MOBOCMF_ACQ_MAX_PAIRS)
+#define MOBOCMF_EXACT_FIT_STRIP 16
+#define MOBOCMF_EXACT_FIT_SUMS (2 * (MOBOCMF_MAX_D + 1) + 1 + 2 * MOBOCMF_EXACT_FIT_MAX_LEVELS)
+#define MOBOCMF_EXACT_FIT_KERNEL_MIN 0      /* MFKernel */
+#define MOBOCMF_EXACT_FIT_KERNEL_LIN 1      /* MFKernel_lin */
+#define MOBOCMF_EXACT_FIT_IDENTITY 0
+#define MOBOCMF_EXACT_FIT_SOFTPLUS 1
+#define MOBOCMF_EXACT_FIT_SIGMOID 2
+#define MOBOCMF_EXACT_FIT_PARAMS 6
+#define MOBOCMF_EXACT_FIT_P_NOISE 0
+#define MOBOCMF_EXACT_FIT_P_OS_S 1
+#define MOBOCMF_EXACT_FIT_P_LS_S 2
+#define MOBOCMF_EXACT_FIT_P_OS_N 3
+#define MOBOCMF_EXACT_FIT_P_LS_N 4
+#define MOBOCMF_EXACT_FIT_P_RHO 5
+#define MOBOCMF_EXACT_FIT_STEP 0
+#define MOBOCMF_EXACT_FIT_FINISH 1
+#define MOBOCMF_EXACT_FIT_WORDS 8
+#define MOBOCMF_EXACT_FIT_W_IT 0
+#define MOBOCMF_EXACT_FIT_W_STOPPED_AT 1
+#define MOBOCMF_EXACT_FIT_W_BEST_IT 2
+#define MOBOCMF_EXACT_FIT_W_RESTORED 3
+#define MOBOCMF_EXACT_FIT_W_ABANDONED 4
+#define MOBOCMF_EXACT_FIT_W_FINAL_INFO 5
+typedef struct mobocmf_exact_fit_param {
+    double* raw;                     /* the model's own parameter tensor, updated in place */
+    double* best;                    /* the best iterate's copy */
+    double* exp_avg;
+    double* exp_avg_sq;
+    double* grad;                    /* d(-mll) / d raw of the last step */
+    int32_t numel, kind;             /* MOBOCMF_EXACT_FIT_IDENTITY / SOFTPLUS / SIGMOID */
+    double lo, hi;
+} mobocmf_exact_fit_param;
+typedef struct mobocmf_exact_fit_model {
+    int32_t n, d, n_levels, kernel;  /* training rows, input columns, fidelity levels, MOBOCMF_EXACT_FIT_KERNEL_* */
+    int32_t cap, reserved;           /* entries of losses */
+    const double* x;                 /* n x d */
+    const int32_t* lev;              /* n */
+    const double* y;                 /* n (what the caller hands to mobocmf_exact_gp_factor) */
+    mobocmf_exact_fit_param params[MOBOCMF_EXACT_FIT_PARAMS];
+    const double* Linv;              /* npad x npad and npad, inside the factorisation's state */
+    const double* a;
+    const double* mll;               /* the factorisation's likelihood and info words */
+    const int32_t* info;
+    double* losses;                  /* cap */
+    double* stats;                   /* 2: best loss, final loss */
+    int32_t* words;                  /* MOBOCMF_EXACT_FIT_WORDS */
+    void* work;                      /* mobocmf_exact_fit_work_bytes */
+} mobocmf_exact_fit_model;
+int mobocmf_exact_fit_work_bytes(const mobocmf_exact_fit_model* model, int32_t n_models, size_t* bytes);
+int mobocmf_exact_fit_covariance(const mobocmf_exact_fit_model* host_models, const mobocmf_exact_fit_model* dev_models,
+                                 int32_t n_models, mobocmf_stream_t stream);
+int mobocmf_exact_fit_prepare(const mobocmf_exact_fit_model* host_models, const mobocmf_exact_fit_model* dev_models,
+                              int32_t n_models, mobocmf_stream_t stream);
+int mobocmf_exact_fit_gradient(const mobocmf_exact_fit_model* host_models, const mobocmf_exact_fit_model* dev_models,
+                               int32_t n_models, mobocmf_stream_t stream);
+int mobocmf_exact_fit_update(const mobocmf_exact_fit_model* host_models, const mobocmf_exact_fit_model* dev_models,
+                             int32_t n_models, int32_t mode, double lr, double beta1, double beta2, double eps,
+                             mobocmf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

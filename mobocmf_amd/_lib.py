@@ -103,6 +103,37 @@ class ExactPredictModel(ctypes.Structure):
                 ("work", ctypes.c_void_p)]
 
 
+# MOBOCMF_EXACT_FIT_*: limits, the positions of the sums in the slab, parameter slots, constraint kinds, modes, words
+EXACT_FIT_MAX_N, EXACT_FIT_MAX_LEVELS, EXACT_FIT_MAX_MODELS, EXACT_FIT_STRIP, EXACT_FIT_SUMS = 512, 8, 64, 16, 83
+EXACT_FIT_KERNEL_MIN, EXACT_FIT_KERNEL_LIN = 0, 1
+EXACT_FIT_IDENTITY, EXACT_FIT_SOFTPLUS, EXACT_FIT_SIGMOID = 0, 1, 2
+EXACT_FIT_PARAMS = 6
+EXACT_FIT_P_NOISE, EXACT_FIT_P_OS_S, EXACT_FIT_P_LS_S, EXACT_FIT_P_OS_N, EXACT_FIT_P_LS_N, EXACT_FIT_P_RHO = range(6)
+EXACT_FIT_STEP, EXACT_FIT_FINISH = 0, 1
+EXACT_FIT_WORDS = 8
+(EXACT_FIT_W_IT, EXACT_FIT_W_STOPPED_AT, EXACT_FIT_W_BEST_IT, EXACT_FIT_W_RESTORED, EXACT_FIT_W_ABANDONED,
+ EXACT_FIT_W_FINAL_INFO) = range(6)
+EXACT_FIT_S_OS_S, EXACT_FIT_S_LS_S, EXACT_FIT_S_OS_N, EXACT_FIT_S_LS_N, EXACT_FIT_S_TAU, EXACT_FIT_S_SIG, EXACT_FIT_S_NTAB = \
+    0, 1, 33, 34, 66, 67, 75
+
+
+class ExactFitParam(ctypes.Structure):
+    """mobocmf_exact_fit_param: one raw parameter tensor of a model of the device fit, its constraint and its optimiser state."""
+    _fields_ = [("raw", ctypes.c_void_p), ("best", ctypes.c_void_p), ("exp_avg", ctypes.c_void_p), ("exp_avg_sq", ctypes.c_void_p),
+                ("grad", ctypes.c_void_p), ("numel", ctypes.c_int32), ("kind", ctypes.c_int32), ("lo", ctypes.c_double),
+                ("hi", ctypes.c_double)]
+
+
+class ExactFitModel(ctypes.Structure):
+    """mobocmf_exact_fit_model: one exact-GP surrogate of the mobocmf_exact_fit_* launches (read from DEVICE memory)."""
+    _fields_ = [("n", ctypes.c_int32), ("d", ctypes.c_int32), ("n_levels", ctypes.c_int32), ("kernel", ctypes.c_int32),
+                ("cap", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("x", ctypes.c_void_p), ("lev", ctypes.c_void_p), ("y", ctypes.c_void_p),
+                ("params", ExactFitParam * EXACT_FIT_PARAMS),
+                ("Linv", ctypes.c_void_p), ("a", ctypes.c_void_p), ("mll", ctypes.c_void_p), ("info", ctypes.c_void_p),
+                ("losses", ctypes.c_void_p), ("stats", ctypes.c_void_p), ("words", ctypes.c_void_p), ("work", ctypes.c_void_p)]
+
+
 class NatgradSmallLayer(ctypes.Structure):
     """mobocmf_natgrad_small_layer: one layer of mobocmf_natgrad_small_step (the kernel reads the array from DEVICE memory)."""
     _fields_ = [("M", ctypes.c_int32), ("n_guard_info", ctypes.c_int32), ("m", ctypes.c_void_p), ("L_S", ctypes.c_void_p),
@@ -261,6 +292,11 @@ SYMBOLS = {
     "mobocmf_frozen_predict_split": [_P, _P, _I32, _I32, _P],
     "mobocmf_exact_predict_work_bytes": [ctypes.POINTER(ExactPredictModel), _I32, ctypes.POINTER(_SZ)],
     "mobocmf_exact_predict": [_P, _P, _I32, _I32, _P],
+    "mobocmf_exact_fit_work_bytes": [ctypes.POINTER(ExactFitModel), _I32, ctypes.POINTER(_SZ)],
+    "mobocmf_exact_fit_covariance": [_P, _P, _I32, _P],
+    "mobocmf_exact_fit_prepare": [_P, _P, _I32, _P],
+    "mobocmf_exact_fit_gradient": [_P, _P, _I32, _P],
+    "mobocmf_exact_fit_update": [_P, _P, _I32, _I32, _D, _D, _D, _D, _P],
     "mobocmf_mes_group_forward": [_P, _P, _P, _I32, _I32, _I32, _P, _I32, _P, _I32, _P, _I32, _P, _P, _P],
 }
 ACQ_MAX_PAIRS, TOPK_MAX_K, TOPK_MAX_N = 32, 64, 4096      # MOBOCMF_ACQ_MAX_PAIRS / MOBOCMF_TOPK_MAX_K / MOBOCMF_TOPK_MAX_N

@@ -1455,6 +1455,44 @@ def exact_predict_launch(host_models, dev_table, mode, stream=None):
                                          _on(stream)), "mobocmf_exact_predict")
 
 
+def exact_fit_work_bytes(model, n_models=1):
+    """mobocmf_exact_fit_work_bytes of one ``_lib.ExactFitModel`` record (of a table of ``n_models``): the bytes of its ``work``."""
+    nb = ctypes.c_size_t()
+    _lib.check(_lib.load().mobocmf_exact_fit_work_bytes(ctypes.byref(model), int(n_models), ctypes.byref(nb)),
+               "mobocmf_exact_fit_work_bytes")
+    return nb.value
+
+
+def _exact_fit_call(name, host_models, dev_table, stream, *args):
+    lib = _lib.require_device()
+    _lib.check(getattr(lib, name)(ctypes.cast(host_models, ctypes.c_void_p), _ptr(dev_table), len(host_models), *args, _on(stream)),
+               name)
+
+
+def exact_fit_covariance(host_models, dev_table, stream=None):
+    """mobocmf_exact_fit_covariance: the padded training covariance of every model of the table from its current raw parameters,
+    into the models' work areas.  One launch, only enqueues (``host_models`` a ctypes array of ``_lib.ExactFitModel``,
+    ``dev_table`` the same bytes in a device uint8 tensor -- as for ``exact_predict_launch``)."""
+    _exact_fit_call("mobocmf_exact_fit_covariance", host_models, dev_table, stream)
+
+
+def exact_fit_prepare(host_models, dev_table, stream=None):
+    """mobocmf_exact_fit_prepare: L^-T and alpha = L^-T a of every model from its factorisation's state.  One launch."""
+    _exact_fit_call("mobocmf_exact_fit_prepare", host_models, dev_table, stream)
+
+
+def exact_fit_gradient(host_models, dev_table, stream=None):
+    """mobocmf_exact_fit_gradient: every model's slab of partial sums sum_ij G_ij dK_ij / dvalue.  One launch, no atomics."""
+    _exact_fit_call("mobocmf_exact_fit_gradient", host_models, dev_table, stream)
+
+
+def exact_fit_update(host_models, dev_table, mode, lr, betas=(0.9, 0.999), eps=1e-8, stream=None):
+    """mobocmf_exact_fit_update: ``mode`` _lib.EXACT_FIT_STEP (slab sum, stop / best bookkeeping, chain rule, Adam through the
+    pointer table) or _lib.EXACT_FIT_FINISH (the restore decision).  One launch."""
+    _exact_fit_call("mobocmf_exact_fit_update", host_models, dev_table, stream, int(mode), float(lr), float(betas[0]),
+                    float(betas[1]), float(eps))
+
+
 def check_info(info):
     """Synchronising: raises if the last Cholesky reported a non-positive pivot."""
     lib = _lib.require_device()

@@ -244,24 +244,49 @@ class _ExactMFGP(nn.Module):
         self.train()
         return result
 
-    def fit(self, num_iters=200, lr=0.05):
+    def fit(self, num_iters=200, lr=0.05, engine="host"):
         """Maximise the marginal likelihood over the raw parameters with Adam (the reference's experiments call BoTorch's
-        fit_gpytorch_mll; any optimiser of the same objective serves a baseline)."""
+        fit_gpytorch_mll; any optimiser of the same objective serves a baseline).  ``engine="host"``: the loop below;
+        ``"device"``: the same loop as one captured step replayed per iteration and one read at the end (util/exact_fit.py;
+        a model that does not fit that path raises -- there is no fallback; ``last_fit`` keeps the ``ExactFitResult``)."""
+        if engine == "device":
+            from ..util import exact_fit
+            reason = exact_fit.why_not(self)
+            if reason is not None:
+                raise RuntimeError("fit(engine=\"device\"): " + reason)
+            self.last_fit = exact_fit.ExactGPFitStep([self], lr, num_iters=num_iters).fit(num_iters)
+            return self
+        if engine != "host":
+            raise ValueError("fit: engine is \"host\" or \"device\" (got %r)" % (engine,))
+        return self._fit_host(num_iters, lr)
+
+    def _fit_host(self, num_iters, lr, record=None):
+        """The host loop.  ``record``: a dict that receives what the loop saw (losses, best, best_iteration, stopped_at,
+        restored, final) -- from the floats it reads anyway."""
         opt = torch.optim.Adam(self.parameters(), lr=lr)
         best, state = None, None
-        for _ in range(num_iters):
+        seen = dict(losses=[], best=None, best_iteration=None, stopped_at=None, restored=False, final=None)
+        for it in range(num_iters):
             opt.zero_grad()
             loss = -self.marginal_log_likelihood()
             if not bool(torch.isfinite(loss)):
+                seen["stopped_at"] = it
                 break
-            if best is None or float(loss) < best:
-                best, state = float(loss), {k: v.detach().clone() for k, v in self.state_dict().items()}
+            value = float(loss)
+            seen["losses"].append(value)
+            if best is None or value < best:
+                best, state = value, {k: v.detach().clone() for k, v in self.state_dict().items()}
+                seen["best"], seen["best_iteration"] = best, it
             loss.backward()
             opt.step()
         if state is not None:
             final = -self.marginal_log_likelihood()
-            if not bool(torch.isfinite(final)) or float(final) > best:
+            seen["final"] = float(final)
+            if not bool(torch.isfinite(final)) or seen["final"] > best:
                 self.load_state_dict(state)
+                seen["restored"] = True
+        if record is not None:
+            record.update(seen)
         return self
 
 
