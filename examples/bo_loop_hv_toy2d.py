@@ -7,8 +7,13 @@ to ``hypervolumes.txt`` in the reference's six columns:
     hv_iter  optimal_hv  feasible  num_infeasible  num_optimal_points_fini  num_optimal_points_ini
 
 ``--acq jes`` (default) chooses the next point with bo_iteration_toy2d.run (the cost-weighted JES acquisition), ``--acq random``
-with the reference's random baseline (Random_choice).  Objectives are minimised, the constraint is feasible when >= 0; the
-reference point of the hypervolume is (1000, 1000), as there.
+with the reference's random baseline (Random_choice), ``--acq mes`` with the max-value entropy search baseline on exact GPs
+(bo_iteration_mes_toy2d.run: device fit, sampled Pareto front, device acquisition search).  Objectives are minimised, the
+constraint is feasible when >= 0; the reference point of the hypervolume is (1000, 1000), as there.
+
+With ``--acq mes`` the row that is scored comes from ``fit_only``'s MFDGP recommendation on the data the acquisition has
+gathered, as for ``--acq random`` (the exact GPs only choose the next point).  All three acquisitions are thus scored by the same
+recommender, the MFDGP surrogates' ``recommend``, and the columns compare acquisitions, not models.
 
 ``--num-inducing M`` caps the inducing points of every surrogate at M; ``--inducing greedy`` then chooses them among the
 training rows by greedy conditional variance (``inducing_selection="greedy_variance"``) instead of taking the first M rows.
@@ -19,7 +24,7 @@ inputs must extend the old ones, which all training rows and the first M rows do
 
 ``--pareto-samples K`` averages the JES acquisition over K sampled Pareto sets (JESMOC_MFDGP(num_pareto_samples=K)).
 
-    python examples/bo_loop_hv_toy2d.py [--iters 5] [--acq jes|random] [--epochs 300] [--seed 0] [--out .]
+    python examples/bo_loop_hv_toy2d.py [--iters 5] [--acq jes|random|mes] [--epochs 300] [--seed 0] [--out .]
                                         [--num-inducing M] [--inducing first|greedy] [--warm-start [--warm-epochs E]]
                                         [--pareto-samples K]
 """
@@ -36,6 +41,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from bo_iteration_mes_toy2d import run as mes_run  # noqa: E402
 from bo_iteration_toy2d import blackboxes, run  # noqa: E402
 from mobocmf_amd.acquisition_functions.Random_choice import Random_choice  # noqa: E402
 from mobocmf_amd.models.mfdgp import TL  # noqa: E402
@@ -86,12 +92,14 @@ def score(fitter, grid, recommend_search="grid"):
 
 
 def loop_hv(iters=5, acq="jes", seed=0, out_dir=".", epochs=300, verbose=True, num_inducing=None, inducing="first",
-            warm_start=False, warm_epochs=None, pareto_samples=1, pareto_search="grid", recommend_search="grid", **kw):
+            warm_start=False, warm_epochs=None, pareto_samples=1, pareto_search="grid", recommend_search="grid", record=None,
+            **kw):
     """``iters`` BO iterations, each one scored and appended to ``out_dir``/hypervolumes.txt; returns the rows.
     ``warm_start``: every iteration after the first starts from the last one's unconditioned fit, ``warm_epochs`` epochs of
     phase 2 (default: ``epochs``).  ``pareto_samples``: JES averaged over this many sampled Pareto sets.  ``pareto_search``: the fitter's
     (``"evolve"``: NSGA-II on the GPU from the grid's rows).  ``recommend_search``: how the recommendation that is scored is
-    searched (``score``)."""
+    searched (``score``).  ``acq="mes"``: ``kw`` goes to bo_iteration_mes_toy2d.run; ``record``: a list that receives, per
+    iteration, dict(rows, search_engine, sample_engines, tries) of the MES iteration."""
     warm_epochs = (epochs if warm_epochs is None else warm_epochs) if warm_start else None
     previous = None
     model_kwargs = {"pareto_search": pareto_search}
@@ -117,6 +125,14 @@ def loop_hv(iters=5, acq="jes", seed=0, out_dir=".", epochs=300, verbose=True, n
                               warm_epochs=warm_epochs)
             previous = fitter if warm_start else None
             cand, fidelity = chooser.get_nextpoint_coupled(iteration=it)
+        elif acq == "mes":
+            fitter = fit_only(x, fid, epochs, seed + it, model_kwargs=model_kwargs, previous=previous,
+                              warm_epochs=warm_epochs)
+            previous = fitter if warm_start else None
+            _, front, mes, cand, fidelity, _ = mes_run(seed=seed + it, data=(x, fid), verbose=False, **kw)
+            if record is not None:
+                record.append(dict(rows=x.shape[0], search_engine=dict(mes.last_search_engine),
+                                   sample_engines=dict(front.engines), tries=front.tries))
         else:
             fitter, jes, cand, fidelity = run(seed=seed + it, data=(x, fid), epochs=epochs, verbose=False,
                                               model_kwargs=model_kwargs, previous=previous, warm_epochs=warm_epochs,
@@ -137,7 +153,7 @@ def loop_hv(iters=5, acq="jes", seed=0, out_dir=".", epochs=300, verbose=True, n
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=5)
-    ap.add_argument("--acq", choices=["jes", "random"], default="jes")
+    ap.add_argument("--acq", choices=["jes", "random", "mes"], default="jes")
     ap.add_argument("--epochs", type=int, default=300)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--out", default=".")

@@ -1370,6 +1370,78 @@ int mobocmf_exact_fit_update(const mobocmf_exact_fit_model* host_models, const m
                              int32_t n_models, int32_t mode, double lr, double beta1, double beta2, double eps,
                              mobocmf_stream_t stream);
 
+/* ---- Posterior FUNCTION samples of the EXACT-GP surrogates on the device (csrc/exact_sample.hip): the stage of a max-value
+ * entropy search iteration between the fit and the acquisition search, for n_problems (model, sample) problems of different n
+ * at once (util/exact_sample.py).  Both baseline kernels have the form
+ *   k([x, t], [x', t']) = s(t) s(t') k_sig(x, x') + ntab[min(t, t')] k_noi(x, x'),     ntab[m] = sum_{l <= m} delta_l, delta_l >= 0
+ * (sig / ntab: the tables of mobocmf_exact_predict; sqd[l] = sqrt(delta_l)).  With F random features per ARD-RBF kernel,
+ *   C_sig = cos(W_sig x + b_sig),  C_noi = cos(W_noi x + b_noi)   (F x n; W already divided by the lengthscales)
+ *   c_sig = sqrt(2 a_sig / F),     c_noi = sqrt(2 a_noi / F)      (scal = [a_sig, a_noi, noise], device data)
+ * the weight-space feature map Phi has (1 + n_levels) F rows: block 0 is s(l_i) c_sig C_sig[:, i]; block 1 + l is
+ * sqd[l] c_noi C_noi[:, i] for the rows with l_i >= l and zero for the others.  Matheron's rule in the n-dimensional function
+ * space, theta0 ~ N(0, I) ((1 + n_levels) F, block order) and e ~ N(0, noise I_n) being OPERANDS (the kernels draw nothing):
+ *   G     = Phi^T Phi + noise I
+ *         = s_i s_j c_sig^2 (C_sig^T C_sig)_ij + ntab[min(l_i, l_j)] c_noi^2 (C_noi^T C_noi)_ij + noise [i == j]
+ *   r     = y - Phi^T theta0 - e
+ *   w     = G^-1 r
+ *   theta = theta0 + Phi w
+ * and the sampled function at output level f is ONE random-feature layer of 2F features,
+ *   g_f(x) = s(f) c_sig theta_sig . cos(W_sig x + b_sig) + c_noi (sum_{l <= f} sqd[l] theta_noi,l) . cos(W_noi x + b_noi).
+ * mobocmf_exact_sample_gram: G of every problem in one launch, ld npad = n rounded up to 128, zeros in the padding and identity
+ *   on the padded diagonal (the input of mobocmf_exact_gp_factor, as mobocmf_exact_fit_covariance writes it), and r (n).  A
+ *   workgroup owns a 64 x 64 tile on or below the diagonal and stores its mirror image too; the cosines are formed in LDS in
+ *   chunks of MOBOCMF_EXACT_SAMPLE_CHUNK features and both n x n x F products run on v_mfma_f64_16x16x4_f64 from there: Phi is
+ *   never written to memory; the level and scale combination is the epilogue.
+ * The caller then runs mobocmf_exact_gp_factor per problem with r as its right-hand side (Linv, a, info: where the descriptor
+ *   says).
+ * mobocmf_exact_sample_weights: two launches -- w = L^-T a (n) and info_out[0] = info[0]; then theta ((1 + n_levels) F, block
+ *   order) and, for each of the n_out requested levels out_level[o], the packed one-layer chain sample (layers/rff.py,
+ *   RFFChainSample.pack: header 1, 1, d, 2F, length, kind 0; alpha = F, 0, 0, 0, s0 = 1, 0, 0; W1 = [W_sig; W_noi] (2F x d);
+ *   b1 = [b_sig; b_noi]; theta' = [s(f) c_sig theta_sig; c_noi sum_{l <= f} sqd[l] theta_noi,l]) at chain + o (13 + 2F (d + 2)).
+ * Nothing is shared between workgroups, sums run in a fixed order: no atomics, no in-launch wait; two runs are bitwise equal.
+ * The kernels read the descriptors from DEVICE memory (dev_problems); host_problems is the same array in host memory, for
+ * validation and launch geometry.  A level outside [0, n_levels) makes G, r and theta NaN and is never used as an index.
+ * Limits: 1 <= n <= MOBOCMF_EXACT_SAMPLE_MAX_N; 1 <= d <= MOBOCMF_MAX_D; 1 <= n_levels <= MOBOCMF_EXACT_SAMPLE_MAX_LEVELS;
+ * 1 <= F <= MOBOCMF_EXACT_SAMPLE_MAX_F; 0 <= n_out <= MOBOCMF_EXACT_SAMPLE_MAX_LEVELS, 0 <= out_level[o] < n_levels; 1 <=
+ * n_problems <= MOBOCMF_EXACT_SAMPLE_MAX_PROBLEMS.  MOBOCMF_BAD_ARG otherwise or for a NULL pointer among those the entry point
+ * uses, on the host before any HIP call. */
+#define MOBOCMF_EXACT_SAMPLE_MAX_N 512
+#define MOBOCMF_EXACT_SAMPLE_MAX_LEVELS 8
+#define MOBOCMF_EXACT_SAMPLE_MAX_F 65536
+#define MOBOCMF_EXACT_SAMPLE_MAX_PROBLEMS (2 * MOBOCMF_ACQ_MAX_PAIRS)
+#define MOBOCMF_EXACT_SAMPLE_CHUNK 16
+typedef struct mobocmf_exact_sample_problem {
+    int32_t n, d, n_levels, F;       /* training rows, input columns (without the fidelity column), levels, features per kernel */
+    int32_t n_out, reserved;         /* output levels of the weights launch */
+    int32_t out_level[MOBOCMF_EXACT_SAMPLE_MAX_LEVELS];
+    const double* x;                 /* n x d */
+    const int32_t* lev;              /* n */
+    const double* y;                 /* n */
+    const double* sig;               /* n_levels: s(level) */
+    const double* ntab;              /* n_levels */
+    const double* sqd;               /* n_levels: sqrt(ntab[l] - ntab[l - 1]), sqrt(ntab[0]) */
+    const double* scal;              /* 3: a_sig, a_noi, noise */
+    const double* W_sig;             /* F x d */
+    const double* b_sig;             /* F */
+    const double* W_noi;
+    const double* b_noi;
+    const double* theta0;            /* (1 + n_levels) F */
+    const double* e;                 /* n */
+    double* G;                       /* npad x npad (gram) */
+    double* r;                       /* n (gram) */
+    const double* Linv;              /* npad x npad and npad, inside the factorisation's state (weights) */
+    const double* a;
+    const int32_t* info;             /* the factorisation's info word */
+    double* w;                       /* n */
+    double* theta;                   /* (1 + n_levels) F */
+    double* chain;                   /* n_out x (13 + 2F (d + 2)) */
+    int32_t* info_out;
+} mobocmf_exact_sample_problem;
+int mobocmf_exact_sample_gram(const mobocmf_exact_sample_problem* host_problems, const mobocmf_exact_sample_problem* dev_problems,
+                              int32_t n_problems, mobocmf_stream_t stream);
+int mobocmf_exact_sample_weights(const mobocmf_exact_sample_problem* host_problems, const mobocmf_exact_sample_problem* dev_problems,
+                                 int32_t n_problems, mobocmf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -134,6 +134,22 @@ class ExactFitModel(ctypes.Structure):
                 ("losses", ctypes.c_void_p), ("stats", ctypes.c_void_p), ("words", ctypes.c_void_p), ("work", ctypes.c_void_p)]
 
 
+# MOBOCMF_EXACT_SAMPLE_*: limits and the feature chunk of the gram launch
+EXACT_SAMPLE_MAX_N, EXACT_SAMPLE_MAX_LEVELS, EXACT_SAMPLE_MAX_F, EXACT_SAMPLE_MAX_PROBLEMS, EXACT_SAMPLE_CHUNK = 512, 8, 65536, 64, 16
+
+
+class ExactSampleProblem(ctypes.Structure):
+    """mobocmf_exact_sample_problem: one (model, sample) of the mobocmf_exact_sample_* launches (read from DEVICE memory)."""
+    _fields_ = [("n", ctypes.c_int32), ("d", ctypes.c_int32), ("n_levels", ctypes.c_int32), ("F", ctypes.c_int32),
+                ("n_out", ctypes.c_int32), ("reserved", ctypes.c_int32), ("out_level", ctypes.c_int32 * EXACT_SAMPLE_MAX_LEVELS),
+                ("x", ctypes.c_void_p), ("lev", ctypes.c_void_p), ("y", ctypes.c_void_p), ("sig", ctypes.c_void_p),
+                ("ntab", ctypes.c_void_p), ("sqd", ctypes.c_void_p), ("scal", ctypes.c_void_p),
+                ("W_sig", ctypes.c_void_p), ("b_sig", ctypes.c_void_p), ("W_noi", ctypes.c_void_p), ("b_noi", ctypes.c_void_p),
+                ("theta0", ctypes.c_void_p), ("e", ctypes.c_void_p), ("G", ctypes.c_void_p), ("r", ctypes.c_void_p),
+                ("Linv", ctypes.c_void_p), ("a", ctypes.c_void_p), ("info", ctypes.c_void_p), ("w", ctypes.c_void_p),
+                ("theta", ctypes.c_void_p), ("chain", ctypes.c_void_p), ("info_out", ctypes.c_void_p)]
+
+
 class NatgradSmallLayer(ctypes.Structure):
     """mobocmf_natgrad_small_layer: one layer of mobocmf_natgrad_small_step (the kernel reads the array from DEVICE memory)."""
     _fields_ = [("M", ctypes.c_int32), ("n_guard_info", ctypes.c_int32), ("m", ctypes.c_void_p), ("L_S", ctypes.c_void_p),
@@ -298,6 +314,8 @@ SYMBOLS = {
     "mobocmf_exact_fit_gradient": [_P, _P, _I32, _P],
     "mobocmf_exact_fit_update": [_P, _P, _I32, _I32, _D, _D, _D, _D, _P],
     "mobocmf_mes_group_forward": [_P, _P, _P, _I32, _I32, _I32, _P, _I32, _P, _I32, _P, _I32, _P, _P, _P],
+    "mobocmf_exact_sample_gram": [_P, _P, _I32, _P],
+    "mobocmf_exact_sample_weights": [_P, _P, _I32, _P],
 }
 ACQ_MAX_PAIRS, TOPK_MAX_K, TOPK_MAX_N = 32, 64, 4096      # MOBOCMF_ACQ_MAX_PAIRS / MOBOCMF_TOPK_MAX_K / MOBOCMF_TOPK_MAX_N
 ACQ_MAX_COLUMNS = 1 << 24                                 # MOBOCMF_ACQ_MAX_COLUMNS

@@ -12,7 +12,7 @@ force=0
 ccver=$($HIPCC --version 2>/dev/null | sha256sum | cut -c1-16)
 objs=""
 pids=""
-for f in gemm_f64 chol gram gram_rows elementwise rff rff_opt pareto pareto_evolve recommend inducing minibatch natgrad natgrad_small acq_search frozen_predict exact_predict exact_fit tiny_step coop_step api; do
+for f in gemm_f64 chol gram gram_rows elementwise rff rff_opt pareto pareto_evolve recommend inducing minibatch natgrad natgrad_small acq_search frozen_predict exact_predict exact_fit exact_sample tiny_step coop_step api; do
   want=$( (echo "$ccver $FLAGS"; cat $f.hip *.h ../../include/mobocmf_hip.h) | sha256sum | cut -c1-32)
   have=$(cat $f.o.stamp 2>/dev/null || true)
   if [ $force = 1 ] || [ ! -f $f.o ] || [ "$want" != "$have" ]; then

@@ -1493,6 +1493,19 @@ def exact_fit_update(host_models, dev_table, mode, lr, betas=(0.9, 0.999), eps=1
                     float(betas[1]), float(eps))
 
 
+def exact_sample_gram(host_problems, dev_table, stream=None):
+    """mobocmf_exact_sample_gram: G = Phi^T Phi + noise I (padded for the factorisation) and r = y - Phi^T theta0 - e of every
+    (model, sample) problem of the table.  One launch, only enqueues (``host_problems`` a ctypes array of
+    ``_lib.ExactSampleProblem``, ``dev_table`` the same bytes in a device uint8 tensor)."""
+    _exact_fit_call("mobocmf_exact_sample_gram", host_problems, dev_table, stream)
+
+
+def exact_sample_weights(host_problems, dev_table, stream=None):
+    """mobocmf_exact_sample_weights: w = L^-T a, theta = theta0 + Phi w and the packed one-layer chain samples of the requested
+    output levels; copies each factorisation's info word next to the others.  Two launches, only enqueues."""
+    _exact_fit_call("mobocmf_exact_sample_weights", host_problems, dev_table, stream)
+
+
 def check_info(info):
     """Synchronising: raises if the last Cholesky reported a non-positive pivot."""
     lib = _lib.require_device()

@@ -302,6 +302,13 @@ class RFFChainSample:
                 return self._device(xt.to(self.device).contiguous()).cpu().numpy()
             return self._torch(xt).numpy()
 
+    def negated(self):
+        """The sample -f: the same layers with the top layer's ``theta`` negated (a maximised objective handed to a MOOP,
+        which minimises)."""
+        layers = [dict(L) for L in self.layers]
+        layers[-1]["theta"] = -layers[-1]["theta"]
+        return RFFChainSample(layers, self.d, self.device)
+
     # ------------------------------------------------------------------ packing
     def pack(self):
         """1-D float64 CPU tensor: header (version, L, d, F, length, the L kinds), then per layer its 7 scalars and the

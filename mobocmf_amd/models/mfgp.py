@@ -260,6 +260,15 @@ class _ExactMFGP(nn.Module):
             raise ValueError("fit: engine is \"host\" or \"device\" (got %r)" % (engine,))
         return self._fit_host(num_iters, lr)
 
+    def sample_chain_from_posterior(self, fidelity, nFeatures=500, generator=None, engine="device"):
+        """One posterior function sample at level ``fidelity`` as an ``RFFChainSample`` (one kind-0 layer of 2 nFeatures
+        features) by Matheron's rule in the n-dimensional function space (util/exact_sample.py: the algebra, and the order of
+        the draws from ``generator``).  ``engine="device"``: csrc/exact_sample.hip (a model that does not fit raises -- there is
+        no fallback); ``"host"``: the same algebra in float64 torch on the CPU from the same draws, so one generator state gives
+        the same function on either engine, up to rounding.  ``last_draw`` keeps the ``ChainDraw``."""
+        from ..util import exact_sample
+        return exact_sample.sample_chain_from_posterior(self, fidelity, nFeatures=nFeatures, generator=generator, engine=engine)
+
     def _fit_host(self, num_iters, lr, record=None):
         """The host loop.  ``record``: a dict that receives what the loop saw (losses, best, best_iteration, stopped_at,
         restored, final) -- from the floats it reads anyway."""
