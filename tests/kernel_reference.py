@@ -1323,7 +1323,10 @@ def _gram_df2_abs(c, xdiv, T):
 def _layer_forward(c, T):
     """(state, shadow state) of the forward in the number format ``T`` converts to.  As a layer of a model (_model_run) ``c``
     may hold "sf", the shadow of its f column [N']: f then carries an error of u sf, which the leaves it enters -- K_mn and
-    k_nn -- pass on through their derivatives, |d K / d f| sf joining sum |term| and |d knn / d f| sf joining k_nn."""
+    k_nn -- pass on through their derivatives, |d K / d f| sf joining sum |term| and |d knn / d f| sf joining k_nn.
+    With "chain" -- a GIVEN chain state -- the statements are _chain_forward's."""
+    if c.get("chain") is not None:
+        return _chain_forward(c, T)
     M = c["M"]
     cmm, cmn = _gram_operands(c)
     Kmm = _gram(c["kind"], cmm, 1, T)[0] + T(c["jitter"]) * np.eye(M, dtype=T(0.0).dtype)
@@ -1356,7 +1359,10 @@ def _layer_forward(c, T):
 def _layer_backward(c, st, sst, T, phi_diag=0.5):
     """(gradients, their shadows) from the forward states.  ``phi_diag``: the factor on Phi's diagonal (1/2; the CPU test's
     mutation drops it).  As a layer of a model ``c`` may hold "s_g_mean" / "s_g_var", the SHADOWS of its upstream gradients,
-    which then stand where |g_mean| / |g_var| stand for a layer by itself, and "sf" (see _layer_forward)."""
+    which then stand where |g_mean| / |g_var| stand for a layer by itself, and "sf" (see _layer_forward).  With "chain" the
+    statements are _chain_backward's."""
+    if c.get("chain") is not None:
+        return _chain_backward(c, st, sst, T)
     kind, xdiv = c["kind"], c["xdiv"]
     cmm, cmn = _gram_operands(c)
     gm, gkl = T(c["g_mean"]), T(c["g_kl"])
@@ -1399,6 +1405,113 @@ def _layer_backward(c, st, sst, T, phi_diag=0.5):
             o["g_zf_mn"], o["g_zf_mm"] = bmn["g_f1"][pick], bmm["g_f1"][pick] + bmm["g_f2"][pick]
             o["g_zf"] = o["g_zf_mn"] + o["g_zf_mm"]
         res.append(o)
+    return res
+
+
+def _gram_df2(c, xdiv, T):
+    """(d K / d f2 [n1 x nbase2 xdiv], d knn / d f2), signed, of a kind 1 Gram case (_gram_df2_abs's terms before the magnitudes)."""
+    x1, x2, hyp, f1, f2 = T(c["x1"]), T(c["x2"]), T(c["hyp"]), T(c["f1"]), T(c["f2"])
+    d = x1.shape[1]
+    a1, af, nu, _, lsf = hyp[:5]
+    t = (x1[:, None, :] - x2[None, :, :]) / hyp[5:5 + d]
+    g1 = np.repeat(T(0.5) * (t * t).sum(-1), xdiv, axis=1)
+    fd = f2[None, :] - f1[:, None]
+    gf = T(0.5) * (fd / lsf) ** 2
+    return a1 * np.exp(-g1) * nu * f1[:, None] - a1 * np.exp(-(g1 + gf)) * af * fd / (lsf * lsf), 2 * a1 * nu * f2
+
+
+# ---- a layer on a GIVEN chain state (csrc/frozen_predict.hip; tests/frozen_predict_reference.py): c["chain"] = {Linv, LinvT, U,
+# UT, a}, float64, is exact data -- no K_mm, no Cholesky, no inverse -- read the way the kernel reads it: A through the L^-T
+# array, C through the U array, dA through U^T, dK through L^-1.  The shadow takes the factors' magnitudes and gives them no
+# error of their own: it is the shadow of what THIS layer computes, absolute values through every sum and product.  What the
+# layer INHERITS -- the error u sf of f from the layer below, the error of the upstream gradients from the layer above -- is
+# not sent through those magnitudes again.  Under the workload's conditioning (cond(K_mm) of 1e8 .. 1e9: |L^-1||K| is 1e4 ..
+# 1e5 |A|) that charges every inherited error this layer's cancellation a second time and the next layer's a third, and the
+# composed figure admits anything.  The layer's outputs are smooth functions of what it inherits, so first order an inherited
+# error moves them by the SIGNED derivative, formed in the reference's own format:
+#   q = |A|^2, r = |C|^2   S(q) = 2 |A| S(A) (>= A^2: the product's own rounding), where S(A)^2 counts the error of A against S(A)
+#                          although it multiplies |A| only.
+#   f, forward             |d mean / d f| sf and |d raw / d f| sf with d mean / d f = a^T B, d raw / d f = d k_nn / d f - 2 A . B +
+#                          2 C . U^T B, B = L^-1 dK / df.
+#   upstream gradients     the layer's gradients are linear in (g_mean, g_var): |d g / d g_mean_j| and |d g / d g_var_j| from one
+#                          run each on unit upstream gradients (a column depends on its own pair only), times the shadows
+#                          handed down less the magnitudes.
+#   f, backward            |d g / d f_j| sf_j by a central difference of the value statements (step 2^-20: its own error is
+#                          1e-12 of the derivative in longdouble, and the derivative only scales a bound).
+# c["defect"] plants one of frozen_predict_reference.FROZEN_DEFECTS in the values, never in the shadow.
+def _chain_forward(c, T, values_only=False):
+    M, ch, defect = c["M"], c["chain"], c.get("defect")
+    cmn = _gram_operands(c)[1]
+    Kmn, _, knn, Kabs = _gram(c["kind"], cmn, c["xdiv"], T)
+    X, a, U = T(ch["LinvT"]).T, T(ch["a"]), T(ch["U"])
+    A = X @ Kmn
+    mean, C = A.T @ a, U.T @ A
+    q, r = (A * A).sum(0), (C * C).sum(0)
+    if defect == "last_row_out_of_q":
+        q = (A[:-1] * A[:-1]).sum(0)
+    if defect == "stale_pad_rows":                                          # rows M .. Mr-1 of the A panel keep what K left there
+        stale = Kmn[:min(-M % 16, M)]
+        q = q + (stale * stale).sum(0)
+    varraw = (knn - q) + r
+    st = dict(X=X, A=A, a=a, U=U, C=C, q=q, r=r, knn=knn, pos=knn - q > 0, varraw=varraw, mean=mean,
+              var=np.maximum(varraw, T(c["min_var"])), kl=T(0.0), Ub=T(ch["UT"]).T, XTb=T(ch["Linv"]).T)
+    if values_only:
+        return st, None
+    aX, aa, aU = np.abs(X), np.abs(a), np.abs(U)
+    sA = aX @ Kabs
+    sC = aU.T @ sA
+    smean, sq, sr = sA.T @ aa, 2 * (np.abs(A) * sA).sum(0), 2 * (np.abs(C) * sC).sum(0)
+    svar = knn + sq + sr
+    if c.get("sf") is not None:
+        dK, dknn = _gram_df2(cmn, c["xdiv"], T)
+        B = X @ dK
+        smean = smean + np.abs(B.T @ a) * T(c["sf"])
+        svar = svar + np.abs(dknn - 2 * (A * B).sum(0) + 2 * (C * (U.T @ B)).sum(0)) * T(c["sf"])
+    sst = dict(X=aX, A=sA, a=aa, U=aU, C=sC, q=sq, r=sr, knn=knn, pos=st["pos"], varraw=svar, mean=smean, var=svar, kl=T(0.0),
+               Ub=np.abs(st["Ub"]), XTb=np.abs(st["XTb"]))
+    return st, sst
+
+
+def _chain_backward(c, st, sst, T):
+    """(g_x, g_f) and their shadows: gv = g_var [raw > floor], dA = 2 U (C gv) + a g_mean - 2 A gv, dK = L^-T dA, the Gram
+    backward of K_mn and k_nn.  The factors are constants: nothing else has a gradient."""
+    kind, xdiv, defect = c["kind"], c["xdiv"], c.get("defect")
+    cmn = _gram_operands(c)[1]
+    above = st["varraw"] > T(c["min_var"])                                     # clamp_min passes gradient above the floor only
+
+    def run(s, g, w, sh, case=cmn, div=xdiv):
+        dA = s["Ub"] @ (2 * s["C"] * w[None, :]) + np.outer(s["a"], g)
+        if sh or defect != "A_gv_dropped":
+            dA = dA + (2 if sh else -2) * s["A"] * w[None, :]
+        gknn = None if (defect == "dknn_df_dropped" and not sh) else w
+        b = _gram_bwd(kind, case, div, s["XTb"] @ dA, gknn, None, T)
+        pick = 2 if sh else 0
+        return b["g_x2"][pick], (b["g_f2"][pick] if kind == 1 else None)
+
+    gm, gv = T(c["g_mean"]), np.where(above, T(c["g_var"]), 0)
+    gx, gf = run(st, gm, T(c["g_var"]) if defect == "floor_gate_ignored" else gv, False)
+    sgx, sgf = run(sst, np.abs(gm), np.abs(gv), True)                          # this layer's own: f and the upstream pair exact
+    cols = dict(cmn, x2=np.repeat(T(cmn["x2"]), xdiv, axis=0))                 # every column its own base row: no replica sum
+    fold = lambda jx, e: (np.abs(jx) * e[:, None]).reshape(c["nbase"], xdiv, -1).sum(1)
+    if c.get("s_g_mean") is not None:                                          # a layer of a model: the shadows handed down
+        eg = np.maximum(T(c["s_g_mean"]) - np.abs(gm), 0)
+        ew = np.where(above, np.maximum(T(c["s_g_var"]) - np.abs(T(c["g_var"])), 0), 0)
+        one, zero = np.ones(c["Np"], gm.dtype), np.zeros(c["Np"], gm.dtype)
+        for unit_g, unit_w, e in ((one, zero, eg), (zero, np.where(above, one, 0), ew)):
+            jx, jf = run(st, unit_g, unit_w, False, cols, 1)
+            sgx = sgx + fold(jx, e)
+            if kind == 1:
+                sgf = sgf + np.abs(jf) * e
+    if c.get("sf") is not None:
+        h, side = T(2.0 ** -20), []
+        for sign in (1, -1):
+            fh = T(c["f"]) + sign * h
+            side.append(run(_chain_forward(dict(c, f=fh, sf=None, defect=None), T, values_only=True)[0], gm, gv, False, dict(cols, f2=fh), 1))
+        sgx = sgx + fold((side[0][0] - side[1][0]) / (2 * h), T(c["sf"]))
+        sgf = sgf + np.abs((side[0][1] - side[1][1]) / (2 * h)) * T(c["sf"])
+    res = [dict(g_x=gx), dict(g_x=sgx)]
+    if kind == 1:
+        res[0]["g_f"], res[1]["g_f"] = gf, sgf
     return res
 
 
@@ -1782,7 +1895,7 @@ def _inv_softplus(h):
     return h + np.log(-np.expm1(-h))
 
 
-def model_case(L, d, M, rows, S, seed=0, clamp=0, weights=False, seeds=None, predict=False):
+def model_case(L, d, M, rows, S, seed=0, clamp=0, weights=False, seeds=None, predict=False, zx=None, floor=False):
     """One well-conditioned whole-model problem (cached, read-only): L layers sharing Z_x -- layer_case's jittered lattice (d <=
     3) or uniform points, and its lengthscale ranges, so that cond(K_mm + jitter I) <= LAYER_COND_MAX for every Z~_l = [Z_x,
     m_{l-1}] (asserted by the CPU test).  ``rows`` = (N, rows[1], ...), descending: the rows are in the kernels' order, row b
@@ -1792,14 +1905,21 @@ def model_case(L, d, M, rows, S, seed=0, clamp=0, weights=False, seeds=None, pre
     that f = m_{l-1}[b % M] in the layers above -- under jitter = CLAMP_JITTER.  ``weights``: row_weight in [0.5, 2], every
     fourth row 0.  ``seeds``: "both" | "mean" | "var" -- seed_gmean / seed_gvar standard normal (the other one zeros),
     seed_scale = -0.75.  ``predict``: the eval branch at N test points: rows[l] = N, no row scored (fid = -1), kl_scale = 0,
-    eps[l] = S fixed samples tiled over the points, and every third row's seeds zero."""
+    eps[l] = S fixed samples tiled over the points, and every third row's seeds zero.  ``zx`` = "uniform" (d <= 2): Z_x uniform
+    in [0, 1]^d with lengthscales 0.4 .. 0.6 under jitter 1e-6 -- the workload's conditioning, cond(K_mm + jitter I) of 1e8 ..
+    1e9, which only a reference on the GIVEN chain (frozen_predict_ref) can gate.  ``floor`` (prediction, d = 8): the last test
+    point lies ON Z_x[7 % M], L_S of layer 0 is 1e-7 I and jitter 1e-12: that column of layer 0 sits on the variance floor."""
     rows = tuple(int(r) for r in rows)
-    key = ("model", L, d, M, rows, S, seed, clamp, weights, seeds, predict)
+    key = ("model", L, d, M, rows, S, seed, clamp, weights, seeds, predict) + ((zx, floor) if zx or floor else ())
     if key in _model_cases:
         return _model_cases[key]
     assert len(rows) == L and all(rows[l] >= rows[l + 1] >= 1 for l in range(L - 1)) and not (predict and clamp)
     rng = np.random.default_rng(7919 * L + 1009 * M + 31 * rows[0] + 7 * d + S + 131071 * seed)
-    if d <= 3:
+    assert zx in (None, "uniform") and not (zx and d > 2) and not (floor and not (predict and d == 8))
+    if zx:
+        Zx = rng.random((M, d))
+        ls = lambda: rng.uniform(0.4, 0.6, d)
+    elif d <= 3:
         side = int(np.ceil(M ** (1.0 / d)))
         h = 1.0 / side
         grid = np.stack(np.meshgrid(*[np.arange(side)] * d, indexing="ij"), -1).reshape(-1, d)
@@ -1827,6 +1947,10 @@ def model_case(L, d, M, rows, S, seed=0, clamp=0, weights=False, seeds=None, pre
              noise_lo=[MODEL_NOISE_LO if i else 0.0 for i in interval], noise_hi=[0.3 + 0.2 * l if i else 0.0 for l, i in enumerate(interval)],
              raw_noise=[0.5 * rng.standard_normal() if i else 0.05 + 0.1 * rng.random() for i in interval],
              row_weight=None, seed_gmean=None, seed_gvar=None, seed_scale=0.0)
+    if floor:
+        c["x"] = np.concatenate([x[:-1], Zx[7 % M][None, :]])
+        c["L_S"] = [1e-7 * np.eye(M)] + c["L_S"][1:]
+        c["jitter"] = 1e-12
     if predict:
         c["samples"] = [None] + [rng.standard_normal(S) for _ in range(1, L)]
         c["eps"] = [None] + [np.tile(s, N) for s in c["samples"][1:]]
@@ -1859,27 +1983,38 @@ def _softplus(x):
     return np.where(x > 20, x, np.log1p(np.exp(np.minimum(x, 20))))
 
 
-def model_layer(mc, l, T, f=None, sf=None):
-    """Layer ``l`` of the model as a case of the layer statements (layer_case's fields) in ``T``'s number format."""
+def model_layer(mc, l, T, f=None, sf=None, chains=None):
+    """Layer ``l`` of the model as a case of the layer statements (layer_case's fields) in ``T``'s number format.  ``chains``
+    [l]: the layer's GIVEN chain state (_layer_forward, "chain") with the packed hyper-parameters "hyp" the kernel was handed --
+    data like the factors, where the model's own are softplus(raw) in ``T``'s format."""
     nb, xdiv = mc["rows"][l], (mc["S"] if l else 1)
-    return dict(kind=int(l > 0), d=mc["d"], M=mc["M"], nbase=nb, xdiv=xdiv, Np=nb * xdiv, branch=mc["branch"], want_dx=int(mc["predict"]),
-                jitter=mc["jitter"], min_var=1e-10, x=mc["x"][:nb], f=f, sf=sf, Zx=mc["Zx"], zf=T(mc["m"][l - 1]) if l else None,
-                hyp=_softplus(T(mc["raw"][l])), m=mc["m"][l], L_S=mc["L_S"][l])
+    c = dict(kind=int(l > 0), d=mc["d"], M=mc["M"], nbase=nb, xdiv=xdiv, Np=nb * xdiv, branch=mc["branch"], want_dx=int(mc["predict"]),
+             jitter=mc["jitter"], min_var=1e-10, x=mc["x"][:nb], f=f, sf=sf, Zx=mc["Zx"], zf=T(mc["m"][l - 1]) if l else None,
+             hyp=_softplus(T(mc["raw"][l])), m=mc["m"][l], L_S=mc["L_S"][l])
+    if chains is not None:
+        c.update(chain=chains[l], hyp=T(chains[l]["hyp"]), defect=mc.get("defect"))
+    return c
 
 
-def _model_forward(mc, T, stop=None):
-    """[(layer case, state, shadow state)] of the layers 0 .. stop - 1 (all): the propagation with its shadow."""
+def _model_forward(mc, T, stop=None, chains=None):
+    """[(layer case, state, shadow state)] of the layers 0 .. stop - 1 (all): the propagation with its shadow; ``chains``: on
+    the layers' GIVEN chain states (model_layer)."""
     L, S, rows = mc["L"], mc["S"], mc["rows"]
     out, f, sf = [], None, None
     for l in range(L if stop is None else stop):
-        lc = model_layer(mc, l, T, f, sf)
+        lc = model_layer(mc, l, T, f, sf, chains)
         st, sst = _layer_forward(lc, T)
         out.append((lc, st, sst))
         if l + 1 < L:
             idx = np.arange(rows[l + 1] * S) // (S if l == 0 else 1)
             mean, sd, e = st["mean"][idx], np.sqrt(st["var"][idx]), T(mc["eps"][l + 1])
             f = mean + sd * e
-            sf = sst["mean"][idx] + sst["var"][idx] * np.abs(e) / (2 * sd) + np.abs(mean) + sd * np.abs(e)
+            svar = sst["var"][idx]
+            if chains is not None:
+                # a column ON the floor (frozen_predict_ref asserts every floor decision robust) holds the constant 1e-10 on both
+                # sides: its variance carries no error into f, where S(var) / (2 sqrt(1e-10)) would admit anything
+                svar = np.where(st["varraw"][idx] > lc["min_var"], svar, 0)
+            sf = sst["mean"][idx] + svar * np.abs(e) / (2 * sd) + np.abs(mean) + sd * np.abs(e)
     return out
 
 
@@ -1913,12 +2048,13 @@ def model_names(mc, what):
     return fw + {"forward": (), "input": ("g_x",), "gradients": tuple(k for k, _, _ in model_layout(mc))}[what]
 
 
-def _model_run(mc, T, loss_only=False):
+def _model_run(mc, T, loss_only=False, chains=None):
     """(values, shadows, forward states) of the whole model in ``T``'s number format; ``loss_only``: the scalar the gradients
-    are of, -ELBO + seed_scale (<seed_gmean, top mean> + <seed_gvar, top var>), from the forward alone."""
+    are of, -ELBO + seed_scale (<seed_gmean, top mean> + <seed_gvar, top var>), from the forward alone.  ``chains``: on the
+    layers' GIVEN chain states (model_layer) -- the parameters are constants, so of the gradients only g_x exists."""
     L, S, rows, N = mc["L"], mc["S"], mc["rows"], mc["N"]
     dt = T(0.0).dtype
-    fw = _model_forward(mc, T)
+    fw = _model_forward(mc, T, chains=chains)
     y, fid, ks = T(mc["y"]), mc["fid"], T(mc["kl_scale"])
     w = T(np.ones(N) if mc["row_weight"] is None else mc["row_weight"])
     half, log2pi = T(0.5), T(LOG_2PI)
@@ -1959,18 +2095,20 @@ def _model_run(mc, T, loss_only=False):
         lc, st, sst = fw[l]
         gm, gv, sgm, sgv = ups[l]
         g, sg = _layer_backward(dict(lc, g_mean=gm, g_var=gv, g_kl=ks, s_g_mean=sgm, s_g_var=sgv), st, sst, T)
-        sig = 1 / (1 + np.exp(-T(mc["raw"][l])))
-        flat["g_hyp%d" % l], sflat["g_hyp%d" % l] = g["g_hyp"] * sig, sg["g_hyp"] * sig
-        flat["g_m%d" % l], sflat["g_m%d" % l] = g["g_m"], sg["g_m"]
-        if zshare[0] is not None:                                          # g_zf of the layer above: Z~_{l+1} = [Z_x, m_l]
-            flat["g_m%d" % l], sflat["g_m%d" % l] = g["g_m"] + zshare[0], sg["g_m"] + zshare[1]
-        flat["g_LS%d" % l], sflat["g_LS%d" % l] = g["g_LS"], sg["g_LS"]
+        if chains is None:
+            sig = 1 / (1 + np.exp(-T(mc["raw"][l])))
+            flat["g_hyp%d" % l], sflat["g_hyp%d" % l] = g["g_hyp"] * sig, sg["g_hyp"] * sig
+            flat["g_m%d" % l], sflat["g_m%d" % l] = g["g_m"], sg["g_m"]
+            if zshare[0] is not None:                                      # g_zf of the layer above: Z~_{l+1} = [Z_x, m_l]
+                flat["g_m%d" % l], sflat["g_m%d" % l] = g["g_m"] + zshare[0], sg["g_m"] + zshare[1]
+            flat["g_LS%d" % l], sflat["g_LS%d" % l] = g["g_LS"], sg["g_LS"]
         if mc["predict"]:
             gx[:rows[l]] += g["g_x"]
             sgx[:rows[l]] += sg["g_x"]
         if l:
-            zshare = (g["g_zf"], sg["g_zf"])
-            res["g_zf%d" % l], sha["g_zf%d" % l] = zshare
+            if chains is None:
+                zshare = (g["g_zf"], sg["g_zf"])
+                res["g_zf%d" % l], sha["g_zf%d" % l] = zshare
             ncn, fdiv = lc["Np"], S if l == 1 else 1                       # this layer's columns feed on the layer below
             k = ncn // fdiv
             _, stb, sstb = fw[l - 1]
@@ -1984,7 +2122,8 @@ def _model_run(mc, T, loss_only=False):
     flat["g_noise"], sflat["g_noise"] = gn, sgn
     for d_, s_ in ((res, flat), (sha, sflat)):
         d_.update(s_)
-        d_["grad"] = np.concatenate([np.ravel(s_[k]) for k, _, _ in model_layout(mc)])
+        if chains is None:
+            d_["grad"] = np.concatenate([np.ravel(s_[k]) for k, _, _ in model_layout(mc)])
     if mc["predict"]:
         res["g_x"], sha["g_x"] = gx, sgx
     return res, sha, fw

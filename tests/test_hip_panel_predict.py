@@ -1,6 +1,7 @@
 """The frozen-chain predict kernel (csrc/frozen_predict.hip) through PanelPredictGroup (util/panel_predict.py): moments and input
 gradient of surrogates with 128 < M <= 512 against MFDGP.predict_for_acquisition through the layer entry points, the group's
-freeze / thaw and reuse, the seeds' zeros, the variance floor, and the refusals."""
+freeze / thaw and reuse, the seeds' zeros, the variance floor, and the refusals.
+(The componentwise gate of the kernel itself, on the chain state it reads: tests/test_hip_frozen_predict_conformance.py.)"""
 import pytest
 import torch
 

@@ -1,7 +1,8 @@
 """The split frozen-chain predict kernel (csrc/frozen_predict.hip, CW = 8) through SplitPredictGroup (util/panel_predict.py):
 moments and input gradient of surrogates with 128 < M <= 1024 against MFDGP.predict_for_acquisition through the layer entry
 points and against the 16-column kernel, the group's freeze / thaw and reuse, `work`, the seeds' zeros, the variance floor, and
-the refusals."""
+the refusals.
+(The componentwise gate of the kernel itself, on the chain state it reads: tests/test_hip_frozen_predict_conformance.py.)"""
 import pytest
 import torch
 
