@@ -27,6 +27,13 @@
  * code; a non-positive-definite K_mm is reported through the device word `info` (0 = OK, k>0 = pivot k
  * failed), mirroring LAPACK potrf / torch.linalg.cholesky_ex, so the caller may retry with more jitter
  * (gpytorch psd_safe_cholesky semantics) without a sync on the fast path.
+ *
+ * The Python binding (mobocmf_amd/_lib.py) is DERIVED from this file at import, and reads three declaration forms only:
+ *   constants   `#define MOBOCMF_X <integer expression>` (literals, ( ) + * <<, earlier MOBOCMF_ names) and the anonymous enum;
+ *   structs     `typedef struct [tag] { ... } name;` with fields of int32_t / uint32_t / int64_t / uint64_t / double / size_t,
+ *               pointers, earlier structs of this file, and 1- or 2-dimensional arrays of these with constant bounds;
+ *   functions   `int mobocmf_name(args);` with scalars of those types, pointers and mobocmf_stream_t.
+ * Anything else of these kinds (a bitfield, a function pointer, a float, a function-like macro) makes the import raise.
  */
 #ifndef MOBOCMF_HIP_H
 #define MOBOCMF_HIP_H

@@ -95,15 +95,8 @@ def test_descriptor_validation_is_done_on_the_host():
 
 
 def test_python_constants_match_the_header():
-    import os
-    import re
+    """The relations between the constants; their values are the compiler's (tests/test_abi_cpu.py)."""
     from mobocmf_amd import _lib
-    text = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "mobocmf_hip.h")).read()
-    for name in ("MAX_N", "MAX_LEVELS", "STRIP", "KERNEL_MIN", "KERNEL_LIN", "IDENTITY", "SOFTPLUS", "SIGMOID", "PARAMS", "P_NOISE",
-                 "P_OS_S", "P_LS_S", "P_OS_N", "P_LS_N", "P_RHO", "STEP", "FINISH", "WORDS", "W_IT", "W_STOPPED_AT", "W_BEST_IT",
-                 "W_RESTORED", "W_ABANDONED", "W_FINAL_INFO"):
-        m = re.search(r"#define MOBOCMF_EXACT_FIT_%s (\d+)\b" % name, text)
-        assert m and int(m.group(1)) == getattr(_lib, "EXACT_FIT_" + name), name
     assert _lib.EXACT_FIT_SUMS == 2 * (_lib.MAX_D + 1) + 1 + 2 * _lib.EXACT_FIT_MAX_LEVELS == R.SUMS
     assert _lib.EXACT_FIT_MAX_MODELS == 2 * _lib.ACQ_MAX_PAIRS
     assert (_lib.EXACT_FIT_S_OS_S, _lib.EXACT_FIT_S_LS_S, _lib.EXACT_FIT_S_OS_N, _lib.EXACT_FIT_S_LS_N, _lib.EXACT_FIT_S_TAU,

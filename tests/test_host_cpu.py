@@ -26,6 +26,11 @@ def test_library_exports_every_declared_symbol():
     for name in declared:
         assert hasattr(lib, name)
     assert lib.mobocmf_version() >= 100           # host-only call, no GPU needed
+    # ... and nothing else: the library's dynamic mobocmf_* functions are exactly the declared ones
+    import subprocess
+    nm = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    exported = set(re.findall(r"^\w+ T (mobocmf_\w+)$", nm, flags=re.M))
+    assert exported == declared, exported ^ declared
 
 
 def test_workspace_query_and_bad_args():
