@@ -486,9 +486,11 @@ int panel_backward(const mobocmf_layer_desc* desc, const Dims& D, const ChainWs&
     return launch_sum_partials_multi(tk, nt, s);
 }
 
-// CHAIN half, backward, of n layers:  dL = -tril(L^-T [dA A^T + dU_tot U^T + da_tot a^T]) + gkl diag(1/L_ii), g_m, g_LS,
-// Cholesky backward, Gram backward of K_mm.  H, Hc, da come from the PANEL halves (zero[z]: layer z had none -- no
-// upstream mean / var gradient).  acc[z]: add to g_hyp / g_zf (the PANEL half wrote its share there) instead of overwriting.
+// CHAIN half, backward, of n layers:  g_m, g_LS, dKmm = sym(L^-T Wn L^-1) with
+//   Wn = gkl/2 I - a da^T + Hc - gkl/2 a a^T - F U^T,  F = 2 H U + gkl/2 U
+// (every term of the loss is a function of K_mm^-1: dKmm is formed directly, the factor L gets no gradient of its own --
+// DESIGN 1), Gram backward of K_mm.  H, Hc, da come from the PANEL halves and are only read (zero[z]: layer z had none -- no
+// upstream mean / var gradient -- they are cleared first).  acc[z]: add to g_hyp / g_zf (the PANEL half wrote its share there) instead of overwriting.
 // fold[z]: zf of layer z IS the variational mean of layer z - 1 of this batch (Z~_z = [Z_x, m_{z-1}], mfdgp_hidden_layer.py:
 // 555-556): its whole gradient -- the K_mm share formed here plus the PANEL half's share waiting in g_zf[z] if acc[z] -- is
 // added to g_m[z - 1] in the last launch, and g_zf[z] is not written (autograd would add the two tensors in a launch of its own).
@@ -496,8 +498,8 @@ int chain_backward(int n, const ChainWs& c, int64_t zs, const ChainIO& io, const
                    const bool* fold, hipStream_t s) {
     const int Mp = D.Mp;
     const int64_t mm = (int64_t)Mp * Mp;
-    double *G1 = c.W[0], *G2 = c.W[1], *X = c.W[2], *dU = c.W[3], *Y = c.W[4], *T1 = c.W[5], *T2 = c.W[6], *LT = c.W[7];
-    double *dL = G1, *T4 = G2, *Gm = X;   // reused once their first content is dead
+    // (Gm = W[2]: chain_rows_partials reads it there)
+    double *G1 = c.W[0], *F = c.W[1], *Gm = c.W[2], *dU = c.W[3], *Wn = c.W[4], *T1 = c.W[5], *T4 = c.W[6], *T2 = c.W[7];
     bool any_clamp_branch = false;
     for (int z = 0; z < n; ++z) {
         if (zero[z]) {
@@ -516,47 +518,30 @@ int chain_backward(int n, const ChainWs& c, int64_t zs, const ChainIO& io, const
         GemmArgs g1 = gemm_args(c.UT, Mp, c.H, Mp, G1, Mp, Mp, Mp, Mp, TRI_UPPER_A, 1.0);          // G1 = U^T H
         g1.Kreal = D.M;      // the contraction's padded tail multiplies zeros (small problems)
         TRY(chain_gemm(g1, false, c, n, zs, s));
-        GemmArgs g2 = gemm_args(c.U, Mp, G1, Mp, G2, Mp, Mp, Mp, Mp, TRI_LOWER_A, 1.0);            // G2 = U U^T H
-        g2.Kreal = D.M;
-        TRY(chain_gemm(g2, false, c, n, zs, s));
-        // X = H U is G1^T (H symmetric): dU_tot = 2 tril(X) + gkl U reads it out of G1, in the launch that also forms Y
-        TRY(launch_dutot_y_z(G1, G2, Hc, c.U, c.da, c.a, io.g_kl, Mp, dU, c.da_tot, Y, n, zs, s));
+        // X = H U is G1^T (H symmetric): F, dU_tot and da_tot read it out of G1, in the launch that also starts Wn
+        TRY(launch_chain_glue_z(G1, Hc, c.U, c.da, c.a, io.g_kl, D.M, Mp, F, dU, c.da_tot, Wn, n, zs, s));
+        GemmArgs gw = gemm_args(F, Mp, c.UT, Mp, Wn, Mp, Mp, Mp, Mp, TRI_UPPER_B, -1.0);           // Wn -= F U^T (as F x UT: the A B form)
+        gw.accumulate = 1;
+        gw.Kreal = D.M;
+        TRY(chain_gemm(gw, false, c, n, zs, s));
     }
-    // Y += dU_tot U^T (as dU_tot x UT: both products in the A B form) and T1 = L^-T dU_tot are independent: one launch for
-    // the pair where the mid-size kernel takes them.  g_LS = tril(T1) - gkl diag(1/LS_ii) and g_m = L^-T da_tot: the user
-    // tensors of all layers in one launch
+    // T1 = L^-T dU_tot and T4 = L^-T Wn are independent: one launch for the pair where the mid-size kernel takes them.
+    // g_LS = tril(T1) - gkl diag(1/LS_ii) and g_m = L^-T da_tot: the user tensors of all layers in one launch
     {
-        GemmArgs g4 = gemm_args(dU, Mp, c.UT, Mp, Y, Mp, Mp, Mp, Mp, TRI_LOWER_A | TRI_UPPER_B, 1.0);
-        g4.accumulate = 1;
-        g4.Kreal = D.M;
         GemmArgs ga = gemm_args(c.LinvT, Mp, dU, Mp, T1, Mp, Mp, Mp, Mp, TRI_UPPER_A | TRI_LOWER_B, 1.0);
         ga.lower_out = 1;
         ga.Kreal = D.M;
+        GemmArgs gb = gemm_args(c.LinvT, Mp, Wn, Mp, T4, Mp, Mp, Mp, Mp, TRI_UPPER_A, 1.0);
+        gb.Kreal = D.M;
         if (n > 1) {
-            g4.zlayers = ga.zlayers = n;
-            g4.zsA = g4.zsB = g4.zsC = ga.zsA = ga.zsB = ga.zsC = zs;
+            ga.zlayers = gb.zlayers = n;
+            ga.zsA = ga.zsB = ga.zsC = gb.zsA = gb.zsB = gb.zsC = zs;
         }
-        TRY(launch_gemm_auto_pair(g4, ga, c.slabs, c.slab_elems, s));
+        TRY(launch_gemm_auto_pair(ga, gb, c.slabs, c.slab_elems, s));
         TRY(launch_chain_outputs_z(T1, c.LSp, c.LinvT, c.da_tot, D.M, Mp, io.g_kl, io.g_LS, io.g_m, n, zs, s));
     }
-    // dL
+    // dKmm = sym(L^-T Wn L^-1)
     {
-        GemmArgs ga = gemm_args(c.LinvT, Mp, Y, Mp, T2, Mp, Mp, Mp, Mp, TRI_UPPER_A, 1.0);
-        ga.lower_out = 1;
-        ga.Kreal = D.M;
-        TRY(chain_gemm(ga, false, c, n, zs, s));
-        TRY(launch_dl_from_t2_z(T2, c.L, io.g_kl, D.M, Mp, dL, n, zs, s));
-    }
-    // Cholesky backward: dKmm = sym(L^-T Phi(L^T dL) L^-1)
-    {
-        TRY(launch_transpose_z(c.L, Mp, LT, Mp, Mp, Mp, n, zs, s));
-        GemmArgs ga = gemm_args(LT, Mp, dL, Mp, T2, Mp, Mp, Mp, Mp, TRI_UPPER_A | TRI_LOWER_B, 1.0);
-        ga.Kreal = D.M;
-        TRY(chain_gemm(ga, false, c, n, zs, s));
-        TRY(launch_phi_z(T2, Mp, T1, n, zs, s));
-        GemmArgs gb = gemm_args(c.LinvT, Mp, T1, Mp, T4, Mp, Mp, Mp, Mp, TRI_UPPER_A | TRI_LOWER_B, 1.0);
-        gb.Kreal = D.M;
-        TRY(chain_gemm(gb, false, c, n, zs, s));
         GemmArgs gc = gemm_args(T4, Mp, c.Linv, Mp, T2, Mp, Mp, Mp, Mp, TRI_LOWER_B, 1.0);
         gc.Kreal = D.M;
         TRY(chain_gemm(gc, false, c, n, zs, s));

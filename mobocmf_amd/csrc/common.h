@@ -217,8 +217,6 @@ int launch_mirror_lower(const double* src, int64_t lds, double* dst, int64_t ldd
 // layer-batched forms (blockIdx.z = layer, workspace pointers + z*zs doubles, user tensors as tables)
 int launch_chain_outputs_z(const double* X, const double* LSp, const double* LinvT, const double* da_tot, int M, int Mp,
                            const double* const* gkl, double* const* gLS, double* const* gm, int nz, int64_t zs, hipStream_t s);
-int launch_transpose_z(const double* in, int64_t ldi, double* out, int64_t ldo, int64_t rows, int64_t cols, int nz,
-                       int64_t zs, hipStream_t s);
 int launch_gemv_rows_z(const double* Mat, int64_t ld, const double* vec, double* out, int rows, int64_t cols, double scale,
                        int accumulate, int nz, int64_t zs, hipStream_t s);
 int launch_transpose_pad_z(const double* in, double* out, int Mp, const double* const* LS, const double* const* m, int M,
@@ -227,9 +225,8 @@ int launch_transpose_gemv_z(const double* in, double* out, int Mp, const double*
                             int64_t zs, hipStream_t s);
 int launch_kl_z(const double* L, const double* LSp, const double* U, const double* a, int M, int Mp, double* const* kl,
                 double* part, int nz, int64_t zs, hipStream_t s);
-int launch_dutot_y_z(const double* G1, const double* G2, const double* Hc, const double* U, const double* da, const double* a,
-                     const double* const* gkl, int Mp, double* dU, double* da_tot, double* Y, int nz, int64_t zs, hipStream_t s);
-int launch_dl_from_t2_z(const double* T2, const double* L, const double* const* gkl, int M, int Mp, double* dL, int nz,
+int launch_chain_glue_z(const double* G1, const double* Hc, const double* U, const double* da, const double* a,
+                        const double* const* gkl, int M, int Mp, double* F, double* dU, double* da_tot, double* Wn, int nz,
                         int64_t zs, hipStream_t s);
 int launch_phi_z(const double* T3, int Mp, double* P, int nz, int64_t zs, hipStream_t s);
 int launch_symmetrize_z(const double* S, int Mp, double* G, int nz, int64_t zs, hipStream_t s);

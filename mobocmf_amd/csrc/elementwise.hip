@@ -72,26 +72,6 @@ int launch_pad_vec(const double* src, int64_t n, double* dst, int64_t np, hipStr
 // the user tensors of every layer of a chain batch (transpose_pad_z: LSp + z*zs = tril(L_S[z]) padded, mp + z*zs = m[z] padded)
 struct PadZ { const double* LS[MAX_ZL]; const double* m[MAX_ZL]; };
 
-// out[c][r] = in[r][c]   (rows x cols -> cols x rows), 32x32 LDS tiles
-__global__ void transpose_kernel(const double* in, int64_t ldi, double* out, int64_t ldo, int64_t rows, int64_t cols,
-                                 int64_t zs) {
-    __shared__ double t[32][33];
-    in += blockIdx.z * zs;
-    out += blockIdx.z * zs;
-    int64_t c = (int64_t)blockIdx.x * 32 + threadIdx.x, r0 = (int64_t)blockIdx.y * 32;
-    for (int k = threadIdx.y; k < 32; k += 8)
-        if (r0 + k < rows && c < cols) t[k][threadIdx.x] = in[(r0 + k) * ldi + c];
-    __syncthreads();
-    int64_t r = r0 + threadIdx.x, c0 = (int64_t)blockIdx.x * 32;
-    for (int k = threadIdx.y; k < 32; k += 8)
-        if (c0 + k < cols && r < rows) out[(c0 + k) * ldo + r] = t[threadIdx.x][k];
-}
-int launch_transpose_z(const double* in, int64_t ldi, double* out, int64_t ldo, int64_t rows, int64_t cols, int nz,
-                       int64_t zs, hipStream_t s) {
-    dim3 grid((unsigned)((cols + 31) / 32), (unsigned)((rows + 31) / 32), (unsigned)nz);
-    hipLaunchKernelGGL(transpose_kernel, grid, dim3(32, 8), 0, s, in, ldi, out, ldo, rows, cols, zs);
-    return CHECK_LAUNCH();
-}
 // Two pairs of independent launches of the chain forward as ONE launch each (the chain is a string of latency-bound launches:
 // at the reference's own sizes every one of them is ~4.5 us of a ~300 us step):
 //   transpose_pad_z:   out = in^T (Mp x Mp, L^-1 -> L^-T)    +  the padded copies of the user tensors L_S, m of every layer
@@ -390,67 +370,54 @@ int launch_reduce_slabs_sym(const double* slabs, int64_t slab_stride, int nslab,
     return CHECK_LAUNCH();
 }
 
-// dU_tot = 2 tril(X) + gkl U with X = H U = (U^T H)^T = G1^T (H is exactly symmetric: the slab reduction mirrors it) -- the
-// product X is never formed, its lower triangle is read out of G1 transposed (32 x 32 tiles through LDS);
-// da_tot = da + gkl a;  Y = 2 G2 - 2 Hc + a da^T + da_tot a^T.  One launch for all three, all layers (blockIdx.z).
-__global__ void dutot_y_kernel(const double* G1, const double* G2, const double* Hc, const double* U, const double* da,
-                               const double* a, ScalZ gklz, int Mp, double* dU, double* da_tot, double* Y, int64_t zs) {
+// The glue between G1 = U^T H and the products that form dK_mm directly (backward).  X = H U = G1^T (H is exactly
+// symmetric: the slab reduction mirrors it) is never formed: it is read out of G1 transposed (32 x 32 tiles through LDS).
+//   F      = 2 X + gkl/2 U                      (the full square: the left operand of Wn -= F U^T)
+//   dU_tot = 2 tril(X) + gkl U
+//   da_tot = da + gkl a
+//   Wn     = Hc - a da^T - gkl/2 a a^T + gkl/2 [i == j < M]
+// One launch for all four, all layers (blockIdx.z).  H, Hc and da are only read.
+__global__ void chain_glue_kernel(const double* G1, const double* Hc, const double* U, const double* da, const double* a,
+                                  ScalZ gklz, int M, int Mp, double* F, double* dU, double* da_tot, double* Wn, int64_t zs) {
     __shared__ double tl[32][33];
     const double* gkl = gklz.p[blockIdx.z];
-    const double g = gkl ? gkl[0] : 0.0;
+    const double g = gkl ? gkl[0] : 0.0, hg = 0.5 * g;
     const int64_t zo = blockIdx.z * zs;
-    G1 += zo; G2 += zo; Hc += zo; U += zo; da += zo; a += zo; dU += zo; da_tot += zo; Y += zo;
+    G1 += zo; Hc += zo; U += zo; da += zo; a += zo; F += zo; dU += zo; da_tot += zo; Wn += zo;
     const int nt = Mp / 32, ti = blockIdx.x / nt, tj = blockIdx.x % nt;      // tile (ti, tj) of the outputs
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;                   // 32 x 8 threads
-    if (tj <= ti) {      // the tile touches the lower triangle: stage G1's tile (tj, ti), coalesced along its rows
+    // stage G1's tile (tj, ti), coalesced along its rows
 #pragma unroll
-        for (int r = ty; r < 32; r += 8) tl[r][tx] = G1[(int64_t)(tj * 32 + r) * Mp + ti * 32 + tx];
-    }
+    for (int r = ty; r < 32; r += 8) tl[r][tx] = G1[(int64_t)(tj * 32 + r) * Mp + ti * 32 + tx];
     __syncthreads();
 #pragma unroll
     for (int r = ty; r < 32; r += 8) {
         const int i = ti * 32 + r, j = tj * 32 + tx;
         const int64_t idx = (int64_t)i * Mp + j;
         const double ai = a[i], aj = a[j], dai = da[i], daj = da[j];
-        dU[idx] = j <= i ? 2.0 * tl[tx][r] + g * U[idx] : 0.0;      // X[i][j] = G1[j][i]
-        Y[idx] = 2.0 * (G2[idx] - Hc[idx]) + ai * daj + (dai + g * ai) * aj;
+        const double x2 = 2.0 * tl[tx][r];                           // X[i][j] = G1[j][i]
+        const double u = j <= i ? U[idx] : 0.0;
+        F[idx] = x2 + hg * u;
+        dU[idx] = j <= i ? x2 + g * u : 0.0;
+        double w = Hc[idx] - ai * daj - hg * ai * aj;
+        if (i == j && i < M) w += hg;
+        Wn[idx] = w;
         if (tj == 0 && tx == 0) da_tot[i] = dai + g * ai;
     }
 }
-int launch_dutot_y_z(const double* G1, const double* G2, const double* Hc, const double* U, const double* da, const double* a,
-                     const double* const* gkl, int Mp, double* dU, double* da_tot, double* Y, int nz, int64_t zs, hipStream_t s) {
+int launch_chain_glue_z(const double* G1, const double* Hc, const double* U, const double* da, const double* a,
+                        const double* const* gkl, int M, int Mp, double* F, double* dU, double* da_tot, double* Wn, int nz,
+                        int64_t zs, hipStream_t s) {
     ScalZ t = {};
     for (int z = 0; z < nz; ++z) t.p[z] = gkl[z];
     const int nt = Mp / 32;
-    hipLaunchKernelGGL(dutot_y_kernel, dim3((unsigned)(nt * nt), 1, (unsigned)nz), dim3(256), 0, s, G1, G2, Hc, U, da, a, t, Mp,
-                       dU, da_tot, Y, zs);
+    hipLaunchKernelGGL(chain_glue_kernel, dim3((unsigned)(nt * nt), 1, (unsigned)nz), dim3(256), 0, s, G1, Hc, U, da, a, t, M, Mp,
+                       F, dU, da_tot, Wn, zs);
     return CHECK_LAUNCH();
 }
 
 
 // ------------------------------------------------------------------ Cholesky-chain backward glue (Mp x Mp)
-// dL = -tril(T2) + gkl * diag(1/L_ii)  (rows/cols < M only; zero elsewhere)
-__global__ void dl_from_t2_kernel(const double* T2, const double* L, ScalZ gklz, int M, int Mp, double* dL, int64_t zs) {
-    int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= (int64_t)Mp * Mp) return;
-    const double* gkl = gklz.p[blockIdx.z];
-    T2 += blockIdx.z * zs; L += blockIdx.z * zs; dL += blockIdx.z * zs;
-    int i = (int)(idx / Mp), j = (int)(idx % Mp);
-    double v = 0.0;
-    if (i < M && j <= i) {
-        v = -T2[idx];
-        if (i == j && gkl) v += gkl[0] / L[idx];
-    }
-    dL[idx] = v;
-}
-int launch_dl_from_t2_z(const double* T2, const double* L, const double* const* gkl, int M, int Mp, double* dL, int nz,
-                        int64_t zs, hipStream_t s) {
-    ScalZ t = {};
-    for (int z = 0; z < nz; ++z) t.p[z] = gkl[z];
-    hipLaunchKernelGGL(dl_from_t2_kernel, GRIDZ((int64_t)Mp * Mp, nz), 0, s, T2, L, t, M, Mp, dL, zs);
-    return CHECK_LAUNCH();
-}
-
 // P = Phi(T3): lower triangle with halved diagonal
 __global__ void phi_kernel(const double* T3, int Mp, double* P, int64_t zs) {
     int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
